@@ -12,11 +12,14 @@ tiles of the reference plane (all-gather) through the C ABI's r1_comm_* entry
 points (RCCL), in stream order with the launches.
 
 Prints ONE JSON line on rank 0 (contract in the task statement), carrying
-`roofline` for the dominant kernel (VALU-issue and HBM roofs), `cpu_baseline`
-(vectorised and scalar CPU legs timed on the host cores, rank 0 / N=1 only),
-`parity_checked` / `parity_ok` (the GPU's buffers of the timed steps against
-those CPU legs) and `extra_lines` (chroma planes, mixed filter pairs, mixed
-transform types).
+`roofline` for the dominant kernel (VALU-issue and HBM roofs).  A plain run
+sets up, warms up, times --steps steps and reports them (--dump-outputs DIR:
+what the last timed step computed, as .npy files).  With --full (N = 1) it then
+also measures and checks everything else: the pipelined figure, `rdo_only`
+(--chain pixel), `cpu_baseline` (vectorised and scalar CPU legs timed on the
+host cores), `parity_checked` / `parity_ok` (the GPU's buffers of the timed
+steps against those CPU legs) and `extra_lines` (chroma planes, mixed filter
+pairs, mixed transform types, BASELINE configs 2-4).
 """
 import argparse
 import ctypes as C
@@ -33,7 +36,7 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
@@ -43,7 +46,7 @@ def parse():
     ap.add_argument("--bit-depth", type=int, default=8)
     ap.add_argument("--k", type=int, default=16, help="candidates per block")
     ap.add_argument("--cpu-seconds", type=float, default=15.0,
-                    help="target duration of the CPU-oracle baseline sample (0 = skip)")
+                    help="with --full: target duration of the CPU-oracle baseline sample (0 = skip)")
     ap.add_argument("--backend", default="nccl",
                     help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only for dry runs)")
     ap.add_argument("--single-device", action="store_true",
@@ -84,14 +87,22 @@ def parse():
                     help="N = 1: run the tagged-tile self-check of the exchange through the C-ABI communicator "
                          "(world 1) as the N > 1 runs always do; the result is config.exchange_ok")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the supplementary workloads (chroma planes, mixed filter pairs, mixed "
-                         "transform types) reported under `extra_lines`")
+                    help="with --full: skip the supplementary workloads (chroma planes, mixed filter pairs, "
+                         "mixed transform types) reported under `extra_lines`, and the pipelined figure")
     ap.add_argument("--detail-out", default=None,
                     help="where the long document goes (default gpurun_out/bench_detail.json); stdout carries "
                          "only the compact record (< 4 KB)")
     ap.add_argument("--no-events", action="store_true",
                     help="skip per-kernel event timing (roofline.achieved falls back to step time)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps, everything else this bench measures or checks (N = 1): the "
+                         "pipelined figure, rdo_only (--chain pixel), the supplementary lines (unless --no-extra) "
+                         "and the CPU baseline with its parity check (unless --cpu-seconds 0); off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<buffer>_<size>x<size>.npy (float32 / "
+                         "float64, exact; a fixed seeded sample where a buffer is large, %d MB in all)"
+                         % (DUMP_LIMIT >> 20))
+    return ap.parse_args(argv)
 
 
 def physical_cores():
@@ -563,6 +574,53 @@ def emit(res, detail_out=None):
     sys.stderr.flush()
     print(compact_record(res, detail_path))
     sys.stdout.flush()
+
+
+DUMP_LIMIT = 64 << 20     # bytes --dump-outputs writes, all files together
+DUMP_SEED = 1
+
+
+def dump_plan(outs, limit=DUMP_LIMIT):
+    """--dump-outputs: what is written of each output buffer.  outs = {size: {buffer: tensor}}, dimension 0 of
+    a tensor = the candidates of that size.  Every buffer is written whole if all of them fit in `limit`
+    bytes; otherwise a buffer keeps at most `cap` values (the largest power of two that fits), i.e. the rows
+    of a fixed seeded sample of its candidates: one permutation per (size, candidate count), so the sample
+    is the same in every run with the same arguments and a buffer with longer rows keeps a subset of the
+    candidates a per-candidate buffer keeps.  Integers up to 16 bits and float32 are written as float32,
+    wider ones as float64 (exact either way).  -> [(file name, tensor, sorted row indices or None, dtype)]"""
+    def plan(cap):
+        out = []
+        for s in sorted(outs, reverse=True):
+            for name in sorted(outs[s]):
+                t = outs[s][name]
+                n = t.shape[0]
+                row = max(1, t.numel() // max(1, n))
+                k = n if cap is None else min(n, max(1, cap // row))
+                idx = None
+                if k < n:
+                    idx = np.sort(np.random.default_rng([DUMP_SEED, s, n]).permutation(n)[:k]).astype(np.int64)
+                dt = np.float32 if t.element_size() <= (4 if t.is_floating_point() else 2) else np.float64
+                out.append(("%s_%dx%d" % (name, s, s), t, idx, dt))
+        return out
+
+    def nbytes(p):
+        return sum((t.shape[0] if idx is None else len(idx)) * max(1, t.numel() // max(1, t.shape[0]))
+                   * np.dtype(dt).itemsize for _, t, idx, dt in p)
+    p, cap = plan(None), 1 << 24
+    while nbytes(p) > limit and cap >= 1:
+        p, cap = plan(cap), cap // 2
+    assert nbytes(p) <= limit, nbytes(p)
+    return p
+
+
+def dump_outputs(dirname, outs, prefix="", limit=DUMP_LIMIT):
+    """Write dump_plan(outs, limit) to dirname/<prefix><buffer>_<size>x<size>.npy."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    for name, t, idx, dt in dump_plan(outs, limit):
+        if idx is not None:
+            t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+        np.save(os.path.join(dirname, prefix + name + ".npy"), t.cpu().numpy().astype(dt))
 
 
 def extra_lines(ctx, args):
@@ -1313,7 +1371,7 @@ def main():
             send, gathered = tiles.make_exchange_buffers(ref.data, rank, world)
     push_why = None   # why the peer-store exchange is not the one in use (None: it is, or N = 1)
 
-    full = args.chain != "cand"
+    full = args.chain != "cand"      # the quantizing chains (not args.full)
     pixel = args.chain == "pixel"
     if pixel:
         scales = torch.from_numpy(np.random.default_rng(9).integers(
@@ -1610,6 +1668,9 @@ def main():
         step(True)
     fence()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        # every step writes the same buffers: what they hold now is what the last timed step computed
+        dump_outputs(args.dump_outputs, outs, "" if world == 1 else "rank%d_" % rank)
     # ---- N > 1: is the exchange still right AFTER the timed loop?  Every rank recomputes what every tile of
     # the plane the last step left must hold -- ORIGINAL ^ ring_tag(exchange steps done), the peers' tiles
     # included -- on its own copy; MIN over ranks.  A store that raced the hand-shake, or arrived a ring cycle
@@ -1707,7 +1768,7 @@ def main():
             "kernel_ms_note": "HIP events around each launch of every %dth timed step "
                               "(%d samples per size)" % (EV_EVERY, max([len(v) for v in ev.values()] + [0])),
         }
-        if world == 1 and not fan and not args.no_extra:
+        if args.full and world == 1 and not fan and not args.no_extra:
             # The same K steps with the four launches of a step on four FREE-RUNNING streams (no join
             # between steps: the launches of consecutive steps overlap, as independent batches in
             # flight do -- the tiles of a frame are encoded independently), the 64x64 launch at high
@@ -1736,7 +1797,7 @@ def main():
                                 "note": "the same steps, one free-running stream per block size ('/' separates streams, "
                                         "h / l = queue priority), no join between steps; outputs checked like the "
                                         "serialized steps' (the parity legs below run on what these launches left)"}
-        if pixel and world == 1:
+        if args.full and pixel and world == 1:
             # The same chain as rav1e's RDO runs it: rdo_tx_size_type -> encode_tx_block -> compute_distortion
             # (src/rdo.rs:1073, src/encoder.rs:1404-1661, src/rdo.rs:254-347) never takes SAD or SATD of a
             # candidate -- those belong to the motion search (compute_mv_rd, src/me.rs:1445-1463).  `value` keeps
@@ -1765,12 +1826,12 @@ def main():
                                        "rdo_tx_size_type -> encode_tx_block -> compute_distortion compute per candidate; "
                                        "`value` above keeps both (the motion search's distortions ride along)"}
         bad = []
-        if world == 1 and not full and not args.no_extra:
+        if args.full and world == 1 and not full and not args.no_extra:
             res["extra_lines"] = extra_lines(ctx, args)
             if (fw, fh, bd) == (3840, 2160, 8):   # the default run: BASELINE configs 2-4 beside the headline
                 res["extra_lines"] += config_lines(ctx, args)
             bad += ["extra:" + e["name"] for e in res["extra_lines"] if not e.get("parity_ok", True)]
-        if world == 1 and args.cpu_seconds > 0 and not full:
+        if args.full and world == 1 and args.cpu_seconds > 0 and not full:
             # the CPU legs evaluate strided samples of this very step at 4K: what they return is
             # compared with what the timed launches left in HBM (sad, satd and every coefficient)
             res["cpu_baseline"], parity = cpu_baseline(args, host_org, host_ref, cands, outs)

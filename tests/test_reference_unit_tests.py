@@ -4,7 +4,9 @@ the way rustc would; here the code under execution carries its expected values w
 (`assert_eq!` against the tables the reference's authors wrote), so a transpiler that mis-executes
 integer arithmetic, slices, iterators or the Plane layout fails them.
 
-Runs only where the reference tree is present (the build container); the GPU box skips it.
+Runs only where the reference tree is present (the build container); the GPU box skips it.  The one
+test that compares the project against an executed reference RESULT (the tile grid) reads it from
+tests/golden/tiling_ref.npz and runs everywhere.
 
   src/dist.rs      get_sad_same_u8 / u16, get_satd_same_u8 / u16   (22 block sizes each, :416-533)
   src/predict.rs   pred_matches_u8, pred_max                        (:1514-1693)
@@ -26,7 +28,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference/src"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree is not on this machine")
+needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree is not on this machine")
 
 CASES = [
     ("dist.rs", "get_sad_same_u8"), ("dist.rs", "get_sad_same_u16"),
@@ -55,6 +57,7 @@ def crate_with_tests(rel):
     return c
 
 
+@needs_ref
 @pytest.mark.parametrize("rel,name", CASES)
 def test_reference_unit_test_passes_under_rustlite(rel, name):
     c = crate_with_tests(rel)
@@ -101,6 +104,7 @@ def transform_crate(seed, tamper=None):
     return c
 
 
+@needs_ref
 @pytest.mark.parametrize("name", ["roundtrips_u8", "roundtrips_u16"])
 def test_reference_transform_roundtrips(name):
     """forward_transform (forward.rs:71-161) -> inverse_transform_add (inverse.rs:1633-1705), both
@@ -109,6 +113,7 @@ def test_reference_transform_roundtrips(name):
         transform_crate(seed).get(name)({})
 
 
+@needs_ref
 def test_roundtrip_harness_catches_a_broken_inverse_driver():
     """not vacuous: the same test against an inverse driver whose column-pass rounding shift is
     3 instead of 4 (inverse.rs:1699) panics on the authors' tolerance"""
@@ -132,46 +137,32 @@ def test_roundtrip_harness_catches_a_broken_inverse_driver():
 def test_tile_rects_equal_the_executed_tiling_info():
     """rav1e_amd/workload.py::tile_rects (what shards the frame over the GPUs, SURVEY 8e) against the
     reference's TilingInfo::from_target_tiles EXECUTED (src/tiling/tiler.rs:56-150) inside the tile-count
-    loop of Sequence::new (src/encoder.rs:248-277, eight lines, restated here): same grid, same tile
-    sizes in superblocks, for the frame sizes and tile counts of BASELINE.json and a sweep around them."""
+    loop of Sequence::new (src/encoder.rs:248-277, eight lines, restated): same grid, same tile sizes in
+    superblocks, for the frame sizes and tile counts of BASELINE.json and a sweep around them.  The executed
+    grids are tests/golden/tiling_ref.npz (tests/golden/gen_tiling_ref.py)."""
     sys.path.insert(0, ROOT)
     from rav1e_amd import workload as W
-    c = crate_with_tests("tiling/tiler.rs")
-    ftt = c.get("from_target_tiles", owner="TilingInfo")
-
-    def reference_tiling(w, h, tiles):
-        rl = cl = 0
-        while True:
-            t = ftt({}, 6, w, h, 60.0, cl, rl, False)
-            if t.rows * t.cols >= tiles:
-                return t
-            if not (rl < t.max_tile_rows_log2 or cl < t.max_tile_cols_log2):
-                return t
-            if (t.tile_height_sb >= t.tile_width_sb and t.tile_rows_log2 < t.max_tile_rows_log2) or \
-                    cl >= t.max_tile_cols_log2:
-                rl += 1
-            else:
-                cl += 1
+    cases = np.load(os.path.join(ROOT, "tests", "golden", "tiling_ref.npz"))["cases"]
+    assert len(cases) == 35
     n = 0
-    for (w, h) in ((3840, 2160), (1920, 1080), (1280, 720), (4096, 2304), (640, 360), (3840, 2176), (1000, 600)):
-        for tiles in (1, 2, 4, 8, 16):
-            t = reference_tiling(w, h, tiles)
-            try:
-                rects = W.tile_rects(tiles, w, h)
-            except ValueError:
-                assert t.rows * t.cols != tiles, (w, h, tiles)      # the reference lands on another count too
-                continue
-            assert t.rows * t.cols == tiles, (w, h, tiles, t.cols, t.rows)
-            want = []
-            for r in range(t.rows):
-                for cc in range(t.cols):
-                    x0, y0 = cc * t.tile_width_sb * 64, r * t.tile_height_sb * 64
-                    want.append((x0, y0, min(x0 + t.tile_width_sb * 64, w), min(y0 + t.tile_height_sb * 64, h)))
-            assert rects == want, (w, h, tiles, rects[:3], want[:3])
-            n += 1
+    for (w, h, tiles, t_rows, t_cols, t_wsb, t_hsb) in cases.tolist():
+        try:
+            rects = W.tile_rects(tiles, w, h)
+        except ValueError:
+            assert t_rows * t_cols != tiles, (w, h, tiles)      # the reference lands on another count too
+            continue
+        assert t_rows * t_cols == tiles, (w, h, tiles, t_cols, t_rows)
+        want = []
+        for r in range(t_rows):
+            for cc in range(t_cols):
+                x0, y0 = cc * t_wsb * 64, r * t_hsb * 64
+                want.append((x0, y0, min(x0 + t_wsb * 64, w), min(y0 + t_hsb * 64, h)))
+        assert rects == want, (w, h, tiles, rects[:3], want[:3])
+        n += 1
     assert n >= 25, n
 
 
+@needs_ref
 def test_a_wrong_expectation_is_caught():
     """the harness is not vacuous: the same SATD test with one expected value changed fails"""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -190,6 +181,7 @@ def test_a_wrong_expectation_is_caught():
         c.get("mutated_satd_inner")({"T": "u8"})
 
 
+@needs_ref
 def test_lrf_search_fixture_follows_the_reference_text(tmp_path):
     """lrf_search_ref.npz is what the reference's text computes, not what the generator assumes: the
     generator run on a scratch copy of src/ with (a) `err * fi.dist_scale[pli]` of rdo_loop_plane_error
@@ -222,6 +214,7 @@ def test_lrf_search_fixture_follows_the_reference_text(tmp_path):
 
 
 
+@needs_ref
 def test_loop_decision_fixture_follows_the_reference_text(tmp_path):
     """loop_decision_ref.npz is what rdo_loop_decision's OWN text does, loop and all: the generator run on a scratch
     copy of src/ with (a) the visible width of a restoration unit (rdo.rs:2645-2649) shortened by 8 changes the units'

@@ -9,7 +9,7 @@ mkdir -p $OUT
 cp rav1e_amd/librav1e_hip.so /tmp/lib_orig.so
 run() { # lib bd cpu_seconds
   cp $1 rav1e_amd/librav1e_hip.so
-  python bench.py --steps 20 --warmup 3 --no-extra --cpu-seconds $3 --bit-depth $2 "${@:4}" 2>&1 | tail -1 > /tmp/ab_line.json
+  python bench.py --full --steps 20 --warmup 3 --no-extra --cpu-seconds $3 --bit-depth $2 "${@:4}" 2>&1 | tail -1 > /tmp/ab_line.json
   python3 - "$1" "$2" <<'PY'
 import json, sys
 try:

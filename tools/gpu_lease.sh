@@ -5,7 +5,7 @@
 #   tests         pytest -m gpu (whole suite)
 #   tests:EXPR    pytest -m gpu -k EXPR
 #   smoke         __graft_entry__.smoke()
-#   bench         bench.py, default flags          -> bench.json
+#   bench         bench.py --full                  -> bench.json
 #   chains        bench.py --chain full|pixel, 8- and 10-bit
 #   txs           tools/bench_txsearch.py, 8- and 10-bit, cdef_dist and transform-domain distortion
 #   txs_ab:LIBS   the same with each library of the comma-separated list copied in (same-box A/B)
@@ -30,6 +30,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT || exit 1
+REPO=$PWD
 cp rav1e_amd/librav1e_hip.so /tmp/lib_orig.so
 
 pmc_pass() {   # pmc_pass NAME "COUNTERS" -- cmd...   (one rocprofv3 run per counter group; csv kept small)
@@ -47,7 +48,7 @@ for STEP in "$@"; do
       if [ -n "$ARG" ]; then timeout 1800 python -m pytest tests -m gpu -x -q -k "$ARG" 2>&1 | tail -15 | tee $OUT/pytest_gpu_k.log
       else timeout 1800 python -m pytest tests -m gpu -x -q 2>&1 | tail -8 | tee $OUT/pytest_gpu.log; fi ;;
     smoke) timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | tee $OUT/smoke.log ;;
-    bench) timeout 1200 python bench.py --detail-out gpurun_out/$TAG/bench_detail.json 2>$OUT/bench.err | grep "^{" | tee $OUT/bench.json | cut -c1-400
+    bench) timeout 1200 python bench.py --full --detail-out $OUT/bench_detail.json 2>$OUT/bench.err | grep "^{" | tee $OUT/bench.json | cut -c1-400
            python3 -c "
 import json; s=open('$OUT/bench.json').read(); d=json.loads(s); print('compact bytes', len(s), 'lines', len(s.strip().splitlines()), 'roofline' in d, 'cpu_baseline' in d)
 for e in d['extra_lines']: print(' ', e['name'], e['value'], e.get('unit','Mpx/s'), e['ms_per_step'], e['parity_ok'], e.get('cpu'))" ;;
@@ -57,7 +58,7 @@ for e in d['extra_lines']: print(' ', e['name'], e['value'], e.get('unit','Mpx/s
       for bd in 8 10; do
         [ $bd = 10 ] && timeout 600 python bench.py --cpu-seconds 0 --no-extra --bit-depth 10 --detail-out gpurun_out/$TAG/bench_10bit_detail.json 2>/dev/null | grep "^{" > $OUT/bench_10bit.json
         for chain in full pixel; do
-          timeout 600 python bench.py --cpu-seconds 0 --chain $chain --bit-depth $bd --detail-out gpurun_out/$TAG/${chain}_chain_${bd}bit_detail.json 2>/dev/null | grep "^{" > $OUT/${chain}_chain_${bd}bit.json
+          timeout 600 python bench.py --full --cpu-seconds 0 --chain $chain --bit-depth $bd --detail-out $OUT/${chain}_chain_${bd}bit_detail.json 2>/dev/null | grep "^{" > $OUT/${chain}_chain_${bd}bit.json
           python3 -c "
 import json; d=json.loads(open('$OUT/${chain}_chain_${bd}bit.json').read()); print('$chain $bd', d.get('value'), d.get('kernel_ms'), d.get('rdo_only',{}).get('value'))"
         done
@@ -110,7 +111,7 @@ d=json.loads(sys.stdin.read()); print('%-22s %9.0f Mpx/s kernel_ms %s ok %s' % (
       for pass in 1 2; do for lib in ${ARG//,/ }; do
         cp $lib rav1e_amd/librav1e_hip.so
         for bd in 8 10; do
-          timeout 600 python bench.py --no-extra --cpu-seconds 0 --bit-depth $bd --chain pixel 2>/dev/null | grep '^{' | python3 -c "
+          timeout 600 python bench.py --full --no-extra --cpu-seconds 0 --bit-depth $bd --chain pixel 2>/dev/null | grep '^{' | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('%-22s bd %2d %9.0f Mpx/s rdo_only %s kernel_ms %s ok %s' % ('$lib'.split('/')[-1], $bd, d['value'], d.get('rdo_only',{}).get('value'), d['kernel_ms'], d.get('parity_ok')))"
         done
@@ -145,8 +146,8 @@ import json; d=json.loads(open('$OUT/dry$n.json').read()); print('dry $n', d['va
       PMC_TIMEOUT=120 pmc_pass txs10_write "WRITE_SIZE" -- $TX ;;
     pmc_px)
       for bd in 8 10; do
-        pmc_pass px${bd}_a "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR" -- python $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 1 --prewarm-ms 0 --cpu-seconds 0 --no-extra --chain pixel --bit-depth $bd
-        pmc_pass px${bd}_b "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_ANY SQ_BUSY_CYCLES SQ_WAVE_CYCLES" -- python $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 1 --prewarm-ms 0 --cpu-seconds 0 --no-extra --chain pixel --bit-depth $bd
+        pmc_pass px${bd}_a "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR" -- python $REPO/bench.py --full --steps 5 --warmup 1 --prewarm-ms 0 --cpu-seconds 0 --no-extra --chain pixel --bit-depth $bd
+        pmc_pass px${bd}_b "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_ANY SQ_BUSY_CYCLES SQ_WAVE_CYCLES" -- python $REPO/bench.py --full --steps 5 --warmup 1 --prewarm-ms 0 --cpu-seconds 0 --no-extra --chain pixel --bit-depth $bd
       done ;;
     pmc_frame)   # every kernel of the config-4 frame (ME, pre-screen, chains, type search, deblock, CDEF, LRF search / filter)
       for bd in 10 8; do
@@ -184,7 +185,7 @@ import json; d=json.loads(open('$OUT/dry$n.json').read()); print('dry $n', d['va
       for pass in "tcc1 FETCH_SIZE" "tcc2 WRITE_SIZE" "sq1 SQ_WAVES SQ_INSTS_VALU SQ_WAIT_ANY SQ_WAVE_CYCLES"; do
         set -- $pass; nm=$1; shift
         (cd /tmp && timeout 900 rocprofv3 --kernel-trace --pmc $@ --output-format csv -d /tmp/pmcl_$TAG/$nm -o p -- \
-          python $GRAFT_REPO_ROOT/bench.py --steps 2 --warmup 1 --prewarm-ms 0 --cpu-seconds 0 --no-events > /tmp/pmcl_$TAG.$nm.log 2>&1)
+          python $REPO/bench.py --full --steps 2 --warmup 1 --prewarm-ms 0 --cpu-seconds 0 --no-events > /tmp/pmcl_$TAG.$nm.log 2>&1)
         f=$(find /tmp/pmcl_$TAG/$nm -name "*counter_collection.csv" | head -1)
         [ -n "$f" ] && (head -1 $f; grep -E 'k_[a-z]' $f) > $OUT/pmcl/$nm.csv || (echo "no counters for $nm"; tail -5 /tmp/pmcl_$TAG.$nm.log)
       done

@@ -362,13 +362,11 @@ extern "C" int r1_comm_exchange_halos(r1_comm *c, const R1Plane *plane, const R1
 // The reference-frame all-gather on TILES: rank r owns rects[r] (x0, y0, x1, y1 in plane pixels)
 // of `plane`; afterwards every rank's plane holds every tile.  Tiles are rectangles, so each
 // rank packs its own into a contiguous slot (2-D copy) and the other ranks' tiles are unpacked
-// into place.  What moves the slots:
-//   p2p  (default)  one group of ncclSend (my tile to every peer) + ncclRecv (every peer's tile):
-//        xGMI is point to point -- every GPU has its own link to each of the 7 others -- so the
-//        N - 1 transfers of a rank run on N - 1 links at once, each carrying one tile's exact bytes;
-//   ring (-DR1_COMM_GATHER_RING=1)  one ncclAllGather of equal slots (the size of the largest tile):
-//        RCCL's ring puts the N - 1 hops behind each other on one link per direction.
-// Both orders of operations are the same on every rank (a collective).
+// into place.  The slots move in one group of ncclSend (my tile to every peer) + ncclRecv (every
+// peer's tile): xGMI is point to point -- every GPU has its own link to each of the 7 others -- so
+// the N - 1 transfers of a rank run on N - 1 links at once, each carrying one tile's exact bytes
+// (an ncclAllGather's ring would put the N - 1 hops behind each other on one link per direction).
+// The order of operations is the same on every rank (a collective).
 extern "C" int r1_comm_allgather_tiles(r1_comm *c, const R1Plane *plane, const int32_t *rects4, void *stream) {
   R1_REQUIRE(c && plane && plane->data && rects4);
   hipStream_t st = (hipStream_t)stream;
@@ -382,10 +380,6 @@ extern "C" int r1_comm_allgather_tiles(r1_comm *c, const R1Plane *plane, const i
     if (b > slot) slot = b;
   }
   slot = (slot + 255) & ~(size_t)255;
-#ifndef R1_COMM_GATHER_RING
-#define R1_COMM_GATHER_RING 0   // A/B builds: -DR1_COMM_GATHER_RING=1
-#endif
-  constexpr bool ring = R1_COMM_GATHER_RING != 0;
   CommDeviceGuard guard(c);
   { const int rc = comm_staging(c, slot * (c->world + 1), st); if (rc != R1_OK) return rc; }
   StagingScope staged(c, st);
@@ -400,13 +394,7 @@ extern "C" int r1_comm_allgather_tiles(r1_comm *c, const R1Plane *plane, const i
   const size_t mrb = (size_t)(mine[2] - mine[0]) * bpp;
   R1_HIP_CHECK(hipMemcpy2DAsync(send, mrb, rect_ptr(mine), pitch, mrb, mine[3] - mine[1],
                                 hipMemcpyDeviceToDevice, st));
-  if (ring) {
-    const ncclResult_t r = c->api->AllGather(send, recv, slot, ncclUint8, c->nccl, st);
-    if (r != ncclSuccess) {
-      r1_set_error("r1_comm_allgather_tiles: %s", c->api->GetErrorString(r));
-      return R1_ECOMM;
-    }
-  } else if (c->world > 1) {
+  if (c->world > 1) {
     // the group is always closed (see r1_comm_exchange_halos)
     R1_NCCL_CHECK(c->api, c->api->GroupStart());
     ncclResult_t first = ncclSuccess;

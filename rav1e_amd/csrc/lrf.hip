@@ -626,10 +626,7 @@ __global__ __launch_bounds__(256, BPP == 1 ? 5 : 1) void k_lrf_search_unit(R1Pla
   // a unit next to each other (rdo_loop_decision's loop order): handing an XCD a CONTIGUOUS run of pairs keeps the nine
   // launches that read the same unit -- its pixels and the source's -- on one L2 (before: every set of a unit fetched
   // it again, 135 MB a luma launch for 17 MB of planes; the tile loads are a quarter of a wave's life)
-#ifndef R1_LRF_XCD_RUNS
-#define R1_LRF_XCD_RUNS 1   // A/B switch
-#endif
-  const int pair = R1_LRF_XCD_RUNS ? xcd_run_item(blockIdx.x, gridDim.x) : (int)blockIdx.x;   // common.hpp
+  const int pair = xcd_run_item(blockIdx.x, gridDim.x);   // common.hpp
   const R1SgrSolveUnit u = units[pair];
   const int bd = BPP == 1 ? 8 : lrf_in.bit_depth;
   if (u.w > 64 || u.h > 64 || u.w <= 0 || u.h <= 0) {   // not what max_w / max_h promised: no result
@@ -650,10 +647,7 @@ __global__ __launch_bounds__(256, BPP == 1 ? 5 : 1) void k_lrf_search_unit(R1Pla
     // rows per tile: 32 -- the tile arrays are 9 KB smaller than with 64 and one more workgroup fits a CU at either
     // pixel width; the two extra tiles of a 64-row luma unit cost less than that buys since the tile's fixed part shrank
     // (r05_ab_notes.md ab9 / ab10)
-#ifndef R1_LRF_SEARCH_TROWS
-#define R1_LRF_SEARCH_TROWS 32
-#endif
-    constexpr int TR = R1_LRF_SEARCH_TROWS;
+    constexpr int TR = 32;
     const int ntx = (u.w + TW - 1) / TW;
     for (int ty = 0; ty < u.h; ty += TR)
     for (int tx = 0; tx < ntx; tx++) {
@@ -735,16 +729,14 @@ __global__ __launch_bounds__(256, BPP == 1 ? 5 : 1) void k_lrf_search_unit(R1Pla
   const int bw = CHROMA ? 8 >> xdec : 8, bh = CHROMA ? 8 >> ydec : 8;
   const int nbx = u.w / bw, nby = u.h / bh;
   unsigned long long mine = 0;
-#ifndef R1_LRF_COOP_ERR
-#define R1_LRF_COOP_ERR 1   // A/B switch: 0 = one thread per block (round 4)
-#endif
   // rdo_loop_plane_error (rdo.rs:2027-2093), the whole workgroup on it.  Round 4 gave a block to a thread: 64 of
   // the 256 threads looped over 64 pixels each -- one-pixel global loads of the source at a stride of a plane
   // row -- while the other waves waited at the barrier.  Now a thread owns a ROW SEGMENT of a block (the 8 lanes
   // of a unit row read 64 contiguous source pixels), the rows of a block meet by xor-shuffles inside their wave
   // (a wave covers exactly one row of blocks), the five sums of every block are parked in LDS and ONE wave runs
   // the 64 fixed-point tails (ssim boost, 64-bit arithmetic) side by side instead of one after the other.
-  if constexpr (R1_LRF_COOP_ERR && !CHROMA) {
+  // Chroma keeps a block per thread: the cooperative form LOSES 5-6 % there (profiles/r05_ab_notes.md, ab4).
+  if constexpr (!CHROMA) {
     uint32_t(*bs)[5] = (uint32_t(*)[5]) & F1[0][0];   // 64 x 5 sums over the filter outputs, which are dead by now
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
@@ -794,49 +786,13 @@ __global__ __launch_bounds__(256, BPP == 1 ? 5 : 1) void k_lrf_search_unit(R1Pla
                                          scale_stride, bd);
       }
     }
-#ifndef R1_LRF_COOP_ERR_CHROMA
-#define R1_LRF_COOP_ERR_CHROMA 0   // measured (profiles/r05_ab_notes.md, ab4): the chroma form LOSES 5-6 % -- off
-#endif
-  } else if constexpr (R1_LRF_COOP_ERR_CHROMA && CHROMA) {
-    if (bw == 4 && bh == 4) {
-      // 4:2:0: a block is one 4x4 cell of get_weighted_sse (dist.rs:234-283) with the block's bias.  A thread owns
-      // a 4-pixel row segment; a wave pass covers four unit rows = one row of cells; rows meet by xor-shuffles.
-      const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-      for (int pass = 0; pass < 4; pass++) {
-        const int y = (pass * 4 + wave) * 4 + (lane >> 4), xs = lane & 15;
-        uint32_t cell = 0;
-        const bool in = xs < nbx && y < nby * 4;
-        if (in) {
-          const uint8_t *po = px_addr<BPP>(src, u.x + xs * 4, u.y + y);
-#pragma unroll
-          for (int i = 0; i < 4; i++) {
-            const int32_t d = (int32_t)ld_px<BPP>(po + (size_t)i * BPP) - (int32_t)P[y][xs * 4 + i];
-            cell += (uint32_t)(d * d);
-          }
-        }
-        cell += __shfl_xor(cell, 16, 64);
-        cell += __shfl_xor(cell, 32, 64);
-        if (in && lane < 16) {
-          const int px = u.x + xs * 4, py = u.y + y;
-          const uint32_t sc = scales ? scales[(size_t)((py << ydec) >> 3) * scale_stride + ((px << xdec) >> 3)] : (1u << 14);
-          mine += ((((unsigned long long)cell * sc + 128) >> 8) + 32) >> 6;
-        }
-      }
-    } else {
-      for (int b = threadIdx.x; b < 16 * nby; b += 256) {
-        const int by = b >> 4, bx = b & 15;
-        if (bx >= nbx) continue;
-        mine += lrf_block_err<BPP, CHROMA, 64>(src, &P[by * bh][bx * bw], u.x + bx * bw, u.y + by * bh, bw, bh, xdec, ydec,
-                                               scales, scale_stride, bd);
-      }
+  } else {
+    for (int b = threadIdx.x; b < 16 * nby; b += 256) {   // rows of 16 block slots (a unit is at most 16 blocks wide)
+      const int by = b >> 4, bx = b & 15;
+      if (bx >= nbx) continue;
+      mine += lrf_block_err<BPP, CHROMA, 64>(src, &P[by * bh][bx * bw], u.x + bx * bw, u.y + by * bh, bw, bh, xdec,
+                                             ydec, scales, scale_stride, bd);
     }
-  } else
-  for (int b = threadIdx.x; b < 16 * nby; b += 256) {   // rows of 16 block slots (a unit is at most 16 blocks wide)
-    const int by = b >> 4, bx = b & 15;
-    if (bx >= nbx) continue;
-    mine += lrf_block_err<BPP, CHROMA, 64>(src, &P[by * bh][bx * bw], u.x + bx * bw, u.y + by * bh, bw, bh, xdec, ydec,
-                                           scales, scale_stride, bd);
   }
   const unsigned long long v = wg_sum_u64(mine, epart);
   // Distortion * fi.dist_scale[pli] (rdo.rs:2092; DistortionScale::mul_u64, rdo.rs:613-615)
@@ -848,15 +804,13 @@ __global__ __launch_bounds__(256, BPP == 1 ? 5 : 1) void k_lrf_search_unit(R1Pla
 // on the superblock alone (crop = the superblock; left / above it the area's working copy `cdef_cur` where the edge
 // flags say so), sgrproj_stripe_filter with the chosen (set, xqd) -- and rdo_loop_plane_error of the restored
 // superblock against the source, added to the (superblock, index, plane) sum the CDEF kernels use.
-#ifndef R1_TRIAL_TROWS
-#define R1_TRIAL_TROWS 64   // rows per tile (A/B: 32)
-#endif
+constexpr int TRIAL_TR = 64;   // rows per tile
 template <int BPP, bool CHROMA>
 __global__ __launch_bounds__(256) void k_sgr_trial_err(R1Plane trial, size_t trial_idx_bytes, R1Plane cdef_cur, R1Plane src,
                                                        const R1TrialUnit *__restrict__ units, int pli, int xdec, int ydec,
                                                        const uint32_t *__restrict__ scales, int scale_stride,
                                                        unsigned long long *__restrict__ psum, int n_sb) {
-  constexpr int TR = R1_TRIAL_TROWS;
+  constexpr int TR = TRIAL_TR;
   __shared__ __attribute__((aligned(16))) uint16_t F[TR][TW];
   __shared__ unsigned long long part[4];
   const R1TrialUnit u = units[blockIdx.y];
@@ -892,10 +846,7 @@ __global__ __launch_bounds__(256) void k_sgr_trial_err(R1Plane trial, size_t tri
   const int bw = CHROMA ? 8 >> xdec : 8, bh = CHROMA ? 8 >> ydec : 8;
   const int nbx = t.tw / bw, nby = t.th / bh;
   unsigned long long mine = 0;
-#ifndef R1_TRIAL_COOP
-#define R1_TRIAL_COOP 1   // A/B switch: 0 = one thread per 8x8 block
-#endif
-  if constexpr (R1_TRIAL_COOP && !CHROMA) {
+  if constexpr (!CHROMA) {
     // rdo_loop_plane_error of the tile with the whole workgroup (as k_lrf_search_unit does): a thread owns an
     // 8-pixel row segment of a block -- 16 contiguous source bytes, 16 bytes of LDS -- the 8 rows of a block meet by
     // xor-shuffles (lanes 4 apart), the block sums are parked in LDS and 32 threads run the fixed-point tails
@@ -940,8 +891,7 @@ __global__ __launch_bounds__(256) void k_sgr_trial_err(R1Plane trial, size_t tri
         mine = r1dist::cdef_tile_tail<0>(b[0], b[1], b[2], b[3], b[4], 64, t.cx0 + bx * 8, u.y + t.ty0 + by * 8, scales, scale_stride, bd);
       }
     }
-  } else
-  if ((int)threadIdx.x < nbx * nby) {
+  } else if ((int)threadIdx.x < nbx * nby) {   // chroma: one thread per block
     const int by = (int)threadIdx.x / nbx, bx = (int)threadIdx.x - by * nbx;
     mine = lrf_block_err<BPP, CHROMA, TW>(src, &F[by * bh][bx * bw], t.cx0 + bx * bw, u.y + t.ty0 + by * bh, bw, bh,
                                           xdec, ydec, scales, scale_stride, bd);
@@ -966,7 +916,7 @@ int r1i_sgr_trial_err_launch(const R1Plane &trial, size_t trial_idx_bytes, const
                              const uint32_t *scales, int scale_stride, unsigned long long *psum, int n_sb, hipStream_t st) {
   R1_REQUIRE(lrf_plane_ok(&trial) && lrf_plane_ok(&cdef_cur) && lrf_plane_ok(&src));
   R1_REQUIRE(trial.bytes_per_px == src.bytes_per_px && cdef_cur.bytes_per_px == src.bytes_per_px);
-  const dim3 grid((64 / TW) * (64 / R1_TRIAL_TROWS), n_units, n_idx);
+  const dim3 grid((64 / TW) * (64 / TRIAL_TR), n_units, n_idx);
 #define R1_TRIAL(BPP, CH)                                                                                         \
   hipLaunchKernelGGL((k_sgr_trial_err<BPP, CH>), grid, dim3(256), 0, st, trial, trial_idx_bytes, cdef_cur, src, units, \
                      pli, xdec, ydec, scales, scale_stride, psum, n_sb)

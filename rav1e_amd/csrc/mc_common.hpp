@@ -261,9 +261,6 @@ __device__ __forceinline__ void stage_window_fast(uint8_t *win, int ws, const R1
 // kernel can issue EVERYTHING it needs from memory (source block, window, tap tables) before it
 // waits for any of it -- written as one call, the source's LDS write sits between the source's
 // loads and the window's, and the wave pays two dependent round trips instead of one.
-#ifndef R1_WIN_WIDE_STORE
-#define R1_WIN_WIDE_STORE 1   // A/B switch (tools/build_variant.sh)
-#endif
 template <int BPP, uint32_t XORM, int P, int H, int NL>
 struct WindowStage {
   static constexpr int ROW_BYTES = (P + 7) * BPP;
@@ -335,7 +332,7 @@ struct WindowStage {
       // staging, and a 16-lane group of a b64 store covers two candidates' chunks instead of four
       // (the b32 pairs of neighbouring candidates met on the same banks: SQ_LDS_BANK_CONFLICT was
       // 18 % / 30 % of the LDS cycles of the 8-bit / 10-bit 8x8 launch, all of it here)
-      constexpr bool WIDE = R1_WIN_WIDE_STORE && (CH - 1) * 8 + 4 < WSR;
+      constexpr bool WIDE = (CH - 1) * 8 + 4 < WSR;
 #pragma unroll
       for (int u = 0; u < PASSES; u++)
         if (lane_on && r0 + u * RP < NR) {

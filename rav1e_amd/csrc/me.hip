@@ -207,13 +207,10 @@ struct Block {
     unsigned long long cost;
     uint32_t sad;
     finish(v, in, row, col, cost, sad);
-#ifndef R1_ME_SETTLE_SCALAR
-#define R1_ME_SETTLE_SCALAR 1   // A/B switch (profiles/r06_ab_notes.md, ab5): 0 = the xor-shuffle tournament
-#endif
-#if R1_ME_SETTLE_SCALAR
     // Every lane of a slot holds its slot's (cost, sad, idx, row, col): the NCS costs go to SCALAR registers with
     // v_readlane (a few cycles each, no LDS crossbar round trip as a ds_bpermute shuffle is) and the tournament runs
-    // on the scalar unit.  idx grows with the slot number, so "the lower index wins ties" is a strict less-than.
+    // on the scalar unit (instead of an xor-shuffle tournament: profiles/r06_ab_notes.md, ab5).  idx grows with the
+    // slot number, so "the lower index wins ties" is a strict less-than.
     {
       int ws = 0;
       unsigned long long wc = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(cost >> 32), 0) << 32) |
@@ -231,20 +228,6 @@ struct Block {
       col = __builtin_amdgcn_readlane(col, wl);
       sad = (uint32_t)__builtin_amdgcn_readlane((int)sad, wl);
     }
-#else
-#pragma unroll
-    for (int s = RH; s < 64; s <<= 1) {
-      // (v_permlane16/32_swap instead of these shuffles was tried: no gain, and together with the DPP
-      // row sums above it produced wrong lanes at scale -- left alone)
-      auto other = [&](uint32_t x) -> uint32_t { return (uint32_t)__shfl_xor((int)x, s, 64); };
-      const unsigned long long oc = ((unsigned long long)other((uint32_t)(cost >> 32)) << 32) | other((uint32_t)cost);
-      const int oi = (int)other((uint32_t)idx), orow = (int)other((uint32_t)row), ocol = (int)other((uint32_t)col);
-      const uint32_t os = other(sad);
-      if (oc < cost || (oc == cost && oi < idx)) {
-        cost = oc; idx = oi; row = orow; col = ocol; sad = os;
-      }
-    }
-#endif
     if (cost < best.cost) {
       best = Msr{row, col, cost, sad};
       if (best_idx) *best_idx = idx;
@@ -274,11 +257,7 @@ struct Block {
   template <class GenA, class GenB>
   __device__ __forceinline__ void scan_pair(int na, GenA gen_a, Msr &best_a, int nb, GenB gen_b, Msr &best_b,
                                             bool check) const {
-#ifdef R1_ME_NO_SPEC
-    if (true) {
-#else
     if (na > NCS || nb > NCS) {
-#endif
       scan(na, gen_a, check, best_a, nullptr);
       scan(nb, gen_b, check, best_b, nullptr);
       return;
@@ -708,17 +687,15 @@ __device__ __forceinline__ void setup_block(B &b, const R1MeJob &job, const R1Me
 template <bool AGENT = false, bool WIDE = false>
 __device__ __forceinline__ void store_result(const TileView &t, int size_in_b, int bx, int by,
                                              const Msr &r, int w, int h, int ssdec, int lane) {
-#ifndef R1_ME_FAST_STORE
-#define R1_ME_FAST_STORE 1   // A/B switch (ab5): shifts where the block area / the entry count per row are powers of two
-#endif
+  // shifts where the block area / the entry count per row are powers of two (ab5)
   // (wave-uniform branches: a 64-bit division and two 32-bit ones by run-time values are ~200 dependent instructions
   // between a search's last compare and the progress word its neighbours wait for)
   const uint32_t wh = (uint32_t)(w * h);
-  const uint32_t nsad = (R1_ME_FAST_STORE && (wh & (wh - 1)) == 0)
+  const uint32_t nsad = (wh & (wh - 1)) == 0
                             ? (uint32_t)((((unsigned long long)r.sad) << 14) >> (31 - __clz(wh)))
                             : (uint32_t)((((unsigned long long)r.sad) << 14) / (unsigned long long)wh);
   const int nx = imin(bx + size_in_b, t.tcols) - bx, ny = imin(by + size_in_b, t.trows) - by;
-  const bool nx_p2 = R1_ME_FAST_STORE && (nx & (nx - 1)) == 0;
+  const bool nx_p2 = (nx & (nx - 1)) == 0;
   const int nx_l2 = 31 - __clz((unsigned)nx);
   R1MeStats v;
   v.row = (int16_t)(r.row << ssdec);
@@ -761,13 +738,10 @@ __device__ unsigned long long g_me_prof[3][4];
 // (predictors, candidates, diamond), [3] result stores + publish (100 MHz ticks, summed over the waves)
 __device__ unsigned long long g_me_step[3][4];
 #endif
-#ifndef R1_ME_DIAG_WAVES
-#define R1_ME_DIAG_WAVES 5
-#endif
 template <int BPP>
-__global__ __launch_bounds__(256, R1_ME_DIAG_WAVES) void k_me_diag(const R1MeJob *__restrict__ jobs,
-                                                 const R1MeParams *__restrict__ pp,
-                                                 R1MeStats *const *__restrict__ rbufs, int step) {
+__global__ __launch_bounds__(256, 5) void k_me_diag(const R1MeJob *__restrict__ jobs,
+                                                    const R1MeParams *__restrict__ pp,
+                                                    R1MeStats *const *__restrict__ rbufs, int step) {
   const R1MeParams p = *pp;   // uniform: lives in SGPRs; in device memory so that the launch
                               // arguments (and with them the captured graph) do not depend on it
   // blockIdx.z = role.  0..2: the SEARCH of pass z on diagonal step - kPassSkew * z (pass q works
@@ -900,8 +874,8 @@ __global__ __launch_bounds__(256, R1_ME_DIAG_WAVES) void k_me_diag(const R1MeJob
 // through.  Why not an __ATOMIC_RELEASE store / fence: at agent scope gfx950 spells it `buffer_wbl2 sc1`
 // + s_waitcnt -- a write-back of the XCD's whole L2 per hand-over (round 2 saw that as a "hang": the
 // waits ran out of patience behind it).  Measured in round 4 with every shared entry an agent-scope
-// atomic, fence(release) before the progress word and fence(acquire) behind each wait (-DR1_ME_FORMAL=1,
-// profiles/r04_me_fence_ab.md): bit-exact, no hang, and 1.3x (1 job) .. 4.1x (64 jobs) SLOWER.  The
+// atomic, fence(release) before the progress word and fence(acquire) behind each wait
+// (profiles/r04_me_fence_ab.md): bit-exact, no hang, and 1.3x (1 job) .. 4.1x (64 jobs) SLOWER.  The
 // product keeps the ISA-level argument: the statistics are acknowledged by the memory system
 // (s_waitcnt vmcnt(0)) before the progress word is issued -- written through (sc1) where the
 // readers may sit on another XCD, left in the L2 that all readers share where they are pinned -- and
@@ -914,13 +888,6 @@ __global__ __launch_bounds__(256, R1_ME_DIAG_WAVES) void k_me_diag(const R1MeJob
 // step of a chain without slack -- so the kernel is not held to k_me_diag's 96
 // registers and keeps three candidate batches in flight at every pixel size.
 // Refined vectors live in the second buffer and are never copied: the samples pick their buffer.
-// R1_ME_FORMAL (A/B build switch, profiles/r04_me_fence_ab.md): the hand-over spelled in the language's memory
-// model -- every shared statistics entry an agent-scope atomic, __builtin_amdgcn_fence(release, "agent")
-// before the progress word, fence(acquire, "agent") behind a successful wait.  On gfx950 the release is
-// `buffer_wbl2 sc1` (write back the XCD's L2) and the acquire `buffer_inv sc1`, per block step.
-#ifndef R1_ME_FORMAL
-#define R1_ME_FORMAL 0
-#endif
 struct MeRow { uint16_t job; uint8_t kind, pad; uint16_t gy, nb; };   // kind 0..2 search, 3 / 4 refine for pass 1 / 2
 struct MePersistArgs {
   const R1MeJob *jobs;
@@ -940,12 +907,7 @@ struct MePersistArgs {
 __device__ __forceinline__ bool me_wait(const unsigned int *f, unsigned int epoch, unsigned int need, int spin) {
   for (int it = 0; it < spin; it++) {
     const unsigned int v = __hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if ((v >> 16) == epoch && (v & 0xFFFFu) >= need) {
-#if R1_ME_FORMAL
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#endif
-      return true;
-    }
+    if ((v >> 16) == epoch && (v & 0xFFFFu) >= need) return true;
     if (it > 64) __builtin_amdgcn_s_sleep(8);
     else if (it > 4) __builtin_amdgcn_s_sleep(1);
   }
@@ -961,12 +923,7 @@ __device__ __forceinline__ bool me_wait_lanes(const unsigned int *mf, unsigned i
       const unsigned int v = __hip_atomic_load(mf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       done = (v >> 16) == epoch && (v & 0xFFFFu) >= mn;
     }
-    if (__all(done)) {
-#if R1_ME_FORMAL
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#endif
-      return true;
-    }
+    if (__all(done)) return true;
     if (it > 64) __builtin_amdgcn_s_sleep(8);
     else if (it > 4) __builtin_amdgcn_s_sleep(1);
   }
@@ -1040,7 +997,7 @@ __global__ __launch_bounds__(64, 2) void k_me_persist(MePersistArgs a) {
                                   b.po_y + imin(div8(mvr) + 2, div8(b.mvy_max)), 1);
         TileView tr = t;
         tr.stats = (R1MeStats *)t.rstats;
-        store_result<true, !PIN || R1_ME_FORMAL>(tr, 1 << (log2b + 1), bx, by, r, w, h, ssdec, lane);
+        store_result<true, !PIN>(tr, 1 << (log2b + 1), bx, by, r, w, h, ssdec, lane);
       } else {
         const int sz = MI << log2b;
         const int x = gx * sz, y = row.gy * sz;
@@ -1091,7 +1048,7 @@ __global__ __launch_bounds__(64, 2) void k_me_persist(MePersistArgs a) {
 #ifdef R1_ME_PROF
         const unsigned long long st2 = wall_clock64();
 #endif
-        store_result<true, !PIN || R1_ME_FORMAL>(t, 1 << log2b, bx, by, r, w, h, ssdec, lane);
+        store_result<true, !PIN>(t, 1 << log2b, bx, by, r, w, h, ssdec, lane);
 #ifdef R1_ME_PROF
         __builtin_amdgcn_s_waitcnt(0);
         if (lane == 0) {
@@ -1104,11 +1061,6 @@ __global__ __launch_bounds__(64, 2) void k_me_persist(MePersistArgs a) {
 #endif
       }
       // publish: the statistics first (agent-scope stores, acknowledged), then the progress
-#if R1_ME_FORMAL
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      if (lane == 0)
-        __hip_atomic_store(mine, (a.epoch << 16) | (unsigned int)(gx + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
       asm volatile("" ::: "memory");   // no result store may sink below the wait, no progress store rise above it
       __builtin_amdgcn_s_waitcnt(0);
       asm volatile("" ::: "memory");
@@ -1117,7 +1069,6 @@ __global__ __launch_bounds__(64, 2) void k_me_persist(MePersistArgs a) {
         if constexpr (PIN) __hip_atomic_store(mine, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         else __hip_atomic_store(mine, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
-#endif
     }
     // the error word is host-mapped pinned memory (one per ring slot): the host reads it where the
     // slot's event is waited for, without a copy (r1_me_status / the slot's reuse)
@@ -1401,41 +1352,28 @@ __global__ __launch_bounds__(256) void k_me_blocks(R1MeJob job, R1MeParams p,
 // in the sub-pel diamond the four 16-lane groups of the wave each own one
 // candidate: window staging, put_8tap (lane = column), SATD / SAD with one lane
 // per Hadamard tile, all inside the group; the four costs meet by shuffles.
-// PHASE 0: the whole search in one launch (the product path).  PHASE 1 / 2 (round 6 experiment, kept behind
-// R1_ME_SMALL_SPLIT): the full-pel search and the sub-pel refinement as two launches -- the result of the first travels
-// through `out` (row, col, sad, cost: the whole MotionSearchResult).  What it showed: the full-pel half needs 61 / 64
-// VGPRs; the 168 VGPRs + 168 / 196 B of scratch (381 MB of scratch writes per 4K launch, profiles/r05_pmc_frame.json)
-// are the sub-pel half's alone (eight inlined (size, bit depth) forms of the fused-candidate column filter + SATD), and
-// giving it 223 VGPRs (two workgroups per CU, 0 B scratch) is SLOWER than three with the spills: the launch is a
-// latency chain per block like the tile search, the scratch stores are not on it (profiles/r06_ab_notes.md, ab3).
-#ifndef R1_ME_SMALL_WAVES
-#define R1_ME_SMALL_WAVES(BPP) 3   // A/B: workgroups the register allocator makes room for (x 4 waves)
-#endif
-#ifndef R1_ME_SMALL_WAVES_P1
-#define R1_ME_SMALL_WAVES_P1 4
-#endif
-#ifndef R1_ME_SMALL_WAVES_P2
-#define R1_ME_SMALL_WAVES_P2 3
-#endif
-template <int BPP, int PHASE>
-__global__ __launch_bounds__(256, PHASE == 0 ? R1_ME_SMALL_WAVES(BPP) : (PHASE == 1 ? R1_ME_SMALL_WAVES_P1 : R1_ME_SMALL_WAVES_P2))
-void k_me_blocks_small(R1MeJob job, R1MeParams p,
-                                                         const R1MeBlockCand *__restrict__ cands,
-                                                         int n, int max_w, int max_h, int use_satd,
-                                                         int filter_mode,
-                                                         R1MeResult *__restrict__ out) {
+// The whole search is one launch.  Split in two (the full-pel search, then the sub-pel refinement, the result of the
+// first travelling through `out`), it was 3-7 % SLOWER (profiles/r06_ab_notes.md, ab3).  What that showed: the
+// full-pel half needs 61 / 64 VGPRs; the 168 VGPRs + 168 / 196 B of scratch (381 MB of scratch writes per 4K launch,
+// profiles/r05_pmc_frame.json) are the sub-pel half's alone (eight inlined (size, bit depth) forms of the
+// fused-candidate column filter + SATD), and giving it 223 VGPRs (two workgroups per CU, 0 B scratch) is SLOWER than
+// three with the spills: the launch is a latency chain per block like the tile search, the scratch stores are not on it.
+// (__launch_bounds__: three workgroups of 4 waves the register allocator makes room for)
+template <int BPP>
+__global__ __launch_bounds__(256, 3) void k_me_blocks_small(R1MeJob job, R1MeParams p,
+                                                            const R1MeBlockCand *__restrict__ cands,
+                                                            int n, int max_w, int max_h, int use_satd,
+                                                            int filter_mode,
+                                                            R1MeResult *__restrict__ out) {
   constexpr int WS_MAX = (((16 + 7) * BPP + 3) >> 2) << 2;
   constexpr int GROUP_BYTES = ((23 * WS_MAX + 15) & ~15) + 16 * 16 * BPP;   // window + prediction
-  __shared__ __attribute__((aligned(16))) uint8_t sh_grp[PHASE == 1 ? 1 : 4][PHASE == 1 ? 1 : 4][PHASE == 1 ? 16 : GROUP_BYTES];
-  __shared__ int16_t sh_subsets[PHASE == 2 ? 1 : 4][kSubsetWords];
-  __shared__ __attribute__((aligned(16))) uint8_t sh_src[PHASE == 1 ? 1 : 4][PHASE == 1 ? 16 : 16 * 16 * BPP];
+  __shared__ __attribute__((aligned(16))) uint8_t sh_grp[4][4][GROUP_BYTES];
+  __shared__ int16_t sh_subsets[4][kSubsetWords];
+  __shared__ __attribute__((aligned(16))) uint8_t sh_src[4][16 * 16 * BPP];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   // an XCD takes a contiguous run of the block list (common.hpp): callers list blocks in raster order, and the search
   // windows of neighbouring blocks overlap -- dealt round-robin, every XCD's L2 fetched the whole reference
-#ifndef R1_ME_SMALL_XCD_RUNS
-#define R1_ME_SMALL_XCD_RUNS 1   // A/B switch
-#endif
-  const long long bi = (long long)(R1_ME_SMALL_XCD_RUNS ? xcd_run_item(blockIdx.x, gridDim.x) : (int)blockIdx.x) * 4 + wave;
+  const long long bi = (long long)xcd_run_item(blockIdx.x, gridDim.x) * 4 + wave;
   if (bi >= n) return;                         // wave-uniform; no barriers below
   const R1MeBlockCand cd = cands[bi];
   const int w = cd.w, h = cd.h;
@@ -1457,24 +1395,8 @@ void k_me_blocks_small(R1MeJob job, R1MeParams p,
   b.mc.allow_hp = p.allow_hp;
   for (int k = 0; k < 2; k++) { b.mc.pmv_row[k] = cd.pmv[k][0]; b.mc.pmv_col[k] = cd.pmv[k][1]; }
   Msr best;
-  if constexpr (PHASE != 2) {
-    b.init(org, ref, lane);
-    best = full_pixel_me(b, t, p, cd.bx, cd.by, rng, cd.corner, false, 0, sh_subsets[PHASE == 2 ? 0 : wave]);
-    if constexpr (PHASE == 1) {
-      if (lane == 0) {
-        R1MeResult r;
-        r.row = (int16_t)best.row;
-        r.col = (int16_t)best.col;
-        r.sad = best.sad;
-        r.cost = best.cost;
-        out[bi] = r;
-      }
-      return;
-    }
-  } else {
-    const R1MeResult r = out[bi];      // what PHASE 1 left (the launch before this one on the stream)
-    best = Msr{(int)r.row, (int)r.col, r.cost, r.sad};
-  }
+  b.init(org, ref, lane);
+  best = full_pixel_me(b, t, p, cd.bx, cd.by, rng, cd.corner, false, 0, sh_subsets[wave]);
 
   auto in_range = [&](int row, int col) {
     return col >= b.mvx_min && col <= b.mvx_max && row >= b.mvy_min && row <= b.mvy_max;
@@ -1758,14 +1680,13 @@ int me_launch_persistent(r1_ctx *ctx, int slot, const R1MeJob *jobs, int n_jobs,
   for (int x = 0; x <= 8; x++) a.xoff[x] = c.xoff[x];
   a.prog = (unsigned int *)c.prog; a.foff = (const unsigned int *)c.foff;
   a.epoch = c.epoch;
-  a.spin = getenv("R1_ME_PERSISTENT_SPIN") ? atoi(getenv("R1_ME_PERSISTENT_SPIN")) : (1 << 18);
+  a.spin = 1 << 18;
   // TWO waves per SIMD (256 CUs x 4 SIMDs x 2), not as many as fit: a searching wave wants a VALU
   // instruction every ~8 cycles at 2.6-4.4 issue cycles each, so a third and fourth wave on a SIMD
   // stretch every block step of a chain that has no slack (measured, 24 jobs: grid 4096 1.73 ms,
   // 3072 1.60, 2048 1.50, 1536 1.54; 10-bit 2.08 / 1.96 / 1.89 / 2.03, 1024: 2.11).  Rows beyond the grid are taken by
   // the waves that finish theirs, in key order.
-  const int gmax = getenv("R1_ME_PERSISTENT_GRID") ? atoi(getenv("R1_ME_PERSISTENT_GRID")) : 2048;
-  const int grid = c.n_rows < gmax ? c.n_rows : gmax;
+  const int grid = c.n_rows < 2048 ? c.n_rows : 2048;
   if (getenv("R1_ME_PERSISTENT_DEBUG")) fprintf(stderr, "k_me_persist: %d rows, grid %d, epoch %u\n", c.n_rows, grid, a.epoch);
   if (bpp == 1 && pin) hipLaunchKernelGGL((k_me_persist<1, true>), dim3(grid), dim3(64), 0, st, a);
   else if (bpp == 1) hipLaunchKernelGGL((k_me_persist<1, false>), dim3(grid), dim3(64), 0, st, a);
@@ -1937,8 +1858,7 @@ extern "C" int r1_estimate_tile_motion_batch(r1_ctx *ctx, const R1MeJob *jobs, i
   // unpinned one (3: any wave takes any row, results written through at agent scope).  Measured,
   // 8-bit 4K, ms, diagonal launches / pinned / unpinned: 1 job 4.12 / 9.9 / 2.91, 4 jobs 4.80 / 4.7 /
   // 3.96, 8 jobs 1.74 / 1.14 / 1.31, 16 jobs 2.93 / 2.08 / 2.29, 64 jobs 2.03 / 1.69 / 1.77
-  static const char *force = getenv("R1_ME_PERSISTENT");   // "0" / "1" / "3": A/B switch for tools/bench_me.py (diagonal / pinned / unpinned)
-  int mode = params->launch_mode ? params->launch_mode : (force ? (force[0] == '0' ? 1 : force[0] == '3' ? 3 : 2) : (n_jobs >= 8 ? 2 : 3));
+  int mode = params->launch_mode ? params->launch_mode : (n_jobs >= 8 ? 2 : 3);
   R1_REQUIRE(mode >= 1 && mode <= 3);
   if (mode == 2) {
     if (ctx->me_xcds < 0) { const int rc = me_probe_xcds(ctx, st); if (rc != R1_OK) return rc; }
@@ -1957,17 +1877,6 @@ extern "C" int r1_estimate_tile_motion_batch(r1_ctx *ctx, const R1MeJob *jobs, i
   // (grid z = pass); ndiag + 4 launches instead of 3 * ndiag
   const int nsteps = ndiag + 2 * kPassSkew;
   const void *fn = bpp == 1 ? (const void *)k_me_diag<1> : (const void *)k_me_diag<2>;
-  static const bool use_graph = !getenv("R1_ME_NO_GRAPH");   // A/B switch for tools/bench_me.py
-  if (!use_graph) {
-    R1_HIP_CHECK(hipMemcpyAsync(ctx->me_jobs[slot], ctx->me_jobs_host[slot], bytes, hipMemcpyHostToDevice, st));
-    for (int step = 0; step < nsteps; step++) {
-      if (bpp == 1) hipLaunchKernelGGL(k_me_diag<1>, dim3(dlen, n_jobs, 5), dim3(256), 0, st, djobs, dparams, drbufs, step);
-      else hipLaunchKernelGGL(k_me_diag<2>, dim3(dlen, n_jobs, 5), dim3(256), 0, st, djobs, dparams, drbufs, step);
-    }
-    R1_HIP_CHECK(hipGetLastError());
-    R1_HIP_CHECK(hipEventRecord(ctx->me_done[slot], st));
-    return R1_OK;
-  }
   // The sequence (upload, then one launch per diagonal step, each depending on the one before)
   // is a function of (pixel size, jobs, diagonal length, steps) and of the slot's buffers only --
   // the job contents and the parameters travel through the upload.  It is built once as an
@@ -2040,22 +1949,13 @@ extern "C" int r1_estimate_motion_batch(r1_ctx *ctx, const R1MeJob *tile, const 
   hipStream_t st = (hipStream_t)stream;
   if (max_w <= 16 && max_h <= 16) {   // one wave per block
     const unsigned grid = (unsigned)((n + 3) / 4);
-#ifndef R1_ME_SMALL_SPLIT
-#define R1_ME_SMALL_SPLIT 0   // 1 = two launches (round 6 A/B, profiles/r06_ab_notes.md ab3: 3-7 % SLOWER -- the scratch
-                              // traffic of the one-launch form is not what its waves wait for); env R1_ME_SMALL_SPLIT overrides
-#endif
-#define R1_SMALL(B, PH) hipLaunchKernelGGL((k_me_blocks_small<B, PH>), dim3(grid), dim3(256), 0, st, *tile, *params, cands, n, \
-                                           max_w, max_h, use_satd, filter_mode, out)
-    static const int split = [] {
-      const char *e = getenv("R1_ME_SMALL_SPLIT");
-      return e ? atoi(e) : R1_ME_SMALL_SPLIT;
-    }();
-    if (split) {
-      if (bpp == 1) { R1_SMALL(1, 1); R1_SMALL(1, 2); } else { R1_SMALL(2, 1); R1_SMALL(2, 2); }
+    if (bpp == 1) {
+      hipLaunchKernelGGL(k_me_blocks_small<1>, dim3(grid), dim3(256), 0, st, *tile, *params, cands, n, max_w,
+                         max_h, use_satd, filter_mode, out);
     } else {
-      if (bpp == 1) R1_SMALL(1, 0); else R1_SMALL(2, 0);
+      hipLaunchKernelGGL(k_me_blocks_small<2>, dim3(grid), dim3(256), 0, st, *tile, *params, cands, n, max_w,
+                         max_h, use_satd, filter_mode, out);
     }
-#undef R1_SMALL
     R1_HIP_CHECK(hipGetLastError());
     return R1_OK;
   }

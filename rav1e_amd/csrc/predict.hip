@@ -76,7 +76,7 @@ __global__ __launch_bounds__(64) void k_intra_edges(
     R1Plane rec, int tile_x, int tile_y, int rect_w, int rect_h, int txw, int txh, int lpc_log2,
     const R1IntraEdgeCand *__restrict__ cands, int n, void *__restrict__ edges,
     int edge_stride, uint8_t *__restrict__ lens) {
-  // lpc = lanes per candidate (power of two covering 2*(txw+txh)+1 entries, <= 64)
+  // lpc = lanes per candidate (a power of two; they walk the 2*(txw+txh)+1 entries in strides of lpc)
   const int lpc = 1 << lpc_log2, cpw = 64 >> lpc_log2;
   const int cand = blockIdx.x * cpw + (threadIdx.x >> lpc_log2);
   const int l = threadIdx.x & (lpc - 1);
@@ -195,9 +195,6 @@ __device__ __forceinline__ int32_t filt5(const uint16_t *src, int i, int size, i
 // unrolls, and with SATD_OUT the prediction column never leaves the lane's registers (it used to go
 // through LDS and back: one ds_write + one ds_read per pixel, plus the address arithmetic of loops
 // with a runtime trip count).
-#ifndef R1_PRESCREEN_LOOPED
-#define R1_PRESCREEN_LOOPED 1   // A/B switch
-#endif
 // waves per SIMD the register allocator is asked to make room for in the fixed-size pre-screen
 // instantiations: left alone it takes 79 / 113 VGPRs (16x16 / 32x32); asked, 44 / 68 without a spill
 // (tools/kres.py): launches 0.136 -> 0.133 and 0.126 -> 0.103 ms
@@ -230,7 +227,7 @@ __global__ __launch_bounds__(64, intra_waves_hint(SATD_OUT, WLT)) void k_intra_p
   // 8x8 only: at 16x16 / 32x32 the loop costs registers (131 / 157 VGPRs, 3 waves per SIMD) and the
   // launch gets 15-25 % slower than one wave per (blocks, member); at 8x8 it is 24 % faster
   // (gpurun_out/r04_f: 0.243 -> 0.185 ms for 129600 blocks x 13 modes)
-  constexpr bool LOOPED = IN_REGS && R1_PRESCREEN_LOOPED && HLT == 3;
+  constexpr bool LOOPED = IN_REGS && HLT == 3;
   constexpr bool SRC_REGS = LOOPED && HLT >= 0 && HLT <= 4;
   long long cand = (long long)blockIdx.x * NC + cl;
   bool live = cand < n;
@@ -699,21 +696,12 @@ extern "C" int r1_intra_edges_batch(r1_ctx *ctx, const R1Plane *rec, int tile_x,
   static const uint8_t hl[19] = {2, 3, 4, 5, 6, 3, 2, 4, 3, 5, 4, 6, 5, 4, 2, 5, 3, 6, 4};
   hipStream_t st = (hipStream_t)stream;
   const int txw = 1 << wl[tx_size], txh = 1 << hl[tx_size];
-  int lpc_log2 = 0;
-  while ((1 << lpc_log2) < 2 * (txw + txh) + 1 && lpc_log2 < 6) lpc_log2++;
   // EIGHT lanes per block, whatever its size: what a lane does before it touches an entry (the mode / flag
   // logic, the clipping, the block's address) is the same for every lane of a block and dominates; with 8
   // lanes a wave prepares 8 blocks and walks the 17 .. 129 entries in strides of 8.  Measured against one
   // lane per entry (gpurun_out/r04_g, 4K luma): 4x4 0.097 -> 0.037 ms, 8x8 0.048 -> 0.015, 16x16 0.0165 ->
-  // 0.0124, 32x32 0.0121 -> 0.0119.  (-DR1_EDGES_LPC_SHIFT=0 restores one lane per entry, for A/B builds.)
-  // (the A/B switch is a build-time macro like the others -- -DR1_EDGES_LPC_SHIFT=0 -- not an environment variable:
-  // the shipped library's behaviour does not depend on the process environment)
-#ifndef R1_EDGES_LPC_SHIFT
-#define R1_EDGES_LPC_SHIFT 3
-#endif
-  static_assert(R1_EDGES_LPC_SHIFT >= 0 && R1_EDGES_LPC_SHIFT <= 3, "lanes per candidate stay within 8 .. 64");
-  lpc_log2 = lpc_log2 - R1_EDGES_LPC_SHIFT < 3 ? 3 : lpc_log2 - R1_EDGES_LPC_SHIFT;
-  if (lpc_log2 > 6) lpc_log2 = 6;
+  // 0.0124, 32x32 0.0121 -> 0.0119.
+  const int lpc_log2 = 3;
   const int cpw = 64 >> lpc_log2;
   const unsigned grid = (unsigned)((n + cpw - 1) / cpw);
   if (rec->bytes_per_px == 1)
@@ -793,7 +781,7 @@ extern "C" int r1_intra_satd_batch(r1_ctx *ctx, const R1Plane *src, int tx_size,
   // the pre-screen's sizes (luma transform blocks 8x8 .. 32x32) with the block size as a constant; at 8x8 a
   // wave walks the members of its blocks' groups itself
   const int sq = wl[tx_size] == hl[tx_size] ? wl[tx_size] : 0;
-  if (R1_PRESCREEN_LOOPED && sq == 3) grid /= (unsigned)group;
+  if (sq == 3) grid /= (unsigned)group;
   hipStream_t st = (hipStream_t)stream;
 #define R1_SATD_LAUNCH(B, ...)                                                                            \
   hipLaunchKernelGGL((k_intra_predict<B, true, ##__VA_ARGS__>), dim3(grid), dim3(64), lds, st,            \

@@ -57,10 +57,6 @@ __device__ unsigned long long g_phase[4096][8];
 #define R1_PROF_INIT do {} while (0)
 #endif
 
-// which instantiations stage the source block in LDS (see k_rdo_cand); overridable for A/B builds
-#ifndef R1_SRC_LDS_POLICY
-#define R1_SRC_LDS_POLICY(BPP, P) ((BPP) == 1 || (P) <= 32)
-#endif
 // (Round 3 tried a software pipeline over two candidate groups per wave -- next group's loads in
 // flight under this group's arithmetic.  Measured, profiles/r03_ab_notes.md ab3: -2.3 % on the 8-bit
 // 8x8 launch, a LOSS everywhere else (the launches are VALU-issue bound; the registers of the loads
@@ -78,39 +74,6 @@ __device__ unsigned long long g_phase[4096][8];
 #define R1_RDO_SLICE_TU
 #else
 #define R1_RDO_DISPATCH_TU
-#endif
-
-// which instantiations run their dead candidate slots unmasked (see k_rdo_cand)
-#ifndef R1_TB16_POLICY
-#define R1_TB16_POLICY(BD, WL, HL) ((BD) == 10 && (WL) == 5 && (HL) == 5)
-#endif
-#ifndef R1_TX_TILE_I16
-#define R1_TX_TILE_I16 1
-#endif
-// the coefficient blocks leave with non-temporal stores (see the store loops of k_rdo_cand)
-#ifndef R1_NT_STORE
-#define R1_NT_STORE 1
-#endif
-#ifndef R1_XCD_REMAP
-#define R1_XCD_REMAP 1   // A/B switch (see k_rdo_cand)
-#endif
-#ifndef R1_SRC_KEEP
-#define R1_SRC_KEEP 1   // A/B switch (see k_rdo_cand)
-#endif
-#ifndef R1_SRC_PAD
-#define R1_SRC_PAD 1   // A/B switch: the padded source-block stride in LDS (see k_rdo_cand)
-#endif
-// which instantiations keep the source chunks in registers across the filter and stage them over the
-// dead window afterwards (see k_rdo_cand)
-#ifndef R1_SRC_LATE_POLICY
-#define R1_SRC_LATE_POLICY(BD, P, QM) ((BD) != 8 && ((P) == 32 || ((P) == 16 && (QM) == 0)))
-#endif
-#ifndef R1_UNMASK_POLICY
-#define R1_UNMASK_POLICY(BD, WL, HL) (!((BD) == 8 && (WL) == 6 && (HL) == 6))
-#endif
-// which instantiations send the coefficients through LDS for 16-byte stores
-#ifndef R1_WIDE_STORE_POLICY
-#define R1_WIDE_STORE_POLICY(P) ((P) <= 16)
 #endif
 
 namespace {
@@ -164,37 +127,14 @@ using r1tx::T;
 constexpr int rdo_waves_hint(int bd, int wl, int hl, int qm, bool mt = false) {
   // the type-search instantiations (see the MT loop of k_rdo_cand): their own steps
   if (mt) {
-#ifdef R1_HINT_MT
-    if (R1_HINT_MT_COND) return R1_HINT_MT;
-#endif
     // what the straight-line kernels are asked for leaves the loop with 50-350 B of scratch per lane, and at
     // thousands of waves in flight that is traffic to the Infinity Cache: same-box A/B (r05_ab_notes.md, ab1)
     // 16x16 fan-out 0.754 -> 0.610 ms (8-bit), 0.855 -> 0.602 (10-bit), 10-bit 8x8 0.655 -> 0.553 at the steps below
-#ifndef R1_MT_H8
-#define R1_MT_H8 (qm == 2 ? (bd == 8 ? 7 : 6) : 1)
-#endif
-#ifndef R1_MT_H16
-#define R1_MT_H16 (qm == 2 ? 4 : 1)
-#endif
-    if (wl <= 3 && hl <= 3) return R1_MT_H8;
-    return R1_MT_H16;
+    if (wl <= 3 && hl <= 3) return qm == 2 ? (bd == 8 ? 7 : 6) : 1;
+    return qm == 2 ? 4 : 1;
   }
-#ifdef R1_HINT_8X8
-  if (wl == 3 && hl == 3 && qm == 0) return R1_HINT_8X8;   // A/B: the pipelined 8x8 kernel sits at 69 (8-bit)
-#endif
-#ifdef R1_HINT_16X16
-  if (wl == 4 && hl == 4 && qm == 0) return R1_HINT_16X16;
-#endif
-#ifdef R1_HINT_64_HBD
-  if (wl == 6 && hl == 6 && qm == 0 && bd != 8) return R1_HINT_64_HBD;   // A/B: 10-bit 64x64 sits at 165 (3 waves); 4 = 152 B of spills, launch 0.281 -> 0.365 ms
-#endif
+  // (10-bit 64x64 sits at 165 VGPRs, 3 waves; asked for 4: 152 B of spills, launch 0.281 -> 0.365 ms)
   if (wl == 5 && hl == 5 && qm == 0 && bd != 8) return 6;   // 89 -> 80 VGPRs, no spill: 5 -> 6 waves, launch -1.7 % (ab7)
-#ifdef R1_HINT_X   /* A/B: -DR1_HINT_X=5 '-DR1_HINT_X_COND=(bd==8&&wl==6&&hl==6&&qm==0)' */
-  if (R1_HINT_X_COND) return R1_HINT_X;
-#endif
-#ifdef R1_HINT_Y
-  if (R1_HINT_Y_COND) return R1_HINT_Y;
-#endif
   // the pixel-domain chain sat a few registers above an allocation step at three sizes; asked for the
   // step, the allocator gets there without a spill worth mentioning (same-box, r04_ab_notes.md ab8:
   // 8-bit 290.3 -> 295.0 k, 10-bit 274.2 -> 283.5 k)
@@ -229,10 +169,7 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
   // waves -- and is off.  Row stride 66 int16 = 33 dwords: a candidate's row lanes read 32 banks.
   // The type search's shared tile (COLSHARE, below) is int16 at every bit depth: with both sides <= 16 the column
   // pass's output after shift[1] is bounded by 8193 / 16433 / 16445 at 8 / 10 / 12 bits (tests/test_tx_range.py).
-#ifndef R1_MT_COLSHARE
-#define R1_MT_COLSHARE 1
-#endif
-  constexpr bool TB16 = R1_TX_TILE_I16 && (R1_TB16_POLICY(BD, WL, HL) || (R1_MT_COLSHARE && MT && W <= 16 && H <= 16));
+  constexpr bool TB16 = (BD == 10 && WL == 5 && HL == 5) || (MT && W <= 16 && H <= 16);
   typedef typename std::conditional<TB16, int16_t, T>::type TB;
   constexpr int LSTRIDE = NC * W + (TB16 ? 2 : 1);
   constexpr int ISTRIDE = NC * W + 1;       // the inverse transform's row buffer (QM == 2): int32
@@ -247,49 +184,43 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
   // The quantizer's coded-area tile, one per candidate, P dwords of padding between candidates: at the bare
   // stride (64 / 128 / 256 dwords for 8x8 .. 16x16) the NC candidates of a lane group wrote, gathered and read
   // back the same banks (SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE 0.36 / 0.26 of the pixel chain's 8x8 / 16x16
-  // launches, profiles/r04_v5_pmc_pixel_summary.json); the forward kernel's TPAD, carried over (R1_QT_PAD: A/B)
-#ifndef R1_QT_PAD
-#define R1_QT_PAD 1
-#endif
+  // launches, profiles/r04_v5_pmc_pixel_summary.json); the forward kernel's TPAD, carried over
   // (two candidates per wave sit in different 32-lane groups and never meet in a bank: no padding there --
   // with it the 10-bit 32x32 launch was 2.8 % slower, r05_ab_notes.md ab2)
-  constexpr int QT_PAD = (R1_QT_PAD && NC > 2) ? P : 0;
+  constexpr int QT_PAD = NC > 2 ? P : 0;
   constexpr int QT_STRIDE = (W < 32 ? W : 32) * (H < 32 ? H : 32) + QT_PAD;
   constexpr int QT_BYTES = QM != 0 ? NC * QT_STRIDE * 4 : 0;
   // QM == 2 (pixel-domain leg): only the coded area (32 x 32 of a 64-point side) is quantized, and there is no
   // `tail` energy to sum (encoder.rs:1617-1640 computes it only when rdo_type.needs_tx_dist()), so vertical
   // frequencies >= 32 are never read: the column pass does not store them -- the compiler then prunes the
   // fdct64 network down to the outputs that are (its upper-half outputs are dead) -- and the row pass runs
-  // on rows 0 .. 31 only; horizontal frequencies >= 32 die the same way inside the row lanes (R1_PRUNE64: A/B)
-#ifndef R1_PRUNE64
-#define R1_PRUNE64 1
-#endif
-  constexpr int HU = (R1_PRUNE64 && QM == 2 && H > 32) ? 32 : H;   // vertical frequencies that are used
+  // on rows 0 .. 31 only; horizontal frequencies >= 32 die the same way inside the row lanes
+  constexpr int HU = (QM == 2 && H > 32) ? 32 : H;   // vertical frequencies that are used
   constexpr int REC_BYTES = QM == 2 ? NC * W * H * BPP : 0;
   // The source block is staged in LDS next to the window (16-byte row chunks: H*W*BPP/1024
   // load instructions per wave instead of H one-pixel-per-lane loads) and read back column by
   // column AFTER the motion compensation: the H source registers are not live across the
   // filter any more.  Not for 64-wide 16-bit blocks: + 8 KB of LDS would cost a wave per SIMD.
-  constexpr bool SRC_LDS = R1_SRC_LDS_POLICY(BPP, P);
+  constexpr bool SRC_LDS = BPP == 1 || P <= 32;
   // SRC_LATE: the source chunks wait in registers (SPASS x 4 VGPRs) while the window is filtered and
   // go to LDS afterwards, OVER the dead window -- window + source side by side (10336 B at 10-bit
   // 32x32) held the CU at 15 waves (4 per SIMD after rounding); with the source over the window the
   // footprint is the window's 6240 B and the ~93 VGPRs allow 5.
   // 16-bit 16x16, headline only (the pixel chain keeps its source block in LDS for the distortion,
   // SRC_KEEP below): 6592 -> 4416 B, 6 -> 8 waves, launch 0.2255 -> 0.217 ms (r04_ab_notes.md, ab7)
-  constexpr bool SRC_LATE = SRC_LDS && R1_SRC_LATE_POLICY(BD, P, QM);
+  constexpr bool SRC_LATE = SRC_LDS && BD != 8 && (P == 32 || (P == 16 && QM == 0));
   constexpr int SRC_ROW = W * BPP;
   constexpr int WIN_PAD = (WIN_BYTES + 15) & ~15;
   // A candidate's source block starts max(16, row bytes) past a multiple of its own size: with the bare
   // stride (16 / 32 / 64 / 128 dwords) the column reads of the NC candidates of a lane group hit the SAME
   // banks with different addresses -- 2-way at 8-bit 8x8 and at 16x16, 4-way at 10-bit 8x8: this, not the
   // window staging, was the SQ_LDS_BANK_CONFLICT of those launches (0.18 / 0.30 of the LDS cycles)
-  constexpr int SRC_CSTRIDE = H * SRC_ROW + (NC > 1 && R1_SRC_PAD ? (SRC_ROW > 16 ? SRC_ROW : 16) : 0);
+  constexpr int SRC_CSTRIDE = H * SRC_ROW + (NC > 1 ? (SRC_ROW > 16 ? SRC_ROW : 16) : 0);
   constexpr int SRC_BYTES = SRC_LDS ? NC * SRC_CSTRIDE : 0;
   // SRC_KEEP (pixel-domain chain, blocks up to 16 rows): the staged source block sits BEHIND the work area
   // that the later phases alias (transpose tile, quantizer tile, row buffer), so the distortion at the end of
   // the chain reads its source column from LDS again instead of issuing H more global loads per lane
-  constexpr bool SRC_KEEP = R1_SRC_KEEP && QM == 2 && H <= 16 && SRC_LDS && !SRC_LATE;
+  constexpr bool SRC_KEEP = QM == 2 && H <= 16 && SRC_LDS && !SRC_LATE;
   constexpr int WS_BYTES = SRC_KEEP ? WIN_PAD
                                     : (SRC_LATE ? (WIN_PAD > SRC_BYTES ? WIN_PAD : SRC_BYTES) : WIN_PAD + SRC_BYTES);
   constexpr int LDS_A0 = WS_BYTES > TXB_BYTES ? WS_BYTES : TXB_BYTES;
@@ -300,7 +231,7 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
   // MT, COLSHARE: the transposed output of the column pass in a tile of its own behind everything else -- the later
   // phases of a type alias the work area, and the types that share a column kernel (the seven RAV1E types use three:
   // DCT x3, ADST x2, identity x2) all read their rows from this one tile (see the type loop)
-  constexpr bool COLSHARE = R1_MT_COLSHARE && MT && !SPLIT_T;
+  constexpr bool COLSHARE = MT && !SPLIT_T;
   constexpr int TKEEP_OFF = (LDS_WORK + (SRC_KEEP ? SRC_BYTES : 0) + 15) & ~15;
   constexpr int LDS_BYTES = COLSHARE ? TKEEP_OFF + H * LSTRIDE * (int)sizeof(TB) : LDS_WORK + (SRC_KEEP ? SRC_BYTES : 0);
   __shared__ __attribute__((aligned(16))) uint8_t smem[LDS_BYTES];
@@ -316,12 +247,8 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
   // fetch the window rows again.  So XCD x takes the x-th contiguous eighth of the list: workgroup i works on
   // group (i % 8) * (grid / 8) + i / 8 (the host rounds the grid up to a multiple of 8; groups past the
   // list end return).  Same-box A/B: profiles/r04_ab_notes.md, ab5.
-#if R1_XCD_REMAP
   const unsigned wg = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
   if ((long long)wg * NC >= (long long)n) return;
-#else
-  const unsigned wg = blockIdx.x;
-#endif
   const int lane = threadIdx.x;
   const int cl = lane / P, c = lane % P;
   // n < 2^31 candidates: the liveness test and the lane-local parts of every address are 32-bit;
@@ -336,7 +263,7 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
   // Measured (profiles/r03_ab_notes.md, ab4): -3 % at 8x8, -1 % at 16x16 / 32x32, +2 % on the 10-bit
   // step; the 8-bit 64x64 instantiation alone loses (121 -> 143 VGPRs, 4 -> 3 waves per SIMD) and
   // keeps its masked regions.
-  constexpr bool UNMASK = R1_UNMASK_POLICY(BD, WL, HL);
+  constexpr bool UNMASK = !(BD == 8 && WL == 6 && HL == 6);
   const bool live_st = cand_i < n;
   const bool live = UNMASK || live_st;
   const int cl_ld = live_st ? cl : n - 1 - (int)wg * NC;     // >= 0: the wave's first candidate exists
@@ -532,10 +459,7 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
   }
   // TAIL_DEFER (type search of an 8x8 block under cdef_dist: one 8x8 kernel per candidate, eight lanes per
   // candidate, at most seven types): see the end of the kernel
-#ifndef R1_MT_TAIL_DEFER
-#define R1_MT_TAIL_DEFER 1
-#endif
-  constexpr bool TAIL_DEFER = R1_MT_TAIL_DEFER && MT && QM == 2 && W == 8 && H == 8;
+  constexpr bool TAIL_DEFER = MT && QM == 2 && W == 8 && H == 8;
   // (a mask of more than eight types -- the full AV1 inter set has sixteen -- keeps its tails inside the loop)
   const bool tail_defer = TAIL_DEFER && qa.dist_kind == R1_DIST_CDEF && qa.nt <= 8;   // wave-uniform
   uint32_t tail_keep[5] = {0, 0, 0, 0, 0};
@@ -654,7 +578,7 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
   if constexpr (MT) {
     // the type search keeps its coefficients on the CU
   } else
-  if constexpr (!R1_WIDE_STORE_POLICY(P)) {
+  if constexpr (P > 16) {
     // large blocks: direct element stores (measured: the LDS detour costs more than the
     // 16-byte stores save at 32x32 and 64x64, profiles/r02_wide_store_ab.log)
     if (coeffs && row_live && live_st) {
@@ -662,13 +586,7 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
 #pragma unroll
       for (int cg = 0; cg < W; cg += 32)
 #pragma unroll
-        for (int k = 0; k < WC; k++) {
-#if R1_NT_STORE
-          __builtin_nontemporal_store((CT)u[k + cg], &dst[H * cg + k * OS]);
-#else
-          dst[H * cg + k * OS] = (CT)u[k + cg];
-#endif
-        }
+        for (int k = 0; k < WC; k++) __builtin_nontemporal_store((CT)u[k + cg], &dst[H * cg + k * OS]);
     }
   } else
   if (coeffs) {   // wave-uniform: kernel argument
@@ -714,7 +632,6 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
         uint8_t *dst = gdst + p * CBY + r * CH;
 #pragma unroll
         for (int j = 0; j < NCH; j++) {
-#if R1_NT_STORE
           // The coefficients are not read again by this launch, and a step writes 0.26 GB (8-bit) / 0.53 GB
           // (10-bit) of them per ladder size: written through the L2 as ordinary stores they evict the window
           // rows the K candidates of a block share.  Non-temporal stores (same-box A/B, gpurun_out/r04_ab3):
@@ -729,11 +646,6 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
           } else {
             __builtin_nontemporal_store(*(const uint32_t *)(src + j * P * CH), (uint32_t *)(dst + j * P * CH));
           }
-#else
-          if constexpr (CH == 16) *(uint4 *)(dst + j * P * CH) = *(const uint4 *)(src + j * P * CH);
-          else if constexpr (CH == 8) *(uint2 *)(dst + j * P * CH) = *(const uint2 *)(src + j * P * CH);
-          else *(uint32_t *)(dst + j * P * CH) = *(const uint32_t *)(src + j * P * CH);
-#endif
         }
       }
     }
@@ -813,9 +725,7 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
           }
 #pragma unroll
           for (int k = WC; k < W; k++) w_[k] = 0;
-#ifndef R1_STUB_INVR
           r1itx::inv_1d<W, true>(w_, r1tx::htx_1d(tt), lo, hi);
-#endif
         }
       }
       __syncthreads();   // every coefficient has been read: the tile becomes the row buffer
@@ -837,9 +747,7 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
         }
 #pragma unroll
         for (int rr = HC; rr < H; rr++) rc[rr] = 0;
-#ifndef R1_STUB_INVC
         r1itx::inv_1d<H, true>(rc, r1tx::vtx_1d(tx_type), lo, hi);
-#endif
 #pragma unroll
         for (int rr = 0; rr < H; rr++) {
           const T pr = BPP == 1 ? (T)((ppk[rr >> 2] >> (8 * (rr & 3))) & 0xFF)
@@ -860,9 +768,6 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
         }
       }
       unsigned long long acc = 0;
-#ifdef R1_STUB_DIST   /* timing experiments only (tools/gpu_r4_h.sh): results are wrong */
-      acc = (unsigned long long)(uint32_t)rc[0] + (uint32_t)rc[H - 1];
-#else
       constexpr bool COL_DIST = H <= 16;
       if constexpr (COL_DIST) {
         // ---- H (blocks up to 32 rows): sse_wxh / cdef_dist_wxh with lane = column.  The
@@ -977,7 +882,6 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
                                                  qa.xdec, qa.ydec, BD);
       }
       }
-#endif
       if (!(TAIL_DEFER && tail_defer)) {   // wave-uniform
 #pragma unroll
         for (int m = 1; m < P; m <<= 1) {
@@ -1071,11 +975,7 @@ int launch(const R1Plane &org, const R1Plane &ref, const R1RdoCand *cands, int n
   constexpr int W = 1 << WL, H = 1 << HL, P = W > H ? W : H, NC = 64 / P;
   typedef typename std::conditional<BD == 8, int16_t, int32_t>::type CT;
   const unsigned groups = (unsigned)((n + NC - 1) / NC);
-#if R1_XCD_REMAP
   const unsigned grid = (groups + 7u) & ~7u;     // whole rounds over the 8 XCDs (see the kernel's `wg`)
-#else
-  const unsigned grid = groups;
-#endif
   hipLaunchKernelGGL((k_rdo_cand<BD, WL, HL, CT, QM, MT>), dim3(grid), dim3(64), 0, st,
                      org, ref, cands, n, sad, satd, (CT *)coeffs, pred, qa ? *qa : RdoQuantArgs{});
   R1_HIP_CHECK(hipGetLastError());
@@ -1087,16 +987,12 @@ template <int BD, int QM, bool MT>
 int slice(int tx_size, const R1Plane &org, const R1Plane &ref, const R1RdoCand *cands, int n,
           uint32_t *sad, uint32_t *satd, void *coeffs, void *pred, const RdoQuantArgs *qa,
           hipStream_t st) {
-  // R1_RDO_TU_TSMASK: the transform sizes this unit instantiates (the Makefile cuts the slow QM = 2
-  // slices into parts by size)
-#ifndef R1_RDO_TU_TSMASK
-#define R1_RDO_TU_TSMASK 0x7ffff
-#endif
-  // the type-search slices: sizes up to 16 x 16 (ids 0-2, 5-8, 13, 14).  A 64-point side has TX_SET_DCTONLY
-  // (get_tx_set, src/context/transform_unit.rs:123-131) and a 32-point side DCT_DCT (+ IDTX for inter blocks):
-  // one or two types, which the plain kernel evaluates at twice the occupancy (same-box A/B,
-  // profiles/r05_ab_notes.md: the 32x32 fan-out kernel held 2 waves per SIMD and LOST 13-22 % against two launches)
-  constexpr unsigned TSM = MT ? ((R1_RDO_TU_TSMASK) & 0x61E7u) : (unsigned)(R1_RDO_TU_TSMASK);
+  // the transform sizes this slice instantiates: all 19, except in the type-search slices: sizes up to 16 x 16
+  // (ids 0-2, 5-8, 13, 14).  A 64-point side has TX_SET_DCTONLY (get_tx_set, src/context/transform_unit.rs:123-131)
+  // and a 32-point side DCT_DCT (+ IDTX for inter blocks): one or two types, which the plain kernel evaluates at twice
+  // the occupancy (same-box A/B, profiles/r05_ab_notes.md: the 32x32 fan-out kernel held 2 waves per SIMD and LOST
+  // 13-22 % against two launches)
+  constexpr unsigned TSM = MT ? 0x61E7u : 0x7ffffu;
 #define R1_RC_CASE(ID, WL, HL)                                                                   \
   case ID:                                                                                       \
     if constexpr ((TSM >> ID) & 1)                                                               \

@@ -3,7 +3,7 @@
 on a 4K luma frame: one JSON line per job configuration (tiles x reference frames), plus
 the CPU oracle (one thread, one tile x one reference) for scale.
 
-    python tools/bench_me.py [--width 3840 --height 2160 --bit-depth 8 --reps 5 --cpu]
+    python tools/bench_me.py [--width 3840 --height 2160 --bit-depth 8 --reps 5 --cpu] [--launch-mode 0..3]
 """
 import argparse
 import json
@@ -38,6 +38,9 @@ def main():
     ap.add_argument("--cpu", action="store_true", help="also time the CPU oracle (tens of seconds)")
     ap.add_argument("--only", type=int, default=-1, help="run only tile-ME configuration i (for profiling)")
     ap.add_argument("--tile-only", action="store_true", help="stop after the tile-ME configurations")
+    ap.add_argument("--launch-mode", type=int, default=0, choices=(0, 1, 2, 3),
+                    help="R1MeParams.launch_mode of the tile ME: 0 = automatic, 1 = diagonal launches, "
+                         "2 = persistent pinned, 3 = persistent unpinned")
     args = ap.parse_args()
     import torch
     import oracle_lib as O
@@ -58,13 +61,12 @@ def main():
     ctx = Context(0)
     rows, cols = h // 4, w // 4
 
-    def launch_label(n_jobs):
+    def launch_label(n_jobs, mode):
         # r1_estimate_tile_motion_batch, launch_mode 0: one persistent launch, pinned from 8 jobs on
-        force = os.environ.get("R1_ME_PERSISTENT")
-        if force in (None, "1", "3"):
-            pinned = force == "1" or (force is None and n_jobs >= 8)
-            return "one persistent launch (k_me_persist), jobs %s" % ("pinned to an XCD each" if pinned else "not pinned")
-        return "per-call launches (R1_ME_NO_GRAPH)" if os.environ.get("R1_ME_NO_GRAPH") else "hipGraph replay of the diagonal launches"
+        if mode == 1:
+            return "hipGraph replay of the diagonal launches"
+        pinned = mode == 2 or (mode == 0 and n_jobs >= 8)
+        return "one persistent launch (k_me_persist), jobs %s" % ("pinned to an XCD each" if pinned else "not pinned")
 
     def tiles_of(nx, ny):
         tw = -(-(w // nx) // 64) * 64
@@ -81,7 +83,7 @@ def main():
         def run():
             for s in stats:
                 s.zero_()
-            ctx.estimate_tile_motion(jobs, cols, rows, bd, lam)
+            ctx.estimate_tile_motion(jobs, cols, rows, bd, lam, launch_mode=args.launch_mode)
         run()
         torch.cuda.synchronize()
         W.sustain_clocks(run, args.sustain_ms)
@@ -92,7 +94,7 @@ def main():
         ms = (time.perf_counter() - t0) / args.reps * 1e3
         row = {"kernel": "estimate_tile_motion", "frame": "%dx%d" % (w, h), "bit_depth": bd,
                "tiles": len(tl), "refs": nref, "jobs": len(jobs), "ms": round(ms, 3),
-               "launch": launch_label(len(jobs)),
+               "launch": launch_label(len(jobs), args.launch_mode),
                "Mpixels_s": round(w * h * nref / ms / 1e3, 1),
                "frames_refs_per_s": round(nref / ms * 1e3, 1)}
         # the dependent chain of the largest tile: a block needs its left and its upper neighbour of the same pass

@@ -7,12 +7,13 @@ stream provider only); descriptors are packed as the C structs of
 include/rav1e_amd.h.
 """
 import ctypes as C
+from operator import itemgetter
 
 import numpy as np
 import torch
 
 from . import _lib
-from .types import TX_DIMS, valid_av1_transform
+from .types import TX_DIMS, TxSize, valid_av1_transform
 
 DIST_CAND = np.dtype([("ox", "<i2"), ("oy", "<i2"), ("rx", "<i2"), ("ry", "<i2")])
 MC_CAND = np.dtype([("rx", "<i2"), ("ry", "<i2"), ("col_frac", "u1"), ("row_frac", "u1"),
@@ -54,8 +55,7 @@ class Plane:
         self.yorigin = ypad
         self.stride = (self.xorigin + width + xpad + al - 1) // al * al
         self.alloc_height = self.yorigin + height + ypad
-        dt = torch.uint8 if self.bpp == 1 else torch.int16  # raw 16-bit storage
-        self.data = torch.zeros((self.alloc_height, self.stride), dtype=dt, device=device)
+        self.data = torch.zeros((self.alloc_height, self.stride), dtype=_pix_dtype(self.bpp), device=device)
 
     @classmethod
     def from_numpy(cls, arr, width, height, bit_depth, xpad, ypad, device="cuda"):
@@ -98,12 +98,71 @@ def _stream_ptr():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def _dev_cands(cands, dtype):
-    """numpy structured array (or device uint8 tensor) -> device byte tensor"""
+def _dev_cands(cands, dtype, n=None):
+    """numpy structured array (or device uint8 tensor) -> (device byte tensor, n); n defaults to every
+    record of the list"""
     if isinstance(cands, torch.Tensor):
-        return cands
-    a = np.ascontiguousarray(cands, dtype=dtype)
-    return torch.from_numpy(a.view(np.uint8).reshape(-1)).cuda()
+        dc = cands
+    else:
+        a = np.ascontiguousarray(cands, dtype=dtype)
+        dc = torch.from_numpy(a.view(np.uint8).reshape(-1)).cuda()
+    return dc, dc.numel() // dtype.itemsize if n is None else n
+
+
+def _scales_arg(scales):
+    """an optional DistortionScale grid -> (pointer, row stride in elements) of the C calls"""
+    return (None, 0) if scales is None else (scales.data_ptr(), scales.stride(0))
+
+
+def _pix_dtype(bpp):
+    """torch dtype of a pixel of `bpp` bytes (16-bit pixels are stored raw as int16)"""
+    return torch.uint8 if bpp == 1 else torch.int16
+
+
+def _coeff_dtype(bpp):
+    """torch dtype of a transform coefficient of a plane of `bpp` bytes per pixel"""
+    return torch.int16 if bpp == 1 else torch.int32
+
+
+def _out_spec(*outs):
+    """(key, shape letters, dtype) per output -> (key, shape getter, dtype); the getter maps a call's sizes to an
+    int (one letter: torch.empty's fastest form) or a tuple"""
+    return tuple((k, itemgetter(*shape), dtype) for k, shape, dtype in outs)
+
+
+# The outputs of the fused-candidate wrappers in the order they are allocated.  Shape letters: n candidates, t the
+# slots of the transform types (rdo_txsearch_batch), a the coded area min(w, 32) * min(h, 32), x = w * h, h and w the
+# block; a dtype given as a function takes the plane's bytes per pixel.
+_CAND_OUTS = _out_spec(("sad", "n", torch.int32), ("satd", "n", torch.int32), ("coeffs", "nx", _coeff_dtype),
+                       ("pred", "nhw", _pix_dtype))
+_FULL_CAND_OUTS = _out_spec(("eob", "n", torch.int16), ("tx_dist", "n", torch.int64), ("sad", "n", torch.int32),
+                            ("satd", "n", torch.int32), ("est_rate", "n", torch.int64),
+                            ("qcoeffs", "na", _coeff_dtype), ("coeffs", "nx", _coeff_dtype))
+_PIXEL_CAND_OUTS = _out_spec(("eob", "n", torch.int16), ("dist", "n", torch.int64), ("sad", "n", torch.int32),
+                             ("satd", "n", torch.int32), ("qcoeffs", "na", _coeff_dtype), ("rec", "nhw", _pix_dtype))
+_TXSEARCH_OUTS = _out_spec(("eob", "nt", torch.int16), ("dist", "nt", torch.int64), ("sad", "n", torch.int32),
+                           ("satd", "n", torch.int32), ("est_rate", "nt", torch.int64),
+                           ("qcoeffs", "nta", _coeff_dtype), ("rec", "nthw", _pix_dtype))
+
+
+_CUDA = torch.device("cuda")   # the current device, like "cuda", without parsing the string per allocation
+
+
+def _bind_outs(outs, spec, wants, bpp, n, w, h, nt=1):
+    """outs (a new dict if None) with every output of `spec` allocated that is wanted (wants[i] for spec[i]) and
+    not in it yet"""
+    o = outs if outs is not None else {}
+    size = None
+    for (k, shape, dtype), want in zip(spec, wants):
+        if want and k not in o:
+            size = size or {"n": n, "t": nt, "a": min(w, 32) * min(h, 32), "x": w * h, "h": h, "w": w}
+            o[k] = torch.empty(shape(size), dtype=dtype(bpp) if callable(dtype) else dtype, device=_CUDA)
+    return o
+
+
+def _ptrs(o, *keys):
+    """data pointers of o[k] for the keys, None where o has no such key"""
+    return [o[k].data_ptr() if k in o else None for k in keys]
 
 
 class Context:
@@ -131,8 +190,7 @@ class Context:
     # ---- dist:: ----
     def dist_batch(self, kind, org, ref, w, h, cands, n=None, out=None):
         """get_sad / get_satd (src/dist.rs:31,156) over a candidate list."""
-        dc = _dev_cands(cands, DIST_CAND)
-        n = dc.numel() // DIST_CAND.itemsize if n is None else n
+        dc, n = _dev_cands(cands, DIST_CAND, n)
         if out is None:
             out = torch.empty(n, dtype=torch.int32, device="cuda")
         po, pr = org.cstruct(), ref.cstruct()
@@ -146,16 +204,13 @@ class Context:
         """sse_wxh (kind 2) / cdef_dist_wxh (kind 3) of src/rdo.rs:142-224 over a
         candidate list; scales: (rows, stride) int32 device tensor of Q14
         DistortionScale per 8x8 luma importance block, or None."""
-        dc = _dev_cands(cands, DIST_CAND)
-        n = dc.numel() // DIST_CAND.itemsize if n is None else n
+        dc, n = _dev_cands(cands, DIST_CAND, n)
         if out is None:
             out = torch.empty(n, dtype=torch.int64, device="cuda")
         po, pr = org.cstruct(), ref.cstruct()
         self._check(self.lib.r1_dist_scaled_batch(
-            self.h, int(kind), C.byref(po), C.byref(pr), w, h, dc.data_ptr(), n,
-            scales.data_ptr() if scales is not None else None,
-            scales.stride(0) if scales is not None else 0, xdec, ydec, out.data_ptr(),
-            _stream_ptr()), "r1_dist_scaled_batch")
+            self.h, int(kind), C.byref(po), C.byref(pr), w, h, dc.data_ptr(), n, *_scales_arg(scales), xdec,
+            ydec, out.data_ptr(), _stream_ptr()), "r1_dist_scaled_batch")
         return out
 
     # ---- transform::forward ----
@@ -252,10 +307,8 @@ class Context:
     def intra_edges_batch(self, rec, tile, tx_size, cands, n=None):
         """get_intra_edges (src/partition.rs:639-898) for n transform blocks of
         one tile.  tile = (x, y, w, h) in plane pixels.  -> (edges (n, 257), lens (n, 2))"""
-        dc = _dev_cands(cands, INTRA_EDGE_CAND)
-        n = dc.numel() // INTRA_EDGE_CAND.itemsize if n is None else n
-        edges = torch.empty((n, EDGE_LEN), dtype=torch.uint8 if rec.bpp == 1 else torch.int16,
-                            device="cuda")
+        dc, n = _dev_cands(cands, INTRA_EDGE_CAND, n)
+        edges = torch.empty((n, EDGE_LEN), dtype=_pix_dtype(rec.bpp), device="cuda")
         lens = torch.empty((n, 2), dtype=torch.uint8, device="cuda")
         pr = rec.cstruct()
         self._check(self.lib.r1_intra_edges_batch(self.h, C.byref(pr), tile[0], tile[1], tile[2],
@@ -267,10 +320,9 @@ class Context:
     def predict_intra_batch(self, tx_size, cands, edges, lens, bit_depth, ac=None, n=None):
         """dispatch_predict_intra (src/predict.rs:705-784) for n blocks -> (n, h, w) pixels."""
         w, h = TX_DIMS[int(tx_size)]
-        dc = _dev_cands(cands, INTRA_CAND)
-        n = dc.numel() // INTRA_CAND.itemsize if n is None else n
+        dc, n = _dev_cands(cands, INTRA_CAND, n)
         bpp = 1 if bit_depth == 8 else 2
-        out = torch.empty((n, h, w), dtype=torch.uint8 if bpp == 1 else torch.int16, device="cuda")
+        out = torch.empty((n, h, w), dtype=_pix_dtype(bpp), device="cuda")
         self._check(self.lib.r1_predict_intra_batch(
             self.h, int(tx_size), dc.data_ptr(), n, edges.data_ptr(), edges.stride(0),
             lens.data_ptr(), ac.data_ptr() if ac is not None else None, bit_depth, bpp,
@@ -280,8 +332,7 @@ class Context:
     def intra_satd_batch(self, src, tx_size, cands, group, pos_xy, edges, lens, ac=None, n=None):
         """the intra mode pre-screen (src/rdo.rs:1434-1506): predict `group` modes per block from
         one edge set, get_satd against the source block at pos_xy -> (n,) int32"""
-        dc = _dev_cands(cands, INTRA_CAND)
-        n = dc.numel() // INTRA_CAND.itemsize if n is None else n
+        dc, n = _dev_cands(cands, INTRA_CAND, n)
         out = torch.empty(n, dtype=torch.int32, device="cuda")
         ps = src.cstruct()
         self._check(self.lib.r1_intra_satd_batch(
@@ -319,8 +370,7 @@ class Context:
 
     def cfl_alpha_search_batch(self, src, tx_size, cands, edges, lens, ac, n=None):
         """rdo_cfl_alpha (src/rdo.rs:1593-1688) for one chroma plane -> (alpha int16, sse int64)"""
-        dc = _dev_cands(cands, CFL_ALPHA_CAND)
-        n = dc.numel() // CFL_ALPHA_CAND.itemsize if n is None else n
+        dc, n = _dev_cands(cands, CFL_ALPHA_CAND, n)
         alpha = torch.empty(n, dtype=torch.int16, device="cuda")
         cost = torch.empty(n, dtype=torch.int64, device="cuda")
         ps = src.cstruct()
@@ -332,8 +382,7 @@ class Context:
 
     def cfl_ac_batch(self, luma, bw, bh, xdec, ydec, cands, n=None):
         """pred_cfl_ac (src/predict.rs:1020-1063) -> (n, bh*bw) int16"""
-        dc = _dev_cands(cands, CFL_AC_CAND)
-        n = dc.numel() // CFL_AC_CAND.itemsize if n is None else n
+        dc, n = _dev_cands(cands, CFL_AC_CAND, n)
         ac = torch.empty((n, bw * bh), dtype=torch.int16, device="cuda")
         pl = luma.cstruct()
         self._check(self.lib.r1_cfl_ac_batch(self.h, C.byref(pl), bw, bh, xdec, ydec, dc.data_ptr(),
@@ -343,8 +392,7 @@ class Context:
     # ---- cdef:: ----
     def cdef_find_dir_batch(self, luma, cands, n=None):
         """cdef_find_dir (src/cdef.rs:84-143) -> (dir uint8, var int32)"""
-        dc = _dev_cands(cands, CDEF_DIR_CAND)
-        n = dc.numel() // CDEF_DIR_CAND.itemsize if n is None else n
+        dc, n = _dev_cands(cands, CDEF_DIR_CAND, n)
         d = torch.empty(n, dtype=torch.uint8, device="cuda")
         v = torch.empty(n, dtype=torch.int32, device="cuda")
         pl = luma.cstruct()
@@ -355,8 +403,7 @@ class Context:
 
     def cdef_filter_block_batch(self, src, dst, xdec, ydec, cands, n=None):
         """cdef_filter_block (src/cdef.rs:198-298) for n blocks, src plane -> dst plane"""
-        dc = _dev_cands(cands, CDEF_BLOCK_CAND)
-        n = dc.numel() // CDEF_BLOCK_CAND.itemsize if n is None else n
+        dc, n = _dev_cands(cands, CDEF_BLOCK_CAND, n)
         a, b = src.cstruct(), dst.cstruct()
         self._check(self.lib.r1_cdef_filter_block_batch(self.h, C.byref(a), C.byref(b), xdec, ydec,
                                                         dc.data_ptr(), n, _stream_ptr()),
@@ -434,10 +481,9 @@ class Context:
         scratch = torch.empty(self.lib.r1_cdef_strength_search_scratch_bytes(mi_cols, mi_rows),
                               dtype=torch.uint8, device="cuda")
         self._check(self.lib.r1_cdef_strength_search(
-            self.h, pr, ps, skip_mi.data_ptr(), skip_mi.stride(0), mi_cols, mi_rows,
-            scales.data_ptr() if scales is not None else None,
-            scales.stride(0) if scales is not None else 0, C.byref(prm), err.data_ptr(), best.data_ptr(),
-            scratch.data_ptr(), _stream_ptr()), "r1_cdef_strength_search")
+            self.h, pr, ps, skip_mi.data_ptr(), skip_mi.stride(0), mi_cols, mi_rows, *_scales_arg(scales),
+            C.byref(prm), err.data_ptr(), best.data_ptr(), scratch.data_ptr(), _stream_ptr()),
+            "r1_cdef_strength_search")
         return err, best
 
     def _cdef_search_params(self, n_planes, y_strengths, uv_strengths, damping, bit_depth, n_idx, xdec, ydec, crop_w,
@@ -483,7 +529,7 @@ class Context:
             us = [np.ascontiguousarray(u, TRIAL_UNIT) for u in units] + [np.zeros(0, TRIAL_UNIT)] * (3 - len(units))
             n_units = (C.c_int32 * 3)(*[len(u) for u in us])
             allu = np.concatenate(us)
-            du = _dev_cands(allu, TRIAL_UNIT) if len(allu) else None
+            du = _dev_cands(allu, TRIAL_UNIT)[0] if len(allu) else None
         o = outs if outs is not None else {}
         if "err" not in o:
             o["err"] = torch.empty((n_sby, n_sbx, 8), dtype=torch.int64, device="cuda")
@@ -497,8 +543,7 @@ class Context:
         if scratch is None or scratch.numel() < nb:
             scratch = torch.empty(nb, dtype=torch.uint8, device="cuda")
         self._check(self.lib.r1_cdef_lrf_trial_batch(
-            self.h, pr, pc, ps, skip_mi.data_ptr(), skip_mi.stride(0), mi_cols, mi_rows,
-            scales.data_ptr() if scales is not None else None, scales.stride(0) if scales is not None else 0,
+            self.h, pr, pc, ps, skip_mi.data_ptr(), skip_mi.stride(0), mi_cols, mi_rows, *_scales_arg(scales),
             C.byref(prm), du.data_ptr() if du is not None else None, n_units,
             sb_sel.data_ptr() if sb_sel is not None else None, err.data_ptr(), errp.data_ptr(), best.data_ptr(),
             scratch.data_ptr(), _stream_ptr()), "r1_cdef_lrf_trial_batch")
@@ -582,19 +627,16 @@ class Context:
 
     # ---- mc:: ----
     def put_8tap_batch(self, ref, w, h, cands, n=None, out=None):
-        dc = _dev_cands(cands, MC_CAND)
-        n = dc.numel() // MC_CAND.itemsize if n is None else n
+        dc, n = _dev_cands(cands, MC_CAND, n)
         if out is None:
-            out = torch.empty((n, h, w), dtype=torch.uint8 if ref.bpp == 1 else torch.int16,
-                              device="cuda")
+            out = torch.empty((n, h, w), dtype=_pix_dtype(ref.bpp), device="cuda")
         pr = ref.cstruct()
         self._check(self.lib.r1_mc_put_batch(self.h, C.byref(pr), w, h, dc.data_ptr(), n,
                                              out.data_ptr(), _stream_ptr()), "r1_mc_put_batch")
         return out
 
     def prep_8tap_batch(self, ref, w, h, cands, n=None, out=None):
-        dc = _dev_cands(cands, MC_CAND)
-        n = dc.numel() // MC_CAND.itemsize if n is None else n
+        dc, n = _dev_cands(cands, MC_CAND, n)
         if out is None:
             out = torch.empty((n, h, w), dtype=torch.int16, device="cuda")
         pr = ref.cstruct()
@@ -604,8 +646,7 @@ class Context:
 
     def mc_batch_mfma(self, ref, w, h, cands, prep=False, n=None, out=None):
         """put_8tap / prep_8tap with the horizontal pass on the matrix cores (csrc/mc_mfma.hip)"""
-        dc = _dev_cands(cands, MC_CAND)
-        n = dc.numel() // MC_CAND.itemsize if n is None else n
+        dc, n = _dev_cands(cands, MC_CAND, n)
         if out is None:
             out = torch.empty((n, h, w), dtype=torch.int16 if prep else torch.uint8, device="cuda")
         pr = ref.cstruct()
@@ -617,92 +658,58 @@ class Context:
         n = tmp1.numel() // (w * h)
         bpp = 1 if bit_depth == 8 else 2
         if out is None:
-            out = torch.empty((n, h, w), dtype=torch.uint8 if bpp == 1 else torch.int16,
-                              device="cuda")
+            out = torch.empty((n, h, w), dtype=_pix_dtype(bpp), device="cuda")
         self._check(self.lib.r1_mc_avg_batch(self.h, tmp1.data_ptr(), tmp2.data_ptr(), w, h, n,
                                              bit_depth, bpp, out.data_ptr(), _stream_ptr()),
                     "r1_mc_avg_batch")
         return out
 
+    def _bind_launch(self, name, args, keep):
+        """entry point `name` bound to args: the returned closure is one ctypes call (args + the current
+        stream) and an rc check; it keeps `keep` -- what args point into -- alive"""
+        f = getattr(self.lib, name)
+
+        def launch():
+            rc = f(*args, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            if rc != 0:
+                self._check(rc, name)
+            return keep
+        return launch
 
     def prepare_rdo_cand(self, org, ref, w, h, dcands, n, outs):
         """Bind one fused-candidate launch once (descriptor and output tensors
         stay alive in the returned closure): the per-step host cost is then one
         ctypes call -- what a native caller of the C ABI pays -- instead of
         rebuilding the argument structs in Python every step."""
-        from .types import TxSize
-        tx_size = int(TxSize.by_dims(w, h))
         po, pr = org.cstruct(), ref.cstruct()
-        f = self.lib.r1_rdo_cand_batch
-        args = [self.h, C.byref(po), C.byref(pr), w, h, tx_size, dcands.data_ptr(), n,
-                outs["sad"].data_ptr(), outs["satd"].data_ptr(), outs["coeffs"].data_ptr(), None]
-        keep = (po, pr, dcands, outs)
-
-        def launch():
-            rc = f(*args, C.c_void_p(torch.cuda.current_stream().cuda_stream))
-            if rc != 0:
-                self._check(rc, "r1_rdo_cand_batch")
-            return keep
-        return launch
+        return self._bind_launch("r1_rdo_cand_batch", [
+            self.h, C.byref(po), C.byref(pr), w, h, int(TxSize.by_dims(w, h)), dcands.data_ptr(), n,
+            outs["sad"].data_ptr(), outs["satd"].data_ptr(), outs["coeffs"].data_ptr(), None], (po, pr, dcands, outs))
 
     def prepare_rdo_full_cand(self, org, ref, w, h, dcands, n, qindex, outs, is_intra=0):
         """prepare_rdo_cand for r1_rdo_full_cand_batch (outs: sad, satd, eob, tx_dist, est_rate)."""
-        from .types import TxSize
-        tx_size = int(TxSize.by_dims(w, h))
         po, pr = org.cstruct(), ref.cstruct()
         qp = self._qparams(qindex, org.bit_depth, is_intra, 0, 0)
-        f = self.lib.r1_rdo_full_cand_batch
-        args = [self.h, C.byref(po), C.byref(pr), w, h, tx_size, dcands.data_ptr(), n, C.byref(qp),
-                outs["sad"].data_ptr(), outs["satd"].data_ptr(), outs["eob"].data_ptr(),
-                outs["tx_dist"].data_ptr(), outs["est_rate"].data_ptr(), None, None]
-        keep = (po, pr, qp, dcands, outs)
-
-        def launch():
-            rc = f(*args, C.c_void_p(torch.cuda.current_stream().cuda_stream))
-            if rc != 0:
-                self._check(rc, "r1_rdo_full_cand_batch")
-            return keep
-        return launch
+        return self._bind_launch("r1_rdo_full_cand_batch", [
+            self.h, C.byref(po), C.byref(pr), w, h, int(TxSize.by_dims(w, h)), dcands.data_ptr(), n, C.byref(qp),
+            outs["sad"].data_ptr(), outs["satd"].data_ptr(), outs["eob"].data_ptr(), outs["tx_dist"].data_ptr(),
+            outs["est_rate"].data_ptr(), None, None], (po, pr, qp, dcands, outs))
 
     def rdo_full_cand_batch(self, org, ref, w, h, cands, qindex, is_intra=0, dc_delta_q=0,
                             ac_delta_q=0, n=None, want_sad=True, want_satd=True, want_rate=True,
                             want_qcoeffs=False, want_coeffs=False, outs=None):
         """mc -> sad/satd -> diff -> forward_transform -> quantize -> dequantize ->
         tx-domain distortion -> estimate_rate for every candidate, one launch."""
-        from .types import TxSize
         tx_size = int(TxSize.by_dims(w, h))
-        dc = _dev_cands(cands, RDO_CAND)
-        n = dc.numel() // RDO_CAND.itemsize if n is None else n
-        ct = torch.int16 if org.bpp == 1 else torch.int32
-        o = outs if outs is not None else {}
-        if "eob" not in o:
-            o["eob"] = torch.empty(n, dtype=torch.int16, device="cuda")
-        if "tx_dist" not in o:
-            o["tx_dist"] = torch.empty(n, dtype=torch.int64, device="cuda")
-        if want_sad:
-            if "sad" not in o:
-                o["sad"] = torch.empty(n, dtype=torch.int32, device="cuda")
-        if want_satd:
-            if "satd" not in o:
-                o["satd"] = torch.empty(n, dtype=torch.int32, device="cuda")
-        if want_rate:
-            if "est_rate" not in o:
-                o["est_rate"] = torch.empty(n, dtype=torch.int64, device="cuda")
-        if want_qcoeffs:
-            if "qcoeffs" not in o:
-                o["qcoeffs"] = torch.empty((n, min(w, 32) * min(h, 32)), dtype=ct, device="cuda")
-        if want_coeffs:
-            if "coeffs" not in o:
-                o["coeffs"] = torch.empty((n, w * h), dtype=ct, device="cuda")
+        dc, n = _dev_cands(cands, RDO_CAND, n)
+        o = _bind_outs(outs, _FULL_CAND_OUTS, (True, True, want_sad, want_satd, want_rate, want_qcoeffs, want_coeffs),
+                       org.bpp, n, w, h)
         po, pr = org.cstruct(), ref.cstruct()
         qp = self._qparams(qindex, org.bit_depth, is_intra, dc_delta_q, ac_delta_q)
-
-        def p(k):
-            return o[k].data_ptr() if k in o else None
         self._check(self.lib.r1_rdo_full_cand_batch(
             self.h, C.byref(po), C.byref(pr), w, h, tx_size, dc.data_ptr(), n, C.byref(qp),
-            p("sad"), p("satd"), p("eob"), p("tx_dist"), p("est_rate"), p("qcoeffs"), p("coeffs"),
-            _stream_ptr()), "r1_rdo_full_cand_batch")
+            *_ptrs(o, "sad", "satd", "eob", "tx_dist", "est_rate", "qcoeffs", "coeffs"), _stream_ptr()),
+            "r1_rdo_full_cand_batch")
         return o
 
     # ---- me:: ----
@@ -776,8 +783,7 @@ class Context:
         arr[0].tile_x, arr[0].tile_y, arr[0].tile_w, arr[0].tile_h = job["tile"]
         p = _lib.R1MeParams(w_in_b, h_in_b, cols, rows, bit_depth, int(allow_hp), 0, 1,
                             (C.c_uint32 * 3)(*[int(v) for v in lambdas]), 0)
-        dc = _dev_cands(cands, ME_BLOCK_CAND)
-        n = dc.numel() // ME_BLOCK_CAND.itemsize if n is None else n
+        dc, n = _dev_cands(cands, ME_BLOCK_CAND, n)
         out = torch.empty(n * ME_RESULT.itemsize, dtype=torch.uint8, device="cuda")
         self._check(self.lib.r1_estimate_motion_batch(self.h, arr, C.byref(p), dc.data_ptr(), n, max_w,
                                                       max_h, int(use_satd), filter_mode,
@@ -845,47 +851,20 @@ class Context:
         transform -> reconstruction -> weighted SSE / cdef_dist against the source, one launch.
         pred (dense (n, h, w) device tensor): r1_rdo_pred_cand_batch -- the prediction comes
         from that buffer instead of put_8tap(ref); dist_kind 0 = transform-domain distortion."""
-        from .types import TxSize
         tx_size = int(TxSize.by_dims(w, h))
-        dc = _dev_cands(cands, RDO_CAND)
-        n = dc.numel() // RDO_CAND.itemsize if n is None else n
-        ct = torch.int16 if org.bpp == 1 else torch.int32
-        o = outs if outs is not None else {}
-        if "eob" not in o:
-            o["eob"] = torch.empty(n, dtype=torch.int16, device="cuda")
-        if "dist" not in o:
-            o["dist"] = torch.empty(n, dtype=torch.int64, device="cuda")
-        if want_sad:
-            if "sad" not in o:
-                o["sad"] = torch.empty(n, dtype=torch.int32, device="cuda")
-        if want_satd:
-            if "satd" not in o:
-                o["satd"] = torch.empty(n, dtype=torch.int32, device="cuda")
-        if want_qcoeffs:
-            if "qcoeffs" not in o:
-                o["qcoeffs"] = torch.empty((n, min(w, 32) * min(h, 32)), dtype=ct, device="cuda")
-        if want_rec:
-            if "rec" not in o:
-                o["rec"] = torch.empty((n, h, w), dtype=torch.uint8 if org.bpp == 1 else torch.int16,
-                                            device="cuda")
+        dc, n = _dev_cands(cands, RDO_CAND, n)
+        o = _bind_outs(outs, _PIXEL_CAND_OUTS, (True, True, want_sad, want_satd, want_qcoeffs, want_rec), org.bpp, n,
+                       w, h)
         po = org.cstruct()
         qp = self._qparams(qindex, org.bit_depth, is_intra, dc_delta_q, ac_delta_q)
-
-        def p(k):
-            return o[k].data_ptr() if k in o else None
+        # the two entry points differ in the prediction source only
         if pred is not None:
-            self._check(self.lib.r1_rdo_pred_cand_batch(
-                self.h, C.byref(po), pred.data_ptr(), w, h, tx_size, dc.data_ptr(), n, C.byref(qp),
-                dist_kind, scales.data_ptr() if scales is not None else None,
-                scales.stride(0) if scales is not None else 0, xdec, ydec, p("sad"), p("satd"),
-                p("eob"), p("dist"), p("qcoeffs"), p("rec"), _stream_ptr()), "r1_rdo_pred_cand_batch")
-            return o
-        pr = ref.cstruct()
-        self._check(self.lib.r1_rdo_pixel_cand_batch(
-            self.h, C.byref(po), C.byref(pr), w, h, tx_size, dc.data_ptr(), n, C.byref(qp), dist_kind,
-            scales.data_ptr() if scales is not None else None,
-            scales.stride(0) if scales is not None else 0, xdec, ydec, p("sad"), p("satd"), p("eob"),
-            p("dist"), p("qcoeffs"), p("rec"), _stream_ptr()), "r1_rdo_pixel_cand_batch")
+            name, src = "r1_rdo_pred_cand_batch", pred.data_ptr()
+        else:
+            name, src = "r1_rdo_pixel_cand_batch", C.byref(ref.cstruct())
+        self._check(getattr(self.lib, name)(
+            self.h, C.byref(po), src, w, h, tx_size, dc.data_ptr(), n, C.byref(qp), dist_kind, *_scales_arg(scales),
+            xdec, ydec, *_ptrs(o, "sad", "satd", "eob", "dist", "qcoeffs", "rec"), _stream_ptr()), name)
         return o
 
     def tx_type_mask(self, tx_size, is_inter, use_reduced_set=False, rav1e_types_only=True):
@@ -902,45 +881,19 @@ class Context:
         prediction per candidate -- put_8tap(ref), or the dense `pred` (n, h, w) tensor when ref is None.
         eob / dist (/ est_rate): (n, nt); qcoeffs: (n, nt, coded area); rec: (n, nt, h, w); slot j = the
         j-th set bit of tx_type_mask."""
-        from .types import TxSize
         tx_size = int(TxSize.by_dims(w, h))
-        dc = _dev_cands(cands, RDO_CAND)
-        n = dc.numel() // RDO_CAND.itemsize if n is None else n
-        nt = bin(int(tx_type_mask)).count("1")
-        ct = torch.int16 if org.bpp == 1 else torch.int32
-        o = outs if outs is not None else {}
-        if "eob" not in o:
-            o["eob"] = torch.empty((n, nt), dtype=torch.int16, device="cuda")
-        if "dist" not in o:
-            o["dist"] = torch.empty((n, nt), dtype=torch.int64, device="cuda")
-        if want_sad:
-            if "sad" not in o:
-                o["sad"] = torch.empty(n, dtype=torch.int32, device="cuda")
-        if want_satd:
-            if "satd" not in o:
-                o["satd"] = torch.empty(n, dtype=torch.int32, device="cuda")
-        if want_est_rate:
-            if "est_rate" not in o:
-                o["est_rate"] = torch.empty((n, nt), dtype=torch.int64, device="cuda")
-        if want_qcoeffs:
-            if "qcoeffs" not in o:
-                o["qcoeffs"] = torch.empty((n, nt, min(w, 32) * min(h, 32)), dtype=ct, device="cuda")
-        if want_rec:
-            if "rec" not in o:
-                o["rec"] = torch.empty((n, nt, h, w), dtype=torch.uint8 if org.bpp == 1 else torch.int16,
-                                            device="cuda")
+        dc, n = _dev_cands(cands, RDO_CAND, n)
+        o = _bind_outs(outs, _TXSEARCH_OUTS, (True, True, want_sad, want_satd, want_est_rate, want_qcoeffs, want_rec),
+                       org.bpp, n, w, h, bin(int(tx_type_mask)).count("1"))
         po = org.cstruct()
         pr = ref.cstruct() if ref is not None else None
         qp = self._qparams(qindex, org.bit_depth, is_intra, dc_delta_q, ac_delta_q)
-
-        def p(k):
-            return o[k].data_ptr() if k in o else None
         self._check(self.lib.r1_rdo_txsearch_batch(
             self.h, C.byref(po), C.byref(pr) if pr is not None else None,
             pred.data_ptr() if pred is not None else None, w, h, tx_size, dc.data_ptr(), n, int(tx_type_mask),
-            C.byref(qp), dist_kind, scales.data_ptr() if scales is not None else None,
-            scales.stride(0) if scales is not None else 0, xdec, ydec, p("sad"), p("satd"), p("eob"), p("dist"),
-            p("est_rate"), p("qcoeffs"), p("rec"), _stream_ptr()), "r1_rdo_txsearch_batch")
+            C.byref(qp), dist_kind, *_scales_arg(scales), xdec, ydec,
+            *_ptrs(o, "sad", "satd", "eob", "dist", "est_rate", "qcoeffs", "rec"), _stream_ptr()),
+            "r1_rdo_txsearch_batch")
         return o
 
     # ---- lrf:: ----
@@ -959,8 +912,7 @@ class Context:
     def sgrproj_solve_batch(self, cdeffed, inp, units, max_w=256, max_h=256):
         """sgrproj_solve (src/lrf.rs:847-1096) for (unit, set) pairs; units: SGR_SOLVE_UNIT array (`edges`: SGR_EDGE_* --
         the unit's place in its rdo_loop_decision area, rdo_glue.restoration_unit_edges) -> (n, 2) int8 xqd"""
-        dc = _dev_cands(units, SGR_SOLVE_UNIT)
-        n = dc.numel() // SGR_SOLVE_UNIT.itemsize
+        dc, n = _dev_cands(units, SGR_SOLVE_UNIT)
         scratch = torch.empty(n * 5, dtype=torch.int64, device="cuda")
         out = torch.empty((n, 2), dtype=torch.int8, device="cuda")
         pc, pi = cdeffed.cstruct(), inp.cstruct()
@@ -975,8 +927,7 @@ class Context:
         units: SGR_SOLVE_UNIT array (set 255 = the no-filter option; `edges` from rdo_glue.restoration_unit_edges, 0 for
         one unit per plane and area; list the sets of a unit next to each other); scales: 2-D int32/uint32 device
         tensor (one DistortionScale per 8x8 luma block) or None -> ((n, 2) int8 xqd, (n,) int64 err)"""
-        dc = _dev_cands(units, SGR_SOLVE_UNIT)
-        n = dc.numel() // SGR_SOLVE_UNIT.itemsize
+        dc, n = _dev_cands(units, SGR_SOLVE_UNIT)
         scratch = torch.empty(n * 6, dtype=torch.int64, device="cuda")
         xqd = torch.empty((n, 2), dtype=torch.int8, device="cuda")
         err = torch.empty(n, dtype=torch.int64, device="cuda")
@@ -993,24 +944,12 @@ class Context:
     def rdo_cand_batch(self, org, ref, w, h, cands, n=None, want_sad=True, want_satd=True,
                        want_coeffs=True, want_pred=False, outs=None):
         """mc -> sad/satd -> diff -> forward_transform for every candidate."""
-        from .types import TxSize
         tx_size = int(TxSize.by_dims(w, h))
-        dc = _dev_cands(cands, RDO_CAND)
-        n = dc.numel() // RDO_CAND.itemsize if n is None else n
-        o = outs or {}
-        if want_sad and "sad" not in o:
-            o["sad"] = torch.empty(n, dtype=torch.int32, device="cuda")
-        if want_satd and "satd" not in o:
-            o["satd"] = torch.empty(n, dtype=torch.int32, device="cuda")
-        if want_coeffs and "coeffs" not in o:
-            o["coeffs"] = torch.empty((n, w * h), dtype=torch.int16 if org.bpp == 1 else torch.int32,
-                                      device="cuda")
-        if want_pred and "pred" not in o:
-            o["pred"] = torch.empty((n, h, w), dtype=torch.uint8 if org.bpp == 1 else torch.int16,
-                                    device="cuda")
+        dc, n = _dev_cands(cands, RDO_CAND, n)
+        o = _bind_outs(outs, _CAND_OUTS, (want_sad, want_satd, want_coeffs, want_pred), org.bpp, n, w, h)
         po, pr = org.cstruct(), ref.cstruct()
 
-        def p(k, want):
+        def p(k, want):   # unlike the other fused wrappers: NULL for an unwanted output even if outs holds it
             return o[k].data_ptr() if want else None
         self._check(self.lib.r1_rdo_cand_batch(self.h, C.byref(po), C.byref(pr), w, h, tx_size,
                                                dc.data_ptr(), n, p("sad", want_sad),

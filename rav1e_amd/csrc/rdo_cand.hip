@@ -1121,6 +1121,41 @@ int rdo_dispatch(r1_ctx *ctx, const R1Plane *org, const R1Plane *ref, int w, int
                                                  qa, st);
 #endif
 }
+
+// The RdoQuantArgs of a quantizing entry point, every argument check written once: the quantizer (QM 1 and 2),
+// then the distortion -- dist_kind 0 = the transform-domain distortion (QM 1, no reconstruction), R1_DIST_WSSE /
+// R1_DIST_CDEF = the pixel-domain leg (QM 2).  The scale grid and the decimation are checked for every kind.
+int rdo_quant_args(const r1_ctx *ctx, const R1Plane *org, int tx_size, const R1QuantParams *params, int dist_kind,
+                   const uint32_t *scales, int scale_stride, int xdec, int ydec, uint16_t *eob_out,
+                   uint64_t *dist_out, void *qcoeffs_out, void *rec_out, RdoQuantArgs &qa) {
+  R1_REQUIRE(ctx && org && params && eob_out && dist_out);
+  R1_REQUIRE(tx_size >= 0 && tx_size < 19);
+  R1_REQUIRE(params->bit_depth == org->bit_depth);
+  R1_REQUIRE(dist_kind == 0 || dist_kind == R1_DIST_WSSE || dist_kind == R1_DIST_CDEF);
+  R1_REQUIRE(xdec >= 0 && xdec <= 1 && ydec >= 0 && ydec <= 1);
+  R1_REQUIRE(dist_kind != R1_DIST_CDEF || (xdec == 0 && ydec == 0));   // cdef_dist is luma-only
+  R1_REQUIRE(!scales || scale_stride > 0);
+  R1_REQUIRE(dist_kind != 0 || !rec_out);
+  qa.qp = r1q::make_qparams(*params, tx_size, org->bytes_per_px == 1 ? 2 : 4);
+  for (int k = 0; k < 3; k++) qa.scan[k] = ctx->scan_dev + ctx->scan_off[tx_size][k];
+  qa.tx_size = tx_size;
+  qa.q_bin = params->qindex / 32;   // RDO_QUANT_DIV
+  qa.eob = eob_out;
+  qa.qcoeffs = qcoeffs_out;
+  if (dist_kind == 0) {
+    qa.tx_dist = (unsigned long long *)dist_out;
+    return R1_OK;
+  }
+  qa.dist_kind = dist_kind;
+  qa.inv_shift = r1itx::kInvShift[tx_size];
+  qa.scales = scales;
+  qa.scale_stride = scale_stride;
+  qa.xdec = xdec;
+  qa.ydec = ydec;
+  qa.pix_dist = (unsigned long long *)dist_out;
+  qa.rec = rec_out;
+  return R1_OK;
+}
 }  // namespace
 
 extern "C" int r1_rdo_cand_batch(r1_ctx *ctx, const R1Plane *org,
@@ -1138,18 +1173,12 @@ extern "C" int r1_rdo_full_cand_batch(r1_ctx *ctx, const R1Plane *org, const R1P
                                       uint32_t *satd_out, uint16_t *eob_out,
                                       uint64_t *tx_dist_out, uint64_t *est_rate_out,
                                       void *qcoeffs_out, void *coeffs, void *stream) {
-  R1_REQUIRE(ctx && org && params && eob_out && tx_dist_out);
-  R1_REQUIRE(tx_size >= 0 && tx_size < 19);
-  R1_REQUIRE(params->bit_depth == org->bit_depth);
   RdoQuantArgs qa = {};
-  qa.qp = r1q::make_qparams(*params, tx_size, org->bytes_per_px == 1 ? 2 : 4);
-  for (int k = 0; k < 3; k++) qa.scan[k] = ctx->scan_dev + ctx->scan_off[tx_size][k];
-  qa.tx_size = tx_size;
-  qa.q_bin = params->qindex / 32;   // RDO_QUANT_DIV
-  qa.eob = eob_out;
-  qa.tx_dist = (unsigned long long *)tx_dist_out;
+  // dist_kind 0: tx_dist_out takes the transform-domain distortion
+  const int rc = rdo_quant_args(ctx, org, tx_size, params, 0, nullptr, 0, 0, 0, eob_out, tx_dist_out, qcoeffs_out,
+                                nullptr, qa);
+  if (rc != R1_OK) return rc;
   qa.est_rate = (unsigned long long *)est_rate_out;
-  qa.qcoeffs = qcoeffs_out;
   return rdo_dispatch(ctx, org, ref, w, h, tx_size, cands, n, sad_out, satd_out, coeffs, nullptr,
                       &qa, stream);
 }
@@ -1161,28 +1190,11 @@ extern "C" int r1_rdo_pixel_cand_batch(r1_ctx *ctx, const R1Plane *org, const R1
                                        uint32_t *sad_out, uint32_t *satd_out, uint16_t *eob_out,
                                        uint64_t *dist_out, void *qcoeffs_out, void *rec_out,
                                        void *stream) {
-  R1_REQUIRE(ctx && org && params && eob_out && dist_out);
-  R1_REQUIRE(tx_size >= 0 && tx_size < 19);
-  R1_REQUIRE(params->bit_depth == org->bit_depth);
-  R1_REQUIRE(dist_kind == R1_DIST_WSSE || dist_kind == R1_DIST_CDEF);
-  R1_REQUIRE(xdec >= 0 && xdec <= 1 && ydec >= 0 && ydec <= 1);
-  R1_REQUIRE(dist_kind != R1_DIST_CDEF || (xdec == 0 && ydec == 0));
-  R1_REQUIRE(!scales || scale_stride > 0);
+  R1_REQUIRE(dist_kind != 0);   // the pixel-domain leg only: kind 0 is r1_rdo_full_cand_batch
   RdoQuantArgs qa = {};
-  qa.qp = r1q::make_qparams(*params, tx_size, org->bytes_per_px == 1 ? 2 : 4);
-  for (int k = 0; k < 3; k++) qa.scan[k] = ctx->scan_dev + ctx->scan_off[tx_size][k];
-  qa.tx_size = tx_size;
-  qa.q_bin = params->qindex / 32;
-  qa.eob = eob_out;
-  qa.qcoeffs = qcoeffs_out;
-  qa.dist_kind = dist_kind;
-  qa.inv_shift = r1itx::kInvShift[tx_size];
-  qa.scales = scales;
-  qa.scale_stride = scale_stride;
-  qa.xdec = xdec;
-  qa.ydec = ydec;
-  qa.pix_dist = (unsigned long long *)dist_out;
-  qa.rec = rec_out;
+  const int rc = rdo_quant_args(ctx, org, tx_size, params, dist_kind, scales, scale_stride, xdec, ydec, eob_out,
+                                dist_out, qcoeffs_out, rec_out, qa);
+  if (rc != R1_OK) return rc;
   return rdo_dispatch(ctx, org, ref, w, h, tx_size, cands, n, sad_out, satd_out, nullptr, nullptr,
                       &qa, stream);
 }
@@ -1194,34 +1206,12 @@ extern "C" int r1_rdo_pred_cand_batch(r1_ctx *ctx, const R1Plane *org, const voi
                                       uint32_t *sad_out, uint32_t *satd_out, uint16_t *eob_out,
                                       uint64_t *dist_out, void *qcoeffs_out, void *rec_out,
                                       void *stream) {
-  R1_REQUIRE(ctx && org && pred && params && eob_out && dist_out);
-  R1_REQUIRE(tx_size >= 0 && tx_size < 19);
-  R1_REQUIRE(params->bit_depth == org->bit_depth);
-  R1_REQUIRE(dist_kind == 0 || dist_kind == R1_DIST_WSSE || dist_kind == R1_DIST_CDEF);
-  R1_REQUIRE(xdec >= 0 && xdec <= 1 && ydec >= 0 && ydec <= 1);
-  R1_REQUIRE(dist_kind != R1_DIST_CDEF || (xdec == 0 && ydec == 0));
-  R1_REQUIRE(!scales || scale_stride > 0);
-  R1_REQUIRE(dist_kind != 0 || !rec_out);
+  R1_REQUIRE(pred);
   RdoQuantArgs qa = {};
-  qa.qp = r1q::make_qparams(*params, tx_size, org->bytes_per_px == 1 ? 2 : 4);
-  for (int k = 0; k < 3; k++) qa.scan[k] = ctx->scan_dev + ctx->scan_off[tx_size][k];
-  qa.tx_size = tx_size;
-  qa.q_bin = params->qindex / 32;
-  qa.eob = eob_out;
-  qa.qcoeffs = qcoeffs_out;
+  const int rc = rdo_quant_args(ctx, org, tx_size, params, dist_kind, scales, scale_stride, xdec, ydec, eob_out,
+                                dist_out, qcoeffs_out, rec_out, qa);
+  if (rc != R1_OK) return rc;
   qa.pred_in = pred;
-  if (dist_kind == 0) {
-    qa.tx_dist = (unsigned long long *)dist_out;   // transform-domain distortion (QM 1)
-  } else {
-    qa.dist_kind = dist_kind;
-    qa.inv_shift = r1itx::kInvShift[tx_size];
-    qa.scales = scales;
-    qa.scale_stride = scale_stride;
-    qa.xdec = xdec;
-    qa.ydec = ydec;
-    qa.pix_dist = (unsigned long long *)dist_out;
-    qa.rec = rec_out;
-  }
   return rdo_dispatch(ctx, org, nullptr, w, h, tx_size, cands, n, sad_out, satd_out, nullptr, nullptr,
                       &qa, stream);
 }
@@ -1242,7 +1232,6 @@ extern "C" uint32_t r1_tx_type_mask(int tx_size, int is_inter, int use_reduced_s
   return rav1e_types_only ? (m & 0x0E0Fu) : m;
 }
 
-extern "C" uint32_t r1_tx_type_mask(int tx_size, int is_inter, int use_reduced_set, int rav1e_types_only);
 extern "C" int r1_rdo_txsearch_batch(r1_ctx *ctx, const R1Plane *org, const R1Plane *ref, const void *pred,
                                      int w, int h, int tx_size, const R1RdoCand *cands, int n,
                                      uint32_t tx_type_mask, const R1QuantParams *params, int dist_kind,
@@ -1250,15 +1239,11 @@ extern "C" int r1_rdo_txsearch_batch(r1_ctx *ctx, const R1Plane *org, const R1Pl
                                      uint32_t *sad_out, uint32_t *satd_out, uint16_t *eob_out,
                                      uint64_t *dist_out, uint64_t *est_rate_out, void *qcoeffs_out,
                                      void *rec_out, void *stream) {
-  R1_REQUIRE(ctx && org && params && eob_out && dist_out);
   R1_REQUIRE((ref != nullptr) != (pred != nullptr));
-  R1_REQUIRE(tx_size >= 0 && tx_size < 19);
-  R1_REQUIRE(params->bit_depth == org->bit_depth);
-  R1_REQUIRE(dist_kind == 0 || dist_kind == R1_DIST_WSSE || dist_kind == R1_DIST_CDEF);
-  R1_REQUIRE(xdec >= 0 && xdec <= 1 && ydec >= 0 && ydec <= 1);
-  R1_REQUIRE(dist_kind != R1_DIST_CDEF || (xdec == 0 && ydec == 0));
-  R1_REQUIRE(!scales || scale_stride > 0);
-  R1_REQUIRE(dist_kind != 0 || !rec_out);
+  RdoQuantArgs qa = {};
+  int rc = rdo_quant_args(ctx, org, tx_size, params, dist_kind, scales, scale_stride, xdec, ydec, eob_out, dist_out,
+                          qcoeffs_out, rec_out, qa);
+  if (rc != R1_OK) return rc;
   R1_REQUIRE(dist_kind == 0 || !est_rate_out);
   // WHT (16) has no scan order; the mask is over the 16 TxTypes of the tx sets
   R1_REQUIRE(tx_type_mask != 0 && tx_type_mask <= 0xFFFFu);
@@ -1269,29 +1254,10 @@ extern "C" int r1_rdo_txsearch_batch(r1_ctx *ctx, const R1Plane *org, const R1Pl
   // every type of the mask must exist for the size: the inter sets are the largest (av1_tx_used; a 32-point side has
   // DCT_DCT and IDTX only -- the reference's 1-D tables have no other kernel there and would panic)
   R1_REQUIRE((tx_type_mask & ~r1_tx_type_mask(tx_size, 1, 0, 0)) == 0);
-  RdoQuantArgs qa = {};
-  qa.qp = r1q::make_qparams(*params, tx_size, org->bytes_per_px == 1 ? 2 : 4);
-  for (int k = 0; k < 3; k++) qa.scan[k] = ctx->scan_dev + ctx->scan_off[tx_size][k];
-  qa.tx_size = tx_size;
-  qa.q_bin = params->qindex / 32;
-  qa.eob = eob_out;
-  qa.qcoeffs = qcoeffs_out;
+  qa.est_rate = (unsigned long long *)est_rate_out;
   qa.pred_in = pred;
   qa.tx_mask = tx_type_mask;
   qa.nt = __builtin_popcount(tx_type_mask);
-  if (dist_kind == 0) {
-    qa.tx_dist = (unsigned long long *)dist_out;
-    qa.est_rate = (unsigned long long *)est_rate_out;
-  } else {
-    qa.dist_kind = dist_kind;
-    qa.inv_shift = r1itx::kInvShift[tx_size];
-    qa.scales = scales;
-    qa.scale_stride = scale_stride;
-    qa.xdec = xdec;
-    qa.ydec = ydec;
-    qa.pix_dist = (unsigned long long *)dist_out;
-    qa.rec = rec_out;
-  }
   if (!side64 && !side32)
     return rdo_dispatch(ctx, org, ref, w, h, tx_size, cands, n, sad_out, satd_out, nullptr, nullptr, &qa, stream, true);
   // 32- and 64-point sides: one plain launch per type (at most two), the type forced, results into its slot
@@ -1299,8 +1265,8 @@ extern "C" int r1_rdo_txsearch_batch(r1_ctx *ctx, const R1Plane *org, const R1Pl
   for (uint32_t m = tx_type_mask; m != 0; m &= m - 1, slot++) {
     qa.tx_mask = m & (0u - m);
     qa.slot = slot;
-    const int rc = rdo_dispatch(ctx, org, ref, w, h, tx_size, cands, n, slot == 0 ? sad_out : nullptr,
-                                slot == 0 ? satd_out : nullptr, nullptr, nullptr, &qa, stream, false);
+    rc = rdo_dispatch(ctx, org, ref, w, h, tx_size, cands, n, slot == 0 ? sad_out : nullptr,
+                      slot == 0 ? satd_out : nullptr, nullptr, nullptr, &qa, stream, false);
     if (rc != R1_OK) return rc;
   }
   return R1_OK;

@@ -106,15 +106,7 @@ extern "C" int r1_fwd_txfm_batch(r1_ctx *ctx, const int16_t *residual,
   const r1tx::Shift3 sh = r1tx::fwd_shift(tx_size, tx_type, bit_depth);
 #define R1_TX_CASE(ID, WL, HL) \
   case ID: return launch<WL, HL>(residual, coeffs, n, tx_type, sh, coeff_bytes, st);
-  switch (tx_size) {
-    R1_TX_CASE(0, 2, 2) R1_TX_CASE(1, 3, 3) R1_TX_CASE(2, 4, 4)
-    R1_TX_CASE(3, 5, 5) R1_TX_CASE(4, 6, 6) R1_TX_CASE(5, 2, 3)
-    R1_TX_CASE(6, 3, 2) R1_TX_CASE(7, 3, 4) R1_TX_CASE(8, 4, 3)
-    R1_TX_CASE(9, 4, 5) R1_TX_CASE(10, 5, 4) R1_TX_CASE(11, 5, 6)
-    R1_TX_CASE(12, 6, 5) R1_TX_CASE(13, 2, 4) R1_TX_CASE(14, 4, 2)
-    R1_TX_CASE(15, 3, 5) R1_TX_CASE(16, 5, 3) R1_TX_CASE(17, 4, 6)
-    R1_TX_CASE(18, 6, 4)
-  }
+  switch (tx_size) { R1_TX_SIZES(R1_TX_CASE) }
 #undef R1_TX_CASE
   return R1_EINVAL;
 }

@@ -129,15 +129,7 @@ extern "C" int r1_inv_txfm_add_batch(r1_ctx *ctx, const void *coeffs, int coeff_
                                    bit_depth, sh, st)                                   \
                : launch<2, WL, HL>(coeffs, coeff_stride, pred, rec, n, tx_type,        \
                                    bit_depth, sh, st);
-  switch (tx_size) {
-    R1_ITX_CASE(0, 2, 2) R1_ITX_CASE(1, 3, 3) R1_ITX_CASE(2, 4, 4)
-    R1_ITX_CASE(3, 5, 5) R1_ITX_CASE(4, 6, 6) R1_ITX_CASE(5, 2, 3)
-    R1_ITX_CASE(6, 3, 2) R1_ITX_CASE(7, 3, 4) R1_ITX_CASE(8, 4, 3)
-    R1_ITX_CASE(9, 4, 5) R1_ITX_CASE(10, 5, 4) R1_ITX_CASE(11, 5, 6)
-    R1_ITX_CASE(12, 6, 5) R1_ITX_CASE(13, 2, 4) R1_ITX_CASE(14, 4, 2)
-    R1_ITX_CASE(15, 3, 5) R1_ITX_CASE(16, 5, 3) R1_ITX_CASE(17, 4, 6)
-    R1_ITX_CASE(18, 6, 4)
-  }
+  switch (tx_size) { R1_TX_SIZES(R1_ITX_CASE) }
 #undef R1_ITX_CASE
   return R1_EINVAL;
 }

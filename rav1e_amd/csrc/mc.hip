@@ -8,12 +8,14 @@
 // 8-deep register window (one new LDS row per output row for the vertical
 // taps).  Output blocks are dense (stride = w), so a row's P lanes store P
 // consecutive samples.
+#include "dist_common.hpp"
 #include "mc_common.hpp"
-
-int r1_mc_fast_launch(bool prep, const R1Plane *ref, int w, int h, const R1McCand *cands, int n,
-                      void *dst, hipStream_t st);
+#include "tx_common.hpp"
 
 namespace {
+using r1tx::T;
+#include "mc_taps_packed.inc"
+#include "cand_helpers.inc"
 
 template <int BPP, bool PREP>
 __global__ __launch_bounds__(64) void k_mc(R1Plane ref, int w, int h,
@@ -74,6 +76,76 @@ __global__ __launch_bounds__(256) void k_avg(const int16_t *__restrict__ t1,
   }
 }
 
+// put_8tap / prep_8tap alone on the same machinery (blocks whose size is a
+// transform size): window staged with one round trip, dot4 / dot2 columns.
+template <int BPP, int WL, int HL, bool PREP>
+__global__ __launch_bounds__(64) void k_mc_fast(R1Plane ref, const R1McCand *__restrict__ cands,
+                                                int n, void *__restrict__ dst) {
+  constexpr int W = 1 << WL, H = 1 << HL;
+  constexpr int P = W > H ? W : H, NC = 64 / P;
+  constexpr int WS = (((W + 7) * BPP + 3) >> 2) << 2;
+  __shared__ __attribute__((aligned(16))) uint8_t smem[NC * (H + 7) * WS];
+  const int lane = threadIdx.x;
+  const int cl = lane / P, c = lane % P;
+  // XCD-aware like k_rdo_cand: XCD x takes the x-th contiguous eighth of the list (grid = multiple of 8)
+  const unsigned wg = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+  const long long cand = (long long)wg * NC + cl;
+  const bool live = cand < n;
+  R1McCand cd = {};
+  if (live) cd = cands[cand];
+  uint8_t *win = smem + cl * (H + 7) * WS;
+  if (live)
+    r1mc::stage_window_fast<BPP, BPP == 1 ? 0x80808080u : 0u, W, H, P>(win, WS, ref, cd.rx, cd.ry, c);
+  __syncthreads();
+  const bool any_cf0 = __any(live && cd.col_frac == 0);
+  if (!(live && c < W)) return;
+  int32_t pred[H];
+  if constexpr (BPP == 1)
+    mc8_column<W, H, WS, PREP>(win, c, cd.col_frac, cd.row_frac, cd.mode_x, cd.mode_y, any_cf0, pred);
+  else
+    mc16_column<W, H, WS, PREP>(win, c, cd.col_frac, cd.row_frac, cd.mode_x, cd.mode_y,
+                                ref.bit_depth, pred);
+  // the predictions stream out (non-temporal: they would only push the reference rows out of the L2)
+  if constexpr (PREP || BPP == 2) {
+    uint16_t *pp = (uint16_t *)dst + (size_t)cand * W * H + c;
+#pragma unroll
+    for (int r = 0; r < H; r++) __builtin_nontemporal_store((uint16_t)pred[r], &pp[(size_t)r * W]);
+  } else {
+    uint8_t *pp = (uint8_t *)dst + (size_t)cand * W * H + c;
+#pragma unroll
+    for (int r = 0; r < H; r++) __builtin_nontemporal_store((uint8_t)pred[r], &pp[(size_t)r * W]);
+  }
+}
+
+template <int BPP, int WL, int HL>
+int launch_mc_fast(bool prep, const R1Plane &ref, const R1McCand *cands, int n, void *dst,
+                   hipStream_t st) {
+  constexpr int W = 1 << WL, H = 1 << HL, P = W > H ? W : H, NC = 64 / P;
+  const unsigned grid = ((unsigned)((n + NC - 1) / NC) + 7u) & ~7u;
+  if (prep)
+    hipLaunchKernelGGL((k_mc_fast<BPP, WL, HL, true>), dim3(grid), dim3(64), 0, st, ref, cands, n, dst);
+  else
+    hipLaunchKernelGGL((k_mc_fast<BPP, WL, HL, false>), dim3(grid), dim3(64), 0, st, ref, cands, n, dst);
+  R1_HIP_CHECK(hipGetLastError());
+  return R1_OK;
+}
+
+// The put / prep of block sizes that are transform sizes; returns 1 when (w, h) is not one of them.
+int r1_mc_fast_launch(bool prep, const R1Plane *ref, int w, int h, const R1McCand *cands, int n,
+                      void *dst, hipStream_t st) {
+  int ts = -1;
+  for (int t = 0; t < 19; t++)
+    if ((1 << r1tx::kTxWLog2[t]) == w && (1 << r1tx::kTxHLog2[t]) == h) ts = t;
+  if (ts < 0) return 1;
+#define R1_MF_CASE(ID, WL, HL)                                                         \
+  case ID:                                                                             \
+    return ref->bytes_per_px == 1 ? launch_mc_fast<1, WL, HL>(prep, *ref, cands, n, dst, st) \
+                                  : launch_mc_fast<2, WL, HL>(prep, *ref, cands, n, dst, st);
+  switch (ts) { R1_TX_SIZES(R1_MF_CASE) }
+#undef R1_MF_CASE
+  return 1;
+}
+
 int mc_launch(bool prep, const R1Plane *ref, int w, int h, const R1McCand *cands,
               int n, void *dst, hipStream_t st) {
   R1_REQUIRE(ref && (ref->bytes_per_px == 1 || ref->bytes_per_px == 2));
@@ -82,7 +154,7 @@ int mc_launch(bool prep, const R1Plane *ref, int w, int h, const R1McCand *cands
   if (n <= 0) return R1_OK;
   R1_REQUIRE(cands && dst);
   // block sizes that are transform sizes take the dot4 / dot2 path of the
-  // fused kernel (rdo_cand.hip); the slab kernel below covers the rest
+  // fused kernel (k_mc_fast above); the slab kernel below covers the rest
   // (w = 2, 128-wide / -high blocks, odd aspect ratios)
   {
     const int rc = r1_mc_fast_launch(prep, ref, w, h, cands, n, dst, st);

@@ -1,7 +1,7 @@
 // mc_mfma.hip -- put_8tap / prep_8tap (8-bit) with the HORIZONTAL 8-tap pass on the
 // matrix cores (reference: src/mc.rs:250-451).  BASELINE.json's north_star asks for "MFMA
 // only for the batched put/prep 8-tap separable convolution in mc.rs"; this is that
-// variant, kept beside the dot4 path (rdo_cand.hip mc8_column) so that both can be timed
+// variant, kept beside the dot4 path (cand_helpers.inc mc8_column) so that both can be timed
 // on the same box (tools/bench_mc_mfma.py, profiles/r02_mc_mfma_*).
 //
 // Horizontal pass as a banded-Toeplitz product on v_mfma_i32_16x16x32_i8:

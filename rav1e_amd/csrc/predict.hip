@@ -492,7 +492,7 @@ __global__ __launch_bounds__(64, intra_waves_hint(SATD_OUT, WLT)) void k_intra_p
       // get_satd with 8x8 tiles, lane = column (every lane of the candidate works): the
       // lane re-reads the column it just wrote, takes the vertical Hadamard of each 8-row
       // group on registers and the horizontal one across its 8-lane tile by DPP (the
-      // fused candidate kernel's scheme, rdo_cand.hip) -- with one lane per tile a 16x16
+      // fused candidate kernel's scheme, rdo_cand_kernel.hpp) -- with one lane per tile a 16x16
       // block kept 4 of its 16 lanes busy for 64 pixels each.
       const int32_t s1 = -(int32_t)((lane ^ (lane >> 2)) & 1);
       const int32_t s2 = -(int32_t)(((lane >> 1) ^ (lane >> 2)) & 1);

@@ -1,5 +1,5 @@
 // quant_common.hpp -- the quantizer as a device function shared by
-// quantize.hip (coefficients from HBM) and rdo_cand.hip (coefficients straight
+// quantize.hip (coefficients from HBM) and rdo_cand_kernel.hpp (coefficients straight
 // from the fused forward transform, never leaving the CU).
 //
 // Restates (reference file:line):

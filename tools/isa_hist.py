@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Instruction histogram of the gfx950 code of one .hip file, per kernel.
 
-  python tools/isa_hist.py rav1e_amd/csrc/rdo_cand.hip [kernel-name-substring ...]
-  python tools/isa_hist.py --json profiles/r03_isa_mix.json -DR1_HEADLINE_ONLY rav1e_amd/csrc/rdo_cand.hip k_rdo_cand
-      (the per-kernel VALU mix bench.py's `roofline` prices the VALU-issue roof with)
+  python tools/isa_hist.py rav1e_amd/csrc/lrf.hip [kernel-name-substring ...]
+  python tools/isa_hist.py --json OUT.json -DR1_RDO_TU_BD=8 -DR1_RDO_TU_QM=0 -DR1_HEADLINE_ONLY
+      rav1e_amd/csrc/rdo_cand_slice.hip k_rdo_cand
+      (one slice of the fused kernel; the 8- and 10-bit slices 0 together are the per-kernel VALU mix of
+      profiles/r03_isa_mix.json, which bench.py's `roofline` prices the VALU-issue roof with)
 
 Compiles the file to device assembly (hipcc -S --cuda-device-only) and counts, per kernel,
 VALU / SALU / LDS / VMEM instructions.  VALU is weighted with the issue costs measured by
@@ -30,7 +32,7 @@ def main():
     jpath = None
     if argv and argv[0] == "--json":
         jpath, argv = argv[1], argv[2:]
-    defs = [a for a in argv if a.startswith("-D")]      # e.g. -DR1_HEADLINE_ONLY for rdo_cand.hip
+    defs = [a for a in argv if a.startswith("-D")]      # e.g. the slice of rdo_cand_slice.hip
     argv = [a for a in argv if not a.startswith("-D")]
     src = argv[0]
     pats = argv[1:]

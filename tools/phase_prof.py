@@ -24,8 +24,9 @@ def main():
     bd = int(sys.argv[1]) if len(sys.argv) > 1 else 8
     ctx = Context(0)
     lib = ctx.lib
-    lib.r1_debug_phase_prof.restype = C.c_int
-    lib.r1_debug_phase_prof.argtypes = [C.c_void_p, C.c_int]
+    read_prof = getattr(lib, "r1_debug_phase_prof_b%d" % bd)   # the timers of the profiled slice of this bit depth
+    read_prof.restype = C.c_int
+    read_prof.argtypes = [C.c_void_p, C.c_int]
     fw, fh = 3840, 2160
     org = Plane.from_numpy(W.random_plane_array(fw, fh, bd, 1), fw, fh, bd, 88, 88)
     ref = Plane.from_numpy(W.random_plane_array(fw, fh, bd, 2), fw, fh, bd, 88, 88)
@@ -39,10 +40,10 @@ def main():
             ctx.rdo_cand_batch(org, ref, s, s, dc, n=len(c))
         torch.cuda.synchronize()
         buf = np.zeros((4096, 8), np.uint64)
-        lib.r1_debug_phase_prof(buf.ctypes.data, 1)
+        read_prof(buf.ctypes.data, 1)
         ctx.rdo_cand_batch(org, ref, s, s, dc, n=len(c))
         torch.cuda.synchronize()
-        lib.r1_debug_phase_prof(buf.ctypes.data, 1)
+        read_prof(buf.ctypes.data, 1)
         rows = buf[buf[:, 1] > 0][:, :7].astype(np.float64)
         per = rows.mean(axis=0)
         print(json.dumps({"size": s, "bd": bd, "sampled_waves": len(rows),

@@ -411,7 +411,8 @@ int r1_cdef_strength_search(r1_ctx *ctx, const R1Plane *rec, const R1Plane *src,
  *   units (DEVICE): the superblocks whose restoration unit holds a self-guided choice -- n_units[0]
  *     luma entries, then n_units[1] of U, then n_units[2] of V (n_units: HOST, 3 ints).  (x, y, w, h):
  *     the superblock's visible rectangle in pixels of that plane (w = vis_width, h = vis_height,
- *     rdo.rs:2415-2428; multiples of 8 >> dec), set / xqd: the choice, edges: R1_SGR_EDGE_LEFT when the
+ *     rdo.rs:2415-2428: what is filtered; the error is taken over every block of the grid it touches,
+ *     see "frame sizes" below), set / xqd: the choice, edges: R1_SGR_EDGE_LEFT when the
  *     superblock is not in column 0 of its area, R1_SGR_EDGE_ABOVE when not in row 0, sb = fby * n_sbx + fbx;
  *   cdef_cur: the area working copies as r1_cdef_apply_area leaves them (read only where an edge flag is
  *     set; any valid planes otherwise);
@@ -431,7 +432,20 @@ int r1_cdef_strength_search(r1_ctx *ctx, const R1Plane *rec, const R1Plane *src,
  * CDEF working copy of every area at once (rdo.rs:2546-2560: "keep cdef output up to date"), the input
  * of the restoration leg (rdo.rs:2575-2582).  Superblocks with index < 0 or completely skipped, and
  * skipped 8x8 blocks, are copied from rec.  Areas' borders are picture edges as in the search.  Only
- * pixels of 8x8 blocks inside the block grid are written.  scratch: r1_cdef_strength_search_scratch_bytes(). */
+ * pixels of 8x8 blocks inside the block grid are written.  An index_sb entry outside [0, n_idx) means
+ * "not filtered", like a negative one.  scratch: r1_cdef_strength_search_scratch_bytes().
+ *
+ * Frame sizes that are not multiples of 8 luma pixels.  rdo_loop_plane_error sums EVERY block of the
+ * block grid (rdo.rs:2039-2043; mi_cols = 2 * ceil(crop_w / 8), mi_rows likewise), a last block that is
+ * only partly visible included, whole.  Its pixels past the visible edge are: the source's and the
+ * reconstruction's / CDEF output's own (both cut out of the 8-aligned allocation, rdo.rs:2277-2295),
+ * and, on a plane restored inside a trial, R1_PLANE_NEW_FILL -- the restoration working copy is a fresh
+ * Plane::new (rdo.rs:2331-2341) that the filter writes inside vis_width x vis_height only.  So every
+ * plane handed to these calls must be ALLOCATED out to the block grid (width >= (mi_cols * 4) >> xdec,
+ * height >= (mi_rows * 4) >> ydec, as Frame::new makes them) and carry real pixels there; crop_w /
+ * crop_h stay the visible size.  Planes that do not reach the grid, or a grid that is not the crop's,
+ * are R1_EINVAL; a unit whose blocks leave its planes is not evaluated.  With a subsampled plane
+ * crop % 8 == 1 is not taken (the visible chroma extent no longer touches the last block column). */
 typedef struct R1TrialUnit {
   int16_t x, y, w, h;
   uint8_t set, edges;
@@ -765,6 +779,11 @@ typedef struct R1SgrSolveUnit {
  * (tests/golden/gen_loop_decision_ref.py); up to ABI 5 the kernels decided from the unit's position
  * in the FRAME, which matches the reference only for areas at the frame's left / top edge. */
 enum { R1_SGR_EDGE_LEFT = 1, R1_SGR_EDGE_ABOVE = 2 };
+/* What a pixel of rdo_loop_decision's restoration working copy holds where no filter wrote: the fill
+ * of v_frame's Plane::new, for every bit depth.  v_frame is not part of the reference tree: the value
+ * restates it (docs/PARITY.md).  One constant for product, oracle (R1O_PLANE_NEW_FILL), the fixture
+ * generator and the host driver (rav1e_amd.loop_decision.PLANE_NEW_FILL). */
+#define R1_PLANE_NEW_FILL 128
 int r1_sgrproj_solve_batch(r1_ctx *ctx, const R1Plane *cdeffed, const R1Plane *input,
                            const R1SgrSolveUnit *units, int n, int max_w, int max_h,
                            int64_t *moments_scratch, int8_t *xqd_out, void *stream);
@@ -779,9 +798,14 @@ int r1_sgrproj_solve_batch(r1_ctx *ctx, const R1Plane *cdeffed, const R1Plane *i
  *   (luma x >> 3)] (NULL: the default scale), summed and multiplied by dist_scale (fi.dist_scale[pli],
  *   Q14).
  * units[i].set = 255: the "no filter option" (rdo.rs:2617-2643): err of lrf_in itself, xqd (0, 0).
- * Units start on superblock boundaries; w % (8 >> xdec) == 0 and h % (8 >> ydec) == 0 (a visible
- * frame that is a multiple of 8 luma pixels: the reference's last blocks otherwise read its working
- * copy beyond what the filter wrote; partial blocks are left out here).  scratch: 6 int64 per pair
+ * Units start on superblock boundaries; (w, h) is the unit's VISIBLE size (rdo.rs:2651-2658): what is
+ * solved and filtered.  The error covers every block of the grid the unit touches, ceil(w / bw) x
+ * ceil(h / bh) blocks of bw x bh = (8 >> xdec) x (8 >> ydec) pixels, whole: where a last block reaches
+ * past the visible edge, `src` is read as it is, the no-filter option reads `lrf_in` as it is, and a
+ * filtered unit reads R1_PLANE_NEW_FILL (the reference's restoration working copy is never written
+ * there).  Both planes must be allocated in whole blocks out to that grid, with real pixels (Frame::new
+ * aligns to 8 luma pixels): a width / height that is not a multiple of bw / bh is R1_EINVAL, a unit
+ * whose blocks leave a plane gets err = UINT64_MAX and xqd (0, 0).  scratch: 6 int64 per pair
  * (device).  The host adds cw.fc.count_lrf_switchable's rate to err and keeps the cheapest choice
  * (compute_rd_cost, rdo.rs:718-723). */
 int r1_lrf_search_batch(r1_ctx *ctx, const R1Plane *lrf_in, const R1Plane *src,

@@ -162,7 +162,7 @@ int r1o_cdef_lrf_trial(const r1o_plane *rec, const r1o_plane *work, const r1o_pl
   const int n_sbx = (mi_cols + 15) / 16, n_sby = (mi_rows + 15) / 16, bd = p->bit_depth;
   memset(err, 0, sizeof(uint64_t) * 8 * (size_t)n_sbx * n_sby);
   if (err_planes) memset(err_planes, 0, sizeof(uint64_t) * 24 * (size_t)n_sbx * n_sby);
-  void *restored = malloc(64 * 64 * 2);
+  void *restored = malloc(64 * 64 * 2), *padded = malloc(64 * 64 * 2);
   r1o_plane saved[3];   /* whole-frame scratch planes with work's geometry: the superblock under trial, saved */
   for (int pl = 0; pl < p->planes; pl++) {
     saved[pl] = work[pl];
@@ -196,10 +196,30 @@ int r1o_cdef_lrf_trial(const r1o_plane *rec, const r1o_plane *work, const r1o_pl
             const r1o_trial_unit *u = un[pl];
             if (r1o_sgr_filter_rect(&work[pl], u->x, u->y, u->w, u->h, u->set, u->xqd, u->edges, bd, restored)) {
               free(restored);
+              free(padded);
               for (int q = 0; q < p->planes; q++) free(saved[q].data);
               return -1;
             }
-            sum = r1o_loop_plane_error_rect(&src[pl], restored, u->w, u->x, u->y, u->w, u->h, pl != 0, xdec, ydec, scales,
+            /* the restored superblock sits in the restoration working copy, a Plane::new that nothing else wrote
+             * (rdo.rs:2331-2341, 2475-2488): the blocks of the grid that reach past the visible rectangle see its fill */
+            const int bw = 8 >> xdec, bh = 8 >> ydec;
+            const int gw = (u->w + bw - 1) / bw * bw, gh = (u->h + bh - 1) / bh * bh;
+            if (gw > 64 || gh > 64 || u->x + gw > src[pl].width || u->y + gh > src[pl].height) {
+              free(restored);
+              free(padded);
+              for (int q = 0; q < p->planes; q++) free(saved[q].data);
+              return -1;
+            }
+            const int bpp = work[pl].bytes_per_px;
+            for (int y = 0; y < gh; y++)
+              for (int x = 0; x < gw; x++) {
+                const int in = x < u->w && y < u->h;
+                if (bpp == 1)
+                  ((uint8_t *)padded)[y * gw + x] = in ? ((uint8_t *)restored)[y * u->w + x] : R1O_PLANE_NEW_FILL;
+                else
+                  ((uint16_t *)padded)[y * gw + x] = in ? ((uint16_t *)restored)[y * u->w + x] : R1O_PLANE_NEW_FILL;
+              }
+            sum = r1o_loop_plane_error_rect(&src[pl], padded, gw, u->x, u->y, u->w, u->h, pl != 0, xdec, ydec, scales,
                                             scale_stride, bd);
           } else {
             /* rdo_loop_plane_error over the blocks of the superblock inside the block grid (rdo.rs:2040-2043) */
@@ -224,6 +244,7 @@ int r1o_cdef_lrf_trial(const r1o_plane *rec, const r1o_plane *work, const r1o_pl
       best[sb] = (int8_t)b;
     }
   free(restored);
+  free(padded);
   for (int pl = 0; pl < p->planes; pl++) free(saved[pl].data);
   return 0;
 }

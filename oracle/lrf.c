@@ -310,15 +310,19 @@ void r1o_sgrproj_solve(const r1o_plane *cdeffed, const r1o_plane *input, int x0,
 /* rdo_loop_plane_error's sum over the blocks of a rectangle (src/rdo.rs:2027-2093), before
  * `* fi.dist_scale[pli]`: `test` = the pixels under test, pixel (x0, y0) of the plane at test[0],
  * row stride tstride pixels.  Per 8x8-luma block: cdef_dist_kernel * bias (luma) / sse_wxh with
- * |_, _| bias on (8 >> xdec) x (8 >> ydec) pixels (chroma). */
+ * |_, _| bias on (8 >> xdec) x (8 >> ydec) pixels (chroma).
+ * EVERY block that holds a pixel of the w x h rectangle counts, whole: the reference walks the block
+ * grid (`loop_bo < blocks.cols() / rows()`, 2 * ceil(W / 8) columns), so a last block that is only
+ * partly visible is summed over all its pixels.  `test` and `src` must hold pixels out to
+ * ceil(w / bw) * bw x ceil(h / bh) * bh. */
 uint64_t r1o_loop_plane_error_rect(const r1o_plane *src, const void *test, int tstride, int x0, int y0,
                                    int w, int h, int is_chroma, int xdec, int ydec, const uint32_t *scales,
                                    int scale_stride, int bd) {
   const int bw = 8 >> xdec, bh = 8 >> ydec, hbd = src->bytes_per_px == 2;
   const size_t bpp = (size_t)src->bytes_per_px;
   uint64_t plane_sum = 0;
-  for (int by = 0; by < h / bh; by++)
-    for (int bx = 0; bx < w / bw; bx++) {
+  for (int by = 0; by < (h + bh - 1) / bh; by++)
+    for (int bx = 0; bx < (w + bw - 1) / bw; bx++) {
       const int px_ = x0 + bx * bw, py_ = y0 + by * bh;
       const uint8_t *spx = (const uint8_t *)src->data +
                            ((size_t)(src->yorigin + py_) * src->stride + src->xorigin + px_) * bpp;
@@ -374,27 +378,42 @@ int r1o_sgr_filter_rect(const r1o_plane *plane, int x0, int y0, int w, int h, in
  * the unit are pixels the filter sees: they are when the unit is not in the first unit column /
  * row of the AREA rdo_loop_decision is deciding (its scratch copy has no pixels outside the area;
  * found by executing rdo_loop_decision itself, tests/golden/gen_loop_decision_ref.py).
- * (x0, y0, w, h): the unit in pixels of THIS plane, w % (8 >> xdec) == 0 and h % (8 >> ydec) == 0
- * (the visible frame a multiple of 8 luma pixels: otherwise the reference's last blocks read the
- * working copy beyond what the filter wrote).  scales: one per 8x8 luma block of the frame (NULL:
- * the default scale).  Returns -1 on geometry it does not take. */
+ * (x0, y0, w, h): the unit's VISIBLE rectangle in pixels of THIS plane (rdo.rs:2651-2658): what is
+ * solved and filtered.  The error is taken over every block of the block grid the rectangle touches
+ * -- ceil(w / bw) x ceil(h / bh) blocks of bw x bh = (8 >> xdec) x (8 >> ydec) pixels -- so with a
+ * frame that is not a multiple of 8 luma pixels the last blocks reach past the visible edge: there
+ * the source is read as it is, the no-filter option reads lrf_in as it is (both are cut out of the
+ * 8-aligned allocation, rdo.rs:2277-2295), and a filtered unit reads R1O_PLANE_NEW_FILL: the
+ * restoration working copy is a fresh Plane::new (rdo.rs:2331-2341) that is only ever written
+ * inside the visible rectangle.  Both planes must be allocated out to that grid (width / height of
+ * the descriptor: Frame::new aligns them to 8 luma pixels).  scales: one per 8x8 luma block of the
+ * frame (NULL: the default scale).  Returns -1 on geometry it does not take. */
 int r1o_lrf_search_unit(const r1o_plane *lrf_in, const r1o_plane *src, int x0, int y0, int w, int h,
                         int set, int edges, int is_chroma, int xdec, int ydec, const uint32_t *scales,
                         int scale_stride, uint32_t dist_scale, int bd, int8_t *xqd_out,
                         uint64_t *err_out) {
   const int bw = 8 >> xdec, bh = 8 >> ydec;
-  if (w <= 0 || h <= 0 || w > IMG_MAX || w % bw || h % bh || (set != 255 && (set < 0 || set > 15))) return -1;
+  if (w <= 0 || h <= 0 || w > IMG_MAX || (set != 255 && (set < 0 || set > 15))) return -1;
   if (!is_chroma && (xdec || ydec)) return -1;
+  /* the blocks of the grid the unit touches, in pixels */
+  const int gw = (w + bw - 1) / bw * bw, gh = (h + bh - 1) / bh * bh;
+  if (x0 < 0 || y0 < 0 || x0 + gw > lrf_in->width || y0 + gh > lrf_in->height || x0 + gw > src->width ||
+      y0 + gh > src->height)
+    return -1;   /* a plane that does not reach the block grid */
   const size_t bpp = (size_t)lrf_in->bytes_per_px;
-  uint8_t *tmp = (uint8_t *)malloc((size_t)w * h * bpp);
+  uint8_t *tmp = (uint8_t *)malloc((size_t)gw * gh * bpp);
   xqd_out[0] = xqd_out[1] = 0;
   if (set == 255) {
-    for (int y = 0; y < h; y++)
-      memcpy(tmp + (size_t)y * w * bpp,
+    for (int y = 0; y < gh; y++)
+      memcpy(tmp + (size_t)y * gw * bpp,
              (const uint8_t *)lrf_in->data +
                  ((size_t)(lrf_in->yorigin + y0 + y) * lrf_in->stride + lrf_in->xorigin + x0) * bpp,
-             (size_t)w * bpp);
+             (size_t)gw * bpp);
   } else {
+    for (size_t i = 0; i < (size_t)gw * gh; i++) {   /* Plane::new */
+      if (bpp == 1) tmp[i] = R1O_PLANE_NEW_FILL;
+      else ((uint16_t *)tmp)[i] = R1O_PLANE_NEW_FILL;
+    }
     r1o_sgrproj_solve(lrf_in, src, x0, y0, w, h, set, edges, bd, xqd_out);
     const int rows = h + (h & 1) + 6;
     uint32_t *ii = (uint32_t *)calloc((size_t)IMG_STRIDE * rows * 2, sizeof(uint32_t));
@@ -404,13 +423,13 @@ int r1o_lrf_search_unit(const r1o_plane *lrf_in, const r1o_plane *src, int x0, i
     /* a plane whose pixel (x0, y0) is tmp[0] */
     r1o_plane out = *lrf_in;
     out.data = tmp;
-    out.stride = w;
+    out.stride = gw;
     out.xorigin = -x0;
     out.yorigin = -y0;
     stripe_filter(set, xqd_out, bd, ii, sq, lrf_in, &out, x0, y0, w, h);
     free(ii);
   }
-  const uint64_t plane_sum = r1o_loop_plane_error_rect(src, tmp, w, x0, y0, w, h, is_chroma, xdec, ydec, scales,
+  const uint64_t plane_sum = r1o_loop_plane_error_rect(src, tmp, gw, x0, y0, w, h, is_chroma, xdec, ydec, scales,
                                                        scale_stride, bd);
   free(tmp);
   *err_out = ((uint64_t)dist_scale * plane_sum + 8192) >> 14;            /* Distortion * dist_scale */

@@ -250,6 +250,10 @@ int r1o_lrf_filter_plane(const r1o_plane *cdeffed, const r1o_plane *deblocked, c
 /* edges of a unit of the restoration search: which of its left / upper neighbourhood exists in the
  * area rdo_loop_decision is working on (oracle/lrf.c, setup_integral_image) */
 #define R1O_SGR_EDGE_LEFT 1
+/* what a pixel of the restoration working copy holds where no filter ever wrote: v_frame's Plane::new
+ * fill (rdo.rs:2331-2341).  v_frame is not part of the reference tree: the value restates it
+ * (docs/PARITY.md), one constant for generator, oracle, product and driver. */
+#define R1O_PLANE_NEW_FILL 128
 #define R1O_SGR_EDGE_ABOVE 2
 int r1o_lrf_search_unit(const r1o_plane *lrf_in, const r1o_plane *src, int x0, int y0, int w, int h,
                         int set, int edges, int is_chroma, int xdec, int ydec, const uint32_t *scales,

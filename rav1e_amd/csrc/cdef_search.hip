@@ -137,7 +137,9 @@ __global__ __launch_bounds__(256) void k_cdef_search_pk(SearchArgs a) {
   if (MODE != 2 && all_skip) return;
   if (MODE == 1 && a.sb_sel && !a.sb_sel[sb_i]) return;
   const bool store = MODE == 2 || (MODE == 1 && ((a.sb_lrf[sb_i] >> pli) & 1));   // workgroup-uniform
-  const int apply_idx = MODE == 2 ? (all_skip ? -1 : (int)a.index_sb[sb_i]) : 0;
+  // an index outside [0, n_idx) means "not filtered": the superblock is copied from rec (as < 0)
+  const int want_idx = MODE == 2 && !all_skip ? (int)a.index_sb[sb_i] : -1;
+  const int apply_idx = MODE == 2 ? (want_idx < a.p.n_idx ? want_idx : -1) : 0;
   const R1Plane &rp = a.rec[pli], &sp = a.src[pli];
   const int n_idx = a.p.n_idx;
   const uint8_t *strengths = LUMA ? a.p.y_strengths : a.p.uv_strengths;
@@ -448,8 +450,14 @@ int search_args(r1_ctx *ctx, const R1Plane *rec, const R1Plane *src, const uint8
   R1_REQUIRE((rec[0].bytes_per_px == 1) == (p.bit_depth == 8));
   R1_REQUIRE(np == 1 || (p.xdec == 1 && p.ydec == 1) || (p.xdec == 1 && p.ydec == 0) ||
              (p.xdec == 0 && p.ydec == 0));
-  // the frame is allocated in whole 8x8 blocks (coded frame sizes are padded to 8)
-  R1_REQUIRE(mi_cols * 4 <= rec[0].width + 7 && mi_rows * 4 <= rec[0].height + 7);
+  // the block grid is the frame's: 2 * ceil(crop / 8) units of 4 pixels (FrameBlocks)
+  R1_REQUIRE(mi_cols == 2 * ((p.crop_w + 7) >> 3) && mi_rows == 2 * ((p.crop_h + 7) >> 3));
+  // every plane is allocated out to the block grid (Frame::new pads the coded size to 8 luma pixels): the errors are
+  // taken over whole blocks, a last one that is only partly visible included
+  for (int k = 0; k < np; k++) {
+    const int gw = (mi_cols * 4) >> (k ? p.xdec : 0), gh = (mi_rows * 4) >> (k ? p.ydec : 0);
+    R1_REQUIRE(rec[k].width >= gw && rec[k].height >= gh && src[k].width >= gw && src[k].height >= gh);
+  }
   a = SearchArgs{};
   for (int k = 0; k < 3; k++) {
     a.rec[k] = rec[k < np ? k : 0];
@@ -575,8 +583,10 @@ extern "C" int r1_cdef_lrf_trial_batch(r1_ctx *ctx, const R1Plane *rec, const R1
   }
   R1_REQUIRE(n_tot == 0 || (units && cdef_cur));
   if (n_tot)
-    for (int k = 0; k < np; k++)
+    for (int k = 0; k < np; k++) {
       R1_REQUIRE(cdef_cur[k].data && cdef_cur[k].bytes_per_px == bpp);
+      R1_REQUIRE(cdef_cur[k].width >= rec[k].width && cdef_cur[k].height >= rec[k].height);
+    }
   const ScratchMap m = scratch_map(mi_cols, mi_rows, np == 1 ? 0 : a.p.xdec, np == 1 ? 0 : a.p.ydec, bpp, a.p.n_idx, np);
   for (int k = 0; k < np; k++) R1_REQUIRE(m.plane_bytes[k] < (1ull << 32));   // 32-bit byte offsets in lrf.hip's tile loads
   R1DeviceGuard guard(ctx);

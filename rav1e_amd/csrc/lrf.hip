@@ -544,6 +544,18 @@ __device__ __forceinline__ unsigned long long wg_sum_u64(unsigned long long v, u
   return part4[0] + part4[1] + part4[2] + part4[3];
 }
 
+// rdo_loop_plane_error walks the BLOCK GRID (rdo.rs:2039-2043: `loop_bo < blocks.cols() / rows()`, 2 * ceil(W / 8)
+// columns), so every block a visible extent touches counts whole: the extent rounded up to blocks, in pixels (bw a
+// power of two).  Past the visible edge the source and the unfiltered input are read as they are (both cut out of the
+// 8-aligned allocation, rdo.rs:2277-2295) and a restored plane holds R1_PLANE_NEW_FILL (a fresh Plane::new that is only
+// written inside the visible rectangle, rdo.rs:2331-2341).
+__device__ __forceinline__ int grid_ext(int v, int b) { return (v + b - 1) & -b; }
+// do the planes hold the blocks of the grid a unit touches?  (x, y, w, h) = its visible rectangle
+__device__ __forceinline__ bool unit_in_grid(int x, int y, int w, int h, int bw, int bh, const R1Plane &a, const R1Plane &b) {
+  const int x1 = x + grid_ext(w, bw), y1 = y + grid_ext(h, bh);
+  return w > 0 && h > 0 && x >= 0 && y >= 0 && x1 <= a.width && y1 <= a.height && x1 <= b.width && y1 <= b.height;
+}
+
 // The restoration leg of rdo_loop_decision, per (unit, set) pair (src/rdo.rs:2575-2763): the unit
 // filtered with the weights k_sgr_solve just wrote -- sgrproj_stripe_filter on the unit's OWN padded
 // image (hard-clipped like the solve), never stored -- and rdo_loop_plane_error of the result against
@@ -560,6 +572,8 @@ __global__ __launch_bounds__(256) void k_sgr_unit_err(R1Plane lrf_in, R1Plane sr
   __shared__ uint16_t F[64][TW];
   __shared__ unsigned long long part[4];
   const R1SgrSolveUnit u = units[blockIdx.y];
+  const int bw = CHROMA ? 8 >> xdec : 8, bh = CHROMA ? 8 >> ydec : 8;
+  if (!unit_in_grid(u.x, u.y, u.w, u.h, bw, bh, lrf_in, src)) return;   // k_lrf_err_finish reports it; workgroup-uniform
   const int ntx = (u.w + TW - 1) / TW, nty = (u.h + 63) / 64;
   if ((int)blockIdx.x >= ntx * nty) return;   // workgroup-uniform
   SgrTile t;
@@ -572,12 +586,19 @@ __global__ __launch_bounds__(256) void k_sgr_unit_err(R1Plane lrf_in, R1Plane sr
   t.tw = (u.w - tx * TW) < TW ? (u.w - tx * TW) : TW;
   t.th = (u.h - ty * 64) < 64 ? (u.h - ty * 64) : 64;
   const int bd = lrf_in.bit_depth;
+  // the tile out to the block grid: TW and 64 are whole blocks, so only a unit's last tiles grow
+  const int gtw = grid_ext(t.tw, bw), gth = grid_ext(t.th, bh);
   if (u.set > 15) {
-    for (int e = threadIdx.x; e < t.th * TW; e += 256) {
+    for (int e = threadIdx.x; e < gth * TW; e += 256) {
       const int y = e / TW, x = e % TW;   // TW is a constant: no runtime division
-      if (x < t.tw) F[y][x] = (uint16_t)ld_px<BPP>(px_addr<BPP>(lrf_in, t.cx0 + x, u.y + t.ty0 + y));
+      if (x < gtw) F[y][x] = (uint16_t)ld_px<BPP>(px_addr<BPP>(lrf_in, t.cx0 + x, u.y + t.ty0 + y));
     }
   } else {
+    if (gtw != t.tw || gth != t.th)   // workgroup-uniform; the filter below writes inside t.tw x t.th only
+      for (int e = threadIdx.x; e < gth * TW; e += 256) {
+        const int y = e / TW, x = e % TW;
+        if (x < gtw && (x >= t.tw || y >= t.th)) F[y][x] = R1_PLANE_NEW_FILL;
+      }
     const int w0 = xqd[2 * blockIdx.y], w1 = xqd[2 * blockIdx.y + 1], w2 = 128 - w0 - w1;
     const int32_t pmax = (1 << bd) - 1;
     sgr_tile<BPP, 64, BPP == 1>(lrf_in, lrf_in, t, u.set, bd, nullptr, 0, 0,
@@ -589,8 +610,7 @@ __global__ __launch_bounds__(256) void k_sgr_unit_err(R1Plane lrf_in, R1Plane sr
     }, [] {});
   }
   __syncthreads();
-  const int bw = CHROMA ? 8 >> xdec : 8, bh = CHROMA ? 8 >> ydec : 8;
-  const int nbx = t.tw / bw, nby = t.th / bh;
+  const int nbx = gtw / bw, nby = gth / bh;   // ceil(t.tw / bw), ceil(t.th / bh)
   unsigned long long mine = 0;
   if ((int)threadIdx.x < nbx * nby) {
     const int by = (int)threadIdx.x / nbx, bx = (int)threadIdx.x - by * nbx;
@@ -629,17 +649,20 @@ __global__ __launch_bounds__(256, BPP == 1 ? 5 : 1) void k_lrf_search_unit(R1Pla
   const int pair = xcd_run_item(blockIdx.x, gridDim.x);   // common.hpp
   const R1SgrSolveUnit u = units[pair];
   const int bd = BPP == 1 ? 8 : lrf_in.bit_depth;
-  if (u.w > 64 || u.h > 64 || u.w <= 0 || u.h <= 0) {   // not what max_w / max_h promised: no result
+  const int bw = CHROMA ? 8 >> xdec : 8, bh = CHROMA ? 8 >> ydec : 8;
+  // not what max_w / max_h promised, or planes that do not hold the blocks the unit touches: no result
+  if (u.w > 64 || u.h > 64 || !unit_in_grid(u.x, u.y, u.w, u.h, bw, bh, lrf_in, src)) {
     if (threadIdx.x == 0) {
       err_out[pair] = ~0ull;
       xqd_out[2 * pair] = xqd_out[2 * pair + 1] = 0;
     }
     return;
   }
+  const int gw = grid_ext(u.w, bw), gh = grid_ext(u.h, bh);   // the unit out to the block grid (<= 64)
   if (u.set > 15) {
-    for (int e = threadIdx.x; e < 64 * u.h; e += 256) {
+    for (int e = threadIdx.x; e < 64 * gh; e += 256) {
       const int y = e >> 6, x = e & 63;   // rows of 64: no runtime division
-      if (x < u.w) P[y][x] = (PT)ld_px<BPP>(px_addr<BPP>(lrf_in, u.x + x, u.y + y));
+      if (x < gw) P[y][x] = (PT)ld_px<BPP>(px_addr<BPP>(lrf_in, u.x + x, u.y + y));
     }
     if (threadIdx.x == 0) xqd_out[2 * pair] = xqd_out[2 * pair + 1] = 0;
   } else {
@@ -713,6 +736,11 @@ __global__ __launch_bounds__(256, BPP == 1 ? 5 : 1) void k_lrf_search_unit(R1Pla
     __syncthreads();
     const int w0 = xq[0], w1 = xq[1], w2 = 128 - w0 - w1;
     const int32_t pmax = (1 << bd) - 1;
+    if (gw != u.w || gh != u.h)   // workgroup-uniform; never written by the filter: the working copy's initial fill
+      for (int e = threadIdx.x; e < 64 * gh; e += 256) {
+        const int y = e >> 6, x = e & 63;
+        if (x < gw && (x >= u.w || y >= u.h)) P[y][x] = (PT)R1_PLANE_NEW_FILL;
+      }
     for (int e = threadIdx.x; e < 64 * u.h; e += 256) {
       const int y = e >> 6, x = e & 63;
       if (x >= u.w) continue;
@@ -726,8 +754,7 @@ __global__ __launch_bounds__(256, BPP == 1 ? 5 : 1) void k_lrf_search_unit(R1Pla
     }
   }
   __syncthreads();
-  const int bw = CHROMA ? 8 >> xdec : 8, bh = CHROMA ? 8 >> ydec : 8;
-  const int nbx = u.w / bw, nby = u.h / bh;
+  const int nbx = gw / bw, nby = gh / bh;   // ceil(u.w / bw), ceil(u.h / bh)
   unsigned long long mine = 0;
   // rdo_loop_plane_error (rdo.rs:2027-2093), the whole workgroup on it.  Round 4 gave a block to a thread: 64 of
   // the 256 threads looped over 64 pixels each -- one-pixel global loads of the source at a stride of a plane
@@ -817,8 +844,8 @@ __global__ __launch_bounds__(256) void k_sgr_trial_err(R1Plane trial, size_t tri
   const int idx = blockIdx.z;
   // a unit that is not what the header promises (a superblock's visible rectangle inside the plane, a known parameter
   // set, a superblock of this frame) is skipped, never read or accumulated: workgroup-uniform
-  if (u.w <= 0 || u.h <= 0 || u.w > 64 || u.h > 64 || u.set > 15 || u.sb < 0 || u.sb >= n_sb || u.x < 0 || u.y < 0 ||
-      u.x + u.w > trial.width || u.y + u.h > trial.height || u.x + u.w > src.width + 7 || u.y + u.h > src.height + 7)
+  const int bw = CHROMA ? 8 >> xdec : 8, bh = CHROMA ? 8 >> ydec : 8;
+  if (u.w > 64 || u.h > 64 || u.set > 15 || u.sb < 0 || u.sb >= n_sb || !unit_in_grid(u.x, u.y, u.w, u.h, bw, bh, trial, src))
     return;
   const int ntx = (u.w + TW - 1) / TW, nty = (u.h + TR - 1) / TR;
   if ((int)blockIdx.x >= ntx * nty) return;
@@ -842,9 +869,16 @@ __global__ __launch_bounds__(256) void k_sgr_trial_err(R1Plane trial, size_t tri
     const int32_t sft = (v + (1 << 10)) >> 11;
     F[y][x] = (uint16_t)(sft < 0 ? 0 : (sft > pmax ? pmax : sft));
   }, [] {});
+  // the tile out to the block grid (TW and TR are whole blocks: only the superblock's last tiles grow): the restoration
+  // working copy was never written there
+  const int gtw = grid_ext(t.tw, bw), gth = grid_ext(t.th, bh);
+  if (gtw != t.tw || gth != t.th)   // workgroup-uniform
+    for (int e = threadIdx.x; e < gth * TW; e += 256) {
+      const int y = e / TW, x = e % TW;
+      if (x < gtw && (x >= t.tw || y >= t.th)) F[y][x] = R1_PLANE_NEW_FILL;
+    }
   __syncthreads();
-  const int bw = CHROMA ? 8 >> xdec : 8, bh = CHROMA ? 8 >> ydec : 8;
-  const int nbx = t.tw / bw, nby = t.th / bh;
+  const int nbx = gtw / bw, nby = gth / bh;   // ceil(t.tw / bw), ceil(t.th / bh)
   unsigned long long mine = 0;
   if constexpr (!CHROMA) {
     // rdo_loop_plane_error of the tile with the whole workgroup (as k_lrf_search_unit does): a thread owns an
@@ -901,10 +935,19 @@ __global__ __launch_bounds__(256) void k_sgr_trial_err(R1Plane trial, size_t tri
 }
 
 // Distortion * fi.dist_scale[pli] (rdo.rs:2092; DistortionScale::mul_u64, rdo.rs:613-615)
+// a unit whose blocks the planes do not hold has no result (as in k_lrf_search_unit)
 __global__ void k_lrf_err_finish(const unsigned long long *__restrict__ acc, int n, uint32_t dist_scale,
-                                 unsigned long long *__restrict__ err) {
+                                 const R1SgrSolveUnit *__restrict__ units, R1Plane lrf_in, R1Plane src, int bw, int bh,
+                                 int8_t *__restrict__ xqd, unsigned long long *__restrict__ err) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) err[i] = ((unsigned long long)dist_scale * acc[i] + 8192) >> 14;
+  if (i >= n) return;
+  const R1SgrSolveUnit u = units[i];
+  if (unit_in_grid(u.x, u.y, u.w, u.h, bw, bh, lrf_in, src)) {
+    err[i] = ((unsigned long long)dist_scale * acc[i] + 8192) >> 14;
+  } else {
+    err[i] = ~0ull;
+    xqd[2 * i] = xqd[2 * i + 1] = 0;
+  }
 }
 
 }  // namespace
@@ -1007,6 +1050,9 @@ extern "C" int r1_lrf_search_batch(r1_ctx *ctx, const R1Plane *lrf_in, const R1P
   R1_REQUIRE(max_w > 0 && max_h > 0 && max_w <= 384 && max_h <= 384);
   R1_REQUIRE(xdec >= 0 && xdec <= 1 && ydec >= 0 && ydec <= 1 && (is_chroma || (!xdec && !ydec)));
   R1_REQUIRE(!scales || scale_stride > 0);
+  // the error walks the block grid: planes allocated in whole blocks (Frame::new aligns to 8 luma pixels)
+  const int bw = is_chroma ? 8 >> xdec : 8, bh = is_chroma ? 8 >> ydec : 8;
+  R1_REQUIRE(lrf_in->width % bw == 0 && lrf_in->height % bh == 0 && src->width % bw == 0 && src->height % bh == 0);
   if (n <= 0) return R1_OK;
   R1_REQUIRE(units && scratch && xqd_out && err_out);
   hipStream_t st = (hipStream_t)stream;
@@ -1046,8 +1092,8 @@ extern "C" int r1_lrf_search_batch(r1_ctx *ctx, const R1Plane *lrf_in, const R1P
     if (is_chroma) R1_LRF_ERR(2, true); else R1_LRF_ERR(2, false);
   }
 #undef R1_LRF_ERR
-  hipLaunchKernelGGL(k_lrf_err_finish, dim3((n + 127) / 128), dim3(128), 0, st, acc, n, dist_scale,
-                     (unsigned long long *)err_out);
+  hipLaunchKernelGGL(k_lrf_err_finish, dim3((n + 127) / 128), dim3(128), 0, st, acc, n, dist_scale, units, *lrf_in, *src,
+                     bw, bh, xqd_out, (unsigned long long *)err_out);
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }

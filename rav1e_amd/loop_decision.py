@@ -23,6 +23,9 @@ import numpy as np
 
 from . import rdo_glue as RG
 
+# the fill of v_frame's Plane::new = what the restoration working copy holds where no filter wrote (include/rav1e_amd.h:
+# R1_PLANE_NEW_FILL; restated, not executed: docs/PARITY.md).  The backends apply it; the driver only names the grid
+PLANE_NEW_FILL = 128
 SGR_SETS = {"Full": tuple(range(16)), "Reduced": (1, 3, 5, 7, 9, 11, 13, 15)}   # src/lrf.rs:76-93
 
 
@@ -32,6 +35,11 @@ class LoopDecision:
         """skip_mi: (mi_rows, mi_cols) numpy uint8 (Block::skip per 4x4); rate_fn(pli, None | (set, xqd0, xqd1)) ->
         cw.fc.count_lrf_switchable in 1/8 bit; lam: fi.lambda"""
         self.b, self.W, self.H, self.xdec, self.ydec = backend, width, height, xdec, ydec
+        # The backends take a rectangle's VISIBLE size and sum the error over every block of the grid it touches
+        # (rdo.rs:2039-2043).  With a subsampled plane and a size of 8 k + 1 the visible chroma extent (W >> 1 = 4 k)
+        # stops short of the grid's last block column, which the reference still sums: not modelled
+        if (xdec and width % 8 == 1) or (ydec and height % 8 == 1):
+            raise ValueError("frame size %d x %d: 8 k + 1 with a subsampled plane is not taken" % (width, height))
         self.lam, self.rate_fn, self.n_idx, self.sets = float(lam), rate_fn, n_idx, tuple(sgr_sets)
         self.enable_cdef, self.enable_restoration = enable_cdef, enable_restoration
         assert lru_on_skip, "speed settings with lru_on_skip = false are not modelled (every preset sets it)"

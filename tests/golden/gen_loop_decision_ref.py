@@ -39,7 +39,15 @@ Cases, in the formats the existing tests read:
   restoration working copy; value in _trace_err), 1 = solve (set, px, py, vis_w, vis_h, xqd0 * 256 + (xqd1 & 255)),
   2 = cdef_filter_superblock (loop_sbx, loop_sby, index), 3 = area start (sbx0, sby0)
 
-Run in the build container:  python tests/golden/gen_loop_decision_ref.py      (about 3 minutes)
+Frames that are not a multiple of 8 wide / high (ldl4-6, ldc3-4, ldb3-5) go to loop_decision_crop_ref.npz, same keys:
+<c>_meta's W / H = fi.width / fi.height, the planes (_in / _rec / _src) are stored out to the 8-aligned allocation
+(Frame::new) -- the strip of the reconstruction past the visible edge holds content of its own -- and <c>_fill = the
+value of a fresh Plane::new, which the partly visible blocks of a restored plane are compared against (v_frame is not
+in the reference tree: tools/rustlite/runtime.py restates it, docs/PARITY.md).  rows' w / h and the solves' sizes are
+the VISIBLE sizes; the errors are the reference's, over every block of the grid.
+
+Run in the build container:  python tests/golden/gen_loop_decision_ref.py      (about 15 minutes; a full run asserts
+that every array of the committed loop_decision_ref.npz comes out bit-identical and leaves that file alone)
 """
 import os
 import time
@@ -68,7 +76,30 @@ CASES = [
     # CDEF output left of / above itself)
     ("ldb1", 136, 72, 1, 1, 10, 100, "Reduced", 2, 0.25, 400.0),
     ("ldb2", 192, 128, 1, 1, 8, 180, "Reduced", 1, 0.2, 90.0),
+    # frame sizes that are NOT multiples of 8 (854x480, 1366x768 scaled down): the planes are allocated to the 8-aligned
+    # size as Frame::new does (tiler.rs:64-65, encoder.rs:852-853), fi.width / fi.height stay as they are.  The last
+    # block column / row of the block grid is partly outside the visible frame: rdo_loop_plane_error sums it all the
+    # same, reading the source and the CDEF output out to the grid and, on a restored plane, Plane::new's fill where
+    # the filter never wrote.  Remainders 2 / 6: a partial 4x4 chroma block under 4:2:0 as well
+    # The restoration leg clips a unit to unit_size (rdo.rs:2651-2658) and has_restoration_unit(.., stretch = false) leaves
+    # out the superblocks a last unit is stretched over, so a partly visible block is RESTORED only where the frame's
+    # remainder is a unit of its own: more than half a unit (166 = 2 * 64 + 38, chroma 83 = 2 * 32 + 19; 102 = 64 + 38)
+    ("ldl4", 166, 102, 1, 1, 8, 100, "Reduced", 0, 0.0, 90.0),      # both
+    ("ldl5", 166, 72, 1, 1, 10, 100, "Reduced", 0, 0.0, 400.0),     # W only
+    ("ldl6", 102, 102, 0, 0, 8, 100, "Reduced", 0, 0.0, 60.0),      # 4:4:4, both
+    ("ldc3", 136, 102, 1, 1, 8, 100, "Full", 2, 0.3, 90.0),         # H only
+    ("ldc4", 150, 76, 1, 1, 10, 100, "Full", 2, 0.3, 400.0),        # both (854 x 480 scaled down)
+    ("ldb3", 166, 102, 1, 1, 8, 100, "Reduced", 2, 0.25, 90.0),
+    ("ldb4", 102, 166, 1, 1, 10, 100, "Reduced", 2, 0.25, 400.0),
+    # qindex 180: 128-pixel luma units, one area of 4 x 3 superblocks.  198 = 128 + 70: the partial column is in a luma
+    # unit of its own, 70 wide (and in the one chroma unit, 99 wide); 134 = 128 + 6: the partial row belongs to units
+    # STRETCHED over the frame's remainder -- not restored, measured on the CDEF output
+    ("ldb5", 198, 134, 1, 1, 8, 180, "Reduced", 1, 0.2, 90.0),
 ]
+PLANE_NEW_FILL = 128      # v_frame's Plane::new fill as tools/rustlite/runtime.py restates it (NOT executed text: docs/PARITY.md)
+
+
+CROPPED = {c[0] for c in CASES if c[1] % 8 or c[2] % 8}
 
 
 def crate():
@@ -194,7 +225,19 @@ def main():
         g["U"] = g["T"]
         dt = L.np_dtype(bd)
         cs = L.enum(c, "ChromaSampling", {(1, 1): "Cs420", (1, 0): "Cs422", (0, 0): "Cs444"}[(xdec, ydec)])
-        src, rec = images(rng, ci, W, H, xdec, ydec, bd)
+        # Frame::new: planes allocated to the next multiple of 8 luma pixels, the tile covers all of it
+        Wa, Ha = (W + 7) // 8 * 8, (H + 7) // 8 * 8
+        src, rec = images(rng, ci, Wa, Ha, xdec, ydec, bd)
+        if (Wa, Ha) != (W, H):
+            # the strip between the visible edge and the aligned edge of rec: content of its own (no rng: the draws of
+            # the cases above stay as they were), far from a replica of the edge
+            for pl in range(3):
+                xd, yd = (0, 0) if pl == 0 else (xdec, ydec)
+                vw, vh = W >> xd, H >> yd
+                yy, xx = np.mgrid[0:rec[pl].shape[0], 0:rec[pl].shape[1]]
+                alt = np.clip(rec[pl] + ((((xx * 5 + yy * 3) % 7) - 3) * 9 << (bd - 8)), 0, (1 << bd) - 1)
+                out_vis = (xx >= vw) | (yy >= vh)
+                rec[pl] = np.where(out_vis, alt, rec[pl])
 
         def mk(a, pl):
             xd, yd = (0, 0) if pl == 0 else (xdec, ydec)
@@ -203,7 +246,7 @@ def main():
             return p
         rec_frame = Frame(planes=R.RSlice([mk(rec[p], p) for p in range(3)]))
         in_frame = Frame(planes=R.RSlice([mk(src[p], p) for p in range(3)]))
-        rect = TileRect(x=0, y=0, width=W, height=H)
+        rect = TileRect(x=0, y=0, width=Wa, height=Ha)
         sbw, sbh = (W + 63) // 64, (H + 63) // 64
         gw, gh = (W + 7) // 8, (H + 7) // 8
         grid = rng.integers(1 << 12, 1 << 16, (gh, gw)).astype(np.uint32)
@@ -235,7 +278,7 @@ def main():
         for y in range(mi_rows):
             for x in range(mi_cols):
                 fb.blocks[y * mi_cols + x].skip = bool(skip[y, x])
-        ts = Obj(sbo=PSBO(SBO(x=0, y=0)), sb_size_log2=6, sb_width=sbw, sb_height=sbh, width=W, height=H,
+        ts = Obj(sbo=PSBO(SBO(x=0, y=0)), sb_size_log2=6, sb_width=sbw, sb_height=sbh, width=Wa, height=Ha,
                  rec=TileMut_new(g, rec_frame, rect), input_tile=Tile_new(g, in_frame, rect),
                  restoration=TRSM_new({}, rs, PSBO(SBO(x=0, y=0)), sbw, sbh),
                  integral_buffer=IIB({}, c.const_value("SOLVE_IMAGE_SIZE")), deblock=None)
@@ -285,6 +328,9 @@ def main():
             for sx in range(sbw):
                 best[sy, sx] = int(fb.blocks[(sy * 16) * mi_cols + sx * 16].cdef_index) if kind in "cb" else -1
         out[name + "_geo"] = np.array(geo, np.int32)
+        if (Wa, Ha) != (W, H):
+            assert R.Plane.new(8, 8, 0, 0, 0, 0).data[0] == PLANE_NEW_FILL
+            out[name + "_fill"] = np.array([PLANE_NEW_FILL], np.int32)
         out[name + "_q"] = np.array([q, 1 if sgr == "Full" else 0], np.int32)      # base_q_idx, all 16 sets / the reduced 8
         out[name + "_areas"] = np.array(areas, np.int32)
         out[name + "_rate"] = np.array([RATE_NONE, RATE_SGR, RATE_PER_SET], np.int32)
@@ -382,7 +428,20 @@ def main():
                 out[name + "_best_final"], out[name + "_choice"] = best, np.array(choice, np.int32)
         print(name, W, H, bd, "geo", geo, "areas", len(areas), "events", len(tr), "best", best.ravel().tolist(),
               "choices", [tuple(r[3:]) for r in choice][:6], "%.0f s" % (time.time() - t0), flush=True)
-    L.save("loop_decision_ref.npz", out)
+    # the cropped cases go into a file of their own (no committed file grows); the old file's arrays must come out
+    # bit-identical
+    old = {k: v for k, v in out.items() if k.split("_")[0] not in CROPPED}
+    new = {k: v for k, v in out.items() if k.split("_")[0] in CROPPED}
+    if not only:
+        was = np.load(os.path.join(L.HERE, "loop_decision_ref.npz"))
+        assert sorted(was.files) == sorted(old), "the set of arrays of loop_decision_ref.npz changed"
+        for k in was.files:
+            assert was[k].dtype == old[k].dtype and np.array_equal(was[k], old[k]), "array %s changed" % k
+        print("loop_decision_ref.npz: all %d arrays bit-identical to the committed file" % len(old))
+    if old and (only or os.environ.get("R1_GOLDEN_OUT")):      # a full run in place leaves the committed file alone
+        L.save("loop_decision_ref.npz", old)
+    if new:
+        L.save("loop_decision_crop_ref.npz", new)
 
 
 if __name__ == "__main__":

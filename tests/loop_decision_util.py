@@ -11,12 +11,30 @@ import oracle_lib as O
 from rav1e_amd import loop_decision as LD
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "loop_decision_ref.npz")
+# the cases whose frame is not a multiple of 8 wide / high: planes stored out to the 8-aligned allocation, <c>_meta's
+# W / H = fi.width / fi.height
+GOLD_CROP = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "loop_decision_crop_ref.npz")
 TRIAL_UNIT = np.dtype([("x", "<i2"), ("y", "<i2"), ("w", "<i2"), ("h", "<i2"), ("set", "u1"), ("edges", "u1"),
                        ("xqd", "i1", (2,)), ("sb", "<i4")])       # r1o_trial_unit == R1TrialUnit
 
 
+class _Cases:
+    """the arrays of both fixture files under one roof, as np.load hands them out (`.files`, `[key]`)"""
+
+    def __init__(self, *paths):
+        self._z = [np.load(p) for p in paths]
+        self.files = [k for z in self._z for k in z.files]
+        assert len(set(self.files)) == len(self.files)
+
+    def __getitem__(self, k):
+        for z in self._z:
+            if k in z.files:
+                return z[k]
+        raise KeyError(k)
+
+
 def load():
-    return np.load(GOLD)
+    return _Cases(GOLD, GOLD_CROP)
 
 
 def both_cases(L):
@@ -204,9 +222,13 @@ def check_one_filter_cases(L, make_backend):
 
 def synthetic_case(W, H, xdec, ydec, bd, q, seed, n_idx=4, p_skip=0.2, noise=6):
     """a frame the fixtures do not have, in the form `driver` / the backends take: smooth source + coding noise, random
-    skip flags (one superblock completely skipped), random strengths, scale grid and plane scales, the stated rate"""
+    skip flags (one superblock completely skipped), random strengths, scale grid and plane scales, the stated rate.
+    W, H = fi.width, fi.height: the planes are allocated to the next multiple of 8 luma pixels as Frame::new does, and
+    the strip of the reconstruction past the visible edge carries content of its own (not a replica of the edge)"""
     from rav1e_amd import rdo_glue as RG
     rng = np.random.default_rng(seed)
+    vis_w, vis_h = W, H
+    W, H = (W + 7) // 8 * 8, (H + 7) // 8 * 8
     yy, xx = np.mgrid[0:H, 0:W]
     mx = (1 << bd) - 1
     base = ((np.sin(xx / 7.0) + np.cos((yy + 2 * xx) / 11.0)) * 45 + 128) * (1 << (bd - 8))
@@ -216,6 +238,13 @@ def synthetic_case(W, H, xdec, ydec, bd, q, seed, n_idx=4, p_skip=0.2, noise=6):
         src.append(np.clip(src[0][::1 << ydec, ::1 << xdec][:chh, :cw] // (k + 1) + (30 << (bd - 8)) * k, 0, mx))
     rec = [np.clip(p + rng.integers(-noise << (bd - 8), (noise << (bd - 8)) + 1, p.shape) * (rng.random(p.shape) < 0.6), 0, mx)
            for p in src]
+    if (W, H) != (vis_w, vis_h):
+        for k in range(3):
+            xd, yd = (0, 0) if k == 0 else (xdec, ydec)
+            py, px = np.mgrid[0:rec[k].shape[0], 0:rec[k].shape[1]]
+            alt = np.clip(rec[k] + ((((px * 5 + py * 3) % 7) - 3) * 9 << (bd - 8)), 0, mx)
+            rec[k] = np.where((px >= vis_w >> xd) | (py >= vis_h >> yd), alt, rec[k])
+    W, H = vis_w, vis_h
     c = {"rec": [O.plane_from_image(p, bd, 16, 16) for p in rec], "src": [O.plane_from_image(p, bd, 16, 16) for p in src]}
     gw, gh = (W + 7) // 8, (H + 7) // 8
     skip = (rng.random((2 * gh, 2 * gw)) < p_skip).astype(np.uint8)

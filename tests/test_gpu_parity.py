@@ -1659,7 +1659,8 @@ def test_sgrproj_solve_ref(ctx, bd):
 
 
 def _lrf_search_cases():
-    L = np.load(os.path.join(GOLD, "loop_decision_ref.npz"))
+    import loop_decision_util as U
+    L = U.load()      # + loop_decision_crop_ref.npz: frames that are not a multiple of 8 wide / high
     return ["s0", "s1", "s2", "s3"] + sorted(k[:-5] for k in L.files if k.startswith("ldl") and k.endswith("_meta"))
 
 
@@ -1674,7 +1675,11 @@ def test_lrf_search_ref(ctx, case):
     left of / above themselves are that function's)"""
     import torch
     from rav1e_amd.api import SGR_SOLVE_UNIT
-    REF = np.load(os.path.join(GOLD, "loop_decision_ref.npz" if case.startswith("ld") else "lrf_search_ref.npz"))
+    if case.startswith("ld"):
+        import loop_decision_util as U
+        REF = U.load()
+    else:
+        REF = np.load(os.path.join(GOLD, "lrf_search_ref.npz"))
     W, H, xdec, ydec, bd, lru_sb = [int(v) for v in REF[case + "_meta"]]
     rows, want = REF[case + "_rows"], REF[case + "_err"]
     edges = REF[case + "_edges"] if case + "_edges" in REF.files else np.full(len(rows), 3, np.uint8)

@@ -555,15 +555,25 @@ def test_me_ref_tile_motion_and_block_searches(ctx, name, launch_mode):
 
 
 # ---- a14: the CDEF strength search against the executed reference (gen_cdef_search_ref.py) ----
+# loop_decision_crop_ref.npz: frames that are not a multiple of 8 wide / high (planes stored out to the 8-aligned size)
+LOOP_FILES = ("loop_decision_ref.npz", "loop_decision_crop_ref.npz")
+
+
 def _cdef_search_file(name):
     # ldc* / ldb*: the CDEF leg as rdo_loop_decision ITSELF, executed whole, ran it (gen_loop_decision_ref.py)
-    return os.path.join(GOLD, "loop_decision_ref.npz" if name.startswith("ld") else "cdef_search_ref.npz")
+    if not name.startswith("ld"):
+        return os.path.join(GOLD, "cdef_search_ref.npz")
+    for f in LOOP_FILES:
+        if name + "_meta" in np.load(os.path.join(GOLD, f)).files:
+            return os.path.join(GOLD, f)
+    raise KeyError(name)
 
 
 def _cdef_search_cases():
-    S, L = np.load(os.path.join(GOLD, "cdef_search_ref.npz")), np.load(os.path.join(GOLD, "loop_decision_ref.npz"))
+    S = np.load(os.path.join(GOLD, "cdef_search_ref.npz"))
     return sorted(k[:-5] for k in S.files if k.endswith("_meta")) + \
-        sorted(k[:-5] for k in L.files if k.startswith(("ldc", "ldb")) and k.endswith("_meta"))
+        sorted(k[:-5] for f in LOOP_FILES for k in np.load(os.path.join(GOLD, f)).files
+               if k.startswith(("ldc", "ldb")) and k.endswith("_meta"))
 
 
 def run_cdef_search_gpu(ctx, rec, src, skip, scales, prm):

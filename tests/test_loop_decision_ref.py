@@ -5,17 +5,20 @@ those legs are (tests/test_oracle_lrf.py, tests/test_oracle_cdef_search.py, and 
 around r1_lrf_search_batch -- which units a frame has and in which order, their visible sizes, which of them see
 pixels left of / above themselves (R1SgrSolveUnit.edges), the cost of an option and the choice -- rav1e_amd.rdo_glue
 against what the executed function did."""
-import os
 
 import numpy as np
 import pytest
 
 from rav1e_amd import rdo_glue as RG
 
-L = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "loop_decision_ref.npz"))
+import loop_decision_util as U   # noqa: E402
+
+# both files: loop_decision_ref.npz and the cases whose frame is not a multiple of 8 (loop_decision_crop_ref.npz)
+L = U.load()
 LRF_CASES = sorted(k[:-5] for k in L.files if k.startswith("ldl") and k.endswith("_meta"))
 # base_q_idx of the cases (gen_loop_decision_ref.py, CASES): the unit sizes follow from it
-Q = {"ldl0": 100, "ldl1": 180, "ldl2": 100, "ldl3": 100}
+Q = {c: int(L[c + "_q"][0]) for c in LRF_CASES}
+assert {k: Q[k] for k in ("ldl0", "ldl1", "ldl2", "ldl3")} == {"ldl0": 100, "ldl1": 180, "ldl2": 100, "ldl3": 100}
 
 
 @pytest.mark.parametrize("case", LRF_CASES)
@@ -101,8 +104,6 @@ def test_the_both_filters_trace_alternates_the_legs_as_the_integration_notes_say
 
 
 # ---- round 6: the whole iteration, both filters on, through the host driver (rav1e_amd/loop_decision.py) ----
-import loop_decision_util as U   # noqa: E402
-
 BOTH = U.both_cases(L)
 
 
@@ -139,3 +140,37 @@ def test_driver_with_one_filter_enabled_on_the_oracle():
     """speed settings with only CDEF (ldc0-2) or only restoration (ldl0-3): the same driver, enable_restoration / enable_cdef
     off, against the executed function -- every error in call order, every pick and choice"""
     assert U.check_one_filter_cases(L, lambda c: U.OracleBackend(c)) > 300
+
+
+def test_the_fill_of_a_fresh_plane_is_one_number_everywhere():
+    """what a partly visible block sees on a restored plane (Plane::new's fill; restated, docs/PARITY.md): the header,
+    the oracle, the driver and every fixture case that depends on it name the same value"""
+    import os
+    import re
+    from rav1e_amd import loop_decision as LD
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    got = {LD.PLANE_NEW_FILL}
+    for f, name in (("include/rav1e_amd.h", "R1_PLANE_NEW_FILL"), ("oracle/r1_oracle.h", "R1O_PLANE_NEW_FILL")):
+        m = re.findall(r"#define %s (\d+)" % name, open(os.path.join(root, f)).read())
+        assert len(m) == 1, f
+        got.add(int(m[0]))
+    fills = [int(L[k][0]) for k in L.files if k.endswith("_fill")]
+    assert len(fills) == 8 and got | set(fills) == {128}
+    # ... and those are exactly the cases whose frame is not a multiple of 8
+    crop = {k[:-5] for k in L.files if k.endswith("_meta") and (L[k][0] % 8 or L[k][1] % 8)}
+    assert crop == {k[:-5] for k in L.files if k.endswith("_fill")}
+    for c in crop:       # planes stored out to the 8-aligned allocation
+        W, H = int(L[c + "_meta"][0]), int(L[c + "_meta"][1])
+        assert L[c + "_src0"].shape == ((H + 7) // 8 * 8, (W + 7) // 8 * 8)
+
+
+def test_driver_refuses_the_sizes_it_does_not_model():
+    """8 k + 1 with a subsampled plane: the visible chroma extent stops short of the grid's last block column, which
+    the reference still sums -- refused, not floored"""
+    from rav1e_amd import loop_decision as LD
+    skip = np.zeros((2 * 10, 2 * 9), np.uint8)
+    for (w, h, xd, yd) in ((65, 80, 1, 1), (72, 73, 1, 1), (65, 80, 1, 0)):
+        with pytest.raises(ValueError):
+            LD.LoopDecision(None, w, h, xd, yd, 100, skip, 90.0, lambda p, f: 0, 4, LD.SGR_SETS["Reduced"])
+    LD.LoopDecision(None, 72, 73, 1, 0, 100, skip, 90.0, lambda p, f: 0, 4, LD.SGR_SETS["Reduced"])     # 4:2:2: full height
+    LD.LoopDecision(None, 65, 73, 0, 0, 100, np.zeros((20, 18), np.uint8), 90.0, lambda p, f: 0, 4, LD.SGR_SETS["Reduced"])

@@ -132,8 +132,11 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 SEARCH = dict(np.load(os.path.join(GOLDEN, "lrf_search_ref.npz")))
 # + the restoration-only cases of loop_decision_ref.npz: the same rows, but made by EXECUTING rdo_loop_decision itself
 # (gen_loop_decision_ref.py) instead of a hand-stated loop around its callees
-LOOP = np.load(os.path.join(GOLDEN, "loop_decision_ref.npz"))
-SEARCH.update({k: LOOP[k] for k in LOOP.files if k.startswith("ldl")})
+# (loop_decision_crop_ref.npz: frames that are not a multiple of 8 wide / high -- w, h are the units' VISIBLE sizes, the
+# planes are stored out to the 8-aligned allocation and the errors include the partly visible blocks)
+for f in ("loop_decision_ref.npz", "loop_decision_crop_ref.npz"):
+    LOOP = np.load(os.path.join(GOLDEN, f))
+    SEARCH.update({k: LOOP[k] for k in LOOP.files if k.startswith("ldl")})
 
 
 def search_cases():
@@ -166,12 +169,25 @@ def test_lrf_search_units_equal_the_executed_reference(oracle, case):
 
 
 def test_lrf_search_rejects_partial_blocks(oracle):
-    a = np.full((64, 64), 100, np.int64)
-    p = O.plane_from_image(a, 8, 16, 16)
-    c = p.cstruct()
+    """A width / height that cuts a block is the unit's VISIBLE size: taken where the planes are allocated out to the
+    block grid (the cut block counts whole: source and unfiltered input as they are, a filtered unit sees
+    R1O_PLANE_NEW_FILL = 128 where the filter did not write), refused where the allocation stops short of the grid."""
     xqd, err = np.zeros(2, np.int8), np.zeros(1, np.uint64)
-    args = lambda w, h, s: (C.byref(c), C.byref(c), 0, 0, w, h, s, 0, 0, 0, 0, None, 0, 1 << 14, 8, xqd.ctypes.data,
-                            err.ctypes.data)
-    assert oracle.r1o_lrf_search_unit(*args(60, 64, 3)) == -1      # a width that cuts an 8x8 block
-    assert oracle.r1o_lrf_search_unit(*args(64, 64, 16)) == -1     # no such parameter set
-    assert oracle.r1o_lrf_search_unit(*args(64, 64, 255)) == 0 and int(err[0]) == 0   # identical planes
+
+    def run(plane, w, h, s):
+        c = plane.cstruct()
+        return oracle.r1o_lrf_search_unit(C.byref(c), C.byref(c), 0, 0, w, h, s, 0, 0, 0, 0, None, 0, 1 << 14, 8,
+                                          xqd.ctypes.data, err.ctypes.data)
+    p100 = O.plane_from_image(np.full((64, 64), 100, np.int64), 8, 16, 16)
+    p128 = O.plane_from_image(np.full((64, 64), 128, np.int64), 8, 16, 16)
+    short = O.plane_from_image(np.full((64, 60), 100, np.int64), 8, 16, 16)
+    assert run(short, 60, 64, 3) == -1 and run(short, 60, 64, 255) == -1      # the plane ends inside the last block column
+    assert run(O.plane_from_image(np.full((60, 64), 100, np.int64), 8, 16, 16), 64, 60, 3) == -1      # ... block row
+    assert run(p100, 64, 64, 16) == -1                                        # no such parameter set
+    assert run(p100, 64, 64, 255) == 0 and int(err[0]) == 0                   # identical planes
+    assert run(p100, 60, 64, 255) == 0 and int(err[0]) == 0                   # ... out to the grid
+    assert run(p100, 64, 64, 3) == 0 and int(err[0]) == 0                     # a flat unit filters to itself
+    assert run(p128, 60, 60, 3) == 0 and int(err[0]) == 0                     # the fill equals the flat source
+    assert run(p100, 60, 64, 3) == 0 and int(err[0]) > 0                      # 4 columns of 128 against 100
+    e_w = int(err[0])
+    assert run(p100, 60, 60, 3) == 0 and int(err[0]) > e_w                    # + 4 rows

@@ -373,15 +373,15 @@ __global__ __launch_bounds__(256) void k_cdef_search_pk(SearchArgs a) {
     if (!(r[0] & 1)) return;
     const uint32_t *ap = acc + (tb * 8 + tidx) * 3;
     const uint32_t bias = r[1];
-    const unsigned long long d = r1dist::cdef_tile_tail(acc[32 * 8 * 3 + tb * 2], ap[0], acc[32 * 8 * 3 + tb * 2 + 1], ap[1],
-                                                        ap[2], 64, 0, 0, &bias, 0, bd);
+    const r1dist::CdefMoments m{acc[32 * 8 * 3 + tb * 2], ap[0], acc[32 * 8 * 3 + tb * 2 + 1], ap[1], ap[2]};
+    const unsigned long long d = r1dist::cdef_tile_tail(m, 64, 0, 0, &bias, 0, bd);
     atomicAdd(&ps[tidx * 3 + 0], d);
   } else {
     if (tb >= NB) return;
     const uint32_t *r = rec + tb * SR_REC;
     if (!(r[0] & 1)) return;
     const uint32_t bias = r[1];
-    // sse_wxh with a constant bias: 4x4 cells, each (sse * bias + 128) >> 8, the block's sum through
+    // sse_wxh with a constant bias: 4x4 cells, each weighted by it (wsse_cell), the block's sum through
     // get_weighted_sse's (sum + 32) / 64 (rdo.rs:177-224, dist.rs:234-283)
     const int cx0 = (tb % NBX) * (xs / 4), cy0 = (tb / NBX) * (ys / 4);
     unsigned long long w = 0;
@@ -389,7 +389,7 @@ __global__ __launch_bounds__(256) void k_cdef_search_pk(SearchArgs a) {
     for (int cy = 0; cy < ys / 4; cy++)
 #pragma unroll
       for (int cx = 0; cx < xs / 4; cx++)
-        w += ((unsigned long long)acc[((cy0 + cy) * 8 + cx0 + cx) * 8 + tidx] * bias + 128) >> 8;
+        w += r1dist::wsse_cell(acc[((cy0 + cy) * 8 + cx0 + cx) * 8 + tidx], bias);
     atomicAdd(&ps[tidx * 3 + pli], (w + 32) >> 6);
   }
 }
@@ -404,7 +404,7 @@ __global__ __launch_bounds__(64) void k_cdef_search_final(SearchArgs a, unsigned
   unsigned long long e = 0;
   if (lane < 8 && lane < a.p.n_idx && !skip)
     for (int pl = 0; pl < a.p.planes; pl++) {
-      const unsigned long long ep = ((unsigned long long)a.p.dist_scale[pl] * a.psum[sb * 24 + lane * 3 + pl] + 8192) >> 14;
+      const unsigned long long ep = r1dist::dist_scale_mul(a.p.dist_scale[pl], a.psum[sb * 24 + lane * 3 + pl]);
       if (err_planes) err_planes[sb * 24 + lane * 3 + pl] = ep;
       e += ep;
     }

@@ -436,8 +436,8 @@ TwoBlocks upload_pair(r1_ctx *c, const void *src, ptrdiff_t ss, const void *dst,
   return t;
 }
 
-// WeightedSseFn (src/asm/x86/dist/sse.rs:18-34): the raw sum over 4x4 cells of
-// (cell_sse * scale + 128) >> 8; `scale_stride` in BYTES like every asm stride (sse.rs:113)
+// WeightedSseFn (src/asm/x86/dist/sse.rs:18-34): the raw sum over 4x4 cells of the scaled cell
+// (r1dist::wsse_cell); `scale_stride` in BYTES like every asm stride (sse.rs:113)
 uint64_t wsse_shim(const void *src, ptrdiff_t ss, const void *dst, ptrdiff_t ds, const uint32_t *scale,
                    ptrdiff_t scale_stride_bytes, int w, int h, int bpp) {
   std::lock_guard<std::mutex> lk(g_mu);

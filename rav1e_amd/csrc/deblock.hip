@@ -340,16 +340,8 @@ __device__ __forceinline__ void deblock_sse_walk(const R1Plane &rec, const R1Pla
   }
   }
   {
-    uint32_t lo = (uint32_t)none_sum, hi = (uint32_t)((unsigned long long)none_sum >> 32);
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) {
-      const unsigned long long o = ((unsigned long long)(uint32_t)__shfl_xor((int)hi, m, 64) << 32) |
-                                   (uint32_t)__shfl_xor((int)lo, m, 64);
-      const unsigned long long t = (((unsigned long long)hi << 32) | lo) + o;
-      lo = (uint32_t)t;
-      hi = (uint32_t)(t >> 32);
-    }
-    if ((threadIdx.x & 63) == 0 && (lo | hi)) atomicAdd(&tally[0], ((unsigned long long)hi << 32) | lo);
+    const unsigned long long t = xor_sum_u64((unsigned long long)none_sum, WAVE);
+    if ((threadIdx.x & 63) == 0 && t) atomicAdd(&tally[0], t);
   }
   __syncthreads();
   for (int k = threadIdx.x; k < MAX_LF + 2; k += 256)

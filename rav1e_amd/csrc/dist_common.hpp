@@ -1,5 +1,14 @@
 // dist_common.hpp -- the per-tile SAD / SATD arithmetic shared by dist.hip
-// (candidates from HBM) and me.hip (sub-pel candidates predicted into LDS).
+// (candidates from HBM) and me.hip (sub-pel candidates predicted into LDS), and
+// the reference's pixel-domain distortion arithmetic, each rule stated once for
+// every kernel that needs it (dist_scaled.hip, the fused candidate kernel,
+// lrf.hip, cdef_search.hip):
+//   CdefMoments       cdef_dist_kernel's five sums: add / xor_sum / store / load
+//   cdef_tile_vars    its fixed-point tail -> (svar, dvar, sse)
+//   cdef_tile_tail    ... + apply_ssim_boost + the block's DistortionScale
+//   dist_scale_at     the DistortionScale of an importance block
+//   wsse_cell         one 4x4 cell of get_weighted_sse
+//   dist_scale_mul    DistortionScale::mul_u64
 // Reference: get_sad src/dist.rs:31-52, get_satd 156-221, hadamard4_1d 61,
 // hadamard8_1d 84, hadamard2d 122; get_weighted_sse 234-283, cdef_dist_kernel
 // 302-372, apply_ssim_boost src/activity.rs:109-186 (see dist_scaled.hip).
@@ -103,16 +112,54 @@ __device__ __forceinline__ void load_row(const uint8_t *p, int kw, int32_t *out)
 }
 
 
-// cdef_dist_kernel's fixed-point tail (dist.rs:350-372) + the ssim boost + the
-// DistortionScale of the 8x8 importance block at (px, py), from the five sums
-// of a tile of `area` pixels.
+// cdef_dist_kernel's five moments of a tile (dist.rs:316-345): s = source, d = distorted
+struct CdefMoments {
+  uint32_t s = 0, d = 0, s2 = 0, d2 = 0, sd = 0;
+  __device__ __forceinline__ void add(uint32_t sv, uint32_t dv) {
+    s += sv; d += dv;
+    s2 += sv * sv; d2 += dv * dv; sd += sv * dv;
+  }
+  // every lane adds the lanes that differ from it in the bits from <= m < to (powers of two)
+  __device__ __forceinline__ void xor_sum(int from, int to) {
+#pragma unroll
+    for (int m = from; m < to; m <<= 1) {
+      s += __shfl_xor(s, m, WAVE); d += __shfl_xor(d, m, WAVE);
+      s2 += __shfl_xor(s2, m, WAVE); d2 += __shfl_xor(d2, m, WAVE);
+      sd += __shfl_xor(sd, m, WAVE);
+    }
+  }
+  // parked in five dwords (LDS) between the lanes that gather a tile and the lane that runs its tail
+  __device__ __forceinline__ void store(uint32_t *b) const {
+    b[0] = s; b[1] = d; b[2] = s2; b[3] = d2; b[4] = sd;
+  }
+  __device__ __forceinline__ static CdefMoments load(const uint32_t *b) {
+    return CdefMoments{b[0], b[1], b[2], b[3], b[4]};
+  }
+};
+
+// The DistortionScale of the 8x8 importance block that holds luma position (lx, ly); no table: 1.0 in Q14
+// (compute_bias / distortion_scale, rdo.rs:443-459)
+__device__ __forceinline__ uint32_t dist_scale_at(const uint32_t *__restrict__ scales, int scale_stride, int lx,
+                                                  int ly) {
+  return scales ? scales[(size_t)(ly >> 3) * scale_stride + (lx >> 3)] : (1u << 14);
+}
+// one 4x4 cell of get_weighted_sse: (sse * scale + (1 << 7)) >> 8 (dist.rs:274-275; the caller's sum still needs
+// the final (sum + 32) / 64, dist.rs:281-282)
+__device__ __forceinline__ unsigned long long wsse_cell(uint32_t cell, uint32_t sc) {
+  return ((unsigned long long)cell * sc + 128) >> 8;
+}
+// DistortionScale::mul_u64 (rdo.rs:613-615): (scale * v + (1 << 13)) >> 14
+__device__ __forceinline__ unsigned long long dist_scale_mul(uint32_t scale, unsigned long long v) {
+  return ((unsigned long long)scale * v + 8192) >> 14;
+}
+
+// cdef_dist_kernel's fixed-point tail (dist.rs:350-372) from the five sums of a tile of `area` pixels: the three
+// values apply_ssim_boost takes.
 // BDT: the bit depth when the caller knows it at compile time (8 / 10: sum^2 fits 32 bits), 0 otherwise.
 template <int BDT = 0>
-__device__ __forceinline__ unsigned long long cdef_tile_tail(
-    uint32_t sum_s, uint32_t sum_d, uint32_t sum_s2, uint32_t sum_d2, uint32_t sum_sd, int area, int px,
-    int py, const uint32_t *__restrict__ scales, int scale_stride, int bit_depth) {
-  const uint32_t sse = sum_d2 + sum_s2 - 2 * sum_sd;
-  uint32_t svar, dvar;
+__device__ __forceinline__ void cdef_tile_vars(const CdefMoments &m, int area, uint32_t &svar, uint32_t &dvar,
+                                               uint32_t &sse) {
+  sse = m.d2 + m.s2 - 2 * m.sd;
   if ((area & (area - 1)) == 0) {
     // area = 2^la (every tile of 4 / 8 pixel sides): AREA_DIVISORS[area - 1] = 2^(14 - la) exactly, so
     //   (x * div + 2^13) >> 14 = (x + area / 2) >> la        and        (v * div + 128) >> 8 = v << (6 - la)
@@ -121,27 +168,34 @@ __device__ __forceinline__ unsigned long long cdef_tile_tail(
     const int la = 31 - __builtin_clz((unsigned)area);
     uint32_t ms, md;
     if constexpr (BDT == 8 || BDT == 10) {        // sum <= 64 * 1023: the square fits 32 bits
-      ms = (sum_s * sum_s + (uint32_t)(area >> 1)) >> la;
-      md = (sum_d * sum_d + (uint32_t)(area >> 1)) >> la;
+      ms = (m.s * m.s + (uint32_t)(area >> 1)) >> la;
+      md = (m.d * m.d + (uint32_t)(area >> 1)) >> la;
     } else {
-      ms = (uint32_t)(((unsigned long long)sum_s * sum_s + (unsigned long long)(area >> 1)) >> la);
-      md = (uint32_t)(((unsigned long long)sum_d * sum_d + (unsigned long long)(area >> 1)) >> la);
+      ms = (uint32_t)(((unsigned long long)m.s * m.s + (unsigned long long)(area >> 1)) >> la);
+      md = (uint32_t)(((unsigned long long)m.d * m.d + (unsigned long long)(area >> 1)) >> la);
     }
-    svar = (sum_s2 > ms ? sum_s2 - ms : 0) << (6 - la);
-    dvar = (sum_d2 > md ? sum_d2 - md : 0) << (6 - la);
+    svar = (m.s2 > ms ? m.s2 - ms : 0) << (6 - la);
+    dvar = (m.d2 > md ? m.d2 - md : 0) << (6 - la);
   } else {
     const unsigned long long div = area_divisor(area);
-    const uint32_t ms = (uint32_t)(((unsigned long long)sum_s * sum_s * div + 8192) >> 14);
-    const uint32_t md = (uint32_t)(((unsigned long long)sum_d * sum_d * div + 8192) >> 14);
-    svar = sum_s2 > ms ? sum_s2 - ms : 0;
-    dvar = sum_d2 > md ? sum_d2 - md : 0;
+    const uint32_t ms = (uint32_t)(((unsigned long long)m.s * m.s * div + 8192) >> 14);
+    const uint32_t md = (uint32_t)(((unsigned long long)m.d * m.d * div + 8192) >> 14);
+    svar = m.s2 > ms ? m.s2 - ms : 0;
+    dvar = m.d2 > md ? m.d2 - md : 0;
     svar = (uint32_t)(((unsigned long long)svar * div + 128) >> 8);
     dvar = (uint32_t)(((unsigned long long)dvar * div + 128) >> 8);
   }
-  const unsigned long long v = apply_ssim_boost(sse, svar, dvar, bit_depth);
-  const unsigned long long sc =
-      scales ? scales[(size_t)(py >> 3) * scale_stride + (px >> 3)] : (1u << 14);
-  return (sc * v + 8192) >> 14;
+}
+
+// RawDistortion(cdef_dist_kernel) * bias (rdo.rs:142-173): the tail above + the ssim boost + the DistortionScale
+// of the 8x8 importance block at (px, py)
+template <int BDT = 0>
+__device__ __forceinline__ unsigned long long cdef_tile_tail(const CdefMoments &m, int area, int px, int py,
+                                                             const uint32_t *__restrict__ scales, int scale_stride,
+                                                             int bit_depth) {
+  uint32_t svar, dvar, sse;
+  cdef_tile_vars<BDT>(m, area, svar, dvar, sse);
+  return dist_scale_mul(dist_scale_at(scales, scale_stride, px, py), apply_ssim_boost(sse, svar, dvar, bit_depth));
 }
 
 // One 8x8 (or edge 4-wide / 4-high) tile of sse_wxh (KIND 2: four 4x4 cells,
@@ -177,13 +231,11 @@ __device__ __forceinline__ unsigned long long tile_scaled_dist(
       for (int cx = 0; cx < 2; cx++) {
         if (cy * 4 < kh && cx * 4 < kw) {
           const int lx = (px + cx * 4) << xdec, ly = (py + cy * 4) << ydec;
-          const uint32_t sc =
-              scales ? scales[(size_t)(ly >> 3) * scale_stride + (lx >> 3)] : (1u << 14);
-          acc += ((unsigned long long)cell[cy][cx] * sc + 128) >> 8;
+          acc += wsse_cell(cell[cy][cx], dist_scale_at(scales, scale_stride, lx, ly));
         }
       }
   } else {
-    uint32_t sum_s = 0, sum_d = 0, sum_s2 = 0, sum_d2 = 0, sum_sd = 0;
+    CdefMoments m;
 #pragma unroll
     for (int r = 0; r < 8; r++) {
       if (r < kh) {
@@ -191,15 +243,10 @@ __device__ __forceinline__ unsigned long long tile_scaled_dist(
         load_row<BPP>(po + r * so, kw, a);
         load_row<BPP>(pr + r * sr, kw, b);
 #pragma unroll
-        for (int i = 0; i < 8; i++) {
-          const uint32_t s = (uint32_t)a[i], d = (uint32_t)b[i];
-          sum_s += s; sum_d += d;
-          sum_s2 += s * s; sum_d2 += d * d; sum_sd += s * d;
-        }
+        for (int i = 0; i < 8; i++) m.add((uint32_t)a[i], (uint32_t)b[i]);
       }
     }
-    acc = cdef_tile_tail(sum_s, sum_d, sum_s2, sum_d2, sum_sd, kw * kh, px, py, scales, scale_stride,
-                         bit_depth);
+    acc = cdef_tile_tail(m, kw * kh, px, py, scales, scale_stride, bit_depth);
   }
   return acc;
 }

@@ -45,12 +45,7 @@ __global__ __launch_bounds__(256) void k_dist_scaled(
                                               scale_stride, xdec, ydec, org.bit_depth);
   }
   // segmented u64 reduction over the candidate's tiles
-  const int seg = tpc_log2 < 6 ? tpc_log2 : 6;
-  for (int m = 1; m < (1 << seg); m <<= 1) {
-    const uint32_t lo = __shfl_xor((uint32_t)acc, m, WAVE);
-    const uint32_t hi = __shfl_xor((uint32_t)(acc >> 32), m, WAVE);
-    acc += ((unsigned long long)hi << 32) | lo;
-  }
+  acc = xor_sum_u64(acc, 1 << (tpc_log2 < 6 ? tpc_log2 : 6));
   if (tpc_log2 > 6) {
     if ((tid & 63) == 0) wave_part[tid >> 6] = acc;
     __syncthreads();
@@ -79,21 +74,12 @@ __global__ __launch_bounds__(64) void k_cdef_dist_raw(R1Plane org, R1Plane ref, 
   const uint8_t *po = px_addr<BPP>(org, c.ox, c.oy);
   const uint8_t *pr = px_addr<BPP>(ref, c.rx, c.ry);
   const size_t so = (size_t)org.stride * BPP, sr = (size_t)ref.stride * BPP;
-  uint32_t sum_s = 0, sum_d = 0, sum_s2 = 0, sum_d2 = 0, sum_sd = 0;
+  r1dist::CdefMoments m;
   for (int r = 0; r < h; r++)
-    for (int x = 0; x < w; x++) {
-      const uint32_t s = (uint32_t)ld_px<BPP>(po + r * so + x * BPP), d = (uint32_t)ld_px<BPP>(pr + r * sr + x * BPP);
-      sum_s += s; sum_d += d;
-      sum_s2 += s * s; sum_d2 += d * d; sum_sd += s * d;
-    }
-  const uint32_t sse = sum_d2 + sum_s2 - 2 * sum_sd;
-  const unsigned long long div = r1dist::area_divisor(w * h);
-  const uint32_t ms = (uint32_t)(((unsigned long long)sum_s * sum_s * div + 8192) >> 14);
-  const uint32_t md = (uint32_t)(((unsigned long long)sum_d * sum_d * div + 8192) >> 14);
-  uint32_t svar = sum_s2 > ms ? sum_s2 - ms : 0;
-  uint32_t dvar = sum_d2 > md ? sum_d2 - md : 0;
-  svar = (uint32_t)(((unsigned long long)svar * div + 128) >> 8);
-  dvar = (uint32_t)(((unsigned long long)dvar * div + 128) >> 8);
+    for (int x = 0; x < w; x++)
+      m.add((uint32_t)ld_px<BPP>(po + r * so + x * BPP), (uint32_t)ld_px<BPP>(pr + r * sr + x * BPP));
+  uint32_t svar, dvar, sse;
+  r1dist::cdef_tile_vars<0>(m, w * h, svar, dvar, sse);
   out3[3 * i] = svar;
   out3[3 * i + 1] = dvar;
   out3[3 * i + 2] = sse;

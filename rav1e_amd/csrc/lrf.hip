@@ -425,16 +425,8 @@ __global__ __launch_bounds__(256) void k_sgr_moments(R1Plane cdeffed, R1Plane in
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int k = 0; k < 5; k++) {
-    uint32_t lo = (uint32_t)m[k], hi = (uint32_t)((unsigned long long)m[k] >> 32);
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-      const unsigned long long o = ((unsigned long long)(uint32_t)__shfl_xor((int)hi, s, 64) << 32) |
-                                   (uint32_t)__shfl_xor((int)lo, s, 64);
-      const unsigned long long v = (((unsigned long long)hi << 32) | lo) + o;
-      lo = (uint32_t)v;
-      hi = (uint32_t)(v >> 32);
-    }
-    if (lane == 0) part[wave][k] = (long long)(((unsigned long long)hi << 32) | lo);
+    const long long v = (long long)xor_sum_u64((unsigned long long)m[k], WAVE);
+    if (lane == 0) part[wave][k] = v;
   }
   __syncthreads();
   if (threadIdx.x < 5) {
@@ -498,19 +490,14 @@ __device__ __forceinline__ unsigned long long lrf_block_err(const R1Plane &src, 
   const uint8_t *po = px_addr<BPP>(src, px, py);
   const size_t so = (size_t)src.stride * BPP;
   if constexpr (!CHROMA) {
-    uint32_t sum_s = 0, sum_d = 0, sum_s2 = 0, sum_d2 = 0, sum_sd = 0;
+    r1dist::CdefMoments m;
     for (int r = 0; r < 8; r++)
-      for (int i = 0; i < 8; i++) {
-        const uint32_t sv = (uint32_t)ld_px<BPP>(po + r * so + (size_t)i * BPP), dv = test[r * TS + i];
-        sum_s += sv; sum_d += dv;
-        sum_s2 += sv * sv; sum_d2 += dv * dv; sum_sd += sv * dv;
-      }
+      for (int i = 0; i < 8; i++) m.add((uint32_t)ld_px<BPP>(po + r * so + (size_t)i * BPP), test[r * TS + i]);
     // RawDistortion(cdef_dist_kernel) * bias: the tail multiplies by the block's DistortionScale
-    return r1dist::cdef_tile_tail<0>(sum_s, sum_d, sum_s2, sum_d2, sum_sd, 64, px, py, scales, scale_stride, bd);
+    return r1dist::cdef_tile_tail<0>(m, 64, px, py, scales, scale_stride, bd);
   } else {
     // sse_wxh with one bias for the block: get_weighted_sse over its 4x4 cells (dist.rs:234-283)
-    const uint32_t sc = scales ? scales[(size_t)((py << ydec) >> 3) * scale_stride + ((px << xdec) >> 3)]
-                               : (1u << 14);
+    const uint32_t sc = r1dist::dist_scale_at(scales, scale_stride, px << xdec, py << ydec);
     unsigned long long sum = 0;
     for (int cy = 0; cy < bh; cy += 4)
       for (int cx = 0; cx < bw; cx += 4) {
@@ -521,27 +508,48 @@ __device__ __forceinline__ unsigned long long lrf_block_err(const R1Plane &src, 
                               (int32_t)test[(cy + r) * TS + cx + i];
             cell += (uint32_t)(d * d);
           }
-        sum += ((unsigned long long)cell * sc + 128) >> 8;
+        sum += r1dist::wsse_cell(cell, sc);
       }
     return (sum + 32) >> 6;
   }
 }
 
-// sum of a 64-bit value over the workgroup (256 threads); valid in thread 0
-__device__ __forceinline__ unsigned long long wg_sum_u64(unsigned long long v, unsigned long long *part4) {
-  uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
+// rdo_loop_plane_error (rdo.rs:2027-2093) of luma, the whole workgroup on it.  Round 4 gave a block to a thread: 64 of
+// the 256 threads looped over 64 pixels each -- one-pixel global loads of the source at a stride of a plane
+// row -- while the other waves waited at the barrier.  Now a thread owns a ROW SEGMENT of a block (the LPR lanes
+// of a row read 8 * LPR contiguous source pixels), the rows of a block meet by xor-shuffles inside their wave
+// (lanes LPR apart), the caller parks the five sums of every block in LDS and lets ONE pass run the fixed-point
+// tails (ssim boost, 64-bit arithmetic) side by side instead of one after the other.
+// Chroma keeps a block per thread: the cooperative form LOSES 5-6 % there (profiles/r05_ab_notes.md, ab4).
+// This is the middle of it: the moments of segment xs of row y of the tile -- eight pixels of `src`, where the tile
+// lies at (x0, y0), against the eight filtered pixels in `test` (LDS, TS pixels a row) -- where `live`, summed over
+// the block's rows: every lane of a block's column returns the block's moments.
+template <int BPP, int LPR, int TS, typename DT>
+__device__ __forceinline__ r1dist::CdefMoments luma_block_moments(bool live, const R1Plane &src, int x0, int y0,
+                                                                  int xs, int y, const DT (*test)[TS]) {
+  typedef typename std::conditional<BPP == 1, uint8_t, uint16_t>::type ST;
+  r1dist::CdefMoments m;
+  if (live) {
+    const uint8_t *po = px_addr<BPP>(src, x0 + xs * 8, y0 + y);
+    // eight source pixels in one load where the segment is aligned (units start at multiples of 8 pixels in
+    // every configuration the encoder ships; anything else takes the pixel-by-pixel path), eight filtered
+    // pixels in one LDS read
+    ST sv8[8];
+    DT dv8[8];
+    if (((uintptr_t)po & (8 * BPP - 1)) == 0) {
+      if constexpr (BPP == 1) *(uint2 *)sv8 = *(const uint2 *)po;
+      else *(uint4 *)sv8 = *(const uint4 *)po;
+    } else {
 #pragma unroll
-  for (int sft = 1; sft < 64; sft <<= 1) {
-    const unsigned long long o = ((unsigned long long)(uint32_t)__shfl_xor((int)hi, sft, 64) << 32) |
-                                 (uint32_t)__shfl_xor((int)lo, sft, 64);
-    const unsigned long long t = (((unsigned long long)hi << 32) | lo) + o;
-    lo = (uint32_t)t;
-    hi = (uint32_t)(t >> 32);
+      for (int i = 0; i < 8; i++) sv8[i] = (ST)ld_px<BPP>(po + (size_t)i * BPP);
+    }
+    if constexpr (sizeof(DT) == 1) *(uint2 *)dv8 = *(const uint2 *)&test[y][xs * 8];
+    else *(uint4 *)dv8 = *(const uint4 *)&test[y][xs * 8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) m.add(sv8[i], dv8[i]);
   }
-  __syncthreads();   // part4 may still be read from a previous use
-  if ((threadIdx.x & 63) == 0) part4[threadIdx.x >> 6] = ((unsigned long long)hi << 32) | lo;
-  __syncthreads();
-  return part4[0] + part4[1] + part4[2] + part4[3];
+  m.xor_sum(LPR, 8 * LPR);     // the 8 rows of a block: lanes LPR apart
+  return m;
 }
 
 // rdo_loop_plane_error walks the BLOCK GRID (rdo.rs:2039-2043: `loop_bo < blocks.cols() / rows()`, 2 * ceil(W / 8)
@@ -714,16 +722,8 @@ __global__ __launch_bounds__(256, BPP == 1 ? 5 : 1) void k_lrf_search_unit(R1Pla
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < 5; k++) {
-      uint32_t lo = (uint32_t)m[k], hi = (uint32_t)((unsigned long long)m[k] >> 32);
-#pragma unroll
-      for (int sft = 1; sft < 64; sft <<= 1) {
-        const unsigned long long o = ((unsigned long long)(uint32_t)__shfl_xor((int)hi, sft, 64) << 32) |
-                                     (uint32_t)__shfl_xor((int)lo, sft, 64);
-        const unsigned long long v = (((unsigned long long)hi << 32) | lo) + o;
-        lo = (uint32_t)v;
-        hi = (uint32_t)(v >> 32);
-      }
-      if (lane == 0) mpart[wave][k] = (long long)(((unsigned long long)hi << 32) | lo);
+      const long long v = (long long)xor_sum_u64((unsigned long long)m[k], WAVE);
+      if (lane == 0) mpart[wave][k] = v;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -756,61 +756,24 @@ __global__ __launch_bounds__(256, BPP == 1 ? 5 : 1) void k_lrf_search_unit(R1Pla
   __syncthreads();
   const int nbx = gw / bw, nby = gh / bh;   // ceil(u.w / bw), ceil(u.h / bh)
   unsigned long long mine = 0;
-  // rdo_loop_plane_error (rdo.rs:2027-2093), the whole workgroup on it.  Round 4 gave a block to a thread: 64 of
-  // the 256 threads looped over 64 pixels each -- one-pixel global loads of the source at a stride of a plane
-  // row -- while the other waves waited at the barrier.  Now a thread owns a ROW SEGMENT of a block (the 8 lanes
-  // of a unit row read 64 contiguous source pixels), the rows of a block meet by xor-shuffles inside their wave
-  // (a wave covers exactly one row of blocks), the five sums of every block are parked in LDS and ONE wave runs
-  // the 64 fixed-point tails (ssim boost, 64-bit arithmetic) side by side instead of one after the other.
-  // Chroma keeps a block per thread: the cooperative form LOSES 5-6 % there (profiles/r05_ab_notes.md, ab4).
   if constexpr (!CHROMA) {
+    // the whole workgroup on it (luma_block_moments): a wave covers exactly one row of blocks per half
     uint32_t(*bs)[5] = (uint32_t(*)[5]) & F1[0][0];   // 64 x 5 sums over the filter outputs, which are dead by now
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int half = 0; half < 2; half++) {
       const int y = half * 32 + wave * 8 + (lane >> 3), xs = lane & 7;    // unit row, 8-pixel segment of it
-      uint32_t sum_s = 0, sum_d = 0, sum_s2 = 0, sum_d2 = 0, sum_sd = 0;
-      if (xs < nbx && y < nby * 8) {
-        const uint8_t *po = px_addr<BPP>(src, u.x + xs * 8, u.y + y);
-        // eight source pixels in one load where the segment is aligned (units start at multiples of 8 pixels in
-        // every configuration the encoder ships; anything else takes the pixel-by-pixel path), eight filtered
-        // pixels in one LDS read
-        PT sv8[8], dv8[8];
-        if (((uintptr_t)po & (8 * BPP - 1)) == 0) {
-          if constexpr (BPP == 1) *(uint2 *)sv8 = *(const uint2 *)po;
-          else *(uint4 *)sv8 = *(const uint4 *)po;
-        } else {
-#pragma unroll
-          for (int i = 0; i < 8; i++) sv8[i] = (PT)ld_px<BPP>(po + (size_t)i * BPP);
-        }
-        if constexpr (BPP == 1) *(uint2 *)dv8 = *(const uint2 *)&P[y][xs * 8];
-        else *(uint4 *)dv8 = *(const uint4 *)&P[y][xs * 8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-          const uint32_t sv = sv8[i], dv = dv8[i];
-          sum_s += sv; sum_d += dv;
-          sum_s2 += sv * sv; sum_d2 += dv * dv; sum_sd += sv * dv;
-        }
-      }
-#pragma unroll
-      for (int m = 8; m < 64; m <<= 1) {     // the 8 rows of a block: lanes 8 apart
-        sum_s += __shfl_xor(sum_s, m, 64); sum_d += __shfl_xor(sum_d, m, 64);
-        sum_s2 += __shfl_xor(sum_s2, m, 64); sum_d2 += __shfl_xor(sum_d2, m, 64);
-        sum_sd += __shfl_xor(sum_sd, m, 64);
-      }
-      if (lane < 8) {
-        uint32_t *b = bs[(half * 4 + wave) * 8 + lane];
-        b[0] = sum_s; b[1] = sum_d; b[2] = sum_s2; b[3] = sum_d2; b[4] = sum_sd;
-      }
+      const r1dist::CdefMoments m =
+          luma_block_moments<BPP, 8>(xs < nbx && y < nby * 8, src, u.x, u.y, xs, y, P);
+      if (lane < 8) m.store(bs[(half * 4 + wave) * 8 + lane]);
     }
     __syncthreads();
     if (threadIdx.x < 64) {
       const int by = threadIdx.x >> 3, bx = threadIdx.x & 7;
       if (bx < nbx && by < nby) {
-        const uint32_t *b = bs[threadIdx.x];
         // RawDistortion(cdef_dist_kernel) * bias: the tail multiplies by the block's DistortionScale
-        mine = r1dist::cdef_tile_tail<0>(b[0], b[1], b[2], b[3], b[4], 64, u.x + bx * 8, u.y + by * 8, scales,
-                                         scale_stride, bd);
+        mine = r1dist::cdef_tile_tail<0>(r1dist::CdefMoments::load(bs[threadIdx.x]), 64, u.x + bx * 8, u.y + by * 8,
+                                         scales, scale_stride, bd);
       }
     }
   } else {
@@ -823,7 +786,7 @@ __global__ __launch_bounds__(256, BPP == 1 ? 5 : 1) void k_lrf_search_unit(R1Pla
   }
   const unsigned long long v = wg_sum_u64(mine, epart);
   // Distortion * fi.dist_scale[pli] (rdo.rs:2092; DistortionScale::mul_u64, rdo.rs:613-615)
-  if (threadIdx.x == 0) err_out[pair] = ((unsigned long long)dist_scale * v + 8192) >> 14;
+  if (threadIdx.x == 0) err_out[pair] = r1dist::dist_scale_mul(dist_scale, v);
 }
 
 // A later pass of rdo_loop_decision's CDEF leg (rdo.rs:2407-2530): the superblock's trial output (cdef_search.hip,
@@ -881,48 +844,18 @@ __global__ __launch_bounds__(256) void k_sgr_trial_err(R1Plane trial, size_t tri
   const int nbx = gtw / bw, nby = gth / bh;   // ceil(t.tw / bw), ceil(t.th / bh)
   unsigned long long mine = 0;
   if constexpr (!CHROMA) {
-    // rdo_loop_plane_error of the tile with the whole workgroup (as k_lrf_search_unit does): a thread owns an
-    // 8-pixel row segment of a block -- 16 contiguous source bytes, 16 bytes of LDS -- the 8 rows of a block meet by
-    // xor-shuffles (lanes 4 apart), the block sums are parked in LDS and 32 threads run the fixed-point tails
+    // the whole workgroup on it (luma_block_moments): 4 lanes per tile row, 32 threads run the tails
     __shared__ uint32_t bs[TR / 2][5];
     const int y = (int)threadIdx.x >> 2, xs = (int)threadIdx.x & 3;
-    uint32_t sum_s = 0, sum_d = 0, sum_s2 = 0, sum_d2 = 0, sum_sd = 0;
-    if (xs < nbx && y < nby * 8 && y < TR) {
-      typedef typename std::conditional<BPP == 1, uint8_t, uint16_t>::type PT;
-      const uint8_t *po = px_addr<BPP>(src, t.cx0 + xs * 8, u.y + t.ty0 + y);
-      PT sv8[8];
-      if (((uintptr_t)po & (8 * BPP - 1)) == 0) {
-        if constexpr (BPP == 1) *(uint2 *)sv8 = *(const uint2 *)po;
-        else *(uint4 *)sv8 = *(const uint4 *)po;
-      } else {
-#pragma unroll
-        for (int i = 0; i < 8; i++) sv8[i] = (PT)ld_px<BPP>(po + (size_t)i * BPP);
-      }
-      uint16_t dv8[8];
-      *(uint4 *)dv8 = *(const uint4 *)&F[y][xs * 8];
-#pragma unroll
-      for (int i = 0; i < 8; i++) {
-        const uint32_t sv = sv8[i], dv = dv8[i];
-        sum_s += sv; sum_d += dv;
-        sum_s2 += sv * sv; sum_d2 += dv * dv; sum_sd += sv * dv;
-      }
-    }
-#pragma unroll
-    for (int m = 4; m < 32; m <<= 1) {     // the 8 rows of a block: lanes 4 apart
-      sum_s += __shfl_xor(sum_s, m, 64); sum_d += __shfl_xor(sum_d, m, 64);
-      sum_s2 += __shfl_xor(sum_s2, m, 64); sum_d2 += __shfl_xor(sum_d2, m, 64);
-      sum_sd += __shfl_xor(sum_sd, m, 64);
-    }
-    if ((y & 7) == 0 && y < TR) {
-      uint32_t *b = bs[(y >> 3) * 4 + xs];
-      b[0] = sum_s; b[1] = sum_d; b[2] = sum_s2; b[3] = sum_d2; b[4] = sum_sd;
-    }
+    const r1dist::CdefMoments m =
+        luma_block_moments<BPP, 4>(xs < nbx && y < nby * 8 && y < TR, src, t.cx0, u.y + t.ty0, xs, y, F);
+    if ((y & 7) == 0 && y < TR) m.store(bs[(y >> 3) * 4 + xs]);
     __syncthreads();
     if (threadIdx.x < TR / 2) {
       const int by = (int)threadIdx.x >> 2, bx = (int)threadIdx.x & 3;
       if (bx < nbx && by < nby) {
-        const uint32_t *b = bs[threadIdx.x];
-        mine = r1dist::cdef_tile_tail<0>(b[0], b[1], b[2], b[3], b[4], 64, t.cx0 + bx * 8, u.y + t.ty0 + by * 8, scales, scale_stride, bd);
+        mine = r1dist::cdef_tile_tail<0>(r1dist::CdefMoments::load(bs[threadIdx.x]), 64, t.cx0 + bx * 8,
+                                         u.y + t.ty0 + by * 8, scales, scale_stride, bd);
       }
     }
   } else if ((int)threadIdx.x < nbx * nby) {   // chroma: one thread per block
@@ -943,7 +876,7 @@ __global__ void k_lrf_err_finish(const unsigned long long *__restrict__ acc, int
   if (i >= n) return;
   const R1SgrSolveUnit u = units[i];
   if (unit_in_grid(u.x, u.y, u.w, u.h, bw, bh, lrf_in, src)) {
-    err[i] = ((unsigned long long)dist_scale * acc[i] + 8192) >> 14;
+    err[i] = r1dist::dist_scale_mul(dist_scale, acc[i]);
   } else {
     err[i] = ~0ull;
     xqd[2 * i] = xqd[2 * i + 1] = 0;

@@ -96,6 +96,24 @@ struct Msr {   // MotionSearchResult: wave-uniform, replicated in every lane
 };
 __device__ __forceinline__ Msr msr_empty() { return Msr{0, 0, COST_MAX, 0xFFFFFFFFu}; }
 
+struct MeCand {   // one lane's candidate of a search step
+  unsigned long long cost;
+  int idx, row, col;
+  uint32_t sad;
+  // argmin over the lanes that differ in the bits from <= m < to (powers of two): the lower cost, on a tie the
+  // lower candidate index (`if rd.cost < best.rd.cost { best = cand }` in candidate order); every lane of such a
+  // group ends up with the winner
+  __device__ __forceinline__ void xor_min(int from, int to) {
+#pragma unroll
+    for (int m = from; m < to; m <<= 1) {
+      const unsigned long long oc = shfl_xor_u64(cost, m);
+      const int oi = __shfl_xor(idx, m, WAVE), orow = __shfl_xor(row, m, WAVE), ocol = __shfl_xor(col, m, WAVE);
+      const uint32_t os = (uint32_t)__shfl_xor((int)sad, m, WAVE);
+      if (oc < cost || (oc == cost && oi < idx)) { cost = oc; idx = oi; row = orow; col = ocol; sad = os; }
+    }
+  }
+};
+
 __device__ __forceinline__ int ilog_abs(int d) {   // ILog::ilog(d.abs())
   const uint32_t a = (uint32_t)(d < 0 ? -d : d);
   return a ? 32 - __clz(a) : 0;
@@ -213,12 +231,10 @@ struct Block {
     // slot number, so "the lower index wins ties" is a strict less-than.
     {
       int ws = 0;
-      unsigned long long wc = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(cost >> 32), 0) << 32) |
-                              (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)cost, 0);
+      unsigned long long wc = readlane_u64(cost, 0);
 #pragma unroll
       for (int sl = 1; sl < NCS; sl++) {
-        const unsigned long long c = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(cost >> 32), sl * RH) << 32) |
-                                     (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)cost, sl * RH);
+        const unsigned long long c = readlane_u64(cost, sl * RH);
         if (c < wc) { wc = c; ws = sl; }
       }
       const int wl = ws * RH;
@@ -537,10 +553,7 @@ __device__ __forceinline__ void get_subset_predictors(const TileView &t, int bx,
     }
     mine = load_entry<AGENT && true>(base + (size_t)my_y * t.cols_f + my_x);
   }
-  auto entry = [&](int k) -> unsigned long long {
-    return ((unsigned long long)(uint32_t)__shfl((int)(mine >> 32), k, 64) << 32) |
-           (uint32_t)__shfl((int)(uint32_t)mine, k, 64);
-  };
+  auto entry = [&](int k) -> unsigned long long { return shfl_u64(mine, k); };
   if (ok[0]) process_cand(entry(0), rng, min_sad, s.b + 2 * s.nb++);
   if (ok[1]) process_cand(entry(1), rng, min_sad, s.b + 2 * s.nb++);
   if (ok[2]) process_cand(entry(2), rng, min_sad, s.b + 2 * s.nb++);
@@ -1154,28 +1167,15 @@ struct WgBlock {
   template <class Gen>
   __device__ __forceinline__ void scan(int n, Gen gen, bool check, Msr &best, int *best_idx) const {
     for (int base = 0; base < n; base += 4 * ncs) {
-      int idx = base + wave * ncs + slot;
-      const bool valid = idx < n;
-      int row = 0, col = 0;
-      if (valid) gen(idx, row, col);
-      unsigned long long cost;
-      uint32_t sad;
-      eval(row, col, valid, check, cost, sad);
-      for (int s = RH; s < 64; s <<= 1) {
-        const unsigned long long oc =
-            ((unsigned long long)(uint32_t)__shfl_xor((int)(cost >> 32), s, 64) << 32) |
-            (uint32_t)__shfl_xor((int)(uint32_t)cost, s, 64);
-        const int oi = __shfl_xor(idx, s, 64), orow = __shfl_xor(row, s, 64),
-                  ocol = __shfl_xor(col, s, 64);
-        const uint32_t os = (uint32_t)__shfl_xor((int)sad, s, 64);
-        if (oc < cost || (oc == cost && oi < idx)) {
-          cost = oc; idx = oi; row = orow; col = ocol; sad = os;
-        }
-      }
-      wg_min(cost, idx, row, col, sad);
-      if (cost < best.cost) {
-        best = Msr{row, col, cost, sad};
-        if (best_idx) *best_idx = idx;
+      MeCand c{0, base + wave * ncs + slot, 0, 0, 0};
+      const bool valid = c.idx < n;
+      if (valid) gen(c.idx, c.row, c.col);
+      eval(c.row, c.col, valid, check, c.cost, c.sad);
+      c.xor_min(RH, WAVE);
+      wg_min(c.cost, c.idx, c.row, c.col, c.sad);
+      if (c.cost < best.cost) {
+        best = Msr{c.row, c.col, c.cost, c.sad};
+        if (best_idx) *best_idx = c.idx;
       }
     }
   }
@@ -1498,13 +1498,14 @@ __global__ __launch_bounds__(256, 3) void k_me_blocks_small(R1MeJob job, R1MePar
     uint32_t sad = use_satd ? (s + ((1u << ln) >> 1)) >> ln : s;
     unsigned long long cost = ok ? b.mc.cost(row, col, sad) : COST_MAX;
     if (!ok) sad = 0xFFFFFFFFu;
+    // the same argmin as MeCand::xor_min(16, WAVE), on the loop's own variables: with the candidate in a MeCand this
+    // kernel (168 VGPRs, spills) changed its spill pattern and lost 0.4 - 0.5 % (profiles/r08_reduce_ab_notes.md)
     int idx = g;
 #pragma unroll
-    for (int m = 16; m < 64; m <<= 1) {
-      const unsigned long long oc = ((unsigned long long)(uint32_t)__shfl_xor((int)(cost >> 32), m, 64) << 32) |
-                                    (uint32_t)__shfl_xor((int)(uint32_t)cost, m, 64);
-      const int oi = __shfl_xor(idx, m, 64), orow = __shfl_xor(row, m, 64), ocol = __shfl_xor(col, m, 64);
-      const uint32_t os = (uint32_t)__shfl_xor((int)sad, m, 64);
+    for (int m = 16; m < WAVE; m <<= 1) {
+      const unsigned long long oc = shfl_xor_u64(cost, m);
+      const int oi = __shfl_xor(idx, m, WAVE), orow = __shfl_xor(row, m, WAVE), ocol = __shfl_xor(col, m, WAVE);
+      const uint32_t os = (uint32_t)__shfl_xor((int)sad, m, WAVE);
       if (oc < cost || (oc == cost && oi < idx)) { cost = oc; idx = oi; row = orow; col = ocol; sad = os; }
     }
     if (best.cost <= cost) {

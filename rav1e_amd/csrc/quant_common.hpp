@@ -316,12 +316,7 @@ __device__ __forceinline__ void quantize_group(int32_t *mine, int g0, int l, boo
   }
   eob_out = eob;
   if constexpr (DIST) {
-#pragma unroll
-    for (int m = 1; m < G; m <<= 1) {
-      const uint32_t lo = __shfl_xor((uint32_t)dist, m, 64);
-      const uint32_t hi = __shfl_xor((uint32_t)(dist >> 32), m, 64);
-      dist += ((unsigned long long)hi << 32) | lo;
-    }
+    dist = xor_sum_u64(dist, G);
     const int bits = 2 * (3 - lts);
     dist_out = (dist + (1ull << (bits - 1))) >> bits;
   }

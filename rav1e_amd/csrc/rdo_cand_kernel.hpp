@@ -422,7 +422,7 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
   constexpr bool TAIL_DEFER = MT && QM == 2 && W == 8 && H == 8;
   // (a mask of more than eight types -- the full AV1 inter set has sixteen -- keeps its tails inside the loop)
   const bool tail_defer = TAIL_DEFER && qa.dist_kind == R1_DIST_CDEF && qa.nt <= 8;   // wave-uniform
-  uint32_t tail_keep[5] = {0, 0, 0, 0, 0};
+  r1dist::CdefMoments tail_keep;
   // The loop: groups of types that share the column pass (same vertical 1-D kernel and the same flips; without
   // COLSHARE every type is a group of its own), and inside a group the types in ascending order.  The result slot of
   // a type is its rank in the launch's mask, whatever order the groups come in.
@@ -745,11 +745,11 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
           // of the group alive
           constexpr int NR = H / KH;
           static_assert(NR <= KW, "a tile group has a lane for every tile row");
-          uint32_t S[NR][5];
+          uint32_t S[NR][5];   // the tile rows' moments, parked
 #pragma unroll
           for (int t = 0; t < NR; t++) {
             const int y0 = t * KH;
-            uint32_t sum_s = 0, sum_d = 0, sum_s2 = 0, sum_d2 = 0, sum_sd = 0;
+            r1dist::CdefMoments m;   // a local: the sums sit in registers before the t loop is unrolled
             if (col_live) {
 #pragma unroll
               for (int rr = 0; rr < KH; rr++) {
@@ -757,37 +757,30 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
                 if constexpr (SRC_KEEP) sv = BPP == 1 ? (uint32_t)src_l[(y0 + rr) * SRC_ROW]
                                                       : (uint32_t) * (const uint16_t *)(src_l + (y0 + rr) * SRC_ROW);
                 else sv = (uint32_t)ld_px<BPP>(po + (y0 + rr) * so);
-                const uint32_t dv = (uint32_t)rc[y0 + rr];
-                sum_s += sv; sum_d += dv;
-                sum_s2 += sv * sv; sum_d2 += dv * dv; sum_sd += sv * dv;
+                m.add(sv, (uint32_t)rc[y0 + rr]);
               }
             }
-#pragma unroll
-            for (int m = 1; m < KW; m <<= 1) {
-              sum_s += __shfl_xor(sum_s, m, 64); sum_d += __shfl_xor(sum_d, m, 64);
-              sum_s2 += __shfl_xor(sum_s2, m, 64); sum_d2 += __shfl_xor(sum_d2, m, 64);
-              sum_sd += __shfl_xor(sum_sd, m, 64);
-            }
-            S[t][0] = sum_s; S[t][1] = sum_d; S[t][2] = sum_s2; S[t][3] = sum_d2; S[t][4] = sum_sd;
+            m.xor_sum(1, KW);
+            m.store(S[t]);
           }
+          // the lane select runs on the parked dwords, sum by sum: on an array of CdefMoments, field by field, the
+          // 8-bit 8x8 type-search kernel spilled two dwords more and lost 0.24 % (profiles/r08_reduce_ab_notes.md)
           const int j = c & (KW - 1);
-          uint32_t P5[5];
+          uint32_t P5a[5];
 #pragma unroll
           for (int q5 = 0; q5 < 5; q5++) {
-            P5[q5] = S[0][q5];
+            P5a[q5] = S[0][q5];
 #pragma unroll
-            for (int t = 1; t < NR; t++) P5[q5] = j == t ? S[t][q5] : P5[q5];
+            for (int t = 1; t < NR; t++) P5a[q5] = j == t ? S[t][q5] : P5a[q5];
           }
+          const r1dist::CdefMoments P5 = r1dist::CdefMoments::load(P5a);
           if (TAIL_DEFER && tail_defer) {
             // type search, 8x8: lane `slot` of the candidate's eight keeps this type's five sums; the tails run
             // once, behind the loop
-            if (j == slot) {
-#pragma unroll
-              for (int q5 = 0; q5 < 5; q5++) tail_keep[q5] = P5[q5];
-            }
+            if (j == slot) tail_keep = P5;
           } else if (col_live && j < NR)
-            acc += r1dist::cdef_tile_tail<BD>(P5[0], P5[1], P5[2], P5[3], P5[4], KW * KH, cd.ox + c - j,
-                                              cd.oy + j * KH, qa.scales, qa.scale_stride, BD);
+            acc += r1dist::cdef_tile_tail<BD>(P5, KW * KH, cd.ox + c - j, cd.oy + j * KH, qa.scales, qa.scale_stride,
+                                              BD);
         } else {
 #pragma unroll
           for (int y0 = 0; y0 < H; y0 += 4) {
@@ -807,9 +800,7 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
             cell += __shfl_xor(cell, 2, 64);
             if (col_live && (c & 3) == 0) {
               const int lx = (cd.ox + c) << qa.xdec, ly = (cd.oy + y0) << qa.ydec;
-              const uint32_t sc =
-                  qa.scales ? qa.scales[(size_t)(ly >> 3) * qa.scale_stride + (lx >> 3)] : (1u << 14);
-              acc += ((unsigned long long)cell * sc + 128) >> 8;
+              acc += r1dist::wsse_cell(cell, r1dist::dist_scale_at(qa.scales, qa.scale_stride, lx, ly));
             }
           }
         }
@@ -843,12 +834,7 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
       }
       }
       if (!(TAIL_DEFER && tail_defer)) {   // wave-uniform
-#pragma unroll
-        for (int m = 1; m < P; m <<= 1) {
-          const uint32_t lo = __shfl_xor((uint32_t)acc, m, 64);
-          const uint32_t hi = __shfl_xor((uint32_t)(acc >> 32), m, 64);
-          acc += ((unsigned long long)hi << 32) | lo;
-        }
+        acc = xor_sum_u64(acc, P);
         if (live_st && c == 0) qa.pix_dist[oslot] = qa.dist_kind == R1_DIST_WSSE ? (acc + 32) / 64 : acc;
       }
     }
@@ -863,8 +849,7 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
     // they ran once per type with ONE lane of a candidate's eight alive; here lane j runs the tail of type j --
     // one pass for all (up to seven) types of the candidate
     if (tail_defer && col_live && c < qa.nt) {
-      const unsigned long long d = r1dist::cdef_tile_tail<BD>(tail_keep[0], tail_keep[1], tail_keep[2], tail_keep[3],
-                                                              tail_keep[4], 64, cd.ox, cd.oy, qa.scales, qa.scale_stride, BD);
+      const unsigned long long d = r1dist::cdef_tile_tail<BD>(tail_keep, 64, cd.ox, cd.oy, qa.scales, qa.scale_stride, BD);
       if (live_st) qa.pix_dist[cand * (long long)qa.nt + c] = d;
     }
   }

@@ -116,7 +116,8 @@ const char *r1_last_error(void);
  * 7 (round 6): + r1_cdef_lrf_trial_batch, r1_cdef_lrf_trial_scratch_bytes, r1_cdef_apply_area, R1TrialUnit,
  *    r1_comm_plane_pool_open / _close (additions only; nothing of 6 changed).
  * Additions never changed an existing signature: the peer-store entry points (r1_comm_push_*, round 4) and
- * r1_comm_push_frame (round 5) were added under versions 4 and 5 respectively. */
+ * r1_comm_push_frame (round 5) were added under versions 4 and 5 respectively, and the compound candidate
+ * (r1_rdo_compound_cand_batch, R1CompoundCand) under version 7. */
 int r1_abi_version(void);
 
 /* ---- dist:: (reference: src/dist.rs get_sad 31, get_satd 156; dispatch
@@ -889,6 +890,34 @@ int r1_rdo_pred_cand_batch(r1_ctx *ctx, const R1Plane *org, const void *pred, in
                            int scale_stride, int xdec, int ydec, uint32_t *sad_out,
                            uint32_t *satd_out, uint16_t *eob_out, uint64_t *dist_out,
                            void *qcoeffs_out, void *rec_out, void *stream);
+
+/* ---- the two-reference (compound) inter candidate in ONE launch (added under ABI 7): what
+ * predict_inter_compound (src/predict.rs:339-382) and the SATD ranking of the inter mode pre-screen
+ * (src/rdo.rs:1238-1271, 1328-1352: the eight RAV1E_INTER_COMPOUND_MODES on one reference pair) compute per
+ * candidate:
+ *   t0   = prep_8tap(ref0 @ (rx0, ry0), fracs0)      t1 = prep_8tap(ref1 @ (rx1, ry1), fracs1)   (src/mc.rs:360)
+ *   pred = mc_avg(t0, t1)                                                                         (src/mc.rs:454)
+ *   sad  = get_sad(org @ (ox, oy), pred)   if sad_out      satd = get_satd(org @ (ox, oy), pred)   if satd_out
+ * The int16 intermediates never reach HBM; the prediction does only through pred_out (n dense w*h blocks in
+ * the planes' pixel type -- the `pred` input of r1_rdo_pred_cand_batch / r1_rdo_txsearch_batch).  Each output is
+ * optional (NULL), at least one must be given; every entry of a given output is written exactly once (no
+ * zeroed buffer is needed).  (w, h): what r1_mc_prep_batch takes under this ABI -- w a power of two in 4..128,
+ * h even in 2..128, w or h <= 4 selecting the 4-tap filters as get_filter does; sad_out / satd_out only for the
+ * 22 BlockSizes (R1_EINVAL otherwise).  The three planes share bytes_per_px and bit_depth (8, 10, 12).
+ * Positions may lie in the padding, as for R1McCand.  Chroma planes go through the same call with their own
+ * (w, h) and positions, as motion_compensate does. */
+typedef struct R1CompoundCand {      /* 20 bytes */
+  int16_t ox, oy;                    /* block position in the org (source) plane */
+  int16_t rx0, ry0, rx1, ry1;        /* full-pel positions in ref0 / ref1 (get_mv_params) */
+  uint8_t col_frac0, row_frac0, col_frac1, row_frac1;   /* 0..15 */
+  uint8_t mode_x, mode_y;            /* FilterMode (fi.default_filter for both references) */
+  uint8_t reserved[2];
+} R1CompoundCand;
+int r1_rdo_compound_cand_batch(r1_ctx *ctx, const R1Plane *org, const R1Plane *ref0,
+                               const R1Plane *ref1, int w, int h,
+                               const R1CompoundCand *cands, int n,
+                               uint32_t *sad_out, uint32_t *satd_out, void *pred_out,
+                               void *stream);
 
 /* ---- the transform-type search of one prediction in ONE launch (ABI 5): rdo_tx_type_decision
  * (src/rdo.rs:1701-1817) evaluates every TxType of RAV1E_TX_TYPES (src/transform/mod.rs:28-44) that the

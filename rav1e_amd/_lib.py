@@ -17,6 +17,13 @@ class R1QuantParams(C.Structure):
                 ("dc_delta_q", C.c_int8), ("ac_delta_q", C.c_int8), ("reserved", C.c_uint8 * 3)]
 
 
+class R1CompoundCand(C.Structure):
+    _fields_ = [("ox", C.c_int16), ("oy", C.c_int16), ("rx0", C.c_int16), ("ry0", C.c_int16),
+                ("rx1", C.c_int16), ("ry1", C.c_int16), ("col_frac0", C.c_uint8), ("row_frac0", C.c_uint8),
+                ("col_frac1", C.c_uint8), ("row_frac1", C.c_uint8), ("mode_x", C.c_uint8), ("mode_y", C.c_uint8),
+                ("reserved", C.c_uint8 * 2)]
+
+
 class R1CdefParams(C.Structure):
     _fields_ = [("y_strengths", C.c_uint8 * 8), ("uv_strengths", C.c_uint8 * 8),
                 ("damping", C.c_uint8), ("bit_depth", C.c_uint8), ("reserved", C.c_uint8 * 2)]
@@ -133,6 +140,7 @@ SYMBOLS = {
                                      _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "r1_rdo_pred_cand_batch": (_i, [_vp, _PP, _vp, _i, _i, _i, _vp, _i, C.POINTER(R1QuantParams), _i,
                                     _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "r1_rdo_compound_cand_batch": (_i, [_vp, _PP, _PP, _PP, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "r1_rdo_txsearch_batch": (_i, [_vp, _PP, _PP, _vp, _i, _i, _i, _vp, _i, C.c_uint32, C.POINTER(R1QuantParams),
                                    _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "r1_tx_type_mask": (C.c_uint32, [_i, _i, _i, _i]),

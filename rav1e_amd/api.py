@@ -32,6 +32,11 @@ EDGE_LEN = 257
 RDO_CAND = np.dtype([("ox", "<i2"), ("oy", "<i2"), ("rx", "<i2"), ("ry", "<i2"),
                      ("col_frac", "u1"), ("row_frac", "u1"), ("mode_x", "u1"), ("mode_y", "u1"),
                      ("tx_type", "u1"), ("reserved", "u1", (3,))])
+# R1CompoundCand: one two-reference candidate (r1_rdo_compound_cand_batch)
+COMPOUND_CAND = np.dtype([("ox", "<i2"), ("oy", "<i2"), ("rx0", "<i2"), ("ry0", "<i2"), ("rx1", "<i2"), ("ry1", "<i2"),
+                          ("col_frac0", "u1"), ("row_frac0", "u1"), ("col_frac1", "u1"), ("row_frac1", "u1"),
+                          ("mode_x", "u1"), ("mode_y", "u1"), ("reserved", "u1", (2,))])
+assert COMPOUND_CAND.itemsize == C.sizeof(_lib.R1CompoundCand)
 
 
 class R1Error(RuntimeError):
@@ -135,6 +140,7 @@ def _out_spec(*outs):
 # block; a dtype given as a function takes the plane's bytes per pixel.
 _CAND_OUTS = _out_spec(("sad", "n", torch.int32), ("satd", "n", torch.int32), ("coeffs", "nx", _coeff_dtype),
                        ("pred", "nhw", _pix_dtype))
+_COMPOUND_OUTS = _out_spec(("sad", "n", torch.int32), ("satd", "n", torch.int32), ("pred", "nhw", _pix_dtype))
 _FULL_CAND_OUTS = _out_spec(("eob", "n", torch.int16), ("tx_dist", "n", torch.int64), ("sad", "n", torch.int32),
                             ("satd", "n", torch.int32), ("est_rate", "n", torch.int64),
                             ("qcoeffs", "na", _coeff_dtype), ("coeffs", "nx", _coeff_dtype))
@@ -956,4 +962,19 @@ class Context:
                                                p("satd", want_satd), p("coeffs", want_coeffs),
                                                p("pred", want_pred), _stream_ptr()),
                     "r1_rdo_cand_batch")
+        return o
+
+    def rdo_compound_cand_batch(self, org, ref0, ref1, w, h, cands, n=None, want_sad=False, want_satd=True,
+                                want_pred=False, outs=None):
+        """prep_8tap(ref0), prep_8tap(ref1) -> mc_avg -> sad / satd against the source for every two-reference
+        candidate (COMPOUND_CAND), one launch; pred: (n, h, w) pixels, the `pred` input of rdo_pixel_cand_batch /
+        rdo_txsearch_batch.  An output that is not wanted is a NULL pointer even if outs holds it."""
+        dc, n = _dev_cands(cands, COMPOUND_CAND, n)
+        wants = (want_sad, want_satd, want_pred)
+        o = _bind_outs(outs, _COMPOUND_OUTS, wants, org.bpp, n, w, h)
+        po, p0, p1 = org.cstruct(), ref0.cstruct(), ref1.cstruct()
+        ptrs = [o[k].data_ptr() if want else None for k, want in zip(("sad", "satd", "pred"), wants)]
+        self._check(self.lib.r1_rdo_compound_cand_batch(self.h, C.byref(po), C.byref(p0), C.byref(p1), w, h,
+                                                        dc.data_ptr(), n, *ptrs, _stream_ptr()),
+                    "r1_rdo_compound_cand_batch")
         return o

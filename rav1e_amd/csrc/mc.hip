@@ -64,13 +64,9 @@ __global__ __launch_bounds__(256) void k_avg(const int16_t *__restrict__ t1,
                                              const int16_t *__restrict__ t2,
                                              long long total, int bit_depth,
                                              void *__restrict__ dst_) {
-  const int ib = r1mc::intermediate_bits(bit_depth);
-  const int32_t maxv = (1 << bit_depth) - 1;
-  const int32_t bias = bit_depth == 8 ? 0 : 8192 * 2;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total;
        i += (long long)gridDim.x * 256) {
-    const int32_t v = r1mc::clamp_px(
-        r1mc::round_shift((int32_t)t1[i] + (int32_t)t2[i] + bias, ib + 1), maxv);
+    const int32_t v = r1mc::avg_px((int32_t)t1[i], (int32_t)t2[i], bit_depth);
     if constexpr (BPP == 1) ((uint8_t *)dst_)[i] = (uint8_t)v;
     else ((uint16_t *)dst_)[i] = (uint16_t)v;
   }

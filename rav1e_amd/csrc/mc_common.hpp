@@ -82,6 +82,12 @@ __device__ __forceinline__ int32_t clamp_px(int32_t v, int32_t maxv) {
 __device__ __forceinline__ int intermediate_bits(int bit_depth) {
   return bit_depth == 12 ? 2 : 4;
 }
+// mc_avg (mc.rs:454-479) of two prep_8tap intermediates: both carry -PREP_BIAS for bit depths above 8, which
+// comes back out before the rounding shift by intermediate_bits + 1 and the clamp to the pixel range
+__device__ __forceinline__ int32_t avg_px(int32_t t1, int32_t t2, int bit_depth) {
+  const int32_t bias = bit_depth == 8 ? 0 : 8192 * 2;
+  return clamp_px(round_shift(t1 + t2 + bias, intermediate_bits(bit_depth) + 1), (1 << bit_depth) - 1);
+}
 
 // ---- staging of the reference window into LDS ----
 // A "slab" is up to 64 adjacent columns of one candidate block.  Its window is

@@ -4,6 +4,7 @@ restates a reference function (file:line); tests/golden/rdo_glue_ref.npz pins th
 the kernels by executing the reference's own text (tests/golden/gen_rdo_glue_ref.py).
 
   get_mv_params              src/predict.rs:284-297   (MV -> integer offset + 1/16-pel fractions)
+  compound_cands             src/predict.rs:339-382   (two MV lists -> the descriptors of the compound launch)
   clip_visible_bsize         src/rdo.rs:228-251
   luma_ac_pads               src/predict.rs:644-688   (luma_ac's w_pad / h_pad and its luma offset)
   largest_chroma_tx_size     src/partition.rs:385-393
@@ -29,6 +30,23 @@ def get_mv_params(mv_row, mv_col, po_x, po_y, xdec=0, ydec=0):
     row_frac = (mv_row << (1 - ydec)) & 0xf
     col_frac = (mv_col << (1 - xdec)) & 0xf
     return row_frac, col_frac, po_x + col_offset, po_y + row_offset
+
+
+def compound_cands(x, y, mvs0, mvs1, filter_mode, xdec=0, ydec=0):
+    """The descriptors of r1_rdo_compound_cand_batch for one block at plane position (x, y): candidate i pairs
+    mvs0[i] on the first reference with mvs1[i] on the second, each (row, col) in 1/8 pel -- get_mv_params per
+    reference as predict_inter_compound does (src/predict.rs:339-382), fi.default_filter for both.
+    -> numpy array of api.COMPOUND_CAND"""
+    import numpy as np
+    from .api import COMPOUND_CAND
+    assert len(mvs0) == len(mvs1)
+    c = np.zeros(len(mvs0), COMPOUND_CAND)
+    c["ox"], c["oy"], c["mode_x"], c["mode_y"] = x, y, int(filter_mode), int(filter_mode)
+    for i, pair in enumerate(zip(mvs0, mvs1)):
+        for k, (mv_row, mv_col) in enumerate(pair):
+            rf, cf, px, py = get_mv_params(int(mv_row), int(mv_col), x, y, xdec, ydec)
+            c["rx%d" % k][i], c["ry%d" % k][i], c["col_frac%d" % k][i], c["row_frac%d" % k][i] = px, py, cf, rf
+    return c
 
 
 def clip_visible_bsize(frame_w, frame_h, blk_w, blk_h, x, y):

@@ -8,6 +8,7 @@
 #   bench         bench.py --full                  -> bench.json
 #   chains        bench.py --chain full|pixel, 8- and 10-bit
 #   txs           tools/bench_txsearch.py, 8- and 10-bit, cdef_dist and transform-domain distortion
+#   compound      tools/bench_compound.py, 8- and 10-bit (the compound launch against prep x 2 -> avg -> pred_cand)
 #   txs_ab:LIBS   the same with each library of the comma-separated list copied in (same-box A/B)
 #   lrf_ab:LIBS   tools/bench_lrf_search.py per library
 #   stage_ab:LIBS STAGES=... tools/frame_pipeline.py --stages per library
@@ -67,6 +68,10 @@ import json; d=json.loads(open('$OUT/${chain}_chain_${bd}bit.json').read()); pri
       for bd in 8 10; do for kind in 3 0; do
         timeout 600 python tools/bench_txsearch.py --bit-depth $bd --kind $kind 2>&1 | grep "^{" | tee -a $OUT/txsearch.jsonl | cut -c1-330
       done; done ;;
+    compound)
+      for bd in 8 10; do
+        timeout 600 python tools/bench_compound.py --bit-depth $bd 2>&1 | grep "^{" | tee -a $OUT/compound.jsonl | cut -c1-330
+      done ;;
     txs_ab)   # TXS_SIZES=8 TXS_PASSES=1 narrow the run
       for pass in $(seq 1 ${TXS_PASSES:-2}); do for lib in ${ARG//,/ }; do
         cp $lib rav1e_amd/librav1e_hip.so

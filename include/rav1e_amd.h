@@ -564,7 +564,7 @@ int r1_prescreen_select_batch(r1_ctx *ctx, const uint32_t *keys, int n_groups, i
  * rayon workers, src/encoder.rs encode_tile_group, and loops the reference
  * frames inside, me.rs:190-199) and execute concurrently; inside a job the
  * superblocks go in anti-diagonal wavefronts -- the exact dependence order of
- * the reference's raster walk (see rav1e_amd/csrc/me.hip).
+ * the reference's raster walk (see rav1e_amd/csrc/me_search.hpp).
  *
  * R1MeStats = MEStats (src/me.rs:31-35): mv in 1/8 pel, SAD normalised to a
  * 128x128 block.  stats: the FrameMEStats array of this reference frame

@@ -1,5 +1,5 @@
 // cand_helpers.inc -- what the fused candidate kernel (rdo_cand_kernel.hpp), the RDO-time sub-pel search
-// (me.hip, k_me_blocks_small) and the put / prep of transform-sized blocks (mc.hip, k_mc_fast) share: the DPP Hadamard (SATD with lane = column), v_sad, the packed
+// (me_blocks.hip, k_me_blocks_small) and the put / prep of transform-sized blocks (mc.hip, k_mc_fast) share: the DPP Hadamard (SATD with lane = column), v_sad, the packed
 // i16 helpers, and the put_8tap / prep_8tap column filters on v_dot4 / v_dot2 with their tap loads.
 // Included INSIDE the including file's anonymous namespace, after mc_taps_packed.inc (kTapI8 /
 // kTapI16) and with `T` (= r1tx::T, int32_t) in scope.

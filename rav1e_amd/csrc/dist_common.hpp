@@ -1,5 +1,5 @@
 // dist_common.hpp -- the per-tile SAD / SATD arithmetic shared by dist.hip
-// (candidates from HBM) and me.hip (sub-pel candidates predicted into LDS), and
+// (candidates from HBM) and me_blocks.hip (sub-pel candidates predicted into LDS), and
 // the reference's pixel-domain distortion arithmetic, each rule stated once for
 // every kernel that needs it (dist_scaled.hip, the fused candidate kernel,
 // lrf.hip, cdef_search.hip):

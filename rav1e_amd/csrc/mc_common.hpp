@@ -1,5 +1,5 @@
 // mc_common.hpp -- AV1 sub-pel interpolation filters and the put/prep
-// arithmetic shared by mc.hip, me.hip and rdo_cand_kernel.hpp.
+// arithmetic shared by mc.hip, me_blocks.hip and rdo_cand_kernel.hpp.
 //
 // Restates (reference file:line):
 //   SUBPEL_FILTERS     src/mc.rs:110-219 (AV1 spec tables: regular, smooth,

@@ -171,7 +171,8 @@ import json; d=json.loads(open('$OUT/dry$n.json').read()); print('dry $n', d['va
     pmc_stage_hbm)   # STAGES=substr: FETCH_SIZE of the kernels of those frame stages, 10-bit (its own pass)
       FP="python $GRAFT_REPO_ROOT/tools/frame_pipeline.py --bit-depth ${ARG:-10} --reps 2 --sustain-ms 0 --stages $STAGES"
       PMC_TIMEOUT=60 pmc_pass stage_fetch "FETCH_SIZE" -- $FP ;;
-    me_step)   # ARG = a library built with -DR1_ME_PROF: where a block search of the persistent tile ME spends its time
+    me_step)   # ARG = rav1e_amd/librav1e_hip_meprof.so (make -C rav1e_amd/csrc me_prof: me_tile.hip and me_blocks.hip with
+               # -DR1_ME_PROF): where a block search of the persistent tile ME spends its time
       cp $ARG rav1e_amd/librav1e_hip.so
       for bd in 8 10; do R1_ME_PROF_BD=$bd timeout 300 python tools/me_prof.py 4 2>/dev/null | grep "^{" | sed "s/^/bd $bd /"; done | tee $OUT/me_step.txt
       cp /tmp/lib_orig.so rav1e_amd/librav1e_hip.so ;;

@@ -117,7 +117,8 @@ const char *r1_last_error(void);
  *    r1_comm_plane_pool_open / _close (additions only; nothing of 6 changed).
  * Additions never changed an existing signature: the peer-store entry points (r1_comm_push_*, round 4) and
  * r1_comm_push_frame (round 5) were added under versions 4 and 5 respectively, and the compound candidate
- * (r1_rdo_compound_cand_batch, R1CompoundCand) under version 7. */
+ * (r1_rdo_compound_cand_batch, R1CompoundCand) under version 7, as were the frame's scale maps and segmentation
+ * inputs (r1_frame_scales, r1_scale_kmeans, r1_segmentation_from_centroids, r1_spatiotemporal_scale_batch). */
 int r1_abi_version(void);
 
 /* ---- dist:: (reference: src/dist.rs get_sad 31, get_satd 156; dispatch
@@ -524,6 +525,74 @@ int r1_update_block_importances(r1_ctx *ctx, const uint32_t *intra_costs,
                                 const int16_t *mvs, int w_in_imp_b, int h_in_imp_b, int len,
                                 float *ref_importances, void *scratch, long long scratch_bytes,
                                 void *stream);
+
+/* ---- temporal-RDO scale maps and segmentation inputs (SURVEY.md 8f "N1" -> "N4"): what the reference does once
+ * per coded frame between the lookahead and the first RDO call.  All maps are n = w_in_imp_b * h_in_imp_b entries,
+ * row-major, DEVICE; a DistortionScale is its Q14 u32.  Every result is the reference's integer arithmetic bit for
+ * bit; the one float is the f64 pow(frac, 1/3) of distortion_scale_for, whose last bits do not reach the Q14
+ * result except on a vanishing share of inputs (docs/PARITY.md).
+ *
+ * r1_frame_scales: distortion_scale_for(block_importances[i], intra_costs[i]) per block (src/api/internal.rs:
+ * 1211-1230, src/rdo.rs:506-553; an intra cost of 0 gives 1.0), then CodedFrameData::compute_spatiotemporal_scores
+ * (activity_scales given: score = d * a, both maps times inv_mean(scores)) or compute_temporal_scores
+ * (activity_scales NULL, Tune::Psnr: both outputs are d * inv_mean(d)) (src/encoder.rs:744-777;
+ * DistortionScale::inv_mean, Mul src/rdo.rs:585-630).  distortion_scales_out is the `scales` grid of
+ * r1_dist_scaled_batch and the fused candidates as it stands; spatiotemporal_out feeds r1_scale_kmeans.
+ * stats_out (DEVICE): the sum of blog32_q11 over the scores, inv_mean, and the functions' return value
+ * inv_mean.blog64() >> 1 that rate control takes.  scratch: DEVICE, 256-byte aligned,
+ * r1_frame_scales_scratch_bytes(n) bytes (< 0 on error). */
+typedef struct R1ScaleStats {
+  int64_t log_sum_q11;           /* sum of blog32_q11(score) */
+  uint32_t inv_mean;             /* DistortionScale::inv_mean(scores).0 */
+  uint32_t reserved;
+  int64_t log_isqrt_mean_scale;  /* inv_mean.blog64() >> 1, Q57 */
+} R1ScaleStats;
+long long r1_frame_scales_scratch_bytes(int n);
+int r1_frame_scales(r1_ctx *ctx, const uint32_t *intra_costs, const float *block_importances,
+                    const uint32_t *activity_scales, int n, uint32_t *distortion_scales_out,
+                    uint32_t *spatiotemporal_out, R1ScaleStats *stats_out, void *scratch,
+                    long long scratch_bytes, void *stream);
+
+/* r1_scale_kmeans: the k-means of blog16(score) that segmentation_optimize_inner runs for k = 3 ... 8
+ * (src/segmentation.rs:84-94, src/util/kmeans.rs:11-102) from a histogram of the keys instead of the sorted
+ * array -- the same centroids, thresholds that double-count, rounding and early stop included.
+ * centroids_out: DEVICE, 6 x 8 int16, row r = k = 8 - r (the order of the reference's tuple), unused entries 0.
+ * scratch: DEVICE, 256-byte aligned, r1_scale_kmeans_scratch_bytes(n) bytes (the bin tables; < 0 on error). */
+long long r1_scale_kmeans_scratch_bytes(int n);
+int r1_scale_kmeans(r1_ctx *ctx, const uint32_t *spatiotemporal, int n, int16_t *centroids_out, void *scratch,
+                    long long scratch_bytes, void *stream);
+
+/* r1_segmentation_from_centroids: the rest of segmentation_optimize_inner (src/segmentation.rs:96-160) and
+ * SegmentationState::update_threshold (src/encoder.rs:566-580) on a HOST copy of the 96 bytes above; needs no GPU.
+ * The k whose centroid spacing has the least variance (the last such k), compute_delta (blog64(ac_q), bexp64,
+ * select_ac_qi(..).max(1) - base_q_idx, centroids in reverse, .max(1 - base_q_idx)) -> seg_delta[0 .. k), the
+ * SEG_LVL_ALT_Q data; threshold[i] = DistortionScale::new(base_ac_q^2, q[i + 1] * q[i]), unused entries 0.
+ * update_data / preskip / last_active_segid stay the caller's. */
+typedef struct R1SegmentationData {
+  int16_t seg_delta[8];
+  uint32_t threshold[7];
+  uint8_t min_segment, max_segment;
+  uint8_t k;                     /* max_segment + 1 */
+  uint8_t position;              /* row of the centroid table that was chosen: 8 - k */
+} R1SegmentationData;
+int r1_segmentation_from_centroids(const int16_t *centroids, int base_q_idx, int bit_depth,
+                                   R1SegmentationData *out);
+
+/* r1_spatiotemporal_scale_batch: spatiotemporal_scale (src/rdo.rs:464-504: the rounded mean of d * a over the
+ * importance blocks a coded block covers, clipped to the map) and segment_idx_from_distortion with select_segment's
+ * .max(min_segment) (src/segmentation.rs:180-196) for n coded blocks, one lane each.  blocks: HOST (the library
+ * checks every entry -- a BlockSize outside the 22, or an origin outside the map, is R1_EINVAL -- and uploads the
+ * list on `stream`); bo_x, bo_y in 4x4 units as a PlaneBlockOffset.  activity_scales NULL = 1.0.  thresholds:
+ * HOST, seven entries that never increase (R1SegmentationData.threshold), NULL = segment index min_segment.
+ * scale_out (u32) / sidx_out (u8): DEVICE, either may be NULL. */
+typedef struct R1ScaleBlock {
+  int32_t bo_x, bo_y;
+  int32_t bsize;                 /* BlockSize */
+} R1ScaleBlock;
+int r1_spatiotemporal_scale_batch(r1_ctx *ctx, const uint32_t *distortion_scales,
+                                  const uint32_t *activity_scales, int w_in_imp_b, int h_in_imp_b,
+                                  const R1ScaleBlock *blocks, int n, const uint32_t *thresholds,
+                                  int min_segment, uint32_t *scale_out, uint8_t *sidx_out, void *stream);
 
 /* ---- intra mode pre-screen (SURVEY.md 8f "N1"; src/rdo.rs:1434-1506): for
  * every block the candidate modes are predicted from ONE edge set

@@ -54,6 +54,20 @@ class R1MeJob(C.Structure):
                 ("tile_w", C.c_int32), ("tile_h", C.c_int32)]
 
 
+class R1ScaleStats(C.Structure):
+    _fields_ = [("log_sum_q11", C.c_int64), ("inv_mean", C.c_uint32), ("reserved", C.c_uint32),
+                ("log_isqrt_mean_scale", C.c_int64)]
+
+
+class R1SegmentationData(C.Structure):
+    _fields_ = [("seg_delta", C.c_int16 * 8), ("threshold", C.c_uint32 * 7), ("min_segment", C.c_uint8),
+                ("max_segment", C.c_uint8), ("k", C.c_uint8), ("position", C.c_uint8)]
+
+
+class R1ScaleBlock(C.Structure):
+    _fields_ = [("bo_x", C.c_int32), ("bo_y", C.c_int32), ("bsize", C.c_int32)]
+
+
 # every symbol include/rav1e_amd.h declares: name -> (restype, argtypes)
 _vp, _i, _sz, _pd = C.c_void_p, C.c_int, C.c_size_t, C.c_ssize_t
 _PP = C.POINTER(R1Plane)
@@ -136,6 +150,12 @@ SYMBOLS = {
     "r1_update_block_importances_scratch_bytes": (C.c_longlong, [_i, _i]),
     "r1_update_block_importances": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, C.c_longlong,
                                          _vp]),
+    "r1_frame_scales_scratch_bytes": (C.c_longlong, [_i]),
+    "r1_frame_scales": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, C.c_longlong, _vp]),
+    "r1_scale_kmeans_scratch_bytes": (C.c_longlong, [_i]),
+    "r1_scale_kmeans": (_i, [_vp, _vp, _i, _vp, _vp, C.c_longlong, _vp]),
+    "r1_segmentation_from_centroids": (_i, [_vp, _i, _i, C.POINTER(R1SegmentationData)]),
+    "r1_spatiotemporal_scale_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp]),
     "r1_rdo_pixel_cand_batch": (_i, [_vp, _PP, _PP, _i, _i, _i, _vp, _i, C.POINTER(R1QuantParams), _i,
                                      _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "r1_rdo_pred_cand_batch": (_i, [_vp, _PP, _vp, _i, _i, _i, _vp, _i, C.POINTER(R1QuantParams), _i,

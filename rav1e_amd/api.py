@@ -37,6 +37,9 @@ COMPOUND_CAND = np.dtype([("ox", "<i2"), ("oy", "<i2"), ("rx0", "<i2"), ("ry0", 
                           ("col_frac0", "u1"), ("row_frac0", "u1"), ("col_frac1", "u1"), ("row_frac1", "u1"),
                           ("mode_x", "u1"), ("mode_y", "u1"), ("reserved", "u1", (2,))])
 assert COMPOUND_CAND.itemsize == C.sizeof(_lib.R1CompoundCand)
+# R1ScaleBlock: a coded block of r1_spatiotemporal_scale_batch (origin in 4x4 units, BlockSize)
+SCALE_BLOCK = np.dtype([("bo_x", "<i4"), ("bo_y", "<i4"), ("bsize", "<i4")])
+assert SCALE_BLOCK.itemsize == C.sizeof(_lib.R1ScaleBlock)
 
 
 class R1Error(RuntimeError):
@@ -169,6 +172,21 @@ def _bind_outs(outs, spec, wants, bpp, n, w, h, nt=1):
 def _ptrs(o, *keys):
     """data pointers of o[k] for the keys, None where o has no such key"""
     return [o[k].data_ptr() if k in o else None for k in keys]
+
+
+def segmentation_from_centroids(centroids, base_q_idx, bit_depth, lib=None):
+    """r1_segmentation_from_centroids: a host function of the library (no context, no GPU); see
+    Context.segmentation_from_centroids"""
+    lib = lib or _lib.load()
+    c = centroids.cpu().numpy() if isinstance(centroids, torch.Tensor) else centroids
+    c = np.ascontiguousarray(c, dtype=np.int16)
+    assert c.size == 48
+    out = _lib.R1SegmentationData()
+    rc = lib.r1_segmentation_from_centroids(c.ctypes.data, int(base_q_idx), int(bit_depth), C.byref(out))
+    if rc != 0:
+        raise R1Error("r1_segmentation_from_centroids failed (%d): %s" % (rc, lib.r1_last_error().decode()))
+    return {"seg_delta": np.array(out.seg_delta[:], np.int16), "threshold": np.array(out.threshold[:], np.uint32),
+            "min_segment": out.min_segment, "max_segment": out.max_segment, "k": out.k, "position": out.position}
 
 
 class Context:
@@ -362,6 +380,72 @@ class Context:
             mvs.data_ptr(), w, h, length, ref_importances.data_ptr(), scratch.data_ptr(),
             scratch.numel(), _stream_ptr()), "r1_update_block_importances")
         return ref_importances
+
+    def frame_scales(self, intra_costs, block_importances, activity_scales=None):
+        """distortion_scale_for per importance block + compute_spatiotemporal_scores (activity_scales given) or
+        compute_temporal_scores (None) (src/api/internal.rs:1211-1230, src/encoder.rs:744-777).  Device tensors:
+        int32 intra costs, float32 importances, int32 Q14 activity scales, all of one shape.  -> (distortion
+        scales, spatiotemporal scores, stats): int32 tensors of that shape -- the first is the `scales` grid of the
+        distortion entry points -- and a 24-byte uint8 tensor holding an R1ScaleStats (scale_stats reads it)"""
+        n = intra_costs.numel()
+        dist = torch.empty(intra_costs.shape, dtype=torch.int32, device="cuda")
+        scores = torch.empty(intra_costs.shape, dtype=torch.int32, device="cuda")
+        stats = torch.empty(C.sizeof(_lib.R1ScaleStats), dtype=torch.uint8, device="cuda")
+        need = self.lib.r1_frame_scales_scratch_bytes(n)
+        if need < 0:
+            raise R1Error("r1_frame_scales_scratch_bytes failed")
+        scratch = torch.empty(max(int(need), 256), dtype=torch.uint8, device="cuda")
+        self._check(self.lib.r1_frame_scales(
+            self.h, intra_costs.data_ptr(), block_importances.data_ptr(),
+            activity_scales.data_ptr() if activity_scales is not None else None, n, dist.data_ptr(),
+            scores.data_ptr(), stats.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream_ptr()),
+            "r1_frame_scales")
+        return dist, scores, stats
+
+    @staticmethod
+    def scale_stats(stats):
+        """the R1ScaleStats of frame_scales on the host (synchronises): (log_sum_q11, inv_mean,
+        log_isqrt_mean_scale)"""
+        s = _lib.R1ScaleStats.from_buffer_copy(stats.cpu().numpy().tobytes())
+        return s.log_sum_q11, s.inv_mean, s.log_isqrt_mean_scale
+
+    def scale_kmeans(self, spatiotemporal):
+        """the k-means of blog16(score) for k = 8 ... 3 (src/segmentation.rs:84-94, src/util/kmeans.rs) ->
+        (6, 8) int16 device tensor, row r = k = 8 - r, unused entries 0"""
+        n = spatiotemporal.numel()
+        need = self.lib.r1_scale_kmeans_scratch_bytes(n)
+        if need < 0:
+            raise R1Error("r1_scale_kmeans_scratch_bytes failed")
+        scratch = torch.empty(int(need), dtype=torch.uint8, device="cuda")
+        out = torch.empty((6, 8), dtype=torch.int16, device="cuda")
+        self._check(self.lib.r1_scale_kmeans(self.h, spatiotemporal.data_ptr(), n, out.data_ptr(),
+                                             scratch.data_ptr(), scratch.numel(), _stream_ptr()), "r1_scale_kmeans")
+        return out
+
+    def segmentation_from_centroids(self, centroids, base_q_idx, bit_depth):
+        """the rest of segmentation_optimize_inner + update_threshold (src/segmentation.rs:96-160,
+        src/encoder.rs:566-580) on the host; centroids: the (6, 8) table (a device tensor is downloaded: the one
+        synchronisation of the chain).  -> dict(seg_delta int16[8], threshold uint32[7], min_segment,
+        max_segment, k, position)"""
+        return segmentation_from_centroids(centroids, base_q_idx, bit_depth, self.lib)
+
+    def spatiotemporal_scale_batch(self, distortion_scales, activity_scales, blocks, thresholds=None, min_segment=0):
+        """spatiotemporal_scale + segment_idx_from_distortion (src/rdo.rs:464-504, src/segmentation.rs:180-196)
+        per coded block.  distortion_scales / activity_scales (or None = 1.0): (h_in_imp_b, w_in_imp_b) int32
+        device tensors; blocks: host SCALE_BLOCK records; thresholds: seven host values or None.
+        -> (scale int32[n], sidx uint8[n]) device tensors"""
+        h, w = distortion_scales.shape
+        b = np.ascontiguousarray(blocks, dtype=SCALE_BLOCK)
+        n = len(b)
+        scale = torch.empty(n, dtype=torch.int32, device="cuda")
+        sidx = torch.empty(n, dtype=torch.uint8, device="cuda")
+        thr = None if thresholds is None else np.ascontiguousarray(thresholds, dtype=np.uint32)
+        assert thr is None or thr.size == 7
+        self._check(self.lib.r1_spatiotemporal_scale_batch(
+            self.h, distortion_scales.data_ptr(), activity_scales.data_ptr() if activity_scales is not None else None,
+            w, h, b.ctypes.data, n, thr.ctypes.data if thr is not None else None, min_segment, scale.data_ptr(),
+            sidx.data_ptr(), _stream_ptr()), "r1_spatiotemporal_scale_batch")
+        return scale, sidx
 
     def prescreen_select_batch(self, keys, group, keep_head, k):
         """the selection step of the mode pre-screens (src/rdo.rs:1352-1357, 1504-1509): keys

@@ -374,6 +374,24 @@ class RSlice:
     def get_unchecked_mut(self, i):
         return refmut_index(self, i)
 
+    def clone_from(self, src):  # Box<[T]>::clone_from: the contents of src, whatever the length was
+        self.b[self.o:self.o + self.n] = src._copy().b
+        self.n = src.n
+
+    def partition_point(self, pred):  # core::slice::partition_point's binary search, step for step
+        size, left, right = self.n, 0, self.n
+        while left < right:
+            mid = left + size // 2
+            if pred(self[mid]):
+                left = mid + 1
+            else:
+                right = mid
+            size = right - left
+        return left
+
+    def map(self, f):  # [T; N]::map (by value: a new array)
+        return RSlice([f(x) for x in self.b[self.o:self.o + self.n]], 0, self.n, True)
+
     def copy_from_slice(self, src):
         if src.n != self.n:
             raise Panic("copy_from_slice: source slice length (%d) does not match destination slice length (%d)"
@@ -1076,6 +1094,9 @@ def clamp3(v, lo, hi):
     return lo if v < lo else hi if v > hi else v
 
 
+TRY_INTO_TARGET = None   # see int_method's try_into
+
+
 def int_method(v, t, name, a):
     """v.name(*a) for an integer v of static type t (t may be None when irrelevant)."""
     if name == "min":
@@ -1102,7 +1123,10 @@ def int_method(v, t, name, a):
         t2 = name[3:]          # num_traits::ToPrimitive
         return Some(v) if int_min(t2) <= v <= int_max(t2) else NONE
     if name == "try_into":
-        # the target type is inferred in Rust; every use in the reference goes to an unsigned type
+        # the target type is inferred in Rust; every use in the reference goes to an unsigned type, but for
+        # kmeans' `i64: TryInto<T>`, whose caller names T here (TRY_INTO_TARGET) while it runs
+        if TRY_INTO_TARGET is not None:
+            return try_from(v, TRY_INTO_TARGET)
         return Ok(v) if v >= 0 else Err(None)
     if name == "is_power_of_two":
         return v > 0 and (v & (v - 1)) == 0
@@ -1148,7 +1172,7 @@ def int_method(v, t, name, a):
         op = name[11:]
         t = _need(t, name)
         r = {"add": lambda: v + a[0], "sub": lambda: v - a[0], "mul": lambda: v * a[0],
-             "pow": lambda: v ** a[0]}[op]()
+             "pow": lambda: v ** a[0], "div": lambda: div(v, a[0])}[op]()   # div: only MIN / -1 saturates
         return max(int_min(t), min(int_max(t), r))
     if name.startswith("checked_"):
         op = name[8:]

@@ -2141,6 +2141,8 @@ class FnCompiler:
             return "_S([])"
         if a in VECS and name == "from":
             return "%s.to_vec()" % self.args(argn)[0]
+        if a in VECS and name == "from_iter":      # FromIterator::from_iter: what .collect() into the type does
+            return "_S(list(R.into_iter(%s)))" % self.args(argn)[0]
         if a in WRAPPERS and name in ("new", "from", "uninit", "uninit_array", "uninitialized", "zeroed"):
             if name in ("new", "from"):
                 v = self.args(argn)[0]

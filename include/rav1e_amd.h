@@ -118,7 +118,8 @@ const char *r1_last_error(void);
  * Additions never changed an existing signature: the peer-store entry points (r1_comm_push_*, round 4) and
  * r1_comm_push_frame (round 5) were added under versions 4 and 5 respectively, and the compound candidate
  * (r1_rdo_compound_cand_batch, R1CompoundCand) under version 7, as were the frame's scale maps and segmentation
- * inputs (r1_frame_scales, r1_scale_kmeans, r1_segmentation_from_centroids, r1_spatiotemporal_scale_batch). */
+ * inputs (r1_frame_scales, r1_scale_kmeans, r1_segmentation_from_centroids, r1_spatiotemporal_scale_batch) and the
+ * intra candidate (r1_rdo_intra_cand_batch). */
 int r1_abi_version(void);
 
 /* ---- dist:: (reference: src/dist.rs get_sad 31, get_satd 156; dispatch
@@ -1019,6 +1020,53 @@ int r1_rdo_txsearch_batch(r1_ctx *ctx, const R1Plane *org, const R1Plane *ref, c
                           int scale_stride, int xdec, int ydec, uint32_t *sad_out, uint32_t *satd_out,
                           uint16_t *eob_out, uint64_t *dist_out, uint64_t *est_rate_out,
                           void *qcoeffs_out, void *rec_out, void *stream);
+/* ---- the intra candidate in ONE launch (added under ABI 7): what the loop over the pre-screened intra modes
+ * (src/rdo.rs:1507-1600) makes encode_tx_block (src/encoder.rs:1404-1661) do per mode -- predict_intra from the
+ * block's edges (1458-1503), then the transform chain -- without the prediction travelling through HBM.  For
+ * candidate i the results are those of
+ *   r1_predict_intra_batch(cands, edges, lens, ac)  ->  r1_rdo_txsearch_batch(ref = NULL, pred = that output, ...)
+ * bit for bit; the prediction lives in registers / LDS and reaches HBM only through pred_out (optional: n dense
+ * w*h blocks in the plane's pixel type, written once per candidate).
+ *   cands:      n R1IntraCand as r1_predict_intra_batch takes them (avail_w / avail_h below the tx size at the
+ *               right / bottom frame edge, UV_CFL_PRED with `ac` included).
+ *   edge_group: >= 1 and a divisor of n.  Candidate i uses edge set, `lens` pair and `pos_xy` pair number
+ *               i / edge_group (edges / edge_stride / lens: the outputs of r1_intra_edges_batch; pos_xy: the block
+ *               position in `org`, as r1_intra_satd_batch takes it).  1 = the reference's own shape, one
+ *               get_intra_edges(Some(mode)) per candidate; a larger group lets the modes of a block share one set
+ *               built with mode = -1, as the pre-screen does.  A shared set holds every entry a mode-specific set
+ *               holds, with the same values, EXCEPT the top-left entry of a block with w + h >= 24 under
+ *               enable_intra_edge_filter: get_intra_edges smooths it (partition.rs:886-892) only for a mode whose
+ *               angle lies strictly between 90 and 180 degrees.  There the predictions differ, and callers must
+ *               use edge_group = 1 for D135 / D113 / D157 (and V / H with an angle delta that crosses into that
+ *               range) -- or give those candidates sets of their own.  Every other mode and geometry may share
+ *               (docs/PARITY.md, "intra candidate").
+ *   ac:         candidate i uses AC block i, dense w*h int16 per candidate (UV_CFL_PRED), NULL otherwise.
+ * tx_type_mask, the slot order, dist_kind (0 / R1_DIST_WSSE / R1_DIST_CDEF), which of est_rate_out / rec_out may
+ * be non-NULL for which kind, the output indexing [i * nt + j] and the `scales` grid: r1_rdo_txsearch_batch's.  All
+ * 19 transform sizes, bit depths 8 / 10 / 12.  Sizes up to 16x16 run the fan-out form of the kernel for any mask;
+ * sizes with a 32- or 64-point side run one plain launch per type (at most two), each of which makes the prediction
+ * again on the CU.  The occupancy requests of the kernels are those of the same (size, bit depth) inter
+ * instantiation: the chain behind the prediction is the same code.
+ * Two launches inside the call: where the fused kernel measured slower than the two launches it replaces by more
+ * than the +-3-4 % between boxes (tools/bench_intra_cand.py, profiles/r12_intra_cand.jsonl, profiles/HISTORY.md) the
+ * call predicts into pred_out -- or, without one, into a buffer of the context -- and runs r1_rdo_txsearch_batch's
+ * kernels on it, in the caller's stream: 16x16 with dist_kind 0 (every bit depth); at 10 / 12 bits also 16x16 and
+ * 32x32 with R1_DIST_WSSE / R1_DIST_CDEF and 64x64 with dist_kind 0.  Same slots, same results, same pred_out; the
+ * context keeps up to four such buffers (n * (16 + w * h * bytes per pixel) bytes each) until it is destroyed.
+ * Every other size, bit depth and kind runs the fused kernel: faster than the two launches at 8x8 (2-5 %), within
+ * the box variance elsewhere.
+ * R1_EINVAL: everything r1_rdo_txsearch_batch rejects; edge_group < 1 or not dividing n; edge_stride < 257; a NULL
+ * among cands / edges / lens / pos_xy; a UV_CFL_PRED candidate without `ac` -- checked where the host can read the
+ * descriptors (host or pinned memory; the Python wrapper checks NumPy descriptors before it uploads them);
+ * descriptors in device memory cannot be read without a synchronising copy, and there the kernel predicts such a
+ * candidate's DC and never touches `ac`. */
+int r1_rdo_intra_cand_batch(r1_ctx *ctx, const R1Plane *org, int w, int h, int tx_size,
+                            const R1IntraCand *cands, int n, int edge_group, const int16_t *pos_xy,
+                            const void *edges, int edge_stride, const uint8_t *lens, const int16_t *ac,
+                            uint32_t tx_type_mask, const R1QuantParams *params, int dist_kind,
+                            const uint32_t *scales, int scale_stride, int xdec, int ydec,
+                            uint32_t *sad_out, uint32_t *satd_out, uint16_t *eob_out, uint64_t *dist_out,
+                            uint64_t *est_rate_out, void *qcoeffs_out, void *rec_out, void *pred_out, void *stream);
 /* The mask of that loop: bit t set = TxType t is in av1_tx_used[get_tx_set(tx_size, is_inter,
  * use_reduced_set)]; rav1e_types_only != 0 keeps only RAV1E_TX_TYPES (DCT_DCT, ADST_DCT, DCT_ADST,
  * ADST_ADST, IDTX, V_DCT, H_DCT = 0x0E0F).  0 for an invalid tx_size.  Host arithmetic, no device work. */

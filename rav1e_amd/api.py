@@ -153,6 +153,8 @@ _TXSEARCH_OUTS = _out_spec(("eob", "nt", torch.int16), ("dist", "nt", torch.int6
                            ("satd", "n", torch.int32), ("est_rate", "nt", torch.int64),
                            ("qcoeffs", "nta", _coeff_dtype), ("rec", "nthw", _pix_dtype))
 
+_INTRA_CAND_OUTS = _TXSEARCH_OUTS + _out_spec(("pred", "nhw", _pix_dtype))
+
 
 _CUDA = torch.device("cuda")   # the current device, like "cuda", without parsing the string per allocation
 
@@ -341,12 +343,13 @@ class Context:
                                                   _stream_ptr()), "r1_intra_edges_batch")
         return edges, lens
 
-    def predict_intra_batch(self, tx_size, cands, edges, lens, bit_depth, ac=None, n=None):
-        """dispatch_predict_intra (src/predict.rs:705-784) for n blocks -> (n, h, w) pixels."""
+    def predict_intra_batch(self, tx_size, cands, edges, lens, bit_depth, ac=None, n=None, out=None):
+        """dispatch_predict_intra (src/predict.rs:705-784) for n blocks -> (n, h, w) pixels (into `out` if given)."""
         w, h = TX_DIMS[int(tx_size)]
         dc, n = _dev_cands(cands, INTRA_CAND, n)
         bpp = 1 if bit_depth == 8 else 2
-        out = torch.empty((n, h, w), dtype=_pix_dtype(bpp), device="cuda")
+        if out is None:
+            out = torch.empty((n, h, w), dtype=_pix_dtype(bpp), device="cuda")
         self._check(self.lib.r1_predict_intra_batch(
             self.h, int(tx_size), dc.data_ptr(), n, edges.data_ptr(), edges.stride(0),
             lens.data_ptr(), ac.data_ptr() if ac is not None else None, bit_depth, bpp,
@@ -984,6 +987,32 @@ class Context:
             C.byref(qp), dist_kind, *_scales_arg(scales), xdec, ydec,
             *_ptrs(o, "sad", "satd", "eob", "dist", "est_rate", "qcoeffs", "rec"), _stream_ptr()),
             "r1_rdo_txsearch_batch")
+        return o
+
+    def rdo_intra_cand_batch(self, org, w, h, cands, pos_xy, edges, lens, tx_type_mask, qindex, dist_kind,
+                             edge_group=1, ac=None, scales=None, xdec=0, ydec=0, is_intra=1, dc_delta_q=0,
+                             ac_delta_q=0, n=None, want_sad=False, want_satd=False, want_est_rate=False,
+                             want_qcoeffs=False, want_rec=False, want_pred=False, outs=None):
+        """r1_rdo_intra_cand_batch: predict_intra_batch -> rdo_txsearch_batch(pred=...) in one launch, the prediction
+        made on the CU.  cands: INTRA_CAND list; candidate i uses edge set / lens pair / pos_xy pair i // edge_group
+        (edges, lens: intra_edges_batch's outputs; pos_xy: (n // edge_group, 2) int16 device tensor, the block
+        positions in org) and AC block i of `ac`.  Outputs as rdo_txsearch_batch, + pred: (n, h, w)."""
+        tx_size = int(TxSize.by_dims(w, h))
+        # the library refuses UV_CFL_PRED without `ac` only where it can read the descriptors: before the upload
+        if ac is None and isinstance(cands, np.ndarray) and (cands["mode"][:n] == 13).any():
+            raise R1Error("r1_rdo_intra_cand_batch: a UV_CFL_PRED candidate needs `ac`")
+        dc, n = _dev_cands(cands, INTRA_CAND, n)
+        o = _bind_outs(outs, _INTRA_CAND_OUTS,
+                       (True, True, want_sad, want_satd, want_est_rate, want_qcoeffs, want_rec, want_pred),
+                       org.bpp, n, w, h, bin(int(tx_type_mask)).count("1"))
+        po = org.cstruct()
+        qp = self._qparams(qindex, org.bit_depth, is_intra, dc_delta_q, ac_delta_q)
+        self._check(self.lib.r1_rdo_intra_cand_batch(
+            self.h, C.byref(po), w, h, tx_size, dc.data_ptr(), n, int(edge_group), pos_xy.data_ptr(), edges.data_ptr(),
+            edges.stride(0), lens.data_ptr(), ac.data_ptr() if ac is not None else None, int(tx_type_mask),
+            C.byref(qp), dist_kind, *_scales_arg(scales), xdec, ydec,
+            *_ptrs(o, "sad", "satd", "eob", "dist", "est_rate", "qcoeffs", "rec", "pred"), _stream_ptr()),
+            "r1_rdo_intra_cand_batch")
         return o
 
     # ---- lrf:: ----

@@ -18,6 +18,9 @@
 // array), then every lane walks its column with the reference's index
 // arithmetic.  Rows are stored as W consecutive pixels per candidate
 // (coalesced).
+// Its mode arithmetic has a TWIN: intra_pred_common.hpp states the same predictors as device functions for the fused
+// candidate kernel (rdo_cand_kernel.hpp, PS == 1).  This kernel keeps its inline form because calling the header
+// moved its registers; a change to a predictor here must be made there too.
 #include "common.hpp"
 #include "dist_common.hpp"
 
@@ -202,7 +205,12 @@ constexpr int intra_waves_hint(bool satd, int wlt) {
   return !satd ? 1 : (wlt == 4 ? 7 : (wlt == 5 ? 5 : 1));   // 8x8 at 6 waves (79 VGPRs): +1.7 % on the launch, left alone
 }
 
-template <int BPP, bool SATD_OUT, int WLT = -1, int HLT = -1>
+// EGRP (the dense form only; the two-launch route of r1_rdo_intra_cand_batch): `group` consecutive candidates share
+// one edge set, lens pair and pos_xy pair, as under SATD_OUT, but every candidate's prediction goes to dst in list
+// order -- and the candidate's R1RdoCand (its block position, everything else zero: what r1_rdo_txsearch_batch reads
+// beside a dense prediction) goes to `satd_out`, which is that list here, four dwords per candidate.  A compile-time
+// choice: the instantiations without it are the kernels they were.
+template <int BPP, bool SATD_OUT, int WLT = -1, int HLT = -1, bool EGRP = false>
 __global__ __launch_bounds__(64, intra_waves_hint(SATD_OUT, WLT)) void k_intra_predict(
     int wl, int hl, const R1IntraCand *__restrict__ cands, int n,
     const void *__restrict__ edges, int edge_stride, const uint8_t *__restrict__ lens,
@@ -241,6 +249,13 @@ __global__ __launch_bounds__(64, intra_waves_hint(SATD_OUT, WLT)) void k_intra_p
     ecand = (long long)bg * NC + cl;
     live = ecand < n / group;
     cand = ecand * group + mi;
+  } else if constexpr (EGRP) {
+    ecand = (long long)((unsigned)cand / (unsigned)group);   // n < 2^31
+    if (live && c == 0) {
+      static_assert(sizeof(R1RdoCand) == 16, "R1RdoCand is written as four dwords");
+      const uint32_t ox = (uint16_t)pos_xy[2 * ecand], oy = (uint16_t)pos_xy[2 * ecand + 1];
+      *(uint4 *)(satd_out + 4 * cand) = make_uint4(ox | (oy << 16), 0u, 0u, 0u);
+    }
   }
   uint16_t *raw = smem + cl * EDGE_LEN;
   uint16_t *work = smem + NC * EDGE_LEN + cl * (4 * FL);   // af0 af1 lf0 lf1
@@ -714,6 +729,51 @@ extern "C" int r1_intra_edges_batch(r1_ctx *ctx, const R1Plane *rec, int tile_x,
   return R1_OK;
 }
 
+namespace {
+template <bool EGRP>
+void predict_launch(int tx_size, const R1IntraCand *cands, int n, const void *edges, int edge_stride,
+                    const uint8_t *lens, int group, const int16_t *pos_xy, R1RdoCand *rdo_cands, const int16_t *ac,
+                    int bit_depth, int bytes_per_px, void *dst, hipStream_t st) {
+  static const uint8_t wl[19] = {2, 3, 4, 5, 6, 2, 3, 3, 4, 4, 5, 5, 6, 2, 4, 3, 5, 4, 6};
+  static const uint8_t hl[19] = {2, 3, 4, 5, 6, 3, 2, 4, 3, 5, 4, 6, 5, 4, 2, 5, 3, 6, 4};
+  const int W = 1 << wl[tx_size], H = 1 << hl[tx_size];
+  const int NC = 64 / W, FL = 2 * (W + H) + 1;
+  const size_t lds = (size_t)NC * (EDGE_LEN + 4 * FL) * sizeof(uint16_t);
+  const unsigned grid = (unsigned)((n + NC - 1) / NC);
+#define R1_PRED_LAUNCH(B, WLT, HLT)                                                                       \
+  hipLaunchKernelGGL((k_intra_predict<B, false, WLT, HLT, EGRP>), dim3(grid), dim3(64), lds, st,          \
+                     (int)wl[tx_size], (int)hl[tx_size], cands, n, edges, edge_stride, lens, ac,          \
+                     bit_depth, dst, R1Plane{}, pos_xy, group, (uint32_t *)rdo_cands)
+  // square blocks 4x4 .. 32x32 with the size as a constant (unrolled row loops)
+  const int sq = wl[tx_size] == hl[tx_size] ? wl[tx_size] : 0;
+  if (bytes_per_px == 1) {
+    if (sq == 2) R1_PRED_LAUNCH(1, 2, 2);
+    else if (sq == 3) R1_PRED_LAUNCH(1, 3, 3);
+    else if (sq == 4) R1_PRED_LAUNCH(1, 4, 4);
+    else if (sq == 5) R1_PRED_LAUNCH(1, 5, 5);
+    else R1_PRED_LAUNCH(1, -1, -1);
+  } else {
+    if (sq == 2) R1_PRED_LAUNCH(2, 2, 2);
+    else if (sq == 3) R1_PRED_LAUNCH(2, 3, 3);
+    else if (sq == 4) R1_PRED_LAUNCH(2, 4, 4);
+    else if (sq == 5) R1_PRED_LAUNCH(2, 5, 5);
+    else R1_PRED_LAUNCH(2, -1, -1);
+  }
+#undef R1_PRED_LAUNCH
+}
+}  // namespace
+
+// The first launch of r1_rdo_intra_cand_batch's two-launch route, arguments checked by the caller: candidate i
+// predicts from edge set i / group into dst[i], and rdo_cands[i] takes its block position pos_xy[i / group].
+int r1_predict_intra_route_launch(int tx_size, const R1IntraCand *cands, int n, const void *edges, int edge_stride,
+                                  const uint8_t *lens, int group, const int16_t *pos_xy, R1RdoCand *rdo_cands,
+                                  const int16_t *ac, int bit_depth, int bytes_per_px, void *dst, hipStream_t st) {
+  predict_launch<true>(tx_size, cands, n, edges, edge_stride, lens, group, pos_xy, rdo_cands, ac, bit_depth,
+                       bytes_per_px, dst, st);
+  R1_HIP_CHECK(hipGetLastError());
+  return R1_OK;
+}
+
 extern "C" int r1_predict_intra_batch(r1_ctx *ctx, int tx_size, const R1IntraCand *cands, int n,
                                       const void *edges, int edge_stride, const uint8_t *lens,
                                       const int16_t *ac, int bit_depth, int bytes_per_px,
@@ -726,33 +786,8 @@ extern "C" int r1_predict_intra_batch(r1_ctx *ctx, int tx_size, const R1IntraCan
   R1_REQUIRE(edge_stride >= EDGE_LEN);
   if (n <= 0) return R1_OK;
   R1_REQUIRE(cands && edges && lens && dst);
-  static const uint8_t wl[19] = {2, 3, 4, 5, 6, 2, 3, 3, 4, 4, 5, 5, 6, 2, 4, 3, 5, 4, 6};
-  static const uint8_t hl[19] = {2, 3, 4, 5, 6, 3, 2, 4, 3, 5, 4, 6, 5, 4, 2, 5, 3, 6, 4};
-  const int W = 1 << wl[tx_size], H = 1 << hl[tx_size];
-  const int NC = 64 / W, FL = 2 * (W + H) + 1;
-  const size_t lds = (size_t)NC * (EDGE_LEN + 4 * FL) * sizeof(uint16_t);
-  const unsigned grid = (unsigned)((n + NC - 1) / NC);
-  hipStream_t st = (hipStream_t)stream;
-#define R1_PRED_LAUNCH(B, ...)                                                                            \
-  hipLaunchKernelGGL((k_intra_predict<B, false, ##__VA_ARGS__>), dim3(grid), dim3(64), lds, st,           \
-                     (int)wl[tx_size], (int)hl[tx_size], cands, n, edges, edge_stride, lens, ac,          \
-                     bit_depth, dst, R1Plane{}, (const int16_t *)nullptr, 1, (uint32_t *)nullptr)
-  // square blocks 4x4 .. 32x32 with the size as a constant (unrolled row loops)
-  const int sq = wl[tx_size] == hl[tx_size] ? wl[tx_size] : 0;
-  if (bytes_per_px == 1) {
-    if (sq == 2) R1_PRED_LAUNCH(1, 2, 2);
-    else if (sq == 3) R1_PRED_LAUNCH(1, 3, 3);
-    else if (sq == 4) R1_PRED_LAUNCH(1, 4, 4);
-    else if (sq == 5) R1_PRED_LAUNCH(1, 5, 5);
-    else R1_PRED_LAUNCH(1);
-  } else {
-    if (sq == 2) R1_PRED_LAUNCH(2, 2, 2);
-    else if (sq == 3) R1_PRED_LAUNCH(2, 3, 3);
-    else if (sq == 4) R1_PRED_LAUNCH(2, 4, 4);
-    else if (sq == 5) R1_PRED_LAUNCH(2, 5, 5);
-    else R1_PRED_LAUNCH(2);
-  }
-#undef R1_PRED_LAUNCH
+  predict_launch<false>(tx_size, cands, n, edges, edge_stride, lens, 1, nullptr, nullptr, ac, bit_depth, bytes_per_px,
+                        dst, (hipStream_t)stream);
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }

@@ -1,6 +1,7 @@
 // rdo_cand.hip -- the host side of the fused RDO candidate kernel: the argument checks, the dispatch over the
-// fifteen (bit depth, slice) objects and the C entry points.  The kernel itself is rdo_cand_kernel.hpp, compiled
-// by rdo_cand_slice.hip; this unit sees only what it shares with the slices (rdo_cand_args.hpp).
+// fifteen (bit depth, slice) objects (twelve more for the intra prediction source) and the C entry points.  The
+// kernel itself is rdo_cand_kernel.hpp, compiled by rdo_cand_slice.hip; this unit sees only what it shares with
+// the slices (rdo_cand_args.hpp).
 #include "itx_common.hpp"   // kInvShift
 #include "rdo_cand_args.hpp"
 
@@ -184,6 +185,118 @@ extern "C" int r1_rdo_txsearch_batch(r1_ctx *ctx, const R1Plane *org, const R1Pl
     qa.slot = slot;
     rc = rdo_dispatch(ctx, org, ref, w, h, tx_size, cands, n, slot == 0 ? sad_out : nullptr,
                       slot == 0 ? satd_out : nullptr, nullptr, nullptr, &qa, stream, false);
+    if (rc != R1_OK) return rc;
+  }
+  return R1_OK;
+}
+
+// ---- the intra candidate in one launch: the prediction is made inside the chain (k_rdo_cand with PS = 1) ----
+void r1_intra_scratch_free(r1_ctx *c) {
+  for (int k = 0; k < r1_ctx::kIntraSlots; k++) {
+    if (c->intra_done[k]) {
+      (void)hipEventSynchronize(c->intra_done[k]);
+      (void)hipEventDestroy(c->intra_done[k]);
+    }
+    if (c->intra_scratch[k]) (void)hipFree(c->intra_scratch[k]);
+  }
+}
+
+extern "C" int r1_rdo_intra_cand_batch(r1_ctx *ctx, const R1Plane *org, int w, int h, int tx_size,
+                                       const R1IntraCand *cands, int n, int edge_group, const int16_t *pos_xy,
+                                       const void *edges, int edge_stride, const uint8_t *lens, const int16_t *ac,
+                                       uint32_t tx_type_mask, const R1QuantParams *params, int dist_kind,
+                                       const uint32_t *scales, int scale_stride, int xdec, int ydec,
+                                       uint32_t *sad_out, uint32_t *satd_out, uint16_t *eob_out, uint64_t *dist_out,
+                                       uint64_t *est_rate_out, void *qcoeffs_out, void *rec_out, void *pred_out,
+                                       void *stream) {
+  RdoQuantArgs qa = {};
+  int rc = rdo_quant_args(ctx, org, tx_size, params, dist_kind, scales, scale_stride, xdec, ydec, eob_out, dist_out,
+                          qcoeffs_out, rec_out, qa);
+  if (rc != R1_OK) return rc;
+  // what r1_rdo_txsearch_batch checks, in its order
+  R1_REQUIRE(dist_kind == 0 || !est_rate_out);
+  R1_REQUIRE(tx_type_mask != 0 && tx_type_mask <= 0xFFFFu);
+  const int wl = r1tx::kTxWLog2[tx_size], hl = r1tx::kTxHLog2[tx_size];
+  const int up = wl > hl ? wl : hl;
+  const bool side64 = up > 5, side32 = up == 5;
+  R1_REQUIRE(!side64 || tx_type_mask == 1u);
+  R1_REQUIRE((tx_type_mask & ~r1_tx_type_mask(tx_size, 1, 0, 0)) == 0);
+  R1_REQUIRE(org->bytes_per_px == 1 || org->bytes_per_px == 2);
+  R1_REQUIRE((org->bytes_per_px == 1) == (org->bit_depth == 8));
+  R1_REQUIRE(org->bit_depth == 8 || org->bit_depth == 10 || org->bit_depth == 12);
+  R1_REQUIRE((1 << wl) == w && (1 << hl) == h);
+  // the intra source
+  R1_REQUIRE(edge_stride >= R1_INTRA_EDGE_LEN && edge_group >= 1);
+  if (n <= 0) return R1_OK;
+  R1_REQUIRE(n % edge_group == 0);
+  R1_REQUIRE(cands && edges && lens && pos_xy);
+  if (!ac) {
+    // UV_CFL_PRED needs its AC block.  The descriptors are the caller's memory: where the host can read them
+    // (ordinary or pinned host memory) they are checked here; descriptors in device memory cannot be seen without
+    // a synchronising copy, and there the kernel predicts such a candidate's DC without touching `ac`.
+    hipPointerAttribute_t at = {};
+    const hipError_t e = hipPointerGetAttributes(&at, cands);
+    // an unregistered pointer is hipErrorInvalidValue to older runtimes, and without a device nothing is device
+    // memory; after any other failure the descriptors are left alone
+    int ndev = 0;
+    const bool host_readable =
+        e == hipSuccess ? at.type == hipMemoryTypeUnregistered || at.type == hipMemoryTypeHost
+                        : e == hipErrorInvalidValue || hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0;
+    (void)hipGetLastError();
+    if (host_readable)
+      for (int i = 0; i < n; i++) R1_REQUIRE(cands[i].mode != 13);
+  }
+  RdoIntraArgs ia = {cands, edges, lens, pos_xy, ac, edge_stride, edge_group};
+  qa.est_rate = (unsigned long long *)est_rate_out;
+  qa.tx_mask = tx_type_mask;
+  qa.nt = __builtin_popcount(tx_type_mask);
+  typedef int (*ISliceFn)(R1_INTRA_SLICE_ARGS);
+#define R1_RDO_ISLICE_ENTRY(B, Q) r1_rdo_islice_b##B##_q##Q,
+  static const ISliceFn kISlices[3][4] = {{R1_RDO_ISLICE_ROW(R1_RDO_ISLICE_ENTRY, 8)},
+                                          {R1_RDO_ISLICE_ROW(R1_RDO_ISLICE_ENTRY, 10)},
+                                          {R1_RDO_ISLICE_ROW(R1_RDO_ISLICE_ENTRY, 12)}};
+#undef R1_RDO_ISLICE_ENTRY
+  const ISliceFn *row = kISlices[(org->bit_depth - 8) / 2];
+  const int qm = dist_kind == 0 ? 1 : 2;
+  hipStream_t st = (hipStream_t)stream;
+  if (r1_intra_two_launch(wl, hl, org->bit_depth, qm)) {
+    // predict to pred_out (or to the ring) and run the existing kernels on it: same slots, same results
+    R1DeviceGuard guard(ctx);
+    const size_t cand_bytes = ((size_t)n * sizeof(R1RdoCand) + 255) & ~(size_t)255;
+    const size_t need = cand_bytes + (pred_out ? 0 : (size_t)n * w * h * org->bytes_per_px);
+    std::lock_guard<std::mutex> lock(ctx->intra_mu);
+    const int slot = ctx->intra_next;
+    ctx->intra_next = (slot + 1) % r1_ctx::kIntraSlots;
+    if (!ctx->intra_done[slot]) R1_HIP_CHECK(hipEventCreateWithFlags(&ctx->intra_done[slot], hipEventDisableTiming));
+    else R1_HIP_CHECK(hipEventSynchronize(ctx->intra_done[slot]));
+    if (ctx->intra_scratch_bytes[slot] < need) {
+      if (ctx->intra_scratch[slot]) R1_HIP_CHECK(hipFree(ctx->intra_scratch[slot]));
+      ctx->intra_scratch[slot] = nullptr;
+      ctx->intra_scratch_bytes[slot] = 0;
+      R1_HIP_CHECK(hipMalloc(&ctx->intra_scratch[slot], need));
+      ctx->intra_scratch_bytes[slot] = need;
+    }
+    R1RdoCand *rc_dev = (R1RdoCand *)ctx->intra_scratch[slot];
+    void *pred = pred_out ? pred_out : (void *)((uint8_t *)ctx->intra_scratch[slot] + cand_bytes);
+    rc = r1_predict_intra_route_launch(tx_size, cands, n, edges, edge_stride, lens, edge_group, pos_xy, rc_dev, ac,
+                                       org->bit_depth, org->bytes_per_px, pred, st);
+    if (rc == R1_OK)
+      rc = r1_rdo_txsearch_batch(ctx, org, nullptr, pred, w, h, tx_size, rc_dev, n, tx_type_mask, params, dist_kind,
+                                 scales, scale_stride, xdec, ydec, sad_out, satd_out, eob_out, dist_out, est_rate_out,
+                                 qcoeffs_out, rec_out, stream);
+    R1_HIP_CHECK(hipEventRecord(ctx->intra_done[slot], st));
+    return rc;
+  }
+  if (!side64 && !side32)   // the fan-out form: slices 3 / 4
+    return row[qm + 1](tx_size, *org, n, sad_out, satd_out, pred_out, &qa, &ia, st);
+  // 32- and 64-point sides: one plain launch per type (at most two), the type forced, results into its slot; each
+  // launch makes the prediction again on the CU, the first one writes sad / satd / pred_out
+  int slot = 0;
+  for (uint32_t m = tx_type_mask; m != 0; m &= m - 1, slot++) {
+    qa.tx_mask = m & (0u - m);
+    qa.slot = slot;
+    rc = row[qm - 1](tx_size, *org, n, slot == 0 ? sad_out : nullptr, slot == 0 ? satd_out : nullptr,
+                     slot == 0 ? pred_out : nullptr, &qa, &ia, st);
     if (rc != R1_OK) return rc;
   }
   return R1_OK;

@@ -37,6 +37,20 @@ struct RdoQuantArgs {
   int slot;
 };
 
+// The intra prediction source (k_rdo_cand with PS = 1, r1_rdo_intra_cand_batch): candidate i predicts from edge set
+// i / edge_group (`edges`: edge_stride pixels each, `lens`: init_left / init_above pairs, as r1_intra_edges_batch
+// leaves them) at the block position pos_xy[2 (i / edge_group)], +1 in the source plane; ac: dense w*h int16 per
+// candidate (UV_CFL_PRED) or NULL.
+struct RdoIntraArgs {
+  const R1IntraCand *cands;
+  const void *edges;
+  const uint8_t *lens;
+  const int16_t *pos_xy;
+  const int16_t *ac;
+  int edge_stride, edge_group;
+};
+struct RdoNoIntraArgs {};   // what the PS = 0 instantiations take in its place
+
 #define R1_SLICE_ARGS                                                                         \
   int tx_size, const R1Plane &org, const R1Plane &ref, const R1RdoCand *cands, int n,         \
       uint32_t *sad, uint32_t *satd, void *coeffs, void *pred, const RdoQuantArgs *qa, hipStream_t st
@@ -47,3 +61,27 @@ struct RdoQuantArgs {
 #define R1_RDO_SLICE_DECL(B, Q) int r1_rdo_slice_b##B##_q##Q(R1_SLICE_ARGS);
 R1_RDO_SLICES(R1_RDO_SLICE_DECL)
 #undef R1_RDO_SLICE_DECL
+// The intra slices (PS = 1): X(bit depth, slice), slices 1 / 2 = the plain form of QM 1 / 2 (the ten sizes with a
+// 32- or 64-point side), 3 / 4 = the fan-out form (the nine sizes up to 16 x 16).  One object
+// (rdo_cand_i_b<B>_q<Q>.o) and one function r1_rdo_islice_b<B>_q<Q> each, from the same rdo_cand_slice.hip.
+#define R1_INTRA_SLICE_ARGS                                                                               \
+  int tx_size, const R1Plane &org, int n, uint32_t *sad, uint32_t *satd, void *pred, const RdoQuantArgs *qa, \
+      const RdoIntraArgs *ia, hipStream_t st
+// Where the launch with the prediction made on the CU lost to r1_predict_intra_batch -> r1_rdo_txsearch_batch(pred)
+// by more than the +-3-4 % between boxes (profiles/r12_intra_cand.jsonl, 4K luma, 4 modes per block): those points
+// take the two launches inside r1_rdo_intra_cand_batch and have no intra instantiation.  Measured at 8 and 10
+// bits; 12 bits is the 10-bit code at another constant and follows it, R1_DIST_WSSE shares the chain up to the
+// distortion with R1_DIST_CDEF and follows it.  qm: 1 = dist_kind 0, 2 = a pixel-domain kind.
+//   16x16, dist_kind 0                 +11.5 % (8-bit), +10.9 % (10-bit)
+//   16x16, pixel kinds, 16-bit pixels  +3.6 % (two runs)
+//   64x64, dist_kind 0, 16-bit pixels  +13 %
+//   32x32, pixel kinds, 16-bit pixels  +4.3 %
+constexpr bool r1_intra_two_launch(int wl, int hl, int bd, int qm) {
+  return wl == hl && ((wl == 4 && (qm == 1 || bd != 8)) || (wl == 6 && qm == 1 && bd != 8) ||
+                      (wl == 5 && qm == 2 && bd != 8));
+}
+#define R1_RDO_ISLICE_ROW(X, B) X(B, 1) X(B, 2) X(B, 3) X(B, 4)
+#define R1_RDO_ISLICES(X) R1_RDO_ISLICE_ROW(X, 8) R1_RDO_ISLICE_ROW(X, 10) R1_RDO_ISLICE_ROW(X, 12)
+#define R1_RDO_ISLICE_DECL(B, Q) int r1_rdo_islice_b##B##_q##Q(R1_INTRA_SLICE_ARGS);
+R1_RDO_ISLICES(R1_RDO_ISLICE_DECL)
+#undef R1_RDO_ISLICE_DECL

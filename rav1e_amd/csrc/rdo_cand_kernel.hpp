@@ -30,11 +30,16 @@
 //     transpose through LDS (odd stride, aliasing the dead window).
 //  D  lane = (candidate, row): row transform, stores in the reference's
 //     transposed 32x32-chunk coefficient order.
+// With the intra prediction source (PS = 1) phases A / B read
+//   pred  = predict_intra(edges)     (src/predict.rs:205-249, 705-1505; encode_tx_block, src/encoder.rs:1458-1503)
+// instead: the candidate's edge set goes to LDS in place of the window, the P lanes of a candidate filter /
+// upsample it together, lane = (candidate, column) walks its column into the same registers (intra_pred_common.hpp).
 #pragma once
 #include <cstdlib>
 #include <type_traits>
 
 #include "dist_common.hpp"
+#include "intra_pred_common.hpp"
 #include "itx_common.hpp"
 #include "mc_common.hpp"
 #include "quant_common.hpp"
@@ -71,6 +76,9 @@ static __device__ unsigned long long g_phase[4096][8];   // one per profiled sli
 // slice) pair each (-DR1_RDO_TU_BD=8|10|12 -DR1_RDO_TU_QM=0..4, slices 3 / 4 = MT of QM 1 / 2), the kernel and one
 // r1_rdo_slice_b*_q* launcher per object.  The sixteenth unit, rdo_cand.hip (argument checks, dispatch over the
 // slices, the C entry points), shares rdo_cand_args.hpp with them and does not see this header.
+// The intra prediction source (PS = 1, r1_rdo_intra_cand_batch) adds 114 instantiations -- the fan-out form of the nine
+// sizes up to 16x16, the plain form of QM 1 / 2 for the ten sizes with a 32- or 64-point side, three bit depths -- in
+// twelve more objects of the same unit (-DR1_RDO_TU_INTRA, slices 1..4: r1_rdo_islice_b*_q*).
 // Experiment builds swap slice objects of the shipped library (tools/build_variant.sh, make prof).
 namespace {
 using r1tx::T;
@@ -106,12 +114,18 @@ constexpr int rdo_waves_hint(int bd, int wl, int hl, int qm, bool mt = false) {
   return 1;
 }
 
-template <int BD, int WL, int HL, typename CT, int QM, bool MT = false>
+// PS: where the prediction comes from, a compile-time choice -- 0 = put_8tap of the reference window, or the
+// dense qa.pred_in buffer (a run-time branch of those instantiations); 1 = intra prediction from the candidate's
+// edge set (r1_rdo_intra_cand_batch), made inside the chain by the predictors of intra_pred_common.hpp.  The
+// PS = 0 instantiations do not see the intra code: their kernels are the ones they were before PS existed.
+template <int BD, int WL, int HL, typename CT, int QM, bool MT = false, int PS = 0>
 __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_cand(
     R1Plane org, R1Plane ref, const R1RdoCand *__restrict__ cands, int n,
     uint32_t *__restrict__ sad_out, uint32_t *__restrict__ satd_out,
-    CT *__restrict__ coeffs, void *__restrict__ pred_out, RdoQuantArgs qa) {
+    CT *__restrict__ coeffs, void *__restrict__ pred_out, RdoQuantArgs qa,
+    typename std::conditional<PS == 1, RdoIntraArgs, RdoNoIntraArgs>::type ia) {
   constexpr int BPP = BD == 8 ? 1 : 2;
+  constexpr bool INTRA = PS == 1;
   // forward-transform shifts of this (size, bit depth): immediates
   constexpr int SH0 = r1tx::fwd_shift_ct(WL, HL, BD, 0), SH1 = r1tx::fwd_shift_ct(WL, HL, BD, 1),
                 SH2 = r1tx::fwd_shift_ct(WL, HL, BD, 2);
@@ -119,7 +133,12 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
   constexpr int P = W > H ? W : H, NC = 64 / P;
   constexpr int TS = (W < H ? W : H) == 4 ? 4 : 8;
   constexpr int WS = (((W + 7) * BPP + 3) >> 2) << 2;   // window row stride
-  constexpr int WIN_BYTES = NC * (H + 7) * WS;
+  // INTRA: no reference window.  The candidate's edge arrays (raw edge + the four filter / upsample arrays, FL
+  // entries each) take its place and may lie over the WHOLE allocation: the source block waits in registers until
+  // the prediction is made (see SRC_LATE) and nothing else of the chain is alive yet.
+  constexpr int WIN_BYTES = INTRA ? 0 : NC * (H + 7) * WS;
+  constexpr int FL = 2 * (W + H) + 1;               // entries of one edge array
+  constexpr int EDGE_BYTES = INTRA ? ((NC * 5 * FL * 2 + 15) & ~15) : 0;
   // The transpose tile holds the column pass's outputs after shift[1]: bounded by 16353 at 8-bit
   // (every size and type) and by 23214 at 10-bit with sides up to 32 (tools/tx_range.py: pixel range,
   // shift[0], the L1 gain of the column network, shift[1]), so int16 holds them exactly.  Used for
@@ -168,7 +187,7 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
   // footprint is the window's 6240 B and the ~93 VGPRs allow 5.
   // 16-bit 16x16, headline only (the pixel chain keeps its source block in LDS for the distortion,
   // SRC_KEEP below): 6592 -> 4416 B, 6 -> 8 waves, launch 0.2255 -> 0.217 ms (r04_ab_notes.md, ab7)
-  constexpr bool SRC_LATE = SRC_LDS && BD != 8 && (P == 32 || (P == 16 && QM == 0));
+  constexpr bool SRC_LATE0 = SRC_LDS && BD != 8 && (P == 32 || (P == 16 && QM == 0));
   constexpr int SRC_ROW = W * BPP;
   constexpr int WIN_PAD = (WIN_BYTES + 15) & ~15;
   // A candidate's source block starts max(16, row bytes) past a multiple of its own size: with the bare
@@ -180,7 +199,10 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
   // SRC_KEEP (pixel-domain chain, blocks up to 16 rows): the staged source block sits BEHIND the work area
   // that the later phases alias (transpose tile, quantizer tile, row buffer), so the distortion at the end of
   // the chain reads its source column from LDS again instead of issuing H more global loads per lane
-  constexpr bool SRC_KEEP = QM == 2 && H <= 16 && SRC_LDS && !SRC_LATE;
+  constexpr bool SRC_KEEP = QM == 2 && H <= 16 && SRC_LDS && !SRC_LATE0;
+  // INTRA: the source always goes to LDS after the prediction (to its SRC_KEEP place behind the work area, or over
+  // the dead edge arrays)
+  constexpr bool SRC_LATE = INTRA ? SRC_LDS && !SRC_KEEP : SRC_LATE0;
   constexpr int WS_BYTES = SRC_KEEP ? WIN_PAD
                                     : (SRC_LATE ? (WIN_PAD > SRC_BYTES ? WIN_PAD : SRC_BYTES) : WIN_PAD + SRC_BYTES);
   constexpr int LDS_A0 = WS_BYTES > TXB_BYTES ? WS_BYTES : TXB_BYTES;
@@ -193,7 +215,19 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
   // DCT x3, ADST x2, identity x2) all read their rows from this one tile (see the type loop)
   constexpr bool COLSHARE = MT && !SPLIT_T;
   constexpr int TKEEP_OFF = (LDS_WORK + (SRC_KEEP ? SRC_BYTES : 0) + 15) & ~15;
-  constexpr int LDS_BYTES = COLSHARE ? TKEEP_OFF + H * LSTRIDE * (int)sizeof(TB) : LDS_WORK + (SRC_KEEP ? SRC_BYTES : 0);
+  constexpr int LDS_CHAIN = COLSHARE ? TKEEP_OFF + H * LSTRIDE * (int)sizeof(TB) : LDS_WORK + (SRC_KEEP ? SRC_BYTES : 0);
+  constexpr int LDS_BYTES = LDS_CHAIN > EDGE_BYTES ? LDS_CHAIN : EDGE_BYTES;
+  // INTRA: no more LDS than the PS = 0 instantiation of the same (size, bit depth, QM, MT) -- the formulas above
+  // once more with that kernel's window and its SRC_LATE0
+  constexpr int TW_WIN = (NC * (H + 7) * WS + 15) & ~15;
+  constexpr int TW_WS = SRC_KEEP ? TW_WIN : (SRC_LATE0 ? (TW_WIN > SRC_BYTES ? TW_WIN : SRC_BYTES) : TW_WIN + SRC_BYTES);
+  constexpr int TW_A0 = TW_WS > TXB_BYTES ? TW_WS : TXB_BYTES;
+  constexpr int TW_A = TW_A0 > IRB_BYTES ? TW_A0 : IRB_BYTES;
+  constexpr int TW_WORK = ((TW_A > LDS_B ? TW_A : LDS_B) + 15) & ~15;
+  constexpr int TW_TAIL = TW_WORK + (SRC_KEEP ? SRC_BYTES : 0);
+  constexpr int TW_BYTES = COLSHARE ? ((TW_TAIL + 15) & ~15) + H * LSTRIDE * (int)sizeof(TB) : TW_TAIL;
+  static_assert(!INTRA || LDS_BYTES <= TW_BYTES, "an intra instantiation's LDS must not exceed its inter twin's");
+  static_assert(INTRA || LDS_BYTES == TW_BYTES, "the twin formula has drifted from the kernel's own");
   __shared__ __attribute__((aligned(16))) uint8_t smem[LDS_BYTES];
   T *buf = (T *)smem;
   TB *tbuf = (TB *)smem;
@@ -229,7 +263,18 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
   const int cl_ld = live_st ? cl : n - 1 - (int)wg * NC;     // >= 0: the wave's first candidate exists
   const long long cand_ld = live_st ? cand : (long long)n - 1;
   R1RdoCand cd = {};
-  if (live) cd = (cands + (size_t)wg * NC)[cl_ld];
+  R1IntraCand ic = {};
+  int eset = 0;   // INTRA: the candidate's edge set / lens pair / position pair
+  if constexpr (INTRA) {
+    if (live) {
+      ic = ia.cands[cand_ld];
+      eset = (int)cand_ld / ia.edge_group;
+      cd.ox = ia.pos_xy[2 * eset];
+      cd.oy = ia.pos_xy[2 * eset + 1];
+    }
+  } else {
+    if (live) cd = (cands + (size_t)wg * NC)[cl_ld];
+  }
 #ifdef R1_PHASE_PROF
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   R1_PROF(5);   // A0: descriptor round trip
@@ -279,7 +324,7 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
     for (int r = 0; r < H; r++) v[r] = ld_px<BPP>(po + r * so);
   }
   uint8_t *win = smem + cl * (H + 7) * WS;
-  const bool from_ref = live && !qa.pred_in;   // !pred_in is wave-uniform: kernel argument
+  const bool from_ref = !INTRA && live && !qa.pred_in;   // !pred_in is wave-uniform: kernel argument
   r1mc::WindowStage<BPP, BPP == 1 ? 0x80808080u : 0u, W, H, P> wst;
   if (from_ref) wst.load(ref, cd.rx, cd.ry, c);
   typename std::conditional<BPP == 1, Taps8, Taps16>::type tp = {};
@@ -304,8 +349,21 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
       }
     }
   };
-  if constexpr (SRC_LDS && !SRC_LATE) stage_source();
+  if constexpr (SRC_LDS && !SRC_LATE && !INTRA) stage_source();
   if (from_ref) wst.store(win, WS);
+  // INTRA: the raw edge, the 2 (W + H) + 1 entries around the top-left one that a W x H block can reach (what lies
+  // outside [128 - lens[0], 129 + lens[1]) is undefined in the caller's buffer and never used, as in k_intra_predict),
+  // by the P lanes of the candidate
+  uint16_t *eraw = (uint16_t *)smem + cl * (5 * FL);
+  int left_len = 0, above_len = 0;
+  if constexpr (INTRA) {
+    if (live) {
+      left_len = ia.lens[2 * eset];
+      above_len = ia.lens[2 * eset + 1];
+      const uint8_t *e = (const uint8_t *)ia.edges + ((size_t)eset * ia.edge_stride + (2 * r1ip::MAXTX - (W + H))) * BPP;
+      for (int k = c; k < FL; k += P) eraw[k] = (uint16_t)ld_px<BPP>(e + k * BPP);
+    }
+  }
 #ifdef R1_PHASE_PROF
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   R1_PROF(6);   // A1: source column + window round trip (+ LDS writes issued)
@@ -315,6 +373,60 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
 
   // ---- B: prediction column, residual, SAD / SATD ----
   uint32_t sad_acc = 0;
+  if constexpr (INTRA) {
+    // the cooperative part (edge filter / upsample: every lane of the wave, P per candidate), then lane =
+    // (candidate, column) walks its column into registers
+    const bool directional = live && r1ip::is_directional(ic.mode, ic.angle);
+    const bool enable = directional && ic.ief != 0;
+    const uint16_t *tl = eraw + (W + H);
+    uint16_t *work = eraw + FL;
+    int up_a = 0, up_l = 0;
+    r1ip::edge_filter_upsample(tl, work, W, H, P, c, ic, enable, left_len, above_len, (1 << BD) - 1, up_a, up_l);
+    int32_t pred[H];
+    if (col_live) {
+      // (a CFL candidate without an AC buffer -- the entry point refuses the ones it can see -- predicts its DC)
+      if (ic.mode == r1ip::UV_CFL_PRED && !ia.ac) ic.angle = 0;
+      const int16_t *acb = ic.mode == r1ip::UV_CFL_PRED && ia.ac ? ia.ac + (size_t)cand_ld * (W * H) : nullptr;
+      r1ip::predict_column(W, H, c, ic, directional, enable, up_a, up_l, tl, work, left_len, BD, acb,
+                           [&](int i, int32_t pv) { pred[i] = pv; });
+      if (pred_out && live_st) {
+        if constexpr (BPP == 1) {
+          uint8_t *pp = (uint8_t *)pred_out + (size_t)cand * W * H + c;
+#pragma unroll
+          for (int r = 0; r < H; r++) pp[(size_t)r * W] = (uint8_t)pred[r];
+        } else {
+          uint16_t *pp = (uint16_t *)pred_out + (size_t)cand * W * H + c;
+#pragma unroll
+          for (int r = 0; r < H; r++) pp[(size_t)r * W] = (uint16_t)pred[r];
+        }
+      }
+      if constexpr (QM == 2) {
+#pragma unroll
+        for (int r = 0; r < H; r++) {
+          if constexpr (BPP == 1) ppk[r >> 2] |= (uint32_t)pred[r] << (8 * (r & 3));
+          else ppk[r >> 1] |= (uint32_t)pred[r] << (16 * (r & 1));
+        }
+      }
+    }
+    if constexpr (SRC_LDS) {
+      __syncthreads();   // every lane has made its column: the edge arrays are dead
+      stage_source();
+      __syncthreads();
+    }
+    if (col_live) {
+      if constexpr (SRC_LDS) {
+#pragma unroll
+        for (int r = 0; r < H; r++) {
+          const uint32_t sp = BPP == 1 ? (uint32_t)src_l[r * SRC_ROW] : (uint32_t) * (const uint16_t *)(src_l + r * SRC_ROW);
+          sad_acc = sad_u32(sp, (uint32_t)pred[r], sad_acc);
+          v[r] = (T)sp - pred[r];
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < H; r++) v[r] -= pred[r];
+      }
+    }
+  } else
   if constexpr (BPP == 1) {
     if (col_live) {
       int32_t pred[H];
@@ -855,35 +967,41 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
   }
 }
 
-template <int BD, int WL, int HL, int QM, bool MT>
+template <int BD, int WL, int HL, int QM, bool MT, int PS = 0>
 int launch(const R1Plane &org, const R1Plane &ref, const R1RdoCand *cands, int n,
            uint32_t *sad, uint32_t *satd, void *coeffs, void *pred, const RdoQuantArgs *qa,
-           hipStream_t st) {
+           hipStream_t st, const RdoIntraArgs *ia = nullptr) {
   constexpr int W = 1 << WL, H = 1 << HL, P = W > H ? W : H, NC = 64 / P;
   typedef typename std::conditional<BD == 8, int16_t, int32_t>::type CT;
   const unsigned groups = (unsigned)((n + NC - 1) / NC);
   const unsigned grid = (groups + 7u) & ~7u;     // whole rounds over the 8 XCDs (see the kernel's `wg`)
-  hipLaunchKernelGGL((k_rdo_cand<BD, WL, HL, CT, QM, MT>), dim3(grid), dim3(64), 0, st,
-                     org, ref, cands, n, sad, satd, (CT *)coeffs, pred, qa ? *qa : RdoQuantArgs{});
+  if constexpr (PS == 1)
+    hipLaunchKernelGGL((k_rdo_cand<BD, WL, HL, CT, QM, MT, 1>), dim3(grid), dim3(64), 0, st,
+                       org, ref, cands, n, sad, satd, (CT *)coeffs, pred, *qa, *ia);
+  else
+    hipLaunchKernelGGL((k_rdo_cand<BD, WL, HL, CT, QM, MT>), dim3(grid), dim3(64), 0, st,
+                       org, ref, cands, n, sad, satd, (CT *)coeffs, pred, qa ? *qa : RdoQuantArgs{}, RdoNoIntraArgs{});
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }
 
 // one (bit depth, QM) slice: tx_size -> instantiation
-template <int BD, int QM, bool MT>
+template <int BD, int QM, bool MT, int PS = 0>
 int slice(int tx_size, const R1Plane &org, const R1Plane &ref, const R1RdoCand *cands, int n,
           uint32_t *sad, uint32_t *satd, void *coeffs, void *pred, const RdoQuantArgs *qa,
-          hipStream_t st) {
+          hipStream_t st, const RdoIntraArgs *ia = nullptr) {
   // the transform sizes this slice instantiates: all 19, except in the type-search slices: sizes up to 16 x 16
   // (ids 0-2, 5-8, 13, 14).  A 64-point side has TX_SET_DCTONLY (get_tx_set, src/context/transform_unit.rs:123-131)
   // and a 32-point side DCT_DCT (+ IDTX for inter blocks): one or two types, which the plain kernel evaluates at twice
   // the occupancy (same-box A/B, profiles/r05_ab_notes.md: the 32x32 fan-out kernel held 2 waves per SIMD and LOST
   // 13-22 % against two launches)
-  constexpr unsigned TSM = MT ? 0x61E7u : 0x7ffffu;
+  // The intra slices (PS == 1): the fan-out form for those nine sizes (it serves any mask, a single type included)
+  // and the plain form for the other ten only; none where r1_rdo_intra_cand_batch takes the two launches.
+  constexpr unsigned TSM = MT ? 0x61E7u : (PS == 1 ? 0x7ffffu & ~0x61E7u : 0x7ffffu);
 #define R1_RC_CASE(ID, WL, HL)                                                                   \
   case ID:                                                                                       \
-    if constexpr ((TSM >> ID) & 1)                                                               \
-      return launch<BD, WL, HL, QM, MT>(org, ref, cands, n, sad, satd, coeffs, pred, qa, st);    \
+    if constexpr (((TSM >> ID) & 1) && !(PS == 1 && r1_intra_two_launch(WL, HL, BD, QM)))         \
+      return launch<BD, WL, HL, QM, MT, PS>(org, ref, cands, n, sad, satd, coeffs, pred, qa, st, ia); \
     else                                                                                         \
       break;
   switch (tx_size) {

@@ -48,7 +48,9 @@ extern "C" {
 /* ---- Plane<T> view (v_frame 0.3.9 PlaneConfig layout; reference use:
  * src/tiling/plane_region.rs:185 -- element (x,y) lives at
  * data[(yorigin + y) * stride + xorigin + x]).  `data` is a device pointer to
- * the start of the allocation; stride is in ELEMENTS. */
+ * the start of the allocation; stride is in ELEMENTS.  No alignment beyond the
+ * element's own (1 or 2 bytes) is required of `data`, `stride` or `xorigin`, and
+ * the planes of one call may differ in all of them. */
 typedef struct R1Plane {
   void *data;
   int32_t stride;

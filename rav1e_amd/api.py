@@ -122,6 +122,12 @@ def _scales_arg(scales):
     return (None, 0) if scales is None else (scales.data_ptr(), scales.stride(0))
 
 
+def _blocks_stride(blocks):
+    """row stride, in R1DeblockBlock records, of a (rows, cols, 8) uint8 tensor of them (rows may be views)"""
+    assert blocks.stride(2) == 1 and blocks.stride(1) == 8 and blocks.stride(0) % 8 == 0
+    return blocks.stride(0) // 8
+
+
 def _pix_dtype(bpp):
     """torch dtype of a pixel of `bpp` bytes (16-bit pixels are stored raw as int16)"""
     return torch.uint8 if bpp == 1 else torch.int16
@@ -892,7 +898,7 @@ class Context:
         st = np.ascontiguousarray(state).view(np.uint8)
         assert st.size == 24 and blocks.dtype == torch.uint8 and blocks.shape[2] == 8
         self._check(self.lib.r1_deblock_plane(self.h, st.ctypes.data, C.byref(pc), pli, xdec, ydec,
-                                              blocks.data_ptr(), blocks.shape[1], blocks.shape[1],
+                                              blocks.data_ptr(), _blocks_stride(blocks), blocks.shape[1],
                                               blocks.shape[0], crop_w, crop_h, _stream_ptr()),
                     "r1_deblock_plane")
 
@@ -902,7 +908,7 @@ class Context:
             tallies = torch.zeros((2, 65), dtype=torch.int64, device="cuda")
         pr, ps = rec.cstruct(), src.cstruct()
         self._check(self.lib.r1_deblock_sse_plane(self.h, C.byref(pr), C.byref(ps), pli, xdec, ydec,
-                                                  blocks.data_ptr(), blocks.shape[1], blocks.shape[1],
+                                                  blocks.data_ptr(), _blocks_stride(blocks), blocks.shape[1],
                                                   blocks.shape[0], crop_w, crop_h,
                                                   tallies[0].data_ptr(), tallies[1].data_ptr(),
                                                   _stream_ptr()), "r1_deblock_sse_plane")
@@ -914,7 +920,7 @@ class Context:
         st = np.ascontiguousarray(state).view(np.uint8)
         assert st.size == 24 and blocks.dtype == torch.uint8 and blocks.shape[2] == 8
         self._check(self.lib.r1_deblock_frame(self.h, st.ctypes.data, arr, xdec, ydec, blocks.data_ptr(),
-                                              blocks.shape[1], blocks.shape[1], blocks.shape[0], crop_w,
+                                              _blocks_stride(blocks), blocks.shape[1], blocks.shape[0], crop_w,
                                               crop_h, _stream_ptr()), "r1_deblock_frame")
 
     def deblock_sse_frame(self, rec, src, xdec, ydec, blocks, crop_w, crop_h, tallies=None):
@@ -924,7 +930,7 @@ class Context:
         ra = (_lib.R1Plane * 3)(*[p.cstruct() for p in rec])
         sa = (_lib.R1Plane * 3)(*[p.cstruct() for p in src])
         self._check(self.lib.r1_deblock_sse_frame(self.h, ra, sa, xdec, ydec, blocks.data_ptr(),
-                                                  blocks.shape[1], blocks.shape[1], blocks.shape[0],
+                                                  _blocks_stride(blocks), blocks.shape[1], blocks.shape[0],
                                                   crop_w, crop_h, tallies.data_ptr(), _stream_ptr()),
                     "r1_deblock_sse_frame")
         return tallies
@@ -1053,8 +1059,7 @@ class Context:
         pc, ps = lrf_in.cstruct(), src.cstruct()
         self._check(self.lib.r1_lrf_search_batch(self.h, C.byref(pc), C.byref(ps), dc.data_ptr(), n, max_w, max_h,
                                                  int(bool(is_chroma)), xdec, ydec,
-                                                 scales.data_ptr() if scales is not None else None,
-                                                 scales.shape[1] if scales is not None else 0, int(dist_scale),
+                                                 *_scales_arg(scales), int(dist_scale),
                                                  scratch.data_ptr(), xqd.data_ptr(), err.data_ptr(), _stream_ptr()),
                     "r1_lrf_search_batch")
         return xqd, err

@@ -1,5 +1,5 @@
 // cand_helpers.inc -- what the fused candidate kernel (rdo_cand_kernel.hpp), the RDO-time sub-pel search
-// (me_blocks.hip, k_me_blocks_small) and the put / prep of transform-sized blocks (mc.hip, k_mc_fast) share: the DPP Hadamard (SATD with lane = column), v_sad, the packed
+// (me_blocks.hip, k_me_blocks_small) and the put / prep of transform-sized blocks (mc.hip, k_mc_fast) share: the DPP Hadamard (SATD with lane = column) and its LDS-tile form for the fused kernel, v_sad, the packed
 // i16 helpers, and the put_8tap / prep_8tap column filters on v_dot4 / v_dot2 with their tap loads.
 // Included INSIDE the including file's anonymous namespace, after mc_taps_packed.inc (kTapI8 /
 // kTapI16) and with `T` (= r1tx::T, int32_t) in scope.
@@ -393,6 +393,73 @@ __device__ __forceinline__ void mc16_column_t(const uint8_t *win, int c, const T
   };
   if (six) body(std::true_type{});
   else body(std::false_type{});
+}
+
+// ---- SATD with the horizontal pass in registers (blocks with both sides >= 16, up to 10 bits) ----
+// The lane stages of habs_lanes_pk cost 4.5 instructions per coefficient (DPP moves, +-1 multiplies) against 2 for
+// the vertical half, only because the data sits lane = column.  Here the packed outputs of the vertical half go
+// through LDS once and come back lane = (coefficient row, tile column) with the 8 columns of a tile in 8 registers:
+// two butterfly stages and the folded last one (max(|a|, |b|) = max(max(a, b), -min(a, b))) are 36 packed
+// instructions per 16 coefficients instead of 72.  Same i16 range argument: three vertical and two horizontal
+// stages reach 32 * 1023 before the fold.
+__device__ __forceinline__ uint32_t pk_min(uint32_t a, uint32_t b) {
+  uint32_t r;
+  asm("v_pk_min_i16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+// Vertical half: the lane's column, 16 rows at a time (8-row groups 2g and 2g+1 side by side), to column c of the
+// candidate's tile: W dwords per row, row g * 8 + i = coefficient row i of that group pair.
+template <int W, int H>
+__device__ __forceinline__ void satd_tile_store(const T *v, uint32_t *tcol) {
+#pragma unroll
+  for (int g = 0; g < H / 16; g++) {
+    uint32_t a[8], b[8], d[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) a[k] = pk_pair(v[g * 16 + k], v[g * 16 + 8 + k]);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      b[2 * k] = pk_add(a[2 * k], a[2 * k + 1]);
+      b[2 * k + 1] = pk_sub(a[2 * k], a[2 * k + 1]);
+    }
+    d[0] = pk_add(b[0], b[2]); d[2] = pk_sub(b[0], b[2]);
+    d[1] = pk_add(b[1], b[3]); d[3] = pk_sub(b[1], b[3]);
+    d[4] = pk_add(b[4], b[6]); d[6] = pk_sub(b[4], b[6]);
+    d[5] = pk_add(b[5], b[7]); d[7] = pk_sub(b[5], b[7]);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      tcol[(g * 8 + 2 * k) * W] = pk_add(d[k], d[k + 4]);
+      tcol[(g * 8 + 2 * k + 1) * W] = pk_sub(d[k], d[k + 4]);
+    }
+  }
+}
+// Horizontal half.  A tile row of W dwords is W / 8 items of 8 dwords, so item t of the candidate is dwords
+// [8 t, 8 t + 8) of its tile; lane c of the candidate's P takes items c, c + P, ... (NI of them).  Returns the lane's
+// share of sum |coefficient| (every final pair counts twice: |a + b| + |a - b| = 2 max(|a|, |b|)).
+template <int NI, int P>
+__device__ __forceinline__ uint32_t satd_tile_rows(const uint32_t *tile, int c) {
+  uint32_t acc = 0;
+#pragma unroll
+  for (int m = 0; m < NI; m++) {
+    const uint4 *p = (const uint4 *)(tile + (c + m * P) * 8);
+    const uint4 lo = p[0], hi = p[1];
+    const uint32_t x[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    uint32_t y[8], z[8];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      y[2 * k] = pk_add(x[2 * k], x[2 * k + 1]);
+      y[2 * k + 1] = pk_sub(x[2 * k], x[2 * k + 1]);
+    }
+    z[0] = pk_add(y[0], y[2]); z[2] = pk_sub(y[0], y[2]);
+    z[1] = pk_add(y[1], y[3]); z[3] = pk_sub(y[1], y[3]);
+    z[4] = pk_add(y[4], y[6]); z[6] = pk_sub(y[4], y[6]);
+    z[5] = pk_add(y[5], y[7]); z[7] = pk_sub(y[5], y[7]);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const uint32_t mx = pk_max(pk_max(z[k], z[k + 4]), pk_sub(0u, pk_min(z[k], z[k + 4])));
+      acc = __builtin_amdgcn_udot2(__builtin_bit_cast(v2us_t, mx), __builtin_bit_cast(v2us_t, 0x00020002u), acc, false);
+    }
+  }
+  return acc;
 }
 
 // SATD contribution of one residual column (TS rows at a time).

@@ -25,7 +25,9 @@
 //     1-D paths bit for bit (see the derivation at mc8_column).
 //     The residual COLUMN stays in registers.  SAD is a lane sum.  SATD: the
 //     vertical Hadamard on 8 registers, the horizontal one across the 8
-//     neighbouring lanes with DPP (quad_perm / row_half_mirror) -- no LDS.
+//     neighbouring lanes with DPP (quad_perm / row_half_mirror) -- no LDS; blocks
+//     with both sides >= 16 (up to 10 bits) turn the packed intermediates through
+//     an LDS tile over the dead window instead and finish in registers (SATD_T).
 //  C  column transform on the same registers (24-bit multiplies, exact here),
 //     transpose through LDS (odd stride, aliasing the dead window).
 //  D  lane = (candidate, row): row transform, stores in the reference's
@@ -207,6 +209,19 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
                                     : (SRC_LATE ? (WIN_PAD > SRC_BYTES ? WIN_PAD : SRC_BYTES) : WIN_PAD + SRC_BYTES);
   constexpr int LDS_A0 = WS_BYTES > TXB_BYTES ? WS_BYTES : TXB_BYTES;
   constexpr int LDS_A = LDS_A0 > IRB_BYTES ? LDS_A0 : IRB_BYTES;
+  // SATD_T: the horizontal half of the SATD in registers, through a tile in LDS (cand_helpers.inc, satd_tile_store /
+  // satd_tile_rows): H / 2 rows of W packed dwords per candidate, P dwords between candidates (the bare strides are
+  // multiples of the bank count, as with QT_PAD).  The tile lies at the start of the work area, over the window and
+  // the source block -- dead once the residual and the SAD are formed; a kept source block (SRC_KEEP) sits behind
+  // LDS_WORK and is not touched -- and is taken only where it fits what phases A, C and F need anyway: no
+  // instantiation's LDS grows, an instantiation it does not fit stays on the lane stages (satd_column).  So does the
+  // 64x64 pixel-domain chain: it is held at an allocation step below its need (rdo_waves_hint) and its spills grew
+  // with the tile path (8-bit 68 -> 76 B, 10-bit 100 -> 116 B of scratch per lane).
+  constexpr int SATD_STRIDE = W * H / 2 + (NC > 1 ? P : 0);
+  constexpr int SATD_BYTES = NC * SATD_STRIDE * 4;
+  constexpr bool SATD_T = TS == 8 && BD <= 10 && (W < H ? W : H) >= 16 && SATD_BYTES <= LDS_A &&
+                          !(QM == 2 && WL == 6 && HL == 6);
+  static_assert(SATD_STRIDE % 4 == 0, "16-byte reads stay aligned");
   constexpr int LDS_B = QT_BYTES > REC_BYTES ? QT_BYTES : REC_BYTES;
   constexpr int LDS_WORK = ((LDS_A > LDS_B ? LDS_A : LDS_B) + 15) & ~15;
   constexpr int SRC_OFF = SRC_KEEP ? LDS_WORK : (SRC_LATE ? 0 : WIN_PAD);
@@ -509,7 +524,17 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
     if (live_st && c == 0) (sad_out + (size_t)wg * NC)[cl] = s;
   }
   if (satd_out) {
-    const uint32_t s = group_sum<P>(satd_column<TS, H, BD>(v, lane));
+    uint32_t part;
+    if constexpr (SATD_T) {
+      uint32_t *tile = (uint32_t *)smem + cl * SATD_STRIDE;
+      __syncthreads();   // every lane has read its window and source column
+      if (c < W) satd_tile_store<W, H>(v, tile + c);
+      __syncthreads();
+      part = satd_tile_rows<(W < H ? W : H) / 16, P>(tile, c);   // the reads end before phase C's first barrier
+    } else {
+      part = satd_column<TS, H, BD>(v, lane);
+    }
+    const uint32_t s = group_sum<P>(part);
     constexpr int LN = TS == 4 ? 2 : 3;
     if (live_st && c == 0) (satd_out + (size_t)wg * NC)[cl] = (s + ((1u << LN) >> 1)) >> LN;
   }

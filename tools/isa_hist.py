@@ -80,6 +80,7 @@ def main():
         vmem = sum(n for o, n in c.items() if o.startswith(("global_", "buffer_", "flat_", "scratch_")))
         salu = sum(n for o, n in c.items() if o.startswith("s_"))
         short = re.sub(r"^void \(anonymous namespace\)::", "", name).split("(")[0].replace(" ", "")
+        short = re.sub(r"^(k_rdo_cand<.*,(?:true|false)),0>$", r"\1>", short)   # as tools/pmc_summary.py names it
         jout[short] = {"valu": fast + slow, "fast": fast, "slow": slow, "mfma": mfma, "lds": lds, "vmem": vmem,
                        "salu": salu, "issue_cycles_per_valu": round((fast * COST_FAST + slow * COST_SLOW) /
                                                                     max(1, fast + slow), 4)}

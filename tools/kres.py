@@ -52,4 +52,5 @@ def main():
             print("%-58s vgpr %3d agpr %3d lds %6d scratch %4d block %4d | waves/SIMD by regs %d, by LDS %d" % r)
 
 
-main()
+if __name__ == "__main__":
+    main()

@@ -21,7 +21,11 @@ import sys
 
 def short(name):
     m = re.search(r"(k_\w+)<([^>]*)>", name)
-    return "%s<%s>" % (m.group(1), m.group(2).replace(" ", "")) if m else name[:60]
+    if not m:
+        return name[:60]
+    # k_rdo_cand's prediction-source flag (its last template argument) is left off when 0: the keys stay the ones
+    # of the earlier summaries, which is what bench.py looks up
+    return re.sub(r"^(k_rdo_cand<.*,(?:true|false)),0>$", r"\1>", "%s<%s>" % (m.group(1), m.group(2).replace(" ", "")))
 
 
 def main():

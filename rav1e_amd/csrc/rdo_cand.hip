@@ -1,11 +1,20 @@
 // rdo_cand.hip -- the host side of the fused RDO candidate kernel: the argument checks, the dispatch over the
 // fifteen (bit depth, slice) objects (twelve more for the intra prediction source) and the C entry points.  The
 // kernel itself is rdo_cand_kernel.hpp, compiled by rdo_cand_slice.hip; this unit sees only what it shares with
-// the slices (rdo_cand_args.hpp).
+// the slices (rdo_cand_args.hpp, and through it the plan of rdo_cand_plan.hpp).
 #include "itx_common.hpp"   // kInvShift
 #include "rdo_cand_args.hpp"
 
 namespace {
+// The source plane and the block of every entry point: pixel format against bit depth, w x h against tx_size.
+int rdo_plane_checks(const R1Plane *org, int w, int h, int tx_size) {
+  R1_REQUIRE(org->bytes_per_px == 1 || org->bytes_per_px == 2);
+  R1_REQUIRE((org->bytes_per_px == 1) == (org->bit_depth == 8));
+  R1_REQUIRE(tx_size >= 0 && tx_size < 19);
+  R1_REQUIRE((1 << r1tx::kTxWLog2[tx_size]) == w && (1 << r1tx::kTxHLog2[tx_size]) == h);
+  return R1_OK;
+}
+
 int rdo_dispatch(r1_ctx *ctx, const R1Plane *org, const R1Plane *ref, int w, int h, int tx_size,
                  const R1RdoCand *cands, int n, uint32_t *sad_out, uint32_t *satd_out,
                  void *coeffs, void *pred_out, const RdoQuantArgs *qa, void *stream, bool mt = false) {
@@ -14,12 +23,8 @@ int rdo_dispatch(r1_ctx *ctx, const R1Plane *org, const R1Plane *ref, int w, int
   const R1Plane no_ref = {};
   if (from_pred) ref = &no_ref;
   R1_REQUIRE(from_pred || org->bytes_per_px == ref->bytes_per_px);
-  R1_REQUIRE(org->bytes_per_px == 1 || org->bytes_per_px == 2);
   R1_REQUIRE(from_pred || org->bit_depth == ref->bit_depth);
-  R1_REQUIRE((org->bytes_per_px == 1) == (org->bit_depth == 8));
-  R1_REQUIRE(tx_size >= 0 && tx_size < 19);
-  R1_REQUIRE((1 << r1tx::kTxWLog2[tx_size]) == w &&
-             (1 << r1tx::kTxHLog2[tx_size]) == h);
+  if (const int rc = rdo_plane_checks(org, w, h, tx_size); rc != R1_OK) return rc;
   if (n <= 0) return R1_OK;
   R1_REQUIRE(cands);
   hipStream_t st = (hipStream_t)stream;
@@ -72,6 +77,37 @@ int rdo_quant_args(const r1_ctx *ctx, const R1Plane *org, int tx_size, const R1Q
   qa.ydec = ydec;
   qa.pix_dist = (unsigned long long *)dist_out;
   qa.rec = rec_out;
+  return R1_OK;
+}
+
+// The transform-type mask of a type-search entry point (after rdo_quant_args: tx_size is in range), checked and
+// written into the kernel's argument block: one result slot per set bit.
+int rdo_type_mask_args(int tx_size, uint32_t tx_type_mask, int dist_kind, uint64_t *est_rate_out, RdoQuantArgs &qa) {
+  R1_REQUIRE(dist_kind == 0 || !est_rate_out);
+  // WHT (16) has no scan order; the mask is over the 16 TxTypes of the tx sets
+  R1_REQUIRE(tx_type_mask != 0 && tx_type_mask <= 0xFFFFu);
+  // a 64-point side codes DCT_DCT only (TX_SET_DCTONLY)
+  R1_REQUIRE((r1tx::kTxWLog2[tx_size] <= 5 && r1tx::kTxHLog2[tx_size] <= 5) || tx_type_mask == 1u);
+  // every type of the mask must exist for the size: the inter sets are the largest (av1_tx_used; a 32-point side has
+  // DCT_DCT and IDTX only -- the reference's 1-D tables have no other kernel there and would panic)
+  R1_REQUIRE((tx_type_mask & ~r1_tx_type_mask(tx_size, 1, 0, 0)) == 0);
+  qa.est_rate = (unsigned long long *)est_rate_out;
+  qa.tx_mask = tx_type_mask;
+  qa.nt = __builtin_popcount(tx_type_mask);
+  return R1_OK;
+}
+
+// The type search of a size that does not fan out (a 32- or 64-point side, at most two types): one plain launch per
+// type, the type forced, results into its slot; the first launch also writes what no type changes (sad, satd, pred).
+template <typename Launch>
+int rdo_launch_per_type(RdoQuantArgs &qa, uint32_t tx_type_mask, Launch launch) {
+  int slot = 0;
+  for (uint32_t m = tx_type_mask; m != 0; m &= m - 1, slot++) {
+    qa.tx_mask = m & (0u - m);
+    qa.slot = slot;
+    const int rc = launch(slot == 0);
+    if (rc != R1_OK) return rc;
+  }
   return R1_OK;
 }
 }  // namespace
@@ -162,32 +198,15 @@ extern "C" int r1_rdo_txsearch_batch(r1_ctx *ctx, const R1Plane *org, const R1Pl
   int rc = rdo_quant_args(ctx, org, tx_size, params, dist_kind, scales, scale_stride, xdec, ydec, eob_out, dist_out,
                           qcoeffs_out, rec_out, qa);
   if (rc != R1_OK) return rc;
-  R1_REQUIRE(dist_kind == 0 || !est_rate_out);
-  // WHT (16) has no scan order; the mask is over the 16 TxTypes of the tx sets
-  R1_REQUIRE(tx_type_mask != 0 && tx_type_mask <= 0xFFFFu);
-  const int up = r1tx::kTxWLog2[tx_size] > r1tx::kTxHLog2[tx_size] ? r1tx::kTxWLog2[tx_size] : r1tx::kTxHLog2[tx_size];
-  const bool side64 = up > 5, side32 = up == 5;
-  // a 64-point side codes DCT_DCT only (TX_SET_DCTONLY)
-  R1_REQUIRE(!side64 || tx_type_mask == 1u);
-  // every type of the mask must exist for the size: the inter sets are the largest (av1_tx_used; a 32-point side has
-  // DCT_DCT and IDTX only -- the reference's 1-D tables have no other kernel there and would panic)
-  R1_REQUIRE((tx_type_mask & ~r1_tx_type_mask(tx_size, 1, 0, 0)) == 0);
-  qa.est_rate = (unsigned long long *)est_rate_out;
+  rc = rdo_type_mask_args(tx_size, tx_type_mask, dist_kind, est_rate_out, qa);
+  if (rc != R1_OK) return rc;
   qa.pred_in = pred;
-  qa.tx_mask = tx_type_mask;
-  qa.nt = __builtin_popcount(tx_type_mask);
-  if (!side64 && !side32)
+  if (rdo_type_fanout(r1tx::kTxWLog2[tx_size], r1tx::kTxHLog2[tx_size]))
     return rdo_dispatch(ctx, org, ref, w, h, tx_size, cands, n, sad_out, satd_out, nullptr, nullptr, &qa, stream, true);
-  // 32- and 64-point sides: one plain launch per type (at most two), the type forced, results into its slot
-  int slot = 0;
-  for (uint32_t m = tx_type_mask; m != 0; m &= m - 1, slot++) {
-    qa.tx_mask = m & (0u - m);
-    qa.slot = slot;
-    rc = rdo_dispatch(ctx, org, ref, w, h, tx_size, cands, n, slot == 0 ? sad_out : nullptr,
-                      slot == 0 ? satd_out : nullptr, nullptr, nullptr, &qa, stream, false);
-    if (rc != R1_OK) return rc;
-  }
-  return R1_OK;
+  return rdo_launch_per_type(qa, tx_type_mask, [&](bool first) {
+    return rdo_dispatch(ctx, org, ref, w, h, tx_size, cands, n, first ? sad_out : nullptr, first ? satd_out : nullptr,
+                        nullptr, nullptr, &qa, stream, false);
+  });
 }
 
 // ---- the intra candidate in one launch: the prediction is made inside the chain (k_rdo_cand with PS = 1) ----
@@ -213,18 +232,11 @@ extern "C" int r1_rdo_intra_cand_batch(r1_ctx *ctx, const R1Plane *org, int w, i
   int rc = rdo_quant_args(ctx, org, tx_size, params, dist_kind, scales, scale_stride, xdec, ydec, eob_out, dist_out,
                           qcoeffs_out, rec_out, qa);
   if (rc != R1_OK) return rc;
-  // what r1_rdo_txsearch_batch checks, in its order
-  R1_REQUIRE(dist_kind == 0 || !est_rate_out);
-  R1_REQUIRE(tx_type_mask != 0 && tx_type_mask <= 0xFFFFu);
-  const int wl = r1tx::kTxWLog2[tx_size], hl = r1tx::kTxHLog2[tx_size];
-  const int up = wl > hl ? wl : hl;
-  const bool side64 = up > 5, side32 = up == 5;
-  R1_REQUIRE(!side64 || tx_type_mask == 1u);
-  R1_REQUIRE((tx_type_mask & ~r1_tx_type_mask(tx_size, 1, 0, 0)) == 0);
-  R1_REQUIRE(org->bytes_per_px == 1 || org->bytes_per_px == 2);
-  R1_REQUIRE((org->bytes_per_px == 1) == (org->bit_depth == 8));
+  rc = rdo_type_mask_args(tx_size, tx_type_mask, dist_kind, est_rate_out, qa);
+  if (rc != R1_OK) return rc;
+  rc = rdo_plane_checks(org, w, h, tx_size);
+  if (rc != R1_OK) return rc;
   R1_REQUIRE(org->bit_depth == 8 || org->bit_depth == 10 || org->bit_depth == 12);
-  R1_REQUIRE((1 << wl) == w && (1 << hl) == h);
   // the intra source
   R1_REQUIRE(edge_stride >= R1_INTRA_EDGE_LEN && edge_group >= 1);
   if (n <= 0) return R1_OK;
@@ -247,9 +259,6 @@ extern "C" int r1_rdo_intra_cand_batch(r1_ctx *ctx, const R1Plane *org, int w, i
       for (int i = 0; i < n; i++) R1_REQUIRE(cands[i].mode != 13);
   }
   RdoIntraArgs ia = {cands, edges, lens, pos_xy, ac, edge_stride, edge_group};
-  qa.est_rate = (unsigned long long *)est_rate_out;
-  qa.tx_mask = tx_type_mask;
-  qa.nt = __builtin_popcount(tx_type_mask);
   typedef int (*ISliceFn)(R1_INTRA_SLICE_ARGS);
 #define R1_RDO_ISLICE_ENTRY(B, Q) r1_rdo_islice_b##B##_q##Q,
   static const ISliceFn kISlices[3][4] = {{R1_RDO_ISLICE_ROW(R1_RDO_ISLICE_ENTRY, 8)},
@@ -259,7 +268,8 @@ extern "C" int r1_rdo_intra_cand_batch(r1_ctx *ctx, const R1Plane *org, int w, i
   const ISliceFn *row = kISlices[(org->bit_depth - 8) / 2];
   const int qm = dist_kind == 0 ? 1 : 2;
   hipStream_t st = (hipStream_t)stream;
-  if (r1_intra_two_launch(wl, hl, org->bit_depth, qm)) {
+  const RdoIntraRoute route = rdo_intra_route(r1tx::kTxWLog2[tx_size], r1tx::kTxHLog2[tx_size], org->bit_depth, qm);
+  if (route == RDO_INTRA_TWO_LAUNCH) {
     // predict to pred_out (or to the ring) and run the existing kernels on it: same slots, same results
     R1DeviceGuard guard(ctx);
     const size_t cand_bytes = ((size_t)n * sizeof(R1RdoCand) + 255) & ~(size_t)255;
@@ -287,17 +297,11 @@ extern "C" int r1_rdo_intra_cand_batch(r1_ctx *ctx, const R1Plane *org, int w, i
     R1_HIP_CHECK(hipEventRecord(ctx->intra_done[slot], st));
     return rc;
   }
-  if (!side64 && !side32)   // the fan-out form: slices 3 / 4
+  if (route == RDO_INTRA_FANOUT)   // slices 3 / 4
     return row[qm + 1](tx_size, *org, n, sad_out, satd_out, pred_out, &qa, &ia, st);
-  // 32- and 64-point sides: one plain launch per type (at most two), the type forced, results into its slot; each
-  // launch makes the prediction again on the CU, the first one writes sad / satd / pred_out
-  int slot = 0;
-  for (uint32_t m = tx_type_mask; m != 0; m &= m - 1, slot++) {
-    qa.tx_mask = m & (0u - m);
-    qa.slot = slot;
-    rc = row[qm - 1](tx_size, *org, n, slot == 0 ? sad_out : nullptr, slot == 0 ? satd_out : nullptr,
-                     slot == 0 ? pred_out : nullptr, &qa, &ia, st);
-    if (rc != R1_OK) return rc;
-  }
-  return R1_OK;
+  // each launch makes the prediction again on the CU, the first one writes sad / satd / pred_out
+  return rdo_launch_per_type(qa, tx_type_mask, [&](bool first) {
+    return row[qm - 1](tx_size, *org, n, first ? sad_out : nullptr, first ? satd_out : nullptr,
+                       first ? pred_out : nullptr, &qa, &ia, st);
+  });
 }

@@ -1,8 +1,10 @@
 // rdo_cand_args.hpp -- what the slices of the fused candidate kernel (rdo_cand_slice.hip: the kernel of
 // rdo_cand_kernel.hpp, one (bit depth, slice) each) and the host unit (rdo_cand.hip: argument checks, dispatch,
-// entry points) share: the kernel's quantizer argument block, the slice signature and the list of slices.
+// entry points) share: the kernel's quantizer argument block, the slice signature and the list of slices.  Which
+// instantiations a slice holds and which route a call takes: rdo_cand_plan.hpp.
 #pragma once
 #include "quant_common.hpp"
+#include "rdo_cand_plan.hpp"
 
 // QUANT (the "full" candidate): the coefficients do not go to HBM
 // (unless `coeffs` is also given) but through the quantizer in place --
@@ -67,19 +69,6 @@ R1_RDO_SLICES(R1_RDO_SLICE_DECL)
 #define R1_INTRA_SLICE_ARGS                                                                               \
   int tx_size, const R1Plane &org, int n, uint32_t *sad, uint32_t *satd, void *pred, const RdoQuantArgs *qa, \
       const RdoIntraArgs *ia, hipStream_t st
-// Where the launch with the prediction made on the CU lost to r1_predict_intra_batch -> r1_rdo_txsearch_batch(pred)
-// by more than the +-3-4 % between boxes (profiles/r12_intra_cand.jsonl, 4K luma, 4 modes per block): those points
-// take the two launches inside r1_rdo_intra_cand_batch and have no intra instantiation.  Measured at 8 and 10
-// bits; 12 bits is the 10-bit code at another constant and follows it, R1_DIST_WSSE shares the chain up to the
-// distortion with R1_DIST_CDEF and follows it.  qm: 1 = dist_kind 0, 2 = a pixel-domain kind.
-//   16x16, dist_kind 0                 +11.5 % (8-bit), +10.9 % (10-bit)
-//   16x16, pixel kinds, 16-bit pixels  +3.6 % (two runs)
-//   64x64, dist_kind 0, 16-bit pixels  +13 %
-//   32x32, pixel kinds, 16-bit pixels  +4.3 %
-constexpr bool r1_intra_two_launch(int wl, int hl, int bd, int qm) {
-  return wl == hl && ((wl == 4 && (qm == 1 || bd != 8)) || (wl == 6 && qm == 1 && bd != 8) ||
-                      (wl == 5 && qm == 2 && bd != 8));
-}
 #define R1_RDO_ISLICE_ROW(X, B) X(B, 1) X(B, 2) X(B, 3) X(B, 4)
 #define R1_RDO_ISLICES(X) R1_RDO_ISLICE_ROW(X, 8) R1_RDO_ISLICE_ROW(X, 10) R1_RDO_ISLICE_ROW(X, 12)
 #define R1_RDO_ISLICE_DECL(B, Q) int r1_rdo_islice_b##B##_q##Q(R1_INTRA_SLICE_ARGS);

@@ -10,7 +10,7 @@ set (r1_tx_type_mask(tx_size, 0, 0, 1)).  The edge sets are built once, outside 
                   alone): the prediction is made on the CU.  Timed with edge_group = K (the K modes of a block share
                   the pre-screen's edge set) and with edge_group = 1 (one set per candidate, the reference's shape).
                   "fused" is whatever the entry point runs: at the (size, bit depth, kind) points where the one
-                  launch lost (r1_intra_two_launch, csrc/rdo_cand_args.hpp) it runs two launches itself.
+                  launch lost (r1_intra_two_launch, csrc/rdo_cand_plan.hpp) it runs two launches itself.
   (b) two-launch  r1_predict_intra_batch (n dense s x s blocks to HBM) -> r1_rdo_txsearch_batch(pred = ...) reading
                   them back: the parent's code, untouched by the fused route.
 Both sides are checked for identical eob / dist / sad / satd (and predictions) first, then timed alternately (a, b,

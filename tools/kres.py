@@ -26,27 +26,33 @@ def code_objects(path):
         pos += 24
 
 
-def main():
-    lib = sys.argv[1]
-    pat = sys.argv[2] if len(sys.argv) > 2 else ""
-    rows = []
-    for co in code_objects(lib):
+def kernel_notes(path):
+    """(mangled kernel name, field) of every gfx950 kernel of the library, from the metadata note of its code object:
+    field(key) is the text of the kernel's .key entry ("0" where it has none)"""
+    for co in code_objects(path):
         with tempfile.NamedTemporaryFile(suffix=".co", delete=False) as f:
             f.write(co)
         txt = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--notes", f.name], capture_output=True, text=True).stdout
         os.unlink(f.name)
         for blk in txt.split("- .agpr_count:")[1:]:
-            g = lambda k: (re.search(r"\.%s:\s+(\S+)" % k, blk) or [None, "0"])[1]
-            name = g("name")
-            dem = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
-            dem = re.sub(r"^void \(anonymous namespace\)::", "", dem).split("(")[0]
-            vg, ag = int(g("vgpr_count")), int(blk.split("\n")[0].strip() or 0)
-            lds, scr, wg = int(g("group_segment_fixed_size")), int(g("private_segment_fixed_size")), int(g("max_flat_workgroup_size"))
-            regs = max(vg + ag, 1)
-            w_reg = min(8, 512 // ((regs + 7) // 8 * 8))
-            waves_per_wg = max(1, (wg + 63) // 64)
-            w_lds = 8 if lds == 0 else min(8, (160 * 1024 // lds) * waves_per_wg // 4)
-            rows.append((dem, vg, ag, lds, scr, wg, w_reg, w_lds))
+            blk = ".agpr_count: " + blk
+            yield re.search(r"\.name:\s+(\S+)", blk)[1], lambda k, blk=blk: (re.search(r"\.%s:\s+(\S+)" % k, blk) or [None, "0"])[1]
+
+
+def main():
+    lib = sys.argv[1]
+    pat = sys.argv[2] if len(sys.argv) > 2 else ""
+    rows = []
+    for name, g in kernel_notes(lib):
+        dem = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
+        dem = re.sub(r"^void \(anonymous namespace\)::", "", dem).split("(")[0]
+        vg, ag = int(g("vgpr_count")), int(g("agpr_count"))
+        lds, scr, wg = int(g("group_segment_fixed_size")), int(g("private_segment_fixed_size")), int(g("max_flat_workgroup_size"))
+        regs = max(vg + ag, 1)
+        w_reg = min(8, 512 // ((regs + 7) // 8 * 8))
+        waves_per_wg = max(1, (wg + 63) // 64)
+        w_lds = 8 if lds == 0 else min(8, (160 * 1024 // lds) * waves_per_wg // 4)
+        rows.append((dem, vg, ag, lds, scr, wg, w_reg, w_lds))
     for r in sorted(set(rows)):
         if pat in r[0]:
             print("%-58s vgpr %3d agpr %3d lds %6d scratch %4d block %4d | waves/SIMD by regs %d, by LDS %d" % r)

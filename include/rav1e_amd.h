@@ -121,7 +121,7 @@ const char *r1_last_error(void);
  * r1_comm_push_frame (round 5) were added under versions 4 and 5 respectively, and the compound candidate
  * (r1_rdo_compound_cand_batch, R1CompoundCand) under version 7, as were the frame's scale maps and segmentation
  * inputs (r1_frame_scales, r1_scale_kmeans, r1_segmentation_from_centroids, r1_spatiotemporal_scale_batch) and the
- * intra candidate (r1_rdo_intra_cand_batch). */
+ * intra candidate (r1_rdo_intra_cand_batch) and the coefficient rate (r1_coeff_rate_batch, R1CoeffCdfs, R1TxbCtx). */
 int r1_abi_version(void);
 
 /* ---- dist:: (reference: src/dist.rs get_sad 31, get_satd 156; dispatch
@@ -1073,6 +1073,68 @@ int r1_rdo_intra_cand_batch(r1_ctx *ctx, const R1Plane *org, int w, int h, int t
  * use_reduced_set)]; rav1e_types_only != 0 keeps only RAV1E_TX_TYPES (DCT_DCT, ADST_DCT, DCT_ADST,
  * ADST_ADST, IDTX, V_DCT, H_DCT = 0x0E0F).  0 for an invalid tx_size.  Host arithmetic, no device work. */
 uint32_t r1_tx_type_mask(int tx_size, int is_inter, int use_reduced_set, int rav1e_types_only);
+
+/* ---- the real coefficient rate of the transform-type search on the device (added under ABI 7): per TxType
+ * rdo_tx_type_decision (src/rdo.rs:1744-1799) makes a fresh WriterCounter (rng 0x8000, cnt -9, no bits), takes
+ * tell_frac, writes the block, takes tell_frac again and rolls the CDFs back -- so every type of a block starts from
+ * the same CDF state.  With one transform block per block that rate is the cost of write_coeffs_lv_map
+ * (src/context/block_unit.rs:1783-2016), a pure function of the quantized coefficients, the block's two neighbour
+ * contexts and the CDF state: integer arithmetic throughout.  This call computes it for every (candidate, type) slot
+ * of r1_rdo_txsearch_batch / r1_rdo_intra_cand_batch / r1_rdo_pixel_cand_batch, chained on the same stream with no
+ * copy, against CDF snapshots the host hands over.
+ * The dimensions are the reference's (src/context/transform_unit.rs:27, 200-219). */
+#define R1_TXB_SKIP_CONTEXTS 13
+#define R1_EOB_COEF_CONTEXTS 9
+#define R1_SIG_COEF_CONTEXTS_EOB 4
+#define R1_SIG_COEF_CONTEXTS 42
+#define R1_LEVEL_CONTEXTS 21
+#define R1_BR_CDF_SIZE 4
+#define R1_DC_SIGN_CONTEXTS 3
+#define R1_INTRA_MODES 13
+/* one (txs_ctx, plane_type) slice of the reference's CDFContext, in its own shapes
+ * (src/context/cdf_context.rs:23-96); the host gathers it from its entropy state.  A CDF of N symbols is N entries:
+ * N - 1 probabilities and the adaptation counter. */
+typedef struct R1CoeffCdfs {
+  uint16_t txb_skip[R1_TXB_SKIP_CONTEXTS][2];         /* txb_skip_cdf[txs_ctx] */
+  uint16_t eob_flag[2][11];                           /* eob_flag_cdf{16..1024}[plane_type][eob_multi_ctx]; the first
+                                                         5 + eob_multi_size entries of a row are the CDF */
+  uint16_t eob_extra[R1_EOB_COEF_CONTEXTS][2];        /* eob_extra_cdf[txs_ctx][plane_type] */
+  uint16_t coeff_base_eob[R1_SIG_COEF_CONTEXTS_EOB][3];
+  uint16_t coeff_base[R1_SIG_COEF_CONTEXTS][4];
+  uint16_t coeff_br[R1_LEVEL_CONTEXTS][R1_BR_CDF_SIZE]; /* coeff_br_cdf[min(txs_ctx, TX_32X32)][plane_type] */
+  uint16_t dc_sign[R1_DC_SIGN_CONTEXTS][2];
+  uint16_t tx_type[R1_INTRA_MODES][16];               /* the table write_tx_type would use for this (tx_size, is_inter,
+                                                         reduced set): row = y_mode for intra, row 0 for inter; the
+                                                         first num_tx_set[set] entries of a row are the CDF */
+} R1CoeffCdfs;
+typedef struct R1TxbCtx { uint8_t txb_skip_ctx, dc_sign_ctx, y_mode, cdf_sel; } R1TxbCtx;   /* 4 bytes */
+/*   qcoeffs / eobs: n * nt dense coded-area blocks (coeff_bytes 2 = i16 for 8-bit, 4 = i32 otherwise) and n * nt
+ *                   entries, slot [i * nt + j] = candidate i with the j-th set bit of tx_type_mask (nt = its
+ *                   popcount): the layout the candidate calls write.  A single-type call is a mask of one bit.
+ *   ctxs[i]:        candidate i's contexts (BlockContext::get_txb_ctx, block_unit.rs:442-526; y_mode is read for an
+ *                   intra luma block only but must be < 13); cdfs[ctxs[i].cdf_sel] is the snapshot it starts from,
+ *                   cdf_sel < n_cdfs <= 256.  How stale a snapshot may be -- per frame, tile or superblock -- is
+ *                   the host's choice.
+ *   rate_out[i * nt + j] = wr.tell_frac() - tell of a fresh WriterCounter after write_coeffs_lv_map, in 1/8 bit
+ *                   (OD_BITRES = 3): the txb_skip symbol; for eob > 0 also write_tx_type when plane == 0, the eob,
+ *                   the levels in av1_scan_orders[tx_size][tx_type] with their contexts (tx_class, txs_ctx =
+ *                   get_txsize_entropy_ctx, eob_multi_size = area_log2 - 4, the coded size of the 64-point sizes),
+ *                   the signs and Golomb tails.  Every slot starts from an UNADAPTED copy of its snapshot and adapts
+ *                   it symbol by symbol as update_cdf does (src/ec.rs:935-955); `cdfs` is never written.
+ *   cul_level_out (optional): n * nt bytes, the value write_coeffs_lv_map hands set_coeff_context: min(63, sum |c|)
+ *                   with set_dc_sign applied, 0 for eob == 0 -- what the host stores for the winner.
+ * R1_EINVAL (what the host can check): a NULL required pointer, coeff_bytes not 2 / 4, an invalid tx_size, an empty
+ * mask or one with bits outside r1_tx_type_mask(tx_size, is_inter, use_reduced_tx_set, 0), n_cdfs outside 1..256,
+ * plane outside 0..2.  Device-resident data cannot be checked there: a slot whose eob exceeds the coded area, whose
+ * txb_skip_ctx / dc_sign_ctx / y_mode is out of range or whose cdf_sel >= n_cdfs gets rate 0xFFFFFFFF and cul_level 0,
+ * and nothing is read out of bounds.  Every loop of the kernel is bounded independently of the data's values.
+ * OUT OF SCOPE: blocks that write_tx_tree / write_tx_blocks code as several transform blocks (tx depth > 0, luma and
+ * chroma together) -- their CDFs and neighbour contexts carry from one transform block to the next -- and every
+ * non-coefficient symbol (modes, motion vectors, partition, count_lrf_switchable). */
+int r1_coeff_rate_batch(r1_ctx *ctx, const void *qcoeffs, int coeff_bytes, const uint16_t *eobs, int n,
+                        uint32_t tx_type_mask, int tx_size, int plane, int is_inter, int use_reduced_tx_set,
+                        const R1TxbCtx *ctxs, const R1CoeffCdfs *cdfs, int n_cdfs, uint32_t *rate_out,
+                        uint8_t *cul_level_out, void *stream);
 
 /* ---- multi-GPU: the tile-boundary exchange and the reference-frame all-gather (RCCL over
  * xGMI), SURVEY.md 8(e).  One process (or host thread) per GPU, tile r on rank r.  Rendezvous:

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .types import TX_DIMS, TxSize, valid_av1_transform
+from .types import COEFF_CDFS, COEFF_RATE_INVALID, TX_DIMS, TXB_CTX, TxSize, valid_av1_transform  # noqa: F401
 
 DIST_CAND = np.dtype([("ox", "<i2"), ("oy", "<i2"), ("rx", "<i2"), ("ry", "<i2")])
 MC_CAND = np.dtype([("rx", "<i2"), ("ry", "<i2"), ("col_frac", "u1"), ("row_frac", "u1"),
@@ -1019,6 +1019,36 @@ class Context:
             C.byref(qp), dist_kind, *_scales_arg(scales), xdec, ydec,
             *_ptrs(o, "sad", "satd", "eob", "dist", "est_rate", "qcoeffs", "rec", "pred"), _stream_ptr()),
             "r1_rdo_intra_cand_batch")
+        return o
+
+    def coeff_rate_batch(self, qcoeffs, eobs, tx_type_mask, tx_size, plane, is_inter, ctxs, cdfs,
+                         use_reduced_tx_set=False, want_cul_level=True, outs=None):
+        """r1_coeff_rate_batch: the real rate of every (candidate, type) slot -- write_coeffs_lv_map
+        (src/context/block_unit.rs:1783-2016) on a fresh WriterCounter against an unadapted copy of the slot's CDF
+        snapshot, as rdo_tx_type_decision measures it (src/rdo.rs:1744-1799).
+        qcoeffs / eobs: the (n, nt, coded area) int16 / int32 and (n, nt) uint16 device tensors the candidate calls
+        write (rdo_txsearch_batch(want_qcoeffs=True), ...): chained on the current stream, no copy.
+        ctxs: n TXB_CTX (NumPy array, or a uint8 device tensor (n, 4)); cdfs: COEFF_CDFS array (or a uint8 device tensor
+        (n_cdfs, 1088)) of 1..256 snapshots.  -> {"rate": (n, nt) int32 holding uint32 1/8 bits (COEFF_RATE_INVALID
+        for a slot with out-of-range device inputs), "cul_level": (n, nt) uint8}"""
+        nt = bin(int(tx_type_mask)).count("1")
+        assert qcoeffs.is_cuda and qcoeffs.is_contiguous() and qcoeffs.dtype in (torch.int16, torch.int32)
+        assert eobs.is_cuda and eobs.is_contiguous() and eobs.element_size() == 2
+        dctx, n = _dev_cands(ctxs, TXB_CTX)
+        dcdf, n_cdfs = _dev_cands(cdfs, COEFF_CDFS)
+        assert eobs.numel() == n * nt or nt == 0, (eobs.numel(), n, nt)      # (an empty mask: the library refuses it)
+        dev = qcoeffs.device
+        o = dict(outs) if outs else {}
+        if "rate" not in o:
+            o["rate"] = torch.empty((n, nt), dtype=torch.int32, device=dev)
+        if want_cul_level and "cul_level" not in o:
+            o["cul_level"] = torch.empty((n, nt), dtype=torch.uint8, device=dev)
+        cul = o.get("cul_level") if want_cul_level else None
+        self._check(self.lib.r1_coeff_rate_batch(
+            self.h, qcoeffs.data_ptr(), qcoeffs.element_size(), eobs.data_ptr(), n, int(tx_type_mask), int(tx_size),
+            int(plane), int(bool(is_inter)), int(bool(use_reduced_tx_set)), dctx.data_ptr(), dcdf.data_ptr(),
+            n_cdfs, o["rate"].data_ptr(), cul.data_ptr() if cul is not None else None, _stream_ptr()),
+            "r1_coeff_rate_batch")
         return o
 
     # ---- lrf:: ----

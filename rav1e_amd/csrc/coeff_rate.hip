@@ -1,0 +1,382 @@
+// coeff_rate.hip -- r1_coeff_rate_batch: the real coefficient rate of one transform block per (candidate, type)
+// slot, as rdo_tx_type_decision measures it (src/rdo.rs:1744-1799): a fresh WriterCounter (src/ec.rs:193-201,
+// 317-319), tell_frac, write_coeffs_lv_map (src/context/block_unit.rs:1783-2016), tell_frac, CDFs rolled back.
+// Every slot starts from an unadapted copy of its R1CoeffCdfs snapshot, so the slots are independent.
+//
+// One wave per slot, four slots per workgroup.  Inside a slot:
+//  A  (parallel over the coded area) txb_init_levels: min(|c|, 127), transposed, stride H + TX_PAD_HOR, in LDS.
+//  then, per chunk of 256 scan positions, from eob - 1 down (the order encode_coeffs codes them in):
+//  1  (parallel, four positions per lane) get_nz_map_ctx / the eob context, get_br_ctx and the symbol count of
+//     each position -> a 16-bit token and, by a wave prefix sum, the index of its first symbol in the chunk.
+//  2  (parallel over CDF rows) the only rows a slot hits more than once are coeff_base (42) and coeff_br (21):
+//     lane l < 42 keeps coeff_base[l], lane 42 + r keeps coeff_br[r] in registers, walks the chunk's tokens and,
+//     for those of its row, emits (fl, fh, nms) from its adapting copy (update_cdf, src/ec.rs:935-955) at the
+//     symbol's index.  txb_skip, tx_type, eob_flag, eob_extra, coeff_base_eob and dc_sign are hit once per slot
+//     and are read from the snapshot as they stand.
+//  3  (serial) the chain over (fl, fh, nms) through rng and bits (lr_compute + leading_zeros), run by every lane
+//     on the same values: a dozen instructions per symbol, no divergence.
+//  then encode_coeff_signs, in chunks from scan position 0 up: the values gathered in parallel, the sign bits,
+//  the DC sign symbol and the Golomb tails chained serially (they depend on rng only).
+// Every loop bound is eob <= area, the four base-range rounds or the Golomb length <= 32; no spin-waits, no
+// atomics, no dependence between workgroups.  `cdfs` is never written.
+//
+// Restated from the reference (pinned by tests/golden/coeff_rate_ref.npz through every fixture case):
+//  av1_tx_ind / num_tx_set (transform_unit.rs:36-58) as host tables; tx_type_to_class, eob_to_pos_small /
+//  eob_to_pos_large, k_eob_group_start, k_eob_offset_bits, nz_map_ctx_offset_1d as the closed forms below;
+//  av1_nz_map_ctx_offset by the rule of transform_unit.rs:866-876.
+#include "common.hpp"
+#include "quant_common.hpp"
+
+namespace {
+constexpr int kChunk = 256;               // scan positions per chunk: four per lane
+constexpr int kSymMax = kChunk * 5;       // a base symbol and at most four base-range rounds per position
+constexpr int kLevelBytes = 36 * 36 + 16; // (W + TX_PAD_HOR) columns of stride H + TX_PAD_HOR, W, H <= 32
+constexpr int kBaseRows = R1_SIG_COEF_CONTEXTS, kBrRows = R1_LEVEL_CONTEXTS;
+static_assert(kBaseRows + kBrRows <= 63, "one lane per adapting CDF row, lane 63 for coeff_base_eob");
+static_assert(R1_BR_CDF_SIZE == 4, "coeff_base and coeff_br rows are four-entry CDFs in four registers");
+static_assert(sizeof(R1TxbCtx) == 4 && sizeof(R1CoeffCdfs) == 1088, "ABI layout");
+
+struct RateArgs {
+  const void *qc;
+  const uint16_t *eobs;
+  const R1TxbCtx *ctxs;
+  const R1CoeffCdfs *cdfs;
+  const uint16_t *scan[3];   // av1_scan_orders[tx_size] by kind (quantize.hip)
+  uint32_t *rate;
+  uint8_t *cul;
+  int n_slots, nt, n_cdfs, plane;
+  int w_coded, hl, area;     // coded width, log2 of the coded height, coded area
+  int shape;                 // nominal w < h: 1, w > h: 2, square: 0 (av1_nz_map_ctx_offset)
+  int eob_flag_n;            // 5 + eob_multi_size: the length of the eob_flag CDF
+  int tx_n;                  // num_tx_set of the block's set when write_tx_type codes a symbol, else 0
+  int is_inter;
+  uint8_t type[16], tx_sym[16];   // per slot j: TxType, av1_tx_ind[set][type]
+};
+
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// WriterBase<WriterCounter>: store = lr_compute + leading_zeros.  fl, fh arrive as their top 10 bits (>> EC_PROB_SHIFT),
+// all lr_compute reads of them; fl = 32768 (the first symbol) is 512.
+struct Counter {
+  uint32_t rng = 0x8000, bits = 0;
+  __device__ __forceinline__ void store(uint32_t flq, uint32_t fhq, uint32_t nms) {
+    const uint32_t r8 = rng >> 8;
+    const uint32_t u = flq >= 512 ? rng : ((r8 * flq) >> 1) + 4 * nms;
+    const uint32_t v = ((r8 * fhq) >> 1) + 4 * (nms - 1);
+    const uint32_t r = (u - v) & 0xffffu;
+    const uint32_t d = (uint32_t)__clz((int)r) - 16;    // r == 0 (not a CDF): 16, nothing is indexed by it
+    bits += d;
+    rng = (r << d) & 0xffffu;
+  }
+  // symbol(s, cdf) on a row of the snapshot; n = the CDF's length (its last entry is the counter)
+  __device__ __forceinline__ void symbol(const uint16_t *cdf, int n, int s) {
+    store(s > 0 ? (uint32_t)cdf[s - 1] >> 6 : 512u, (uint32_t)cdf[s] >> 6, (uint32_t)(n - s));
+  }
+  __device__ __forceinline__ void bit(uint32_t b) {     // bool(b, 16384)
+    if (b) store(256, 0, 1);
+    else store(512, 256, 2);
+  }
+  __device__ __forceinline__ uint32_t tell_frac() const {   // frac_compute(tell(), rng); tell = bits + cnt + 10
+    uint32_t r = rng, l = 0;
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+      r = (r * r) >> 15;
+      const uint32_t b = r >> 16;
+      l = (l << 1) | b;
+      r >>= b;
+    }
+    return ((bits + 1) << 3) - l;
+  }
+};
+
+__device__ __forceinline__ uint32_t pack_sym(uint32_t fl, uint32_t fh, uint32_t nms) {
+  return (fl >> 6) | ((fh >> 6) << 10) | (nms << 20);
+}
+__device__ __forceinline__ uint32_t min3(uint32_t v) { return v < 3 ? v : 3; }
+
+template <typename CT>
+__global__ __launch_bounds__(256) void k_coeff_rate(const RateArgs a) {
+  __shared__ __attribute__((aligned(16))) uint8_t s_lv[4][kLevelBytes];
+  __shared__ uint16_t s_tok[4][kChunk];
+  __shared__ uint16_t s_off[4][kChunk];
+  __shared__ uint32_t s_sym[4][kSymMax];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int slot = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + wave);
+  if (slot >= a.n_slots) return;
+  const int ci = slot / a.nt, j = slot - ci * a.nt;
+  const R1TxbCtx cx = a.ctxs[ci];
+  const int eob = __builtin_amdgcn_readfirstlane((int)a.eobs[slot]);
+  const int skip_ctx = __builtin_amdgcn_readfirstlane((int)cx.txb_skip_ctx);
+  const int sign_ctx = __builtin_amdgcn_readfirstlane((int)cx.dc_sign_ctx);
+  const int y_mode = __builtin_amdgcn_readfirstlane((int)cx.y_mode);
+  const int sel = __builtin_amdgcn_readfirstlane((int)cx.cdf_sel);
+  const int area = a.area;
+  if (eob > area || skip_ctx >= R1_TXB_SKIP_CONTEXTS || sign_ctx >= R1_DC_SIGN_CONTEXTS || y_mode >= R1_INTRA_MODES ||
+      sel >= a.n_cdfs) {
+    if (lane == 0) {
+      a.rate[slot] = 0xFFFFFFFFu;
+      if (a.cul) a.cul[slot] = 0;
+    }
+    return;
+  }
+  const R1CoeffCdfs *cdf = a.cdfs + sel;
+  Counter w;
+  const uint32_t tell = w.tell_frac();
+  w.symbol(cdf->txb_skip[skip_ctx], 2, eob == 0);
+  if (eob == 0) {
+    if (lane == 0) {
+      a.rate[slot] = w.tell_frac() - tell;
+      if (a.cul) a.cul[slot] = 0;
+    }
+    return;
+  }
+  const int tx_type = a.type[j];
+  const int cls = tx_type < 10 ? 0 : ((tx_type & 1) ? 1 : 2);   // tx_type_to_class: 2D, HORIZ (H_*), VERT (V_*)
+  const uint16_t *scan = a.scan[tx_type < 10 ? 0 : ((tx_type & 1) ? 2 : 1)];
+  const CT *qc = (const CT *)a.qc + (size_t)slot * (size_t)area;
+  const int hl = a.hl, H = 1 << hl, stride = H + 4;
+  uint8_t *lv = s_lv[wave];
+
+  // A: txb_init_levels (transform_unit.rs:780-792) into zeroed padding
+  for (int e = lane; e < kLevelBytes / 4; e += 64) ((uint32_t *)lv)[e] = 0;
+  wave_sync();
+  for (int e = lane; e < area; e += 64) {
+    const int32_t c = (int32_t)qc[e];
+    const uint32_t m = (uint32_t)(c < 0 ? -c : c);
+    lv[(e >> hl) * stride + (e & (H - 1))] = (uint8_t)(m < 127 ? m : 127);
+  }
+  wave_sync();
+
+  // write_tx_type (luma only), encode_eob
+  if (a.plane == 0 && a.tx_n > 1) w.symbol(cdf->tx_type[a.is_inter ? 0 : y_mode], a.tx_n, a.tx_sym[j]);
+  {
+    // get_eob_pos_token: eob_to_pos_small / eob_to_pos_large, k_eob_group_start, k_eob_offset_bits
+    const int eob_pt = eob < 3 ? eob : (32 - __clz(eob - 1)) + 1;
+    const int extra = eob - (eob_pt < 3 ? eob_pt : (1 << (eob_pt - 2)) + 1);
+    const int nbits = eob_pt < 3 ? 0 : eob_pt - 2;
+    w.symbol(cdf->eob_flag[cls != 0], a.eob_flag_n, eob_pt - 1);
+    if (nbits > 0) {
+      w.symbol(cdf->eob_extra[eob_pt - 3], 2, (extra >> (nbits - 1)) & 1);
+      for (int i = nbits - 2; i >= 0; i--) w.bit((extra >> i) & 1);
+    }
+  }
+
+  // the adapting rows: coeff_base[lane] / coeff_br[lane - 42], four entries each (the last is the counter)
+  uint32_t c0, c1, c2, cnt;
+  {
+    const uint16_t *r = lane < kBaseRows ? cdf->coeff_base[lane] : cdf->coeff_br[lane < 63 ? lane - kBaseRows : 0];
+    c0 = r[0], c1 = r[1], c2 = r[2], cnt = r[3];
+  }
+  // symbol(s) + update_cdf(s) on the lane's row -> the packed (fl, fh, nms)
+  auto row_symbol = [&](uint32_t s) -> uint32_t {
+    const uint32_t fl = s == 0 ? 32768u : (s == 1 ? c0 : (s == 2 ? c1 : c2));
+    const uint32_t fh = s == 0 ? c0 : (s == 1 ? c1 : (s == 2 ? c2 : cnt));
+    uint32_t rate = 3 + 2 + (cnt >> 4);                 // 3 + (nsymbs >> 1).min(2), nsymbs = 4
+    rate = rate < 15 ? rate : 15;                       // (a counter >= 64 is not a CDF; keeps the shift defined)
+    cnt += 1 - (cnt >> 5);
+    c0 = 0 >= s ? c0 - (c0 >> rate) : c0 + ((32768u - c0) >> rate);
+    c1 = 1 >= s ? c1 - (c1 >> rate) : c1 + ((32768u - c1) >> rate);
+    c2 = 2 >= s ? c2 - (c2 >> rate) : c2 + ((32768u - c2) >> rate);
+    return pack_sym(fl, fh, 4 - s);
+  };
+
+  // encode_coeffs: scan positions eob - 1 .. 0
+  for (int hi = eob; hi > 0; hi -= kChunk) {
+    const int np = hi < kChunk ? hi : kChunk;
+    // 1: tokens = ctx | br_ctx << 6 | min(level, 15) << 11 | (position eob - 1) << 15, and symbol counts
+    uint32_t tok[4], ns[4], tot = 0;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const int idx = lane * 4 + q;
+      tok[q] = 0, ns[q] = 0;
+      if (idx < np) {
+        const int c = hi - 1 - idx;
+        const int pos = scan[c];
+        const int col = pos >> hl, row = pos & (H - 1);
+        const uint8_t *p = lv + col * stride + row;
+        const uint32_t level = p[0];
+        uint32_t ctx;
+        if (c == eob - 1) {
+          ctx = c == 0 ? 0 : (c <= (area >> 3) ? 1 : (c <= (area >> 2) ? 2 : 3));   // get_nz_map_ctx, is_eob
+        } else {
+          uint32_t mag = min3(p[1]) + min3(p[stride]);                               // get_nz_mag
+          if (cls == 0) mag += min3(p[stride + 1]) + min3(p[2]) + min3(p[2 * stride]);
+          else if (cls == 2) mag += min3(p[2]) + min3(p[3]) + min3(p[4]);
+          else mag += min3(p[2 * stride]) + min3(p[3 * stride]) + min3(p[4 * stride]);
+          if (cls == 0 && pos == 0) {
+            ctx = 0;
+          } else {
+            ctx = (mag + 1) >> 1;
+            ctx = ctx < 4 ? ctx : 4;
+            if (cls == 0) {   // av1_nz_map_ctx_offset[tx_size][min(row, 4)][min(col, 4)] by its rule
+              if (a.shape == 1 && row < 2) ctx += 11;
+              else if (a.shape == 2 && col < 2) ctx += 16;
+              else ctx += row + col < 2 ? 1 : (row + col < 4 ? 6 : 21);
+            } else {          // nz_map_ctx_offset_1d[col or row]
+              const int k = cls == 1 ? col : row;
+              ctx += 26 + (k == 0 ? 0 : (k == 1 ? 5 : 10));
+            }
+          }
+        }
+        uint32_t br = 0, rounds = 0;
+        if (level > 2) {                                                             // get_br_ctx
+          uint32_t mag = (uint32_t)p[1] + p[stride];
+          bool near;
+          if (cls == 0) mag += p[stride + 1], near = row < 2 && col < 2;
+          else if (cls == 1) mag += p[2 * stride], near = col == 0;
+          else mag += p[2], near = row == 0;
+          mag = (mag + 1) >> 1;
+          mag = mag < 6 ? mag : 6;
+          br = pos == 0 ? mag : (near ? mag + 7 : mag + 14);
+          rounds = (level - 3) / 3 + 1;
+          rounds = rounds < 4 ? rounds : 4;
+        }
+        tok[q] = ctx | (br << 6) | ((level < 15 ? level : 15) << 11) | ((uint32_t)(c == eob - 1) << 15);
+        ns[q] = 1 + rounds;
+      }
+      tot += ns[q];
+    }
+    uint32_t incl = tot;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint32_t t = __shfl_up(incl, d, WAVE);
+      if (lane >= d) incl += t;
+    }
+    const int total = __builtin_amdgcn_readlane((int)incl, 63);
+    uint32_t off = incl - tot;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const int idx = lane * 4 + q;
+      if (idx < np) {
+        s_tok[wave][idx] = (uint16_t)tok[q];
+        s_off[wave][idx] = (uint16_t)off;
+      }
+      off += ns[q];
+    }
+    wave_sync();
+    // 2: every row's lane emits its symbols in coding order
+    for (int idx = 0; idx < np; idx++) {
+      const uint32_t t = s_tok[wave][idx], o = s_off[wave][idx];
+      const uint32_t ctx = t & 63, br = (t >> 6) & 31, level = (t >> 11) & 15;
+      if (t >> 15) {
+        if (lane == 63) {   // coeff_base_eob: one symbol per slot, from the snapshot
+          const uint16_t *r = cdf->coeff_base_eob[ctx];
+          const uint32_t s = (level < 3 ? (level > 1 ? level : 1) : 3) - 1;          // min(level, 3) - 1; level >= 1
+          s_sym[wave][o] = pack_sym(s > 0 ? r[s - 1] : 32768u, r[s], 3 - s);
+        }
+      } else if ((uint32_t)lane == ctx) {
+        s_sym[wave][o] = row_symbol(min3(level));
+      }
+      if (level > 2 && (uint32_t)lane == kBaseRows + br) {
+        for (uint32_t base = level - 3, k = 0; k < 4; k++) {                        // level 15 stands for >= 15
+          const uint32_t s = min3(base - 3 * k);
+          s_sym[wave][o + 1 + k] = row_symbol(s);
+          if (s < 3) break;
+        }
+      }
+    }
+    wave_sync();
+    // 3: the chain
+    for (int k = 0; k < total; k++) {
+      const uint32_t x = s_sym[wave][k];
+      w.store(x & 1023, (x >> 10) & 1023, x >> 20);
+    }
+    wave_sync();   // the next chunk rewrites the three buffers
+  }
+
+  // encode_coeff_signs: scan positions 0 .. eob - 1; cul_level = sum of |c| over them
+  uint32_t sum = 0;
+  for (int lo = 0; lo < eob; lo += kChunk) {
+    const int np = eob - lo < kChunk ? eob - lo : kChunk;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const int idx = q * 64 + lane;
+      if (idx < np) {
+        const int32_t v = (int32_t)qc[scan[lo + idx]];
+        const uint32_t m = (uint32_t)(v < 0 ? -v : v);
+        sum += m;
+        s_sym[wave][idx] = (m << 1) | (uint32_t)(v < 0);
+      }
+    }
+    wave_sync();
+    for (int idx = 0; idx < np; idx++) {
+      const uint32_t x = s_sym[wave][idx], m = x >> 1;
+      if (m == 0) continue;
+      if (lo + idx == 0) w.symbol(cdf->dc_sign[sign_ctx], 2, x & 1);
+      else w.bit(x & 1);
+      if (m > 14) {   // write_golomb(level - COEFF_BASE_RANGE - NUM_BASE_LEVELS - 1)
+        const uint32_t g = m - 14;
+        const int len = 32 - __clz((int)g);
+        for (int i = 0; i < len - 1; i++) w.bit(0);
+        for (int i = len - 1; i >= 0; i--) w.bit((g >> i) & 1);
+      }
+    }
+    wave_sync();
+  }
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) sum += __shfl_xor(sum, m, WAVE);
+  if (lane == 0) {
+    a.rate[slot] = w.tell_frac() - tell;
+    if (a.cul) {
+      const int32_t dc = (int32_t)qc[0];   // coeffs[0]: every scan order starts at coefficient 0
+      uint32_t cul = sum < 63 ? sum : 63;  // COEFF_CONTEXT_MASK, then set_dc_sign (block_unit.rs:325-331)
+      if (dc < 0) cul |= 1u << 6;
+      else if (dc > 0) cul += 2u << 6;
+      a.cul[slot] = (uint8_t)cul;
+    }
+  }
+}
+}  // namespace
+
+extern "C" int r1_coeff_rate_batch(r1_ctx *ctx, const void *qcoeffs, int coeff_bytes, const uint16_t *eobs, int n,
+                                   uint32_t tx_type_mask, int tx_size, int plane, int is_inter,
+                                   int use_reduced_tx_set, const R1TxbCtx *ctxs, const R1CoeffCdfs *cdfs, int n_cdfs,
+                                   uint32_t *rate_out, uint8_t *cul_level_out, void *stream) {
+  R1_REQUIRE(ctx);
+  R1_REQUIRE(coeff_bytes == 2 || coeff_bytes == 4);
+  R1_REQUIRE(tx_size >= 0 && tx_size < 19);
+  R1_REQUIRE(plane >= 0 && plane <= 2);
+  R1_REQUIRE(n_cdfs >= 1 && n_cdfs <= 256);
+  is_inter = is_inter != 0;
+  use_reduced_tx_set = use_reduced_tx_set != 0;
+  const uint32_t allowed = r1_tx_type_mask(tx_size, is_inter, use_reduced_tx_set, 0);
+  R1_REQUIRE(tx_type_mask != 0 && (tx_type_mask & ~allowed) == 0);
+  R1_REQUIRE(qcoeffs && eobs && ctxs && cdfs && rate_out);
+  if (n <= 0) return R1_OK;
+  // num_tx_set / av1_tx_ind (transform_unit.rs:36, 51-58), rows in TxSet order; the set from the mask of its types
+  static const uint8_t kNumTxSet[6] = {1, 2, 5, 7, 12, 16};
+  static const uint32_t kSetMask[6] = {0x0001, 0x0201, 0x020F, 0x0E0F, 0x0FFF, 0xFFFF};
+  static const uint8_t kTxInd[6][16] = {{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0},
+                                        {1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0},
+                                        {1, 3, 4, 2, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0},
+                                        {1, 5, 6, 4, 0, 0, 0, 0, 0, 0, 2, 3, 0, 0, 0, 0},
+                                        {3, 4, 5, 8, 6, 7, 9, 10, 11, 0, 1, 2, 0, 0, 0, 0},
+                                        {7, 8, 9, 12, 10, 11, 13, 14, 15, 0, 1, 2, 3, 4, 5, 6}};
+  int set = 0;
+  while (kSetMask[set] != allowed) set++;
+  const int wl = r1tx::kTxWLog2[tx_size], hl = r1tx::kTxHLog2[tx_size];
+  RateArgs a = {};
+  a.qc = qcoeffs, a.eobs = eobs, a.ctxs = ctxs, a.cdfs = cdfs, a.rate = rate_out, a.cul = cul_level_out;
+  for (int k = 0; k < 3; k++) a.scan[k] = ctx->scan_dev + ctx->scan_off[tx_size][k];
+  a.nt = __builtin_popcount(tx_type_mask);
+  R1_REQUIRE((long long)n * a.nt <= 0x7fffffffLL);
+  a.n_slots = n * a.nt, a.n_cdfs = n_cdfs, a.plane = plane;
+  a.w_coded = r1q::coded_dim(wl);
+  a.hl = r1_ilog2(r1q::coded_dim(hl));
+  a.area = a.w_coded << a.hl;
+  a.shape = wl < hl ? 1 : (wl > hl ? 2 : 0);
+  a.eob_flag_n = 5 + (wl + hl - 4 < 6 ? wl + hl - 4 : 6);   // eob_multi_size = area_log2 - 4; `_ =>`: eob_flag_cdf1024
+  a.tx_n = kNumTxSet[set] > 1 ? kNumTxSet[set] : 0;
+  a.is_inter = is_inter;
+  for (int t = 0, j = 0; t < 16; t++)
+    if ((tx_type_mask >> t) & 1) a.type[j] = (uint8_t)t, a.tx_sym[j] = kTxInd[set][t], j++;
+  R1DeviceGuard guard(ctx);
+  const unsigned grid = (unsigned)((a.n_slots + 3) / 4);
+  if (coeff_bytes == 2) hipLaunchKernelGGL(k_coeff_rate<int16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(k_coeff_rate<int32_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+  R1_HIP_CHECK(hipGetLastError());
+  return R1_OK;
+}

@@ -15,6 +15,10 @@ the kernels by executing the reference's own text (tests/golden/gen_rdo_glue_ref
   compute_distortion         src/rdo.rs:254-347       (composition: luma by tune, chroma sse_wxh per plane)
   rav1e_tx_types / tx_type_slots   src/transform/mod.rs:28-44, src/rdo.rs:1731-1736
                                                       (which slot of r1_rdo_txsearch_batch holds which TxType)
+  txb_ctx                    src/context/block_unit.rs:442-526   (BlockContext::get_txb_ctx: the two neighbour
+                                                       contexts r1_coeff_rate_batch takes per candidate)
+  pick_tx_type               src/rdo.rs:1801-1818     (the tail of rdo_tx_type_decision's loop on the device's rates)
+                             both pinned by tests/golden/coeff_rate_ref.npz / tests/test_coeff_rate_ref.py
 """
 from .types import BlockSize, TxSize
 
@@ -264,3 +268,50 @@ def pick_restoration_filter(options, lam, best_cost=-1.0):
             best_cost, pick = cost, i
     return pick, best_cost
 
+
+
+COEFF_CONTEXT_BITS = 6
+_DC_SIGNS = (0, -1, 1)
+# skip_contexts[min][max] (block_unit.rs:492-498)
+_SKIP_CONTEXTS = ((1, 2, 2, 2, 3), (1, 4, 4, 4, 5), (1, 4, 4, 4, 5), (1, 4, 4, 4, 5), (1, 4, 4, 4, 6))
+
+
+def txb_ctx(above_ctxs, left_ctxs, plane, plane_bsize, tx_size):
+    """BlockContext::get_txb_ctx (src/context/block_unit.rs:442-526) -> (txb_skip_ctx, dc_sign_ctx).
+    above_ctxs / left_ctxs: the entries of above_coeff_context[plane] / left_coeff_context[plane] the transform block
+    covers (frame_clipped_txw >> 2 and frame_clipped_txh >> 2 of them), each the cul_level byte a coded neighbour
+    left there (r1_coeff_rate_batch's cul_level_out)."""
+    above, left = [int(v) for v in above_ctxs], [int(v) for v in left_ctxs]
+    dc_sign = sum(_DC_SIGNS[v >> COEFF_CONTEXT_BITS] for v in above + left)
+    dc_sign_ctx = 0 if dc_sign == 0 else (1 if dc_sign < 0 else 2)
+    top = left_ = 0
+    for v in above:
+        top |= v
+    for v in left:
+        left_ |= v
+    tw, th = TxSize(tx_size).dims
+    bw, bh = BlockSize(plane_bsize).dims
+    if plane == 0:
+        if (bw, bh) == (tw, th):
+            return 0, dc_sign_ctx
+        top, left_ = top & 63, left_ & 63
+        return _SKIP_CONTEXTS[min(min(top, left_), 4)][min(top | left_, 4)], dc_sign_ctx
+    # num_pels_log2_lookup[plane_bsize] > num_pels_log2_lookup[tx_size.block_size()]
+    return (top != 0) + (left_ != 0) + (10 if bw * bh > tw * th else 7), dc_sign_ctx
+
+
+def pick_tx_type(rates, dists, lam, cur_best_rd):
+    """The tail of rdo_tx_type_decision's loop (src/rdo.rs:1801-1818) over the slots of one candidate, in slot order
+    (tx_type_slots): rd = compute_rd_cost(rate, distortion); after the FIRST type the loop ends when rd > cur_best_rd;
+    a type is kept on strict `<`, so a tie keeps the earlier one.  rates: r1_coeff_rate_batch's (1/8 bit), dists: the
+    candidate call's.  -> (slot kept, its rd); (None, f64::MAX) when the early exit left the reference's initial
+    (DCT_DCT, f64::MAX)."""
+    import sys
+    best, best_rd = None, sys.float_info.max
+    for j, (rate, dist) in enumerate(zip(rates, dists)):
+        rd = compute_rd_cost(lam, rate, dist)
+        if j == 0 and rd > cur_best_rd:
+            break
+        if rd < best_rd:
+            best, best_rd = j, rd
+    return best, best_rd

@@ -2,8 +2,13 @@
 
 BlockSize   src/partition.rs:130-153      TxSize  src/transform/mod.rs:101-123
 TxType      src/transform/mod.rs:56-74    FilterMode  src/mc.rs:100-106
+
+COEFF_CDFS / TXB_CTX: the NumPy mirrors of R1CoeffCdfs / R1TxbCtx (include/rav1e_amd.h, r1_coeff_rate_batch); the
+dimensions are the reference's (src/context/transform_unit.rs:27, 200-219).
 """
 import enum
+
+import numpy as np
 
 
 class BlockSize(enum.IntEnum):
@@ -113,3 +118,15 @@ def valid_av1_transform(tx_size, tx_type):
     if m == 32:
         return int(tx_type) in (0, 9)
     return True
+
+
+# ---- r1_coeff_rate_batch: the (txs_ctx, plane_type) slice of the reference's CDFContext, and a block's contexts
+TXB_SKIP_CONTEXTS, EOB_COEF_CONTEXTS, SIG_COEF_CONTEXTS_EOB, SIG_COEF_CONTEXTS = 13, 9, 4, 42
+LEVEL_CONTEXTS, BR_CDF_SIZE, DC_SIGN_CONTEXTS, INTRA_MODES = 21, 4, 3, 13
+COEFF_CDFS = np.dtype([("txb_skip", "<u2", (TXB_SKIP_CONTEXTS, 2)), ("eob_flag", "<u2", (2, 11)),
+                       ("eob_extra", "<u2", (EOB_COEF_CONTEXTS, 2)),
+                       ("coeff_base_eob", "<u2", (SIG_COEF_CONTEXTS_EOB, 3)),
+                       ("coeff_base", "<u2", (SIG_COEF_CONTEXTS, 4)), ("coeff_br", "<u2", (LEVEL_CONTEXTS, BR_CDF_SIZE)),
+                       ("dc_sign", "<u2", (DC_SIGN_CONTEXTS, 2)), ("tx_type", "<u2", (INTRA_MODES, 16))])
+TXB_CTX = np.dtype([("txb_skip_ctx", "u1"), ("dc_sign_ctx", "u1"), ("y_mode", "u1"), ("cdf_sel", "u1")])
+COEFF_RATE_INVALID = 0xFFFFFFFF      # the rate of a slot whose device-resident inputs are out of range

@@ -251,13 +251,14 @@ class RRange:
 
 # ---------------------------------------------------------------- slices
 class RSlice:
-    __slots__ = ("b", "o", "n", "arr")
+    __slots__ = ("b", "o", "n", "arr", "mut")
 
-    def __init__(self, b, o=0, n=None, arr=False):
+    def __init__(self, b, o=0, n=None, arr=False, mut=False):
         self.b = b
         self.o = o
         self.n = len(b) - o if n is None else n
         self.arr = arr
+        self.mut = mut      # a `&mut [T]` handed out by chunks_exact_mut: zipping it by value yields places (RIter.zip)
 
     # -- element access
     def __getitem__(self, i):
@@ -357,6 +358,12 @@ class RSlice:
     def last(self):
         return Some(self[self.n - 1]) if self.n else NONE
 
+    def last_mut(self):
+        return Some(refmut_index(self, self.n - 1)) if self.n else NONE
+
+    def first_mut(self):
+        return Some(refmut_index(self, 0)) if self.n else NONE
+
     def get(self, i):
         if type(i) is RRange:
             try:
@@ -412,7 +419,8 @@ class RSlice:
     def chunks_exact(self, k):
         return RIter(RSlice(self.b, self.o + s, k) for s in range(0, self.n - k + 1, k))
 
-    chunks_exact_mut = chunks_exact
+    def chunks_exact_mut(self, k):
+        return RIter(RSlice(self.b, self.o + s, k, mut=True) for s in range(0, self.n - k + 1, k))
 
     def windows(self, k):
         return RIter(RSlice(self.b, self.o + s, k) for s in range(0, self.n - k + 1))
@@ -887,7 +895,8 @@ class RIter:
             f(v)
 
     def zip(self, o, mut=False):
-        return RIter(zip(self.it, into_iter(o, mut)))
+        # (a `&mut [T]` chunk zipped by value -- `.zip(levels_col)` -- yields places, as `.zip(x.iter_mut())` does)
+        return RIter(zip(self.it, into_iter(o, mut or (type(o) is RSlice and o.mut))))
 
     def enumerate(self):
         return RIter(enumerate(self.it))

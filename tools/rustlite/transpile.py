@@ -822,11 +822,26 @@ class FnCompiler:
             return "_chk(%s, %r, 'return of %s')" % (val, t, self.info.node.name)
         return val
 
+    def cdf_len_bind(self, ty):
+        """`static X: [..[u16; CDF_LEN]..] = cdf_nd([..])` or `[cdf([..]), ..]`, and the same as a struct field's
+        value (src/util/cdf.rs:10-99): the const generics the callee cannot infer from its argument -- CDF_LEN, and
+        the outer lengths N_2D, N_3D, .. of its zero-initialised `out` -- are the lengths of the declared type."""
+        dims, inner = [], ty
+        while inner.k == "tarray":
+            dims.append(self.ex(inner.n))
+            inner = inner.el
+        dims.reverse()
+        names = ["CDF_LEN"] + ["N_%dD" % d for d in range(2, len(dims) + 1)]
+        return "_g = {**_g, %s}" % ", ".join("%r: %s" % (n, d) for n, d in zip(names, dims))
+
     def eval_const(self, init, ty):
         nt = self.norm(ty) if ty is not None else None
         self.expected = nt
+        pre = ""
+        if ty is not None and ty.k == "tarray" and init.k in ("call", "array"):
+            pre = "    " + self.cdf_len_bind(ty) + "\n"
         val = self.ex(init)
-        src = "def _constfn(_g):\n" + "\n".join(self.lines) + "\n    return %s\n" % val
+        src = "def _constfn(_g):\n" + pre + "\n".join(self.lines) + "\n    return %s\n" % val
         g = self.c.G
         try:
             exec(compile(src, "<rustlite const>", "exec"), g)
@@ -1728,6 +1743,9 @@ class FnCompiler:
         def mk(f, n):
             def fn():
                 self.expected = self.norm(st.ftypes.get(f)) if st else None
+                fty = st.ftypes.get(f) if st else None
+                if fty is not None and fty.k == "tarray" and n.k in ("call", "array"):
+                    self.emit(self.cdf_len_bind(fty))
                 v = self.ex(n)
                 if self.needs_copy(n, self.expected if self.expected is not None else self.ty(n)):
                     v = "_cp(%s)" % v
@@ -2464,4 +2482,37 @@ class FnCompiler:
                                   for a, b in zip(*groups)) + "]"
             from .lexer import lex
             return self.ex(Parser(lex(src), "<%s!>" % n).parse_expr())
+        if n == "symbol_with_update" and e.args is None:
+            # macro_rules! symbol_with_update (src/context/cdf_context.rs:564-579), four-argument arm, as what
+            # Writer::symbol_with_update (src/ec.rs:548-562) does to the CDF without the rollback log:
+            #   ($self, $w, $s, $cdf) => $w.symbol($s, $cdf); update_cdf($cdf, $s);     on the CDF array itself
+            # (CDFOffset / CDFContextLog are not modelled; the two-argument arm is empty without desync_finder).
+            # A generator that defines r1_sym_trace (define_py) is told every (cdf, symbol) pair first.
+            toks = e.raw[1:-1]
+            groups, cur, depth = [], [], 0
+            for t in toks:
+                if t.v in ("(", "[", "{"):
+                    depth += 1
+                elif t.v in (")", "]", "}"):
+                    depth -= 1
+                if t.v == "," and depth == 0:
+                    groups.append(cur)
+                    cur = []
+                else:
+                    cur.append(t)
+            if cur:
+                groups.append(cur)
+            if len(groups) != 4:
+                self.err("symbol_with_update! with %d arguments" % len(groups))
+            txt = lambda ts: " ".join(str(t.v[0]) + (t.v[1] or "") if t.k == "int" else str(t.v) for t in ts)
+            _s, w, s, cdf = [txt(g) for g in groups]
+            from .lexer import lex
+            stmts = ["%s.symbol(%s, %s)" % (w, s, cdf), "update_cdf(%s, %s)" % (cdf, s)]
+            if "r1_sym_trace" in self.c.fns:
+                stmts.insert(0, "r1_sym_trace(%s, %s)" % (cdf, s))
+            for src in stmts:
+                v = self.ex(Parser(lex(src), "<symbol_with_update!>").parse_expr())
+                if v and v != "None":
+                    self.emit(v)
+            return None
         self.err("macro %s!" % n)

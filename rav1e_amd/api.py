@@ -122,6 +122,11 @@ def _scales_arg(scales):
     return (None, 0) if scales is None else (scales.data_ptr(), scales.stride(0))
 
 
+def _plane3(planes):
+    """a list of 1 or 3 Planes -> the R1Plane[3] of the C calls (a single plane fills all three entries)"""
+    return (_lib.R1Plane * 3)(*[(planes[k] if k < len(planes) else planes[0]).cstruct() for k in range(3)])
+
+
 def _blocks_stride(blocks):
     """row stride, in R1DeblockBlock records, of a (rows, cols, 8) uint8 tensor of them (rows may be views)"""
     assert blocks.stride(2) == 1 and blocks.stride(1) == 8 and blocks.stride(0) % 8 == 0
@@ -562,19 +567,12 @@ class Context:
         rec / src: lists of 1 or 3 Planes (whole frame; rec deblocked); skip_mi: (mi_rows, mi_cols)
         uint8 device tensor; scales: (h/8, w/8) int32 device tensor (Q14) or None.
         -> (err (n_sby, n_sbx, 8) int64 holding u64, best (n_sby, n_sbx) int8, -1 = skipped)"""
-        prm = _lib.R1CdefSearchParams()
-        for i in range(8):
-            prm.y_strengths[i] = int(y_strengths[i])
-            prm.uv_strengths[i] = int(uv_strengths[i])
-        prm.damping, prm.bit_depth, prm.n_idx, prm.planes = int(damping), int(bit_depth), int(n_idx), len(rec)
-        prm.xdec, prm.ydec, prm.crop_w, prm.crop_h = int(xdec), int(ydec), int(crop_w), int(crop_h)
-        prm.area_sb_w, prm.area_sb_h = int(area_sb[0]), int(area_sb[1])
-        for i in range(3):
-            prm.dist_scale[i] = int(dist_scale[i])
+        prm = self._cdef_search_params(len(rec), y_strengths, uv_strengths, damping, bit_depth, n_idx, xdec, ydec, crop_w,
+                                       crop_h, area_sb, dist_scale)
         mi_rows, mi_cols = skip_mi.shape
         n_sbx, n_sby = (mi_cols + 15) // 16, (mi_rows + 15) // 16
-        pr = (_lib.R1Plane * 3)(*[(rec[k] if k < len(rec) else rec[0]).cstruct() for k in range(3)])
-        ps = (_lib.R1Plane * 3)(*[(src[k] if k < len(src) else src[0]).cstruct() for k in range(3)])
+        pr = _plane3(rec)
+        ps = _plane3(src)
         err = torch.empty((n_sby, n_sbx, 8), dtype=torch.int64, device="cuda")
         best = torch.empty((n_sby, n_sbx), dtype=torch.int8, device="cuda")
         scratch = torch.empty(self.lib.r1_cdef_strength_search_scratch_bytes(mi_cols, mi_rows),
@@ -618,9 +616,9 @@ class Context:
         mi_rows, mi_cols = skip_mi.shape
         n_sbx, n_sby = (mi_cols + 15) // 16, (mi_rows + 15) // 16
         cur = cdef_cur if cdef_cur is not None else rec
-        pr = (_lib.R1Plane * 3)(*[(rec[k] if k < len(rec) else rec[0]).cstruct() for k in range(3)])
-        pc = (_lib.R1Plane * 3)(*[(cur[k] if k < len(cur) else cur[0]).cstruct() for k in range(3)])
-        ps = (_lib.R1Plane * 3)(*[(src[k] if k < len(src) else src[0]).cstruct() for k in range(3)])
+        pr = _plane3(rec)
+        pc = _plane3(cur)
+        ps = _plane3(src)
         if isinstance(units, tuple):          # (device byte tensor or None, (n_y, n_u, n_v)): uploaded once by the caller
             du, counts = units
             n_units = (C.c_int32 * 3)(*[int(v) for v in counts])
@@ -655,8 +653,8 @@ class Context:
         prm = self._cdef_search_params(len(rec), y_strengths, uv_strengths, damping, bit_depth, n_idx, xdec, ydec, crop_w,
                                        crop_h, area_sb, (1 << 14,) * 3)
         mi_rows, mi_cols = skip_mi.shape
-        pr = (_lib.R1Plane * 3)(*[(rec[k] if k < len(rec) else rec[0]).cstruct() for k in range(3)])
-        po = (_lib.R1Plane * 3)(*[(out[k] if k < len(out) else out[0]).cstruct() for k in range(3)])
+        pr = _plane3(rec)
+        po = _plane3(out)
         scratch = torch.empty(self.lib.r1_cdef_strength_search_scratch_bytes(mi_cols, mi_rows),
                               dtype=torch.uint8, device="cuda")
         assert index_sb.dtype == torch.int8 and index_sb.is_contiguous()

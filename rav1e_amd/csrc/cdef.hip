@@ -334,14 +334,13 @@ __global__ __launch_bounds__(64) void k_cdef_filter(R1Plane in, R1Plane out, int
 extern "C" int r1_cdef_find_dir_batch(r1_ctx *ctx, const R1Plane *luma, const R1CdefDirCand *cands,
                                       int n, uint8_t *dir_out, int32_t *var_out, void *stream) {
   R1_REQUIRE(ctx && luma);
-  R1_REQUIRE(luma->bytes_per_px == 1 || luma->bytes_per_px == 2);
+  R1_REQUIRE(r1_px_ok(*luma));
   if (n <= 0) return R1_OK;
   R1_REQUIRE(cands && dir_out && var_out);
   hipStream_t st = (hipStream_t)stream;
-  if (luma->bytes_per_px == 1)
-    hipLaunchKernelGGL((k_cdef_find_dir<1>), dim3(n), dim3(64), 0, st, *luma, cands, n, dir_out, var_out);
-  else
-    hipLaunchKernelGGL((k_cdef_find_dir<2>), dim3(n), dim3(64), 0, st, *luma, cands, n, dir_out, var_out);
+  r1_by_bpp(luma->bytes_per_px, [&](auto B) {
+    hipLaunchKernelGGL((k_cdef_find_dir<B.value>), dim3(n), dim3(64), 0, st, *luma, cands, n, dir_out, var_out);
+  });
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }
@@ -350,17 +349,16 @@ extern "C" int r1_cdef_filter_block_batch(r1_ctx *ctx, const R1Plane *in, const 
                                           int xdec, int ydec, const R1CdefBlockCand *cands, int n,
                                           void *stream) {
   R1_REQUIRE(ctx && in && out);
-  R1_REQUIRE(in->bytes_per_px == out->bytes_per_px);
-  R1_REQUIRE(in->bytes_per_px == 1 || in->bytes_per_px == 2);
+  R1_REQUIRE(r1_same_px(*in, *out));
+  R1_REQUIRE(r1_px_ok(*in));
   R1_REQUIRE(in->data != out->data);   // the filter reads neighbours of other blocks
-  R1_REQUIRE(xdec >= 0 && xdec <= 1 && ydec >= 0 && ydec <= 1);
+  R1_REQUIRE(r1_dec_ok(xdec, ydec));
   if (n <= 0) return R1_OK;
   R1_REQUIRE(cands);
   hipStream_t st = (hipStream_t)stream;
-  if (in->bytes_per_px == 1)
-    hipLaunchKernelGGL((k_cdef_filter<1>), dim3(n), dim3(64), 0, st, *in, *out, xdec, ydec, cands, n);
-  else
-    hipLaunchKernelGGL((k_cdef_filter<2>), dim3(n), dim3(64), 0, st, *in, *out, xdec, ydec, cands, n);
+  r1_by_bpp(in->bytes_per_px, [&](auto B) {
+    hipLaunchKernelGGL((k_cdef_filter<B.value>), dim3(n), dim3(64), 0, st, *in, *out, xdec, ydec, cands, n);
+  });
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }
@@ -373,36 +371,28 @@ int cdef_grid(int tile_w, int tile_h, int *nbx, int *nby) {
   return *nbx * *nby;
 }
 
+// the four decimation pairs (r1_dec_ok) as constants
+template <class F>
+void by_dec(int xdec, int ydec, F &&f) {
+  if (xdec == 0 && ydec == 0) f(r1_int<0>{}, r1_int<0>{});
+  else if (xdec == 1 && ydec == 1) f(r1_int<1>{}, r1_int<1>{});
+  else if (xdec == 1) f(r1_int<1>{}, r1_int<0>{});
+  else f(r1_int<0>{}, r1_int<1>{});
+}
+
 int cdef_filter_launch(const CdefFrameArgs &a, int bpp, hipStream_t st) {
   // plane pixels the grid covers, in 32 x 16 regions
   const int pw = (a.nbx * 8) >> a.xdec, ph = (a.nby * 8) >> a.ydec;
   const dim3 grid((pw + 31) / 32, (ph + 15) / 16);
-#define R1_CDEF_LAUNCH(B, X, Y) hipLaunchKernelGGL((k_cdef_frame<B, X, Y>), grid, dim3(256), 0, st, a)
-#define R1_CDEF_DEC(B)                                   \
-  do {                                                   \
-    if (a.xdec == 0 && a.ydec == 0) R1_CDEF_LAUNCH(B, 0, 0); \
-    else if (a.xdec == 1 && a.ydec == 1) R1_CDEF_LAUNCH(B, 1, 1); \
-    else if (a.xdec == 1) R1_CDEF_LAUNCH(B, 1, 0);       \
-    else R1_CDEF_LAUNCH(B, 0, 1);                        \
-  } while (0)
-  if (bpp == 1) R1_CDEF_DEC(1);
-  else R1_CDEF_DEC(2);
-#undef R1_CDEF_DEC
-#undef R1_CDEF_LAUNCH
+  r1_by_bpp(bpp, [&](auto B) {
+    by_dec(a.xdec, a.ydec, [&](auto X, auto Y) {
+      hipLaunchKernelGGL((k_cdef_frame<B.value, X.value, Y.value>), grid, dim3(256), 0, st, a);
+    });
+  });
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }
 }  // namespace
-
-void r1_cdef_scratch_free(r1_ctx *c) {
-  for (int k = 0; k < r1_ctx::kCdefSlots; k++) {
-    if (c->cdef_done[k]) {
-      (void)hipEventSynchronize(c->cdef_done[k]);
-      (void)hipEventDestroy(c->cdef_done[k]);
-    }
-    if (c->cdef_scratch[k]) (void)hipFree(c->cdef_scratch[k]);
-  }
-}
 
 extern "C" long long r1_cdef_analyze_blocks(int tile_w, int tile_h) {
   int nbx, nby;
@@ -413,8 +403,8 @@ extern "C" int r1_cdef_analyze_frame(r1_ctx *ctx, const R1Plane *luma, int tile_
                                      int mi_cols, int mi_rows, uint8_t *dir_out, int32_t *var_out,
                                      void *stream) {
   R1_REQUIRE(ctx && luma && dir_out && var_out);
-  R1_REQUIRE(luma->bytes_per_px == 1 || luma->bytes_per_px == 2);
-  R1_REQUIRE(luma->bit_depth == 8 || luma->bit_depth == 10 || luma->bit_depth == 12);
+  R1_REQUIRE(r1_px_ok(*luma));
+  R1_REQUIRE(r1_depth_ok(luma->bit_depth));
   R1_REQUIRE(tile_w > 0 && tile_h > 0);
   R1DeviceGuard guard(ctx);
   int nbx, nby;
@@ -429,14 +419,14 @@ int cdef_frame_plane(r1_ctx *ctx, const R1Plane *luma, const uint8_t *dirs, cons
                      const uint8_t *cdef_index_sb, int sb_stride, const R1CdefParams *params,
                      void *stream) {
   R1_REQUIRE(ctx && in && out && params && skip_mi && cdef_index_sb && (luma || (dirs && vars)));
-  R1_REQUIRE(in->bytes_per_px == out->bytes_per_px);
-  R1_REQUIRE(!luma || in->bytes_per_px == luma->bytes_per_px);
-  R1_REQUIRE(in->bytes_per_px == 1 || in->bytes_per_px == 2);
+  R1_REQUIRE(r1_same_px(*in, *out));
+  R1_REQUIRE(!luma || r1_same_px(*in, *luma));
+  R1_REQUIRE(r1_px_ok(*in));
   R1_REQUIRE(in->data != out->data);
-  R1_REQUIRE(p >= 0 && p <= 2 && xdec >= 0 && xdec <= 1 && ydec >= 0 && ydec <= 1);
+  R1_REQUIRE(p >= 0 && p <= 2 && r1_dec_ok(xdec, ydec));
   R1_REQUIRE(p != 0 || (xdec == 0 && ydec == 0));
   R1_REQUIRE(tile_w > 0 && tile_h > 0 && mi_stride >= mi_cols);
-  R1_REQUIRE(params->bit_depth == 8 || params->bit_depth == 10 || params->bit_depth == 12);
+  R1_REQUIRE(r1_depth_ok(params->bit_depth));
   // the analysis takes its coefficient shift from the luma plane, the filter from params: one value
   R1_REQUIRE(!luma || luma->bit_depth == params->bit_depth);
   // without a luma plane the picture limits come from tile_w / tile_h: the plane size as v_frame
@@ -464,29 +454,18 @@ int cdef_frame_plane(r1_ctx *ctx, const R1Plane *luma, const uint8_t *dirs, cons
   }
   // directions of this call only, in a slot of the context's ring (not hipMallocAsync: the default
   // pool hands its memory back at every synchronisation and the next call pays a driver allocation)
-  std::lock_guard<std::mutex> lock(ctx->cdef_mu);
-  const int slot = ctx->cdef_next;
-  ctx->cdef_next = (slot + 1) % r1_ctx::kCdefSlots;
-  if (!ctx->cdef_done[slot]) R1_HIP_CHECK(hipEventCreateWithFlags(&ctx->cdef_done[slot], hipEventDisableTiming));
-  else R1_HIP_CHECK(hipEventSynchronize(ctx->cdef_done[slot]));
-  const size_t need = (size_t)nb * 5;
-  if (ctx->cdef_scratch_bytes[slot] < need) {
-    if (ctx->cdef_scratch[slot]) R1_HIP_CHECK(hipFree(ctx->cdef_scratch[slot]));
-    ctx->cdef_scratch[slot] = nullptr;
-    ctx->cdef_scratch_bytes[slot] = 0;
-    R1_HIP_CHECK(hipMalloc(&ctx->cdef_scratch[slot], need));
-    ctx->cdef_scratch_bytes[slot] = need;
-  }
-  int32_t *v = (int32_t *)ctx->cdef_scratch[slot];
-  uint8_t *d = (uint8_t *)ctx->cdef_scratch[slot] + (size_t)nb * 4;
+  void *scratch;
+  if (const int got = ctx->cdef_ring.acquire((size_t)nb * 5, &scratch); got != R1_OK) return got;
+  int32_t *v = (int32_t *)scratch;
+  uint8_t *d = (uint8_t *)scratch + (size_t)nb * 4;
   int rc = cdef_analyze_launch(luma, a.nbx, a.nby, mi_cols, mi_rows, d, v, st);
   if (rc == R1_OK) {
     a.dirs = d;
     a.vars = v;
     rc = cdef_filter_launch(a, in->bytes_per_px, st);
   }
-  R1_HIP_CHECK(hipEventRecord(ctx->cdef_done[slot], st));
-  return rc;
+  const int rel = ctx->cdef_ring.release(st);
+  return rel != R1_OK ? rel : rc;
 }
 }  // namespace
 

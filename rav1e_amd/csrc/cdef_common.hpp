@@ -222,10 +222,9 @@ __device__ __forceinline__ i16x2 constrain2(i16x2 d, i16x2 thr, u16x2 sh) {
 inline int cdef_analyze_launch(const R1Plane *luma, int nbx, int nby, int mi_cols, int mi_rows,
                         uint8_t *dirs, int32_t *vars, hipStream_t st) {
   const dim3 grid((nbx + 63) / 64, nby);
-  if (luma->bytes_per_px == 1)
-    hipLaunchKernelGGL((k_cdef_analyze<1>), grid, dim3(64), 0, st, *luma, nbx, nby, mi_cols, mi_rows, dirs, vars);
-  else
-    hipLaunchKernelGGL((k_cdef_analyze<2>), grid, dim3(64), 0, st, *luma, nbx, nby, mi_cols, mi_rows, dirs, vars);
+  r1_by_bpp(luma->bytes_per_px, [&](auto B) {
+    hipLaunchKernelGGL((k_cdef_analyze<B.value>), grid, dim3(64), 0, st, *luma, nbx, nby, mi_cols, mi_rows, dirs, vars);
+  });
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }

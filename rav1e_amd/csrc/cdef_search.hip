@@ -438,16 +438,16 @@ int search_args(r1_ctx *ctx, const R1Plane *rec, const R1Plane *src, const uint8
   const R1CdefSearchParams &p = *params;
   R1_REQUIRE(p.n_idx >= 1 && p.n_idx <= 8 && (p.planes == 1 || p.planes == 3));
   R1_REQUIRE(p.area_sb_w >= 1 && p.area_sb_h >= 1 && p.crop_w > 0 && p.crop_h > 0);
-  R1_REQUIRE(p.bit_depth == 8 || p.bit_depth == 10 || p.bit_depth == 12);
+  R1_REQUIRE(r1_depth_ok(p.bit_depth));
   R1_REQUIRE(mi_cols > 0 && mi_rows > 0 && mi_stride >= mi_cols && (mi_cols & 1) == 0 && (mi_rows & 1) == 0);
   R1_REQUIRE(!scales || scale_stride > 0);
   const int np = p.planes;
   for (int k = 0; k < np; k++) {
-    R1_REQUIRE(rec[k].bytes_per_px == rec[0].bytes_per_px && src[k].bytes_per_px == rec[0].bytes_per_px);
+    R1_REQUIRE(r1_same_px(rec[0], rec[k], src[k]));
     R1_REQUIRE(rec[k].data && src[k].data);
   }
-  R1_REQUIRE(rec[0].bytes_per_px == 1 || rec[0].bytes_per_px == 2);
-  R1_REQUIRE((rec[0].bytes_per_px == 1) == (p.bit_depth == 8));
+  R1_REQUIRE(r1_px_ok(rec[0]));
+  R1_REQUIRE(r1_px_fits_depth(rec[0].bytes_per_px, p.bit_depth));
   R1_REQUIRE(np == 1 || (p.xdec == 1 && p.ydec == 1) || (p.xdec == 1 && p.ydec == 0) ||
              (p.xdec == 0 && p.ydec == 0));
   // the block grid is the frame's: 2 * ceil(crop / 8) units of 4 pixels (FrameBlocks)
@@ -477,18 +477,17 @@ int search_launch(const SearchArgs &a, hipStream_t st) {
   const int np = a.p.planes;
   const int xd = np == 1 ? 0 : a.p.xdec, yd = np == 1 ? 0 : a.p.ydec;
   const dim3 grid_y(a.n_sbx * 2, a.n_sby * 4), grid_c((a.n_sbx * 64 >> xd) / 32, (a.n_sby * 64 >> yd) / 16, 2);
-#define R1_CS_LAUNCH(B)                                                                                   \
-  do {                                                                                                    \
-    hipLaunchKernelGGL((k_cdef_search_pk<B, 0, 0, true, MODE>), grid_y, dim3(256), 0, st, a);             \
-    if (np == 3) {                                                                                        \
-      if (xd == 1 && yd == 1) hipLaunchKernelGGL((k_cdef_search_pk<B, 1, 1, false, MODE>), grid_c, dim3(256), 0, st, a); \
-      else if (xd == 1) hipLaunchKernelGGL((k_cdef_search_pk<B, 1, 0, false, MODE>), grid_c, dim3(256), 0, st, a);       \
-      else hipLaunchKernelGGL((k_cdef_search_pk<B, 0, 0, false, MODE>), grid_c, dim3(256), 0, st, a);     \
-    }                                                                                                     \
-  } while (0)
-  if (a.rec[0].bytes_per_px == 1) R1_CS_LAUNCH(1);
-  else R1_CS_LAUNCH(2);
-#undef R1_CS_LAUNCH
+  r1_by_bpp(a.rec[0].bytes_per_px, [&](auto B) {
+    hipLaunchKernelGGL((k_cdef_search_pk<B.value, 0, 0, true, MODE>), grid_y, dim3(256), 0, st, a);
+    if (np != 3) return;
+    // the chroma layouts search_args admits: 4:2:0, 4:2:2, 4:4:4 -- there is no <B, 0, 1>
+    r1_by_bool(xd == 1, [&](auto X) {
+      r1_by_bool(xd == 1 && yd == 1, [&](auto Y) {
+        if constexpr (X.value || !Y.value)
+          hipLaunchKernelGGL((k_cdef_search_pk<B.value, X.value, Y.value, false, MODE>), grid_c, dim3(256), 0, st, a);
+      });
+    });
+  });
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }
@@ -584,7 +583,7 @@ extern "C" int r1_cdef_lrf_trial_batch(r1_ctx *ctx, const R1Plane *rec, const R1
   R1_REQUIRE(n_tot == 0 || (units && cdef_cur));
   if (n_tot)
     for (int k = 0; k < np; k++) {
-      R1_REQUIRE(cdef_cur[k].data && cdef_cur[k].bytes_per_px == bpp);
+      R1_REQUIRE(cdef_cur[k].data && r1_same_px(rec[0], cdef_cur[k]));
       R1_REQUIRE(cdef_cur[k].width >= rec[k].width && cdef_cur[k].height >= rec[k].height);
     }
   const ScratchMap m = scratch_map(mi_cols, mi_rows, np == 1 ? 0 : a.p.xdec, np == 1 ? 0 : a.p.ydec, bpp, a.p.n_idx, np);
@@ -643,7 +642,7 @@ extern "C" int r1_cdef_apply_area(r1_ctx *ctx, const R1Plane *rec, const R1Plane
   int rc = search_args(ctx, rec, rec, skip_mi, mi_stride, mi_cols, mi_rows, nullptr, 0, params, a);
   if (rc != R1_OK) return rc;
   for (int k = 0; k < a.p.planes; k++) {
-    R1_REQUIRE(out[k].data && out[k].data != rec[k].data && out[k].bytes_per_px == rec[0].bytes_per_px);
+    R1_REQUIRE(out[k].data && out[k].data != rec[k].data && r1_same_px(rec[0], out[k]));
     R1_REQUIRE(out[k].width >= rec[k].width && out[k].height >= rec[k].height);
     a.out[k] = out[k];
   }

@@ -337,7 +337,7 @@ extern "C" int r1_coeff_rate_batch(r1_ctx *ctx, const void *qcoeffs, int coeff_b
                                    uint32_t *rate_out, uint8_t *cul_level_out, void *stream) {
   R1_REQUIRE(ctx);
   R1_REQUIRE(coeff_bytes == 2 || coeff_bytes == 4);
-  R1_REQUIRE(tx_size >= 0 && tx_size < 19);
+  R1_REQUIRE(r1_tx_size_ok(tx_size));
   R1_REQUIRE(plane >= 0 && plane <= 2);
   R1_REQUIRE(n_cdfs >= 1 && n_cdfs <= 256);
   is_inter = is_inter != 0;

@@ -309,7 +309,7 @@ extern "C" int r1_comm_exchange_halos(r1_comm *c, const R1Plane *plane, const R1
   if (n == 0) return R1_OK;
   hipStream_t st = (hipStream_t)stream;
   const int bpp = plane->bytes_per_px;
-  R1_REQUIRE(bpp == 1 || bpp == 2);
+  R1_REQUIRE(r1_px_ok(bpp));
   std::vector<size_t> off(n + 1, 0);
   for (int i = 0; i < n; i++) {
     const R1HaloXfer &x = xfers[i];
@@ -371,7 +371,7 @@ extern "C" int r1_comm_allgather_tiles(r1_comm *c, const R1Plane *plane, const i
   R1_REQUIRE(c && plane && plane->data && rects4);
   hipStream_t st = (hipStream_t)stream;
   const int bpp = plane->bytes_per_px;
-  R1_REQUIRE(bpp == 1 || bpp == 2);
+  R1_REQUIRE(r1_px_ok(bpp));
   size_t slot = 0;
   for (int r = 0; r < c->world; r++) {
     const int32_t *q = rects4 + 4 * r;
@@ -589,7 +589,7 @@ extern "C" int r1_push_rects(r1_ctx *ctx, const R1Plane *plane, void *const *pee
                              const R1PushRect *rects, int n, void *stream) {
   R1_REQUIRE(ctx && plane && plane->data && (n == 0 || (rects && peer_data)) && n >= 0);
   const int bpp = plane->bytes_per_px;
-  R1_REQUIRE(bpp == 1 || bpp == 2);
+  R1_REQUIRE(r1_px_ok(bpp));
   const size_t pitch = (size_t)plane->stride * bpp;
   R1_REQUIRE(pitch < (1ull << 32));
   for (int i = 0; i < n; i++) {

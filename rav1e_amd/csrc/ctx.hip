@@ -17,8 +17,17 @@ void r1_set_error(const char *fmt, ...) {
 }
 
 extern "C" const char *r1_last_error(void) { return g_err; }
-// 3: round-3 additions (r1_me_status, r1_comm_library, the predict:: dispatch symbols), R1_ENOMEM /
-// R1_ETIMEDOUT got values of their own, R1MeParams.reserved became launch_mode (round 2)
+// 3: r1_me_status, r1_comm_library, the predict:: dispatch symbols; R1_ENOMEM / R1_ETIMEDOUT got values of their
+//    own, R1MeParams.reserved became launch_mode
+// 4: r1_estimate_tile_motion_batch refuses with R1_ETIMEDOUT until a flagged persistent launch is acknowledged
+//    through r1_me_status; r1_cdef_filter_frame_plane checks luma->bit_depth against params->bit_depth, its _dirs
+//    variant wants 8-aligned tile_w / tile_h; skip_mi bytes are bools in the CDEF filter and the strength search
+// 5: + r1_rdo_txsearch_batch, r1_tx_type_mask (additions only)
+// 6: R1SgrSolveUnit.reserved[0] became `edges` (R1_SGR_EDGE_*); the restoration entry points refuse planes of
+//    4 GiB and more
+// 7: + r1_cdef_lrf_trial_batch, r1_cdef_lrf_trial_scratch_bytes, r1_cdef_apply_area, R1TrialUnit,
+//    r1_comm_plane_pool_open / _close (additions only)
+// (the history in full: include/rav1e_amd.h, above r1_abi_version)
 extern "C" int r1_abi_version(void) { return 7; }
 
 extern "C" int r1_ctx_create(int device, r1_ctx **out) {
@@ -74,8 +83,8 @@ extern "C" void r1_ctx_destroy(r1_ctx *c) {
     if (c->me_jobs[k]) (void)hipFree(c->me_jobs[k]);
     if (c->me_jobs_host[k]) (void)hipHostFree(c->me_jobs_host[k]);
   }
-  r1_cdef_scratch_free(c);
-  r1_intra_scratch_free(c);
+  c->cdef_ring.destroy();
+  c->intra_ring.destroy();
   r1_scan_tables_destroy(c);
   (void)hipStreamDestroy(c->own_stream);
   delete c;
@@ -207,12 +216,10 @@ extern "C" void rav1e_put_8tap_hbd_hip(uint16_t *dst, ptrdiff_t ds,
 extern "C" int rav1e_fwd_txfm_hip(const int16_t *input, void *output,
                                   size_t stride, int tx_size, int tx_type, int bd,
                                   int coeff_bytes) {
-  static const uint8_t wl[19] = {2, 3, 4, 5, 6, 2, 3, 3, 4, 4, 5, 5, 6, 2, 4, 3, 5, 4, 6};
-  static const uint8_t hl[19] = {2, 3, 4, 5, 6, 3, 2, 4, 3, 5, 4, 6, 5, 4, 2, 5, 3, 6, 4};
-  if (tx_size < 0 || tx_size >= 19) return R1_EINVAL;
+  if (!r1_tx_size_ok(tx_size)) return R1_EINVAL;
   std::lock_guard<std::mutex> lk(g_mu);
   r1_ctx *c = shim_ctx();
-  const int w = 1 << wl[tx_size], h = 1 << hl[tx_size];
+  const int w = 1 << r1tx::kTxWLog2[tx_size], h = 1 << r1tx::kTxHLog2[tx_size];
   const size_t ib = align256((size_t)w * h * 2), ob = (size_t)w * h * coeff_bytes;
   uint8_t *d = (uint8_t *)stage(c, ib + ob);
   hipStream_t st = c->own_stream;
@@ -235,12 +242,10 @@ extern "C" int rav1e_fwd_txfm_hip(const int16_t *input, void *output,
 namespace {
 int inv_shim(void *dst, ptrdiff_t ds, const void *coeff, int tx_size, int tx_type, int bpp,
              int bd) {
-  static const uint8_t wl[19] = {2, 3, 4, 5, 6, 2, 3, 3, 4, 4, 5, 5, 6, 2, 4, 3, 5, 4, 6};
-  static const uint8_t hl[19] = {2, 3, 4, 5, 6, 3, 2, 4, 3, 5, 4, 6, 5, 4, 2, 5, 3, 6, 4};
-  if (tx_size < 0 || tx_size >= 19) return R1_EINVAL;
+  if (!r1_tx_size_ok(tx_size)) return R1_EINVAL;
   std::lock_guard<std::mutex> lk(g_mu);
   r1_ctx *c = shim_ctx();
-  const int w = 1 << wl[tx_size], h = 1 << hl[tx_size];
+  const int w = 1 << r1tx::kTxWLog2[tx_size], h = 1 << r1tx::kTxHLog2[tx_size];
   const int area = (w < 32 ? w : 32) * (h < 32 ? h : 32);
   const size_t cbytes = (size_t)area * (bpp == 1 ? 2 : 4), cb = align256(cbytes);
   const size_t prow = (size_t)w * bpp, pb = align256(prow * h);
@@ -364,10 +369,8 @@ extern "C" int rav1e_ipred_hip(void *dst, ptrdiff_t dst_stride, const void *topl
                                int left_len, int above_len, int avail_w, int avail_h,
                                const int16_t *ac, int bit_depth) {
   int tx_size = -1;
-  static const uint8_t wl[19] = {2, 3, 4, 5, 6, 2, 3, 3, 4, 4, 5, 5, 6, 2, 4, 3, 5, 4, 6};
-  static const uint8_t hl[19] = {2, 3, 4, 5, 6, 3, 2, 4, 3, 5, 4, 6, 5, 4, 2, 5, 3, 6, 4};
   for (int t = 0; t < 19; t++)
-    if ((1 << wl[t]) == width && (1 << hl[t]) == height) tx_size = t;
+    if ((1 << r1tx::kTxWLog2[t]) == width && (1 << r1tx::kTxHLog2[t]) == height) tx_size = t;
   if (tx_size < 0 || left_len < 0 || left_len > 128 || above_len < 0 || above_len > 128)
     return R1_EINVAL;
   const int bpp = bit_depth == 8 ? 1 : 2;
@@ -509,12 +512,10 @@ void avg_shim(void *dst, ptrdiff_t ds, const int16_t *t1, const int16_t *t2, int
 // DequantizeFn (src/asm/x86/quantize.rs:22-31): i16 coefficients, coded area of tx_size
 void dequant_shim(int qindex, const int16_t *coeffs, int16_t *rcoeffs, int tx_size, int bit_depth, int dc_delta_q,
                   int ac_delta_q) {
-  static const uint8_t wl[19] = {2, 3, 4, 5, 6, 2, 3, 3, 4, 4, 5, 5, 6, 2, 4, 3, 5, 4, 6};
-  static const uint8_t hl[19] = {2, 3, 4, 5, 6, 3, 2, 4, 3, 5, 4, 6, 5, 4, 2, 5, 3, 6, 4};
-  if (tx_size < 0 || tx_size >= 19) abort();
+  if (!r1_tx_size_ok(tx_size)) abort();
   std::lock_guard<std::mutex> lk(g_mu);
   r1_ctx *c = shim_ctx();
-  const int w = 1 << wl[tx_size], h = 1 << hl[tx_size];
+  const int w = 1 << r1tx::kTxWLog2[tx_size], h = 1 << r1tx::kTxHLog2[tx_size];
   const int area = (w < 32 ? w : 32) * (h < 32 ? h : 32);
   const size_t cb = align256((size_t)area * 2);
   uint8_t *d = (uint8_t *)stage(c, 2 * cb);

@@ -369,10 +369,10 @@ __global__ __launch_bounds__(256) void k_deblock_sse_frame(DeblockSsePlanes s) {
 int make_geom(Geom &g, const R1Plane *p, int pli, int xdec, int ydec, const R1DeblockBlock *blocks,
               int blocks_stride, int blocks_cols, int blocks_rows, int crop_w, int crop_h) {
   R1_REQUIRE(p && blocks);
-  R1_REQUIRE(pli >= 0 && pli <= 2 && xdec >= 0 && xdec <= 1 && ydec >= 0 && ydec <= 1);
+  R1_REQUIRE(pli >= 0 && pli <= 2 && r1_dec_ok(xdec, ydec));
   R1_REQUIRE(pli != 0 || (xdec == 0 && ydec == 0));
-  R1_REQUIRE(p->bytes_per_px == 1 || p->bytes_per_px == 2);
-  R1_REQUIRE((p->bytes_per_px == 1) == (p->bit_depth == 8));
+  R1_REQUIRE(r1_px_ok(*p));
+  R1_REQUIRE(r1_px_fits_depth(*p));
   R1_REQUIRE(blocks_cols > 0 && blocks_rows > 0 && blocks_stride >= blocks_cols && crop_w > 0 &&
              crop_h > 0);
   const int mc = (crop_w + 3) >> 2, mr = (crop_h + 3) >> 2;
@@ -414,10 +414,9 @@ extern "C" int r1_deblock_plane(r1_ctx *ctx, const R1DeblockState *state, const 
     const long long n = pass_threads(g, vertical);
     if (n <= 0) continue;
     const unsigned grid = (unsigned)((n + 255) / 256);
-    if (plane->bytes_per_px == 1)
-      hipLaunchKernelGGL(k_deblock<1>, dim3(grid), dim3(256), 0, st, *plane, g, *state, (int)vertical);
-    else
-      hipLaunchKernelGGL(k_deblock<2>, dim3(grid), dim3(256), 0, st, *plane, g, *state, (int)vertical);
+    r1_by_bpp(plane->bytes_per_px, [&](auto B) {
+      hipLaunchKernelGGL((k_deblock<B.value>), dim3(grid), dim3(256), 0, st, *plane, g, *state, (int)vertical);
+    });
   }
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
@@ -432,7 +431,7 @@ extern "C" int r1_deblock_sse_plane(r1_ctx *ctx, const R1Plane *rec, const R1Pla
   const int rc = make_geom(g, rec, pli, xdec, ydec, blocks, blocks_stride, blocks_cols, blocks_rows,
                            crop_w, crop_h);
   if (rc != R1_OK) return rc;
-  R1_REQUIRE(src->bytes_per_px == rec->bytes_per_px && src->bit_depth == rec->bit_depth);
+  R1_REQUIRE(r1_same_px(*src, *rec) && r1_same_depth(*src, *rec));
   hipStream_t st = (hipStream_t)stream;
   for (int pass = 0; pass < 2; pass++) {
     const bool vertical = pass == 0;
@@ -441,12 +440,10 @@ extern "C" int r1_deblock_sse_plane(r1_ctx *ctx, const R1Plane *rec, const R1Pla
     unsigned grid = (unsigned)((n + 255) / 256);
     grid = grid > 1024 ? 1024 : grid;   // 4 workgroups per CU
     long long *out = (long long *)(vertical ? v_tally : h_tally);
-    if (rec->bytes_per_px == 1)
-      hipLaunchKernelGGL(k_deblock_sse<1>, dim3(grid), dim3(256), 0, st, *rec, *src, g, (int)vertical, n,
+    r1_by_bpp(rec->bytes_per_px, [&](auto B) {
+      hipLaunchKernelGGL((k_deblock_sse<B.value>), dim3(grid), dim3(256), 0, st, *rec, *src, g, (int)vertical, n,
                          out);
-    else
-      hipLaunchKernelGGL(k_deblock_sse<2>, dim3(grid), dim3(256), 0, st, *rec, *src, g, (int)vertical, n,
-                         out);
+    });
   }
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
@@ -463,7 +460,7 @@ extern "C" int r1_deblock_frame(r1_ctx *ctx, const R1DeblockState *state, const 
     const int rc = make_geom(s.g[pli], planes + pli, pli, pli ? xdec : 0, pli ? ydec : 0, blocks,
                              blocks_stride, blocks_cols, blocks_rows, crop_w, crop_h);
     if (rc != R1_OK) return rc;
-    R1_REQUIRE(planes[pli].bytes_per_px == planes[0].bytes_per_px);
+    R1_REQUIRE(r1_same_px(planes[pli], planes[0]));
     s.p[pli] = planes[pli];
     // deblock_plane's early outs (deblock.rs:1302-1319)
     const bool off = pli == 0 ? (state->levels[0] == 0 && state->levels[1] == 0)
@@ -481,10 +478,9 @@ extern "C" int r1_deblock_frame(r1_ctx *ctx, const R1DeblockState *state, const 
     }
     if (n <= 0) continue;
     const dim3 grid((unsigned)((n + 255) / 256), 3);
-    if (planes[0].bytes_per_px == 1)
-      hipLaunchKernelGGL(k_deblock_frame<1>, grid, dim3(256), 0, st, s, *state, (int)vertical, active);
-    else
-      hipLaunchKernelGGL(k_deblock_frame<2>, grid, dim3(256), 0, st, s, *state, (int)vertical, active);
+    r1_by_bpp(planes[0].bytes_per_px, [&](auto B) {
+      hipLaunchKernelGGL((k_deblock_frame<B.value>), grid, dim3(256), 0, st, s, *state, (int)vertical, active);
+    });
   }
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
@@ -501,8 +497,7 @@ extern "C" int r1_deblock_sse_frame(r1_ctx *ctx, const R1Plane *rec, const R1Pla
     const int rc = make_geom(s.g[pli], rec + pli, pli, pli ? xdec : 0, pli ? ydec : 0, blocks,
                              blocks_stride, blocks_cols, blocks_rows, crop_w, crop_h);
     if (rc != R1_OK) return rc;
-    R1_REQUIRE(src[pli].bytes_per_px == rec[pli].bytes_per_px && src[pli].bit_depth == rec[pli].bit_depth &&
-               rec[pli].bytes_per_px == rec[0].bytes_per_px);
+    R1_REQUIRE(r1_same_px(rec[pli], src[pli], rec[0]) && r1_same_depth(src[pli], rec[pli]));
     s.rec[pli] = rec[pli];
     s.src[pli] = src[pli];
     for (int dir = 0; dir < 2; dir++) {
@@ -515,10 +510,9 @@ extern "C" int r1_deblock_sse_frame(r1_ctx *ctx, const R1Plane *rec, const R1Pla
   unsigned gx = (unsigned)((nmax + 255) / 256);
   gx = gx > 512 ? 512 : gx;   // 6 x 512 workgroups, grid-stride inside
   hipStream_t st = (hipStream_t)stream;
-  if (rec[0].bytes_per_px == 1)
-    hipLaunchKernelGGL(k_deblock_sse_frame<1>, dim3(gx, 6), dim3(256), 0, st, s);
-  else
-    hipLaunchKernelGGL(k_deblock_sse_frame<2>, dim3(gx, 6), dim3(256), 0, st, s);
+  r1_by_bpp(rec[0].bytes_per_px, [&](auto B) {
+    hipLaunchKernelGGL((k_deblock_sse_frame<B.value>), dim3(gx, 6), dim3(256), 0, st, s);
+  });
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }

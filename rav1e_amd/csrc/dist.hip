@@ -61,22 +61,6 @@ __global__ __launch_bounds__(256) void k_dist(R1Plane org, R1Plane ref,
   }
 }
 
-template <int BPP, int TS>
-int launch_dist(int kind, const R1Plane &org, const R1Plane &ref, int w, int h,
-                const R1DistCand *cands, int n, uint32_t *out, hipStream_t st) {
-  const int wt_log2 = r1_ilog2(w / TS), tpc_log2 = wt_log2 + r1_ilog2(h / TS);
-  const long long tiles = (long long)n << tpc_log2;
-  const unsigned grid = ((unsigned)((tiles + 255) / 256) + 7u) & ~7u;   // whole rounds over the 8 XCDs
-  if (kind == R1_DIST_SAD)
-    hipLaunchKernelGGL((k_dist<BPP, TS, false>), dim3(grid), dim3(256), 0, st,
-                       org, ref, wt_log2, tpc_log2, cands, n, out);
-  else
-    hipLaunchKernelGGL((k_dist<BPP, TS, true>), dim3(grid), dim3(256), 0, st,
-                       org, ref, wt_log2, tpc_log2, cands, n, out);
-  R1_HIP_CHECK(hipGetLastError());
-  return R1_OK;
-}
-
 }  // namespace
 
 extern "C" int r1_dist_batch(r1_ctx *ctx, int kind, const R1Plane *org,
@@ -85,18 +69,26 @@ extern "C" int r1_dist_batch(r1_ctx *ctx, int kind, const R1Plane *org,
                              void *stream) {
   R1_REQUIRE(ctx && org && ref);
   R1_REQUIRE(kind == R1_DIST_SAD || kind == R1_DIST_SATD);
-  R1_REQUIRE(org->bytes_per_px == ref->bytes_per_px);
-  R1_REQUIRE(org->bytes_per_px == 1 || org->bytes_per_px == 2);
+  R1_REQUIRE(r1_same_px(*org, *ref));
+  R1_REQUIRE(r1_px_ok(*org));
   R1_REQUIRE(r1_is_pow2(w) && r1_is_pow2(h) && w >= 4 && h >= 4 && w <= 128 &&
              h <= 128);
   if (n <= 0) return R1_OK;
   R1_REQUIRE(cands && out);
   hipStream_t st = (hipStream_t)stream;
-  const bool small = (w < h ? w : h) == 4;
   // SAD has no tile-size rule; use the widest tile the block allows.
-  if (org->bytes_per_px == 1)
-    return small ? launch_dist<1, 4>(kind, *org, *ref, w, h, cands, n, out, st)
-                 : launch_dist<1, 8>(kind, *org, *ref, w, h, cands, n, out, st);
-  return small ? launch_dist<2, 4>(kind, *org, *ref, w, h, cands, n, out, st)
-               : launch_dist<2, 8>(kind, *org, *ref, w, h, cands, n, out, st);
+  const int ts = (w < h ? w : h) == 4 ? 4 : 8;
+  const int wt_log2 = r1_ilog2(w / ts), tpc_log2 = wt_log2 + r1_ilog2(h / ts);
+  const long long tiles = (long long)n << tpc_log2;
+  const unsigned grid = ((unsigned)((tiles + 255) / 256) + 7u) & ~7u;   // whole rounds over the 8 XCDs
+  r1_by_bpp(org->bytes_per_px, [&](auto B) {
+    r1_by_value<8, 4>(ts, [&](auto TS) {
+      r1_by_value<R1_DIST_SATD, R1_DIST_SAD>(kind, [&](auto KIND) {
+        hipLaunchKernelGGL((k_dist<B.value, TS.value, KIND.value == R1_DIST_SATD>), dim3(grid), dim3(256), 0, st, *org,
+                           *ref, wt_log2, tpc_log2, cands, n, out);
+      });
+    });
+  });
+  R1_HIP_CHECK(hipGetLastError());
+  return R1_OK;
 }

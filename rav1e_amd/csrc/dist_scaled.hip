@@ -95,21 +95,18 @@ int r1_internal_wsse_raw(const R1Plane *a, const R1Plane *b, int w, int h, const
   const int tpc_log2 = r1_ilog2(tiles);
   const unsigned grid = (unsigned)(((1ll << tpc_log2) + 255) / 256);
   // xdec = ydec = 1 makes the scale lookup (x << 1) >> 3 = x >> 2: per 4x4 cell of the block at (0, 0)
-  if (a->bytes_per_px == 1)
-    hipLaunchKernelGGL((k_dist_scaled<1, 2, true>), dim3(grid), dim3(256), 0, st, *a, *b, w, h, tw, tiles,
+  r1_by_bpp(a->bytes_per_px, [&](auto B) {
+    hipLaunchKernelGGL((k_dist_scaled<B.value, 2, true>), dim3(grid), dim3(256), 0, st, *a, *b, w, h, tw, tiles,
                        tpc_log2, cand, 1, scale, scale_stride, 1, 1, (unsigned long long *)out);
-  else
-    hipLaunchKernelGGL((k_dist_scaled<2, 2, true>), dim3(grid), dim3(256), 0, st, *a, *b, w, h, tw, tiles,
-                       tpc_log2, cand, 1, scale, scale_stride, 1, 1, (unsigned long long *)out);
+  });
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }
 int r1_internal_cdef_dist_raw(const R1Plane *a, const R1Plane *b, int w, int h, const R1DistCand *cand,
                               uint32_t *out3, hipStream_t st) {
-  if (a->bytes_per_px == 1)
-    hipLaunchKernelGGL((k_cdef_dist_raw<1>), dim3(1), dim3(64), 0, st, *a, *b, w, h, cand, 1, out3);
-  else
-    hipLaunchKernelGGL((k_cdef_dist_raw<2>), dim3(1), dim3(64), 0, st, *a, *b, w, h, cand, 1, out3);
+  r1_by_bpp(a->bytes_per_px, [&](auto B) {
+    hipLaunchKernelGGL((k_cdef_dist_raw<B.value>), dim3(1), dim3(64), 0, st, *a, *b, w, h, cand, 1, out3);
+  });
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }
@@ -121,8 +118,8 @@ extern "C" int r1_dist_scaled_batch(r1_ctx *ctx, int kind, const R1Plane *org,
                                     void *stream) {
   R1_REQUIRE(ctx && org && ref);
   R1_REQUIRE(kind == R1_DIST_WSSE || kind == R1_DIST_CDEF);
-  R1_REQUIRE(org->bytes_per_px == ref->bytes_per_px);
-  R1_REQUIRE(org->bytes_per_px == 1 || org->bytes_per_px == 2);
+  R1_REQUIRE(r1_same_px(*org, *ref));
+  R1_REQUIRE(r1_px_ok(*org));
   R1_REQUIRE(w >= 1 && h >= 1 && w <= 128 && h <= 128);
   if (kind == R1_DIST_WSSE) {
     // get_weighted_sse walks whole 4x4 windows (vert_windows(4).step_by(4), dist.rs:248-262): what
@@ -141,7 +138,7 @@ extern "C" int r1_dist_scaled_batch(r1_ctx *ctx, int kind, const R1Plane *org,
   }
   // R1_DIST_CDEF: any w, h >= 1 -- cdef_dist_wxh tiles the visible block in 8x8 kernels and hands
   // cdef_dist_kernel whatever is left at the right / bottom (rdo.rs:152-165, AREA_DIVISORS[w * h - 1])
-  R1_REQUIRE(xdec >= 0 && xdec <= 1 && ydec >= 0 && ydec <= 1);
+  R1_REQUIRE(r1_dec_ok(xdec, ydec));
   // cdef_dist is only defined on non-subsampled planes (rdo.rs:146-149)
   R1_REQUIRE(kind != R1_DIST_CDEF || (xdec == 0 && ydec == 0));
   R1_REQUIRE(!scales || scale_stride > 0);
@@ -152,16 +149,13 @@ extern "C" int r1_dist_scaled_batch(r1_ctx *ctx, int kind, const R1Plane *org,
   const long long lanes = (long long)n << tpc_log2;
   const unsigned grid = (unsigned)((lanes + 255) / 256);
   hipStream_t st = (hipStream_t)stream;
-#define R1_DS_LAUNCH(BPP, KIND)                                                         \
-  hipLaunchKernelGGL((k_dist_scaled<BPP, KIND>), dim3(grid), dim3(256), 0, st, *org,   \
-                     *ref, w, h, tw, tiles, tpc_log2, cands, n, scales, scale_stride,  \
-                     xdec, ydec, (unsigned long long *)out)
-  if (org->bytes_per_px == 1) {
-    if (kind == R1_DIST_WSSE) R1_DS_LAUNCH(1, 2); else R1_DS_LAUNCH(1, 3);
-  } else {
-    if (kind == R1_DIST_WSSE) R1_DS_LAUNCH(2, 2); else R1_DS_LAUNCH(2, 3);
-  }
-#undef R1_DS_LAUNCH
+  static_assert(R1_DIST_WSSE == 2 && R1_DIST_CDEF == 3, "k_dist_scaled takes the kind as 2 / 3");
+  r1_by_bpp(org->bytes_per_px, [&](auto B) {
+    r1_by_value<3, 2>(kind, [&](auto KIND) {
+      hipLaunchKernelGGL((k_dist_scaled<B.value, KIND.value>), dim3(grid), dim3(256), 0, st, *org, *ref, w, h, tw, tiles,
+                         tpc_log2, cands, n, scales, scale_stride, xdec, ydec, (unsigned long long *)out);
+    });
+  });
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }

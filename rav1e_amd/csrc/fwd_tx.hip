@@ -98,7 +98,7 @@ extern "C" int r1_fwd_txfm_batch(r1_ctx *ctx, const int16_t *residual,
                                  int bit_depth, int coeff_bytes, void *stream) {
   R1_REQUIRE(ctx);
   R1_REQUIRE(r1tx::valid_av1_transform(tx_size, tx_type));
-  R1_REQUIRE(bit_depth == 8 || bit_depth == 10 || bit_depth == 12);
+  R1_REQUIRE(r1_depth_ok(bit_depth));
   R1_REQUIRE(coeff_bytes == 2 || coeff_bytes == 4);
   if (n <= 0) return R1_OK;
   R1_REQUIRE(residual && coeffs);

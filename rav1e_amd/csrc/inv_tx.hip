@@ -113,22 +113,20 @@ extern "C" int r1_inv_txfm_add_batch(r1_ctx *ctx, const void *coeffs, int coeff_
                                      void *stream) {
   R1_REQUIRE(ctx);
   R1_REQUIRE(r1tx::valid_av1_transform(tx_size, tx_type));
-  R1_REQUIRE(bit_depth == 8 || bit_depth == 10 || bit_depth == 12);
-  R1_REQUIRE(bytes_per_px == 1 || bytes_per_px == 2);
-  R1_REQUIRE((bytes_per_px == 1) == (bit_depth == 8));
+  R1_REQUIRE(r1_depth_ok(bit_depth));
+  R1_REQUIRE(r1_px_ok(bytes_per_px));
+  R1_REQUIRE(r1_px_fits_depth(bytes_per_px, bit_depth));
   const int w = 1 << r1tx::kTxWLog2[tx_size], h = 1 << r1tx::kTxHLog2[tx_size];
   R1_REQUIRE(coeff_stride >= (w < 32 ? w : 32) * (h < 32 ? h : 32));
   if (n <= 0) return R1_OK;
   R1_REQUIRE(coeffs && pred && rec);
   hipStream_t st = (hipStream_t)stream;
   const int sh = r1itx::kInvShift[tx_size];
-#define R1_ITX_CASE(ID, WL, HL)                                                         \
-  case ID:                                                                              \
-    return bytes_per_px == 1                                                            \
-               ? launch<1, WL, HL>(coeffs, coeff_stride, pred, rec, n, tx_type,        \
-                                   bit_depth, sh, st)                                   \
-               : launch<2, WL, HL>(coeffs, coeff_stride, pred, rec, n, tx_type,        \
-                                   bit_depth, sh, st);
+#define R1_ITX_CASE(ID, WL, HL)                                                                            \
+  case ID:                                                                                                 \
+    return r1_by_bpp(bytes_per_px, [&](auto B) {                                                           \
+      return launch<B.value, WL, HL>(coeffs, coeff_stride, pred, rec, n, tx_type, bit_depth, sh, st);      \
+    });
   switch (tx_size) { R1_TX_SIZES(R1_ITX_CASE) }
 #undef R1_ITX_CASE
   return R1_EINVAL;

@@ -159,15 +159,14 @@ __global__ __launch_bounds__(256) void k_activity(R1Plane p, int wb, int hb,
 extern "C" int r1_estimate_intra_costs(r1_ctx *ctx, const R1Plane *luma, uint32_t *costs,
                                        void *stream) {
   R1_REQUIRE(ctx && luma && costs);
-  R1_REQUIRE(luma->bytes_per_px == 1 || luma->bytes_per_px == 2);
+  R1_REQUIRE(r1_px_ok(*luma));
   const int wb = luma->width / 8, hb = luma->height / 8;
   if (wb * hb == 0) return R1_OK;
   const unsigned grid = (unsigned)((wb * hb + 63) / 64);
   hipStream_t st = (hipStream_t)stream;
-  if (luma->bytes_per_px == 1)
-    hipLaunchKernelGGL((k_intra_costs<1>), dim3(grid), dim3(64), 0, st, *luma, wb, hb, costs);
-  else
-    hipLaunchKernelGGL((k_intra_costs<2>), dim3(grid), dim3(64), 0, st, *luma, wb, hb, costs);
+  r1_by_bpp(luma->bytes_per_px, [&](auto B) {
+    hipLaunchKernelGGL((k_intra_costs<B.value>), dim3(grid), dim3(64), 0, st, *luma, wb, hb, costs);
+  });
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }
@@ -175,16 +174,15 @@ extern "C" int r1_estimate_intra_costs(r1_ctx *ctx, const R1Plane *luma, uint32_
 extern "C" int r1_estimate_inter_costs(r1_ctx *ctx, const R1Plane *org, const R1Plane *ref,
                                        const int16_t *mvs, uint32_t *costs, void *stream) {
   R1_REQUIRE(ctx && org && ref && mvs && costs);
-  R1_REQUIRE(org->bytes_per_px == ref->bytes_per_px);
-  R1_REQUIRE(org->bytes_per_px == 1 || org->bytes_per_px == 2);
+  R1_REQUIRE(r1_same_px(*org, *ref));
+  R1_REQUIRE(r1_px_ok(*org));
   const int wb = org->width / 8, hb = org->height / 8;
   if (wb * hb == 0) return R1_OK;
   const unsigned grid = (unsigned)((wb * hb + 63) / 64);
   hipStream_t st = (hipStream_t)stream;
-  if (org->bytes_per_px == 1)
-    hipLaunchKernelGGL((k_inter_costs<1>), dim3(grid), dim3(64), 0, st, *org, *ref, wb, hb, mvs, costs);
-  else
-    hipLaunchKernelGGL((k_inter_costs<2>), dim3(grid), dim3(64), 0, st, *org, *ref, wb, hb, mvs, costs);
+  r1_by_bpp(org->bytes_per_px, [&](auto B) {
+    hipLaunchKernelGGL((k_inter_costs<B.value>), dim3(grid), dim3(64), 0, st, *org, *ref, wb, hb, mvs, costs);
+  });
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }
@@ -192,19 +190,17 @@ extern "C" int r1_estimate_inter_costs(r1_ctx *ctx, const R1Plane *org, const R1
 extern "C" int r1_importance_block_difference(r1_ctx *ctx, const R1Plane *org, const R1Plane *ref,
                                               uint64_t *sum_out, void *stream) {
   R1_REQUIRE(ctx && org && ref && sum_out);
-  R1_REQUIRE(org->bytes_per_px == ref->bytes_per_px);
-  R1_REQUIRE(org->bytes_per_px == 1 || org->bytes_per_px == 2);
+  R1_REQUIRE(r1_same_px(*org, *ref));
+  R1_REQUIRE(r1_px_ok(*org));
   const int wb = org->width / 8, hb = org->height / 8;
   hipStream_t st = (hipStream_t)stream;
   R1_HIP_CHECK(hipMemsetAsync(sum_out, 0, sizeof(uint64_t), st));
   if (wb * hb == 0) return R1_OK;
   const unsigned grid = (unsigned)((wb * hb + 255) / 256);
-  if (org->bytes_per_px == 1)
-    hipLaunchKernelGGL((k_imp_diff<1>), dim3(grid), dim3(256), 0, st, *org, *ref, wb, hb,
+  r1_by_bpp(org->bytes_per_px, [&](auto B) {
+    hipLaunchKernelGGL((k_imp_diff<B.value>), dim3(grid), dim3(256), 0, st, *org, *ref, wb, hb,
                        (unsigned long long *)sum_out);
-  else
-    hipLaunchKernelGGL((k_imp_diff<2>), dim3(grid), dim3(256), 0, st, *org, *ref, wb, hb,
-                       (unsigned long long *)sum_out);
+  });
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }
@@ -212,16 +208,15 @@ extern "C" int r1_importance_block_difference(r1_ctx *ctx, const R1Plane *org, c
 extern "C" int r1_activity_scales(r1_ctx *ctx, const R1Plane *luma, uint32_t *variances,
                                   uint32_t *scales, void *stream) {
   R1_REQUIRE(ctx && luma && (variances || scales));
-  R1_REQUIRE(luma->bytes_per_px == 1 || luma->bytes_per_px == 2);
-  R1_REQUIRE((luma->bytes_per_px == 1) == (luma->bit_depth == 8));
+  R1_REQUIRE(r1_px_ok(*luma));
+  R1_REQUIRE(r1_px_fits_depth(*luma));
   const int wb = (luma->width + 7) / 8, hb = (luma->height + 7) / 8;
   if (wb * hb == 0) return R1_OK;
   const unsigned grid = (unsigned)((wb * hb + 255) / 256);
   hipStream_t st = (hipStream_t)stream;
-  if (luma->bytes_per_px == 1)
-    hipLaunchKernelGGL((k_activity<1>), dim3(grid), dim3(256), 0, st, *luma, wb, hb, variances, scales);
-  else
-    hipLaunchKernelGGL((k_activity<2>), dim3(grid), dim3(256), 0, st, *luma, wb, hb, variances, scales);
+  r1_by_bpp(luma->bytes_per_px, [&](auto B) {
+    hipLaunchKernelGGL((k_activity<B.value>), dim3(grid), dim3(256), 0, st, *luma, wb, hb, variances, scales);
+  });
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }

@@ -75,7 +75,7 @@ __device__ __forceinline__ int32_t mad_i24(int32_t a, int32_t b, int32_t c) {
 }
 
 // Byte offset of pixel (x, y) from the start of a plane's allocation, in 32 bits with the full-rate multiplier: the
-// entry points require stride, alloc_height < 2^24 and an allocation below 4 GiB (lrf_plane_ok).  A load at
+// entry points require stride, alloc_height < 2^24 and an allocation below 4 GiB (r1_offsets_fit_u32).  A load at
 // `data + offset` then takes the uniform base from SGPRs and needs no 64-bit vector arithmetic (px_addr is a
 // quarter-rate 64-bit multiply-add per address: 20 of them per thread and tile here).
 template <int BPP>
@@ -85,10 +85,6 @@ __device__ __forceinline__ uint32_t px_off(const R1Plane &p, int x, int y) {
 template <int BPP>
 __device__ __forceinline__ uint32_t ld_px_at(const R1Plane &p, uint32_t off) {
   return ld_px<BPP>((const uint8_t *)p.data + off);
-}
-inline bool lrf_plane_ok(const R1Plane *p) {
-  return p->stride > 0 && p->stride < (1 << 24) && p->alloc_height > 0 && p->alloc_height < (1 << 24) &&
-         (unsigned long long)p->stride * (unsigned long long)p->alloc_height * (unsigned long long)p->bytes_per_px < (1ull << 32);
 }
 
 // sgrproj_sum_finish -> a | b << 9.  Every product but (for bit depth 12) the last has operands below 2^24 whatever
@@ -890,18 +886,15 @@ __attribute__((visibility("hidden")))
 int r1i_sgr_trial_err_launch(const R1Plane &trial, size_t trial_idx_bytes, const R1Plane &cdef_cur, const R1Plane &src,
                              const R1TrialUnit *units, int n_units, int n_idx, int pli, int xdec, int ydec,
                              const uint32_t *scales, int scale_stride, unsigned long long *psum, int n_sb, hipStream_t st) {
-  R1_REQUIRE(lrf_plane_ok(&trial) && lrf_plane_ok(&cdef_cur) && lrf_plane_ok(&src));
-  R1_REQUIRE(trial.bytes_per_px == src.bytes_per_px && cdef_cur.bytes_per_px == src.bytes_per_px);
+  R1_REQUIRE(r1_offsets_fit_u32(trial) && r1_offsets_fit_u32(cdef_cur) && r1_offsets_fit_u32(src));
+  R1_REQUIRE(r1_same_px(src, trial, cdef_cur));
   const dim3 grid((64 / TW) * (64 / TRIAL_TR), n_units, n_idx);
-#define R1_TRIAL(BPP, CH)                                                                                         \
-  hipLaunchKernelGGL((k_sgr_trial_err<BPP, CH>), grid, dim3(256), 0, st, trial, trial_idx_bytes, cdef_cur, src, units, \
-                     pli, xdec, ydec, scales, scale_stride, psum, n_sb)
-  if (src.bytes_per_px == 1) {
-    if (pli) R1_TRIAL(1, true); else R1_TRIAL(1, false);
-  } else {
-    if (pli) R1_TRIAL(2, true); else R1_TRIAL(2, false);
-  }
-#undef R1_TRIAL
+  r1_by_bpp(src.bytes_per_px, [&](auto B) {
+    r1_by_bool(pli != 0, [&](auto CH) {
+      hipLaunchKernelGGL((k_sgr_trial_err<B.value, CH.value>), grid, dim3(256), 0, st, trial, trial_idx_bytes, cdef_cur,
+                         src, units, pli, xdec, ydec, scales, scale_stride, psum, n_sb);
+    });
+  });
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }
@@ -911,11 +904,10 @@ extern "C" int r1_lrf_sgrproj_plane(r1_ctx *ctx, const R1Plane *cdeffed, const R
                                     int frame_height, int unit_size, int unit_cols, int unit_rows,
                                     int stripe_height, const R1LrfUnit *units, void *stream) {
   R1_REQUIRE(ctx && cdeffed && deblocked && out && units);
-  R1_REQUIRE(lrf_plane_ok(cdeffed) && lrf_plane_ok(deblocked));   // 32-bit byte offsets in the tile loads
-  R1_REQUIRE(cdeffed->bytes_per_px == deblocked->bytes_per_px &&
-             cdeffed->bytes_per_px == out->bytes_per_px);
-  R1_REQUIRE(cdeffed->bytes_per_px == 1 || cdeffed->bytes_per_px == 2);
-  R1_REQUIRE((cdeffed->bytes_per_px == 1) == (cdeffed->bit_depth == 8));
+  R1_REQUIRE(r1_offsets_fit_u32(*cdeffed) && r1_offsets_fit_u32(*deblocked));   // 32-bit byte offsets in the tile loads
+  R1_REQUIRE(r1_same_px(*cdeffed, *deblocked, *out));
+  R1_REQUIRE(r1_px_ok(*cdeffed));
+  R1_REQUIRE(r1_px_fits_depth(*cdeffed));
   R1_REQUIRE(cdeffed->data != out->data);   // the filter reads CDEF output around what it writes
   R1_REQUIRE(ydec >= 0 && ydec <= 1 && crop_w > 0 && crop_h > 0 && frame_height > 0);
   R1_REQUIRE(unit_size >= 32 && unit_size <= 256 && unit_size % 32 == 0);
@@ -934,10 +926,9 @@ extern "C" int r1_lrf_sgrproj_plane(r1_ctx *ctx, const R1Plane *cdeffed, const R
   g.chunks = (crop_w + TW - 1) / TW;
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid(g.chunks, g.stripe_n);
-  if (cdeffed->bytes_per_px == 1)
-    hipLaunchKernelGGL(k_lrf_sgr<1>, grid, dim3(256), 0, st, *cdeffed, *deblocked, *out, g, units);
-  else
-    hipLaunchKernelGGL(k_lrf_sgr<2>, grid, dim3(256), 0, st, *cdeffed, *deblocked, *out, g, units);
+  r1_by_bpp(cdeffed->bytes_per_px, [&](auto B) {
+    hipLaunchKernelGGL((k_lrf_sgr<B.value>), grid, dim3(256), 0, st, *cdeffed, *deblocked, *out, g, units);
+  });
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }
@@ -946,22 +937,20 @@ extern "C" int r1_sgrproj_solve_batch(r1_ctx *ctx, const R1Plane *cdeffed, const
                                       const R1SgrSolveUnit *units, int n, int max_w, int max_h,
                                       int64_t *moments_scratch, int8_t *xqd_out, void *stream) {
   R1_REQUIRE(ctx && cdeffed && input);
-  R1_REQUIRE(lrf_plane_ok(cdeffed) && lrf_plane_ok(input));
-  R1_REQUIRE(cdeffed->bytes_per_px == input->bytes_per_px && cdeffed->bit_depth == input->bit_depth);
-  R1_REQUIRE(cdeffed->bytes_per_px == 1 || cdeffed->bytes_per_px == 2);
-  R1_REQUIRE((cdeffed->bytes_per_px == 1) == (cdeffed->bit_depth == 8));
+  R1_REQUIRE(r1_offsets_fit_u32(*cdeffed) && r1_offsets_fit_u32(*input));
+  R1_REQUIRE(r1_same_px(*cdeffed, *input) && r1_same_depth(*cdeffed, *input));
+  R1_REQUIRE(r1_px_ok(*cdeffed));
+  R1_REQUIRE(r1_px_fits_depth(*cdeffed));
   R1_REQUIRE(max_w > 0 && max_h > 0 && max_w <= 384 && max_h <= 384);
   if (n <= 0) return R1_OK;
   R1_REQUIRE(units && moments_scratch && xqd_out);
   hipStream_t st = (hipStream_t)stream;
   R1_HIP_CHECK(hipMemsetAsync(moments_scratch, 0, (size_t)n * 5 * sizeof(int64_t), st));
   const dim3 grid(((max_w + TW - 1) / TW) * ((max_h + 63) / 64), n);
-  if (cdeffed->bytes_per_px == 1)
-    hipLaunchKernelGGL(k_sgr_moments<1>, grid, dim3(256), 0, st, *cdeffed, *input, units,
+  r1_by_bpp(cdeffed->bytes_per_px, [&](auto B) {
+    hipLaunchKernelGGL((k_sgr_moments<B.value>), grid, dim3(256), 0, st, *cdeffed, *input, units,
                        (long long *)moments_scratch);
-  else
-    hipLaunchKernelGGL(k_sgr_moments<2>, grid, dim3(256), 0, st, *cdeffed, *input, units,
-                       (long long *)moments_scratch);
+  });
   hipLaunchKernelGGL(k_sgr_solve, dim3((n + 127) / 128), dim3(128), 0, st, units,
                      (const long long *)moments_scratch, n, xqd_out);
   R1_HIP_CHECK(hipGetLastError());
@@ -976,12 +965,12 @@ extern "C" int r1_lrf_search_batch(r1_ctx *ctx, const R1Plane *lrf_in, const R1P
                                    uint32_t dist_scale, int64_t *scratch, int8_t *xqd_out,
                                    uint64_t *err_out, void *stream) {
   R1_REQUIRE(ctx && lrf_in && src);
-  R1_REQUIRE(lrf_plane_ok(lrf_in) && lrf_plane_ok(src));
-  R1_REQUIRE(lrf_in->bytes_per_px == src->bytes_per_px && lrf_in->bit_depth == src->bit_depth);
-  R1_REQUIRE(lrf_in->bytes_per_px == 1 || lrf_in->bytes_per_px == 2);
-  R1_REQUIRE((lrf_in->bytes_per_px == 1) == (lrf_in->bit_depth == 8));
+  R1_REQUIRE(r1_offsets_fit_u32(*lrf_in) && r1_offsets_fit_u32(*src));
+  R1_REQUIRE(r1_same_px(*lrf_in, *src) && r1_same_depth(*lrf_in, *src));
+  R1_REQUIRE(r1_px_ok(*lrf_in));
+  R1_REQUIRE(r1_px_fits_depth(*lrf_in));
   R1_REQUIRE(max_w > 0 && max_h > 0 && max_w <= 384 && max_h <= 384);
-  R1_REQUIRE(xdec >= 0 && xdec <= 1 && ydec >= 0 && ydec <= 1 && (is_chroma || (!xdec && !ydec)));
+  R1_REQUIRE(r1_dec_ok(xdec, ydec) && (is_chroma || (!xdec && !ydec)));
   R1_REQUIRE(!scales || scale_stride > 0);
   // the error walks the block grid: planes allocated in whole blocks (Frame::new aligns to 8 luma pixels)
   const int bw = is_chroma ? 8 >> xdec : 8, bh = is_chroma ? 8 >> ydec : 8;
@@ -991,17 +980,17 @@ extern "C" int r1_lrf_search_batch(r1_ctx *ctx, const R1Plane *lrf_in, const R1P
   hipStream_t st = (hipStream_t)stream;
   if (max_w <= 64 && max_h <= 64) {
     // one launch: a workgroup per pair keeps the filter outputs in LDS between the solve and the projection
-#define R1_LRF_UNIT(BPP, CH, PK)                                                                                  \
-  hipLaunchKernelGGL((k_lrf_search_unit<BPP, CH, PK>), dim3(n), dim3(256), 0, st, *lrf_in, *src, units, xdec, ydec, \
-                     scales, scale_stride, dist_scale, xqd_out, (unsigned long long *)err_out)
-    if (lrf_in->bytes_per_px == 1) {
-      if (is_chroma) R1_LRF_UNIT(1, true, true); else R1_LRF_UNIT(1, false, true);
-    } else if (lrf_in->bit_depth <= 10) {
-      if (is_chroma) R1_LRF_UNIT(2, true, true); else R1_LRF_UNIT(2, false, true);
-    } else {
-      if (is_chroma) R1_LRF_UNIT(2, true, false); else R1_LRF_UNIT(2, false, false);
-    }
-#undef R1_LRF_UNIT
+    r1_by_bpp(lrf_in->bytes_per_px, [&](auto B) {
+      r1_by_bool(is_chroma != 0, [&](auto CH) {
+        // one-byte pixels are always packed: there is no <1, *, false>
+        r1_by_bool(lrf_in->bit_depth <= 10 || lrf_in->bytes_per_px == 1, [&](auto PK) {
+          if constexpr (B.value == 2 || PK.value)
+            hipLaunchKernelGGL((k_lrf_search_unit<B.value, CH.value, PK.value>), dim3(n), dim3(256), 0, st, *lrf_in, *src,
+                               units, xdec, ydec, scales, scale_stride, dist_scale, xqd_out,
+                               (unsigned long long *)err_out);
+        });
+      });
+    });
     R1_HIP_CHECK(hipGetLastError());
     return R1_OK;
   }
@@ -1010,21 +999,18 @@ extern "C" int r1_lrf_search_batch(r1_ctx *ctx, const R1Plane *lrf_in, const R1P
   R1_HIP_CHECK(hipMemsetAsync(scratch, 0, (size_t)n * 6 * sizeof(int64_t), st));
   unsigned long long *acc = (unsigned long long *)scratch + (size_t)n * 5;
   const dim3 grid(((max_w + TW - 1) / TW) * ((max_h + 63) / 64), n);
-  if (lrf_in->bytes_per_px == 1)
-    hipLaunchKernelGGL(k_sgr_moments<1>, grid, dim3(256), 0, st, *lrf_in, *src, units, (long long *)scratch);
-  else
-    hipLaunchKernelGGL(k_sgr_moments<2>, grid, dim3(256), 0, st, *lrf_in, *src, units, (long long *)scratch);
+  r1_by_bpp(lrf_in->bytes_per_px, [&](auto B) {
+    hipLaunchKernelGGL((k_sgr_moments<B.value>), grid, dim3(256), 0, st, *lrf_in, *src, units,
+                       (long long *)scratch);
+  });
   hipLaunchKernelGGL(k_sgr_solve, dim3((n + 127) / 128), dim3(128), 0, st, units, (const long long *)scratch, n,
                      xqd_out);
-#define R1_LRF_ERR(BPP, CH)                                                                                  \
-  hipLaunchKernelGGL((k_sgr_unit_err<BPP, CH>), grid, dim3(256), 0, st, *lrf_in, *src, units,              \
-                     (const int8_t *)xqd_out, xdec, ydec, scales, scale_stride, acc)
-  if (lrf_in->bytes_per_px == 1) {
-    if (is_chroma) R1_LRF_ERR(1, true); else R1_LRF_ERR(1, false);
-  } else {
-    if (is_chroma) R1_LRF_ERR(2, true); else R1_LRF_ERR(2, false);
-  }
-#undef R1_LRF_ERR
+  r1_by_bpp(lrf_in->bytes_per_px, [&](auto B) {
+    r1_by_bool(is_chroma != 0, [&](auto CH) {
+      hipLaunchKernelGGL((k_sgr_unit_err<B.value, CH.value>), grid, dim3(256), 0, st, *lrf_in, *src, units,
+                         (const int8_t *)xqd_out, xdec, ydec, scales, scale_stride, acc);
+    });
+  });
   hipLaunchKernelGGL(k_lrf_err_finish, dim3((n + 127) / 128), dim3(128), 0, st, acc, n, dist_scale, units, *lrf_in, *src,
                      bw, bh, xqd_out, (unsigned long long *)err_out);
   R1_HIP_CHECK(hipGetLastError());

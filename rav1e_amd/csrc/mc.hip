@@ -118,10 +118,9 @@ int launch_mc_fast(bool prep, const R1Plane &ref, const R1McCand *cands, int n, 
                    hipStream_t st) {
   constexpr int W = 1 << WL, H = 1 << HL, P = W > H ? W : H, NC = 64 / P;
   const unsigned grid = ((unsigned)((n + NC - 1) / NC) + 7u) & ~7u;
-  if (prep)
-    hipLaunchKernelGGL((k_mc_fast<BPP, WL, HL, true>), dim3(grid), dim3(64), 0, st, ref, cands, n, dst);
-  else
-    hipLaunchKernelGGL((k_mc_fast<BPP, WL, HL, false>), dim3(grid), dim3(64), 0, st, ref, cands, n, dst);
+  r1_by_bool(prep, [&](auto PREP) {
+    hipLaunchKernelGGL((k_mc_fast<BPP, WL, HL, PREP.value>), dim3(grid), dim3(64), 0, st, ref, cands, n, dst);
+  });
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }
@@ -133,10 +132,11 @@ int r1_mc_fast_launch(bool prep, const R1Plane *ref, int w, int h, const R1McCan
   for (int t = 0; t < 19; t++)
     if ((1 << r1tx::kTxWLog2[t]) == w && (1 << r1tx::kTxHLog2[t]) == h) ts = t;
   if (ts < 0) return 1;
-#define R1_MF_CASE(ID, WL, HL)                                                         \
-  case ID:                                                                             \
-    return ref->bytes_per_px == 1 ? launch_mc_fast<1, WL, HL>(prep, *ref, cands, n, dst, st) \
-                                  : launch_mc_fast<2, WL, HL>(prep, *ref, cands, n, dst, st);
+#define R1_MF_CASE(ID, WL, HL)                                                                             \
+  case ID:                                                                                                 \
+    return r1_by_bpp(ref->bytes_per_px, [&](auto B) {                                                      \
+      return launch_mc_fast<B.value, WL, HL>(prep, *ref, cands, n, dst, st);                               \
+    });
   switch (ts) { R1_TX_SIZES(R1_MF_CASE) }
 #undef R1_MF_CASE
   return 1;
@@ -144,7 +144,7 @@ int r1_mc_fast_launch(bool prep, const R1Plane *ref, int w, int h, const R1McCan
 
 int mc_launch(bool prep, const R1Plane *ref, int w, int h, const R1McCand *cands,
               int n, void *dst, hipStream_t st) {
-  R1_REQUIRE(ref && (ref->bytes_per_px == 1 || ref->bytes_per_px == 2));
+  R1_REQUIRE(ref && r1_px_ok(*ref));
   R1_REQUIRE(r1_is_pow2(w) && w >= 2 && w <= 128);
   R1_REQUIRE(h >= 2 && h <= 128 && (h & 1) == 0);
   if (n <= 0) return R1_OK;
@@ -162,12 +162,11 @@ int mc_launch(bool prep, const R1Plane *ref, int w, int h, const R1McCand *cands
   const size_t lds = (size_t)NS * (h + 7) * ws;
   const long long slabs = (long long)n * spc;
   const unsigned grid = (unsigned)((slabs + NS - 1) / NS);
-#define R1_MC_GO(BPP, PREP)                                                   \
-  hipLaunchKernelGGL((k_mc<BPP, PREP>), dim3(grid), dim3(64), lds, st, *ref, \
-                     w, h, cands, n, dst)
-  if (bpp == 1) { if (prep) R1_MC_GO(1, true); else R1_MC_GO(1, false); }
-  else { if (prep) R1_MC_GO(2, true); else R1_MC_GO(2, false); }
-#undef R1_MC_GO
+  r1_by_bpp(bpp, [&](auto B) {
+    r1_by_bool(prep, [&](auto PREP) {
+      hipLaunchKernelGGL((k_mc<B.value, PREP.value>), dim3(grid), dim3(64), lds, st, *ref, w, h, cands, n, dst);
+    });
+  });
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }
@@ -193,20 +192,18 @@ extern "C" int r1_mc_avg_batch(r1_ctx *ctx, const int16_t *tmp1,
                                int bit_depth, int bytes_per_px, void *dst,
                                void *stream) {
   R1_REQUIRE(ctx);
-  R1_REQUIRE(bytes_per_px == 1 || bytes_per_px == 2);
-  R1_REQUIRE(bit_depth == 8 || bit_depth == 10 || bit_depth == 12);
+  R1_REQUIRE(r1_px_ok(bytes_per_px));
+  R1_REQUIRE(r1_depth_ok(bit_depth));
   R1_REQUIRE(w > 0 && h > 0);
   if (n <= 0) return R1_OK;
   R1_REQUIRE(tmp1 && tmp2 && dst);
   const long long total = (long long)n * w * h;
   long long blocks = (total + 255) / 256;
   if (blocks > 8192) blocks = 8192;
-  if (bytes_per_px == 1)
-    hipLaunchKernelGGL((k_avg<1>), dim3((unsigned)blocks), dim3(256), 0,
-                       (hipStream_t)stream, tmp1, tmp2, total, bit_depth, dst);
-  else
-    hipLaunchKernelGGL((k_avg<2>), dim3((unsigned)blocks), dim3(256), 0,
-                       (hipStream_t)stream, tmp1, tmp2, total, bit_depth, dst);
+  r1_by_bpp(bytes_per_px, [&](auto B) {
+    hipLaunchKernelGGL((k_avg<B.value>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, tmp1, tmp2,
+                       total, bit_depth, dst);
+  });
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }

@@ -236,10 +236,10 @@ extern "C" int r1_rdo_compound_cand_batch(r1_ctx *ctx, const R1Plane *org, const
                                           uint32_t *sad_out, uint32_t *satd_out, void *pred_out, void *stream) {
   R1_REQUIRE(ctx && org && ref0 && ref1);
   const int bd = org->bit_depth, bpp = org->bytes_per_px;
-  R1_REQUIRE(bd == 8 || bd == 10 || bd == 12);
-  R1_REQUIRE(bpp == (bd == 8 ? 1 : 2));
-  R1_REQUIRE(ref0->bit_depth == bd && ref1->bit_depth == bd);
-  R1_REQUIRE(ref0->bytes_per_px == bpp && ref1->bytes_per_px == bpp);
+  R1_REQUIRE(r1_depth_ok(bd));
+  R1_REQUIRE(r1_px_ok(*org) && r1_px_fits_depth(*org));
+  R1_REQUIRE(r1_same_depth(*org, *ref0, *ref1));
+  R1_REQUIRE(r1_same_px(*org, *ref0, *ref1));
   R1_REQUIRE(r1_is_pow2(w) && w >= 4 && w <= 128);
   R1_REQUIRE(h >= 2 && h <= 128 && (h & 1) == 0);
   R1_REQUIRE(sad_out || satd_out || pred_out);
@@ -263,12 +263,10 @@ extern "C" int r1_rdo_compound_cand_batch(r1_ctx *ctx, const R1Plane *org, const
   const int ws = (((P + 7) * bpp + 3) >> 2) << 2;
   const size_t lds = (size_t)NS * (2 * (size_t)(hc + 7) * ws + (size_t)hc * P * 2);   // <= 62720
   const unsigned grid = (unsigned)((n + NS - 1) / NS);
-  if (bpp == 1)
-    hipLaunchKernelGGL((k_compound<1>), dim3(grid), dim3(64), lds, st, *org, *ref0, *ref1, w, h, cands, n,
+  r1_by_bpp(bpp, [&](auto B) {
+    hipLaunchKernelGGL((k_compound<B.value>), dim3(grid), dim3(64), lds, st, *org, *ref0, *ref1, w, h, cands, n,
                        sad_out, satd_out, pred_out);
-  else
-    hipLaunchKernelGGL((k_compound<2>), dim3(grid), dim3(64), lds, st, *org, *ref0, *ref1, w, h, cands, n,
-                       sad_out, satd_out, pred_out);
+  });
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }

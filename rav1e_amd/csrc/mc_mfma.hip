@@ -167,10 +167,9 @@ template <int WL, int HL>
 int launch(bool prep, const R1Plane &ref, const R1McCand *cands, int n, void *dst, hipStream_t st) {
   constexpr int W = 1 << WL, H = 1 << HL, P = W > H ? W : H, NC = 64 / P;
   const unsigned grid = (unsigned)((n + NC - 1) / NC);
-  if (prep)
-    hipLaunchKernelGGL((k_mc_mfma<WL, HL, true>), dim3(grid), dim3(64), 0, st, ref, cands, n, dst);
-  else
-    hipLaunchKernelGGL((k_mc_mfma<WL, HL, false>), dim3(grid), dim3(64), 0, st, ref, cands, n, dst);
+  r1_by_bool(prep, [&](auto PREP) {
+    hipLaunchKernelGGL((k_mc_mfma<WL, HL, PREP.value>), dim3(grid), dim3(64), 0, st, ref, cands, n, dst);
+  });
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }

@@ -503,7 +503,7 @@ extern "C" int r1_estimate_motion_batch(r1_ctx *ctx, const R1MeJob *tile, const 
                                         int use_satd, int filter_mode, R1MeResult *out,
                                         void *stream) {
   R1_REQUIRE(ctx && tile && params);
-  R1_REQUIRE(params->bit_depth == 8 || params->bit_depth == 10 || params->bit_depth == 12);
+  R1_REQUIRE(r1_depth_ok(params->bit_depth));
   R1_REQUIRE(filter_mode >= 0 && filter_mode <= 3);
   R1_REQUIRE(r1_is_pow2(max_w) && r1_is_pow2(max_h) && max_w >= 4 && max_h >= 4 && max_w <= 64 &&
              max_h <= 64);
@@ -511,19 +511,16 @@ extern "C" int r1_estimate_motion_batch(r1_ctx *ctx, const R1MeJob *tile, const 
   R1_REQUIRE(tile->tile_x % SB == 0 && tile->tile_y % SB == 0 && tile->tile_w % MI == 0 &&
              tile->tile_h % MI == 0 && tile->tile_w > 0 && tile->tile_h > 0);
   const int bpp = tile->org[0].bytes_per_px;
-  R1_REQUIRE((bpp == 1 || bpp == 2) && tile->ref[0].bytes_per_px == bpp);
+  R1_REQUIRE(r1_px_ok(bpp) && r1_same_px(tile->org[0], tile->ref[0]));
   if (n <= 0) return R1_OK;
   R1_REQUIRE(cands && out);
   hipStream_t st = (hipStream_t)stream;
   if (max_w <= 16 && max_h <= 16) {   // one wave per block
     const unsigned grid = (unsigned)((n + 3) / 4);
-    if (bpp == 1) {
-      hipLaunchKernelGGL(k_me_blocks_small<1>, dim3(grid), dim3(256), 0, st, *tile, *params, cands, n, max_w,
+    r1_by_bpp(bpp, [&](auto B) {
+      hipLaunchKernelGGL(k_me_blocks_small<B.value>, dim3(grid), dim3(256), 0, st, *tile, *params, cands, n, max_w,
                          max_h, use_satd, filter_mode, out);
-    } else {
-      hipLaunchKernelGGL(k_me_blocks_small<2>, dim3(grid), dim3(256), 0, st, *tile, *params, cands, n, max_w,
-                         max_h, use_satd, filter_mode, out);
-    }
+    });
     R1_HIP_CHECK(hipGetLastError());
     return R1_OK;
   }
@@ -532,13 +529,10 @@ extern "C" int r1_estimate_motion_batch(r1_ctx *ctx, const R1MeJob *tile, const 
   const size_t blk = ((size_t)max_w * max_h * bpp + 15) & ~(size_t)15;
   const size_t lds = blk + 4 * ((((size_t)(max_h + 7) * ws + 15) & ~(size_t)15) + blk);
   R1_REQUIRE(lds <= kMeBlocksMaxLds);
-  if (bpp == 1) {
-    hipLaunchKernelGGL(k_me_blocks<1>, dim3(n), dim3(256), lds, st, *tile, *params, cands, max_w,
-                       max_h, use_satd, filter_mode, out);
-  } else {
-    hipLaunchKernelGGL(k_me_blocks<2>, dim3(n), dim3(256), lds, st, *tile, *params, cands, max_w,
-                       max_h, use_satd, filter_mode, out);
-  }
+  r1_by_bpp(bpp, [&](auto B) {
+    hipLaunchKernelGGL(k_me_blocks<B.value>, dim3(n), dim3(256), lds, st, *tile, *params, cands, max_w, max_h, use_satd,
+                       filter_mode, out);
+  });
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }

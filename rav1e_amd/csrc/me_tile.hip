@@ -530,10 +530,11 @@ int me_launch_persistent(r1_ctx *ctx, const MeStaged &sc, const R1MeJob *jobs, i
   // the waves that finish theirs, in key order.
   const int grid = c.n_rows < 2048 ? c.n_rows : 2048;
   if (getenv("R1_ME_PERSISTENT_DEBUG")) fprintf(stderr, "k_me_persist: %d rows, grid %d, epoch %u\n", c.n_rows, grid, a.epoch);
-  if (bpp == 1 && pin) hipLaunchKernelGGL((k_me_persist<1, true>), dim3(grid), dim3(64), 0, st, a);
-  else if (bpp == 1) hipLaunchKernelGGL((k_me_persist<1, false>), dim3(grid), dim3(64), 0, st, a);
-  else if (pin) hipLaunchKernelGGL((k_me_persist<2, true>), dim3(grid), dim3(64), 0, st, a);
-  else hipLaunchKernelGGL((k_me_persist<2, false>), dim3(grid), dim3(64), 0, st, a);
+  r1_by_bpp(bpp, [&](auto B) {
+    r1_by_bool(pin, [&](auto PIN) {
+      hipLaunchKernelGGL((k_me_persist<B.value, PIN.value>), dim3(grid), dim3(64), 0, st, a);
+    });
+  });
   R1_HIP_CHECK(hipGetLastError());
   R1_HIP_CHECK(hipEventRecord(ctx->me_done[slot], st));
   c.launched = true;
@@ -552,10 +553,10 @@ int me_launch_persistent(r1_ctx *ctx, const MeStaged &sc, const R1MeJob *jobs, i
 int me_check_jobs(const R1MeJob *jobs, int n_jobs, const R1MeParams *params, int &bpp, int &max_sbw, int &max_sbh) {
   R1_REQUIRE(jobs);
   R1_REQUIRE(n_jobs <= 256);   // tiles x reference frames of one frame
-  R1_REQUIRE(params->bit_depth == 8 || params->bit_depth == 10 || params->bit_depth == 12);
+  R1_REQUIRE(r1_depth_ok(params->bit_depth));
   R1_REQUIRE(params->stats_cols > 0 && params->stats_rows > 0);
   bpp = jobs[0].org[0].bytes_per_px;
-  R1_REQUIRE(bpp == 1 || bpp == 2);
+  R1_REQUIRE(r1_px_ok(bpp));
   max_sbw = max_sbh = 0;
   for (int j = 0; j < n_jobs; j++) {
     const R1MeJob &b = jobs[j];
@@ -565,8 +566,7 @@ int me_check_jobs(const R1MeJob *jobs, int n_jobs, const R1MeParams *params, int
     R1_REQUIRE((b.tile_x + b.tile_w) / MI <= params->stats_cols &&
                (b.tile_y + b.tile_h) / MI <= params->stats_rows);
     for (int l = 0; l < 3; l++)
-      R1_REQUIRE(b.org[l].data && b.ref[l].data && b.org[l].bytes_per_px == bpp &&
-                 b.ref[l].bytes_per_px == bpp);
+      R1_REQUIRE(b.org[l].data && b.ref[l].data && r1_same_px(jobs[0].org[0], b.org[l], b.ref[l]));
     const int sbw = (b.tile_w + SB - 1) / SB, sbh = (b.tile_h + SB - 1) / SB;
     max_sbw = sbw > max_sbw ? sbw : max_sbw;
     max_sbh = sbh > max_sbh ? sbh : max_sbh;

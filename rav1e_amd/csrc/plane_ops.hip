@@ -107,7 +107,7 @@ inline bool aligned16(const R1Plane *p) {
 
 extern "C" int r1_plane_pad(r1_ctx *ctx, const R1Plane *plane, int w, int h, int xdec, int ydec, void *stream) {
   R1_REQUIRE(ctx && plane && plane->data);
-  R1_REQUIRE(plane->bytes_per_px == 1 || plane->bytes_per_px == 2);
+  R1_REQUIRE(r1_px_ok(*plane));
   R1_REQUIRE(xdec >= 0 && xdec <= 2 && ydec >= 0 && ydec <= 2);
   const int width = (w + xdec) >> xdec, height = (h + ydec) >> ydec;
   R1_REQUIRE(width >= 1 && height >= 1);
@@ -115,13 +115,11 @@ extern "C" int r1_plane_pad(r1_ctx *ctx, const R1Plane *plane, int w, int h, int
   hipStream_t st = (hipStream_t)stream;
   const bool vec = aligned16(plane);
   const dim3 grid(plane->alloc_height), block(256);
-  if (plane->bytes_per_px == 1) {
-    if (vec) hipLaunchKernelGGL((k_plane_pad<1, true>), grid, block, 0, st, *plane, width, height);
-    else hipLaunchKernelGGL((k_plane_pad<1, false>), grid, block, 0, st, *plane, width, height);
-  } else {
-    if (vec) hipLaunchKernelGGL((k_plane_pad<2, true>), grid, block, 0, st, *plane, width, height);
-    else hipLaunchKernelGGL((k_plane_pad<2, false>), grid, block, 0, st, *plane, width, height);
-  }
+  r1_by_bpp(plane->bytes_per_px, [&](auto B) {
+    r1_by_bool(vec, [&](auto VEC) {
+      hipLaunchKernelGGL((k_plane_pad<B.value, VEC.value>), grid, block, 0, st, *plane, width, height);
+    });
+  });
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }
@@ -129,7 +127,7 @@ extern "C" int r1_plane_pad(r1_ctx *ctx, const R1Plane *plane, int w, int h, int
 extern "C" int r1_plane_downsample(r1_ctx *ctx, const R1Plane *src, const R1Plane *dst, int frame_w,
                                    int frame_h, int dst_xdec, int dst_ydec, void *stream) {
   R1_REQUIRE(ctx && src && dst && src->data && dst->data && src->data != dst->data);
-  R1_REQUIRE(src->bytes_per_px == dst->bytes_per_px && (src->bytes_per_px == 1 || src->bytes_per_px == 2));
+  R1_REQUIRE(r1_same_px(*src, *dst) && r1_px_ok(*src));
   R1_REQUIRE(dst_xdec >= 1 && dst_xdec <= 2 && dst_ydec >= 1 && dst_ydec <= 2);
   const int width = (src->width + 1) / 2, height = (src->height + 1) / 2;
   R1_REQUIRE(dst->width == width && dst->height == height);
@@ -141,13 +139,11 @@ extern "C" int r1_plane_downsample(r1_ctx *ctx, const R1Plane *src, const R1Plan
   hipStream_t st = (hipStream_t)stream;
   const bool vec = aligned16(src) && aligned16(dst) && dst->xorigin % 8 == 0;
   const dim3 grid(dst->alloc_height), block(256);
-  if (src->bytes_per_px == 1) {
-    if (vec) hipLaunchKernelGGL((k_plane_downsample<1, true>), grid, block, 0, st, *src, *dst, pad_w, pad_h);
-    else hipLaunchKernelGGL((k_plane_downsample<1, false>), grid, block, 0, st, *src, *dst, pad_w, pad_h);
-  } else {
-    if (vec) hipLaunchKernelGGL((k_plane_downsample<2, true>), grid, block, 0, st, *src, *dst, pad_w, pad_h);
-    else hipLaunchKernelGGL((k_plane_downsample<2, false>), grid, block, 0, st, *src, *dst, pad_w, pad_h);
-  }
+  r1_by_bpp(src->bytes_per_px, [&](auto B) {
+    r1_by_bool(vec, [&](auto VEC) {
+      hipLaunchKernelGGL((k_plane_downsample<B.value, VEC.value>), grid, block, 0, st, *src, *dst, pad_w, pad_h);
+    });
+  });
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }

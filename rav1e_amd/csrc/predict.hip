@@ -698,8 +698,8 @@ extern "C" int r1_intra_edges_batch(r1_ctx *ctx, const R1Plane *rec, int tile_x,
                                     const R1IntraEdgeCand *cands, int n, void *edges,
                                     int edge_stride, uint8_t *lens, void *stream) {
   R1_REQUIRE(ctx && rec);
-  R1_REQUIRE(rec->bytes_per_px == 1 || rec->bytes_per_px == 2);
-  R1_REQUIRE(tx_size >= 0 && tx_size < 19);
+  R1_REQUIRE(r1_px_ok(*rec));
+  R1_REQUIRE(r1_tx_size_ok(tx_size));
   R1_REQUIRE(edge_stride >= EDGE_LEN);
   R1_REQUIRE(tile_x >= 0 && tile_y >= 0 && tile_w > 0 && tile_h > 0);
   if (n <= 0) return R1_OK;
@@ -707,10 +707,8 @@ extern "C" int r1_intra_edges_batch(r1_ctx *ctx, const R1Plane *rec, int tile_x,
   // rect_w / rect_h: dst.rect() clipped to the plane (partition.rs:701-704)
   const int rect_w = tile_w < rec->width - tile_x ? tile_w : rec->width - tile_x;
   const int rect_h = tile_h < rec->height - tile_y ? tile_h : rec->height - tile_y;
-  static const uint8_t wl[19] = {2, 3, 4, 5, 6, 2, 3, 3, 4, 4, 5, 5, 6, 2, 4, 3, 5, 4, 6};
-  static const uint8_t hl[19] = {2, 3, 4, 5, 6, 3, 2, 4, 3, 5, 4, 6, 5, 4, 2, 5, 3, 6, 4};
   hipStream_t st = (hipStream_t)stream;
-  const int txw = 1 << wl[tx_size], txh = 1 << hl[tx_size];
+  const int txw = 1 << r1tx::kTxWLog2[tx_size], txh = 1 << r1tx::kTxHLog2[tx_size];
   // EIGHT lanes per block, whatever its size: what a lane does before it touches an entry (the mode / flag
   // logic, the clipping, the block's address) is the same for every lane of a block and dominates; with 8
   // lanes a wave prepares 8 blocks and walks the 17 .. 129 entries in strides of 8.  Measured against one
@@ -719,12 +717,10 @@ extern "C" int r1_intra_edges_batch(r1_ctx *ctx, const R1Plane *rec, int tile_x,
   const int lpc_log2 = 3;
   const int cpw = 64 >> lpc_log2;
   const unsigned grid = (unsigned)((n + cpw - 1) / cpw);
-  if (rec->bytes_per_px == 1)
-    hipLaunchKernelGGL((k_intra_edges<1>), dim3(grid), dim3(64), 0, st, *rec, tile_x, tile_y, rect_w,
+  r1_by_bpp(rec->bytes_per_px, [&](auto B) {
+    hipLaunchKernelGGL((k_intra_edges<B.value>), dim3(grid), dim3(64), 0, st, *rec, tile_x, tile_y, rect_w,
                        rect_h, txw, txh, lpc_log2, cands, n, edges, edge_stride, lens);
-  else
-    hipLaunchKernelGGL((k_intra_edges<2>), dim3(grid), dim3(64), 0, st, *rec, tile_x, tile_y, rect_w,
-                       rect_h, txw, txh, lpc_log2, cands, n, edges, edge_stride, lens);
+  });
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }
@@ -734,32 +730,19 @@ template <bool EGRP>
 void predict_launch(int tx_size, const R1IntraCand *cands, int n, const void *edges, int edge_stride,
                     const uint8_t *lens, int group, const int16_t *pos_xy, R1RdoCand *rdo_cands, const int16_t *ac,
                     int bit_depth, int bytes_per_px, void *dst, hipStream_t st) {
-  static const uint8_t wl[19] = {2, 3, 4, 5, 6, 2, 3, 3, 4, 4, 5, 5, 6, 2, 4, 3, 5, 4, 6};
-  static const uint8_t hl[19] = {2, 3, 4, 5, 6, 3, 2, 4, 3, 5, 4, 6, 5, 4, 2, 5, 3, 6, 4};
-  const int W = 1 << wl[tx_size], H = 1 << hl[tx_size];
+  const int wl = r1tx::kTxWLog2[tx_size], hl = r1tx::kTxHLog2[tx_size];
+  const int W = 1 << wl, H = 1 << hl;
   const int NC = 64 / W, FL = 2 * (W + H) + 1;
   const size_t lds = (size_t)NC * (EDGE_LEN + 4 * FL) * sizeof(uint16_t);
   const unsigned grid = (unsigned)((n + NC - 1) / NC);
-#define R1_PRED_LAUNCH(B, WLT, HLT)                                                                       \
-  hipLaunchKernelGGL((k_intra_predict<B, false, WLT, HLT, EGRP>), dim3(grid), dim3(64), lds, st,          \
-                     (int)wl[tx_size], (int)hl[tx_size], cands, n, edges, edge_stride, lens, ac,          \
-                     bit_depth, dst, R1Plane{}, pos_xy, group, (uint32_t *)rdo_cands)
   // square blocks 4x4 .. 32x32 with the size as a constant (unrolled row loops)
-  const int sq = wl[tx_size] == hl[tx_size] ? wl[tx_size] : 0;
-  if (bytes_per_px == 1) {
-    if (sq == 2) R1_PRED_LAUNCH(1, 2, 2);
-    else if (sq == 3) R1_PRED_LAUNCH(1, 3, 3);
-    else if (sq == 4) R1_PRED_LAUNCH(1, 4, 4);
-    else if (sq == 5) R1_PRED_LAUNCH(1, 5, 5);
-    else R1_PRED_LAUNCH(1, -1, -1);
-  } else {
-    if (sq == 2) R1_PRED_LAUNCH(2, 2, 2);
-    else if (sq == 3) R1_PRED_LAUNCH(2, 3, 3);
-    else if (sq == 4) R1_PRED_LAUNCH(2, 4, 4);
-    else if (sq == 5) R1_PRED_LAUNCH(2, 5, 5);
-    else R1_PRED_LAUNCH(2, -1, -1);
-  }
-#undef R1_PRED_LAUNCH
+  r1_by_bpp(bytes_per_px, [&](auto B) {
+    r1_by_value<-1, 2, 3, 4, 5>(wl == hl ? wl : 0, [&](auto S) {
+      hipLaunchKernelGGL((k_intra_predict<B.value, false, S.value, S.value, EGRP>), dim3(grid), dim3(64), lds, st,
+                         wl, hl, cands, n, edges, edge_stride, lens, ac, bit_depth, dst, R1Plane{}, pos_xy, group,
+                         (uint32_t *)rdo_cands);
+    });
+  });
 }
 }  // namespace
 
@@ -779,10 +762,10 @@ extern "C" int r1_predict_intra_batch(r1_ctx *ctx, int tx_size, const R1IntraCan
                                       const int16_t *ac, int bit_depth, int bytes_per_px,
                                       void *dst, void *stream) {
   R1_REQUIRE(ctx);
-  R1_REQUIRE(tx_size >= 0 && tx_size < 19);
-  R1_REQUIRE(bit_depth == 8 || bit_depth == 10 || bit_depth == 12);
-  R1_REQUIRE(bytes_per_px == 1 || bytes_per_px == 2);
-  R1_REQUIRE((bytes_per_px == 1) == (bit_depth == 8));
+  R1_REQUIRE(r1_tx_size_ok(tx_size));
+  R1_REQUIRE(r1_depth_ok(bit_depth));
+  R1_REQUIRE(r1_px_ok(bytes_per_px));
+  R1_REQUIRE(r1_px_fits_depth(bytes_per_px, bit_depth));
   R1_REQUIRE(edge_stride >= EDGE_LEN);
   if (n <= 0) return R1_OK;
   R1_REQUIRE(cands && edges && lens && dst);
@@ -798,42 +781,32 @@ extern "C" int r1_intra_satd_batch(r1_ctx *ctx, const R1Plane *src, int tx_size,
                                    const uint8_t *lens, const int16_t *ac, uint32_t *satd_out,
                                    void *stream) {
   R1_REQUIRE(ctx && src);
-  R1_REQUIRE(tx_size >= 0 && tx_size < 19);
-  R1_REQUIRE(src->bit_depth == 8 || src->bit_depth == 10 || src->bit_depth == 12);
-  R1_REQUIRE(src->bytes_per_px == 1 || src->bytes_per_px == 2);
-  R1_REQUIRE((src->bytes_per_px == 1) == (src->bit_depth == 8));
+  R1_REQUIRE(r1_tx_size_ok(tx_size));
+  R1_REQUIRE(r1_depth_ok(src->bit_depth));
+  R1_REQUIRE(r1_px_ok(*src));
+  R1_REQUIRE(r1_px_fits_depth(*src));
   R1_REQUIRE(edge_stride >= EDGE_LEN && group >= 1);
   if (n <= 0) return R1_OK;
   R1_REQUIRE(n % group == 0);
   R1_REQUIRE(cands && edges && lens && pos_xy && satd_out);
-  static const uint8_t wl[19] = {2, 3, 4, 5, 6, 2, 3, 3, 4, 4, 5, 5, 6, 2, 4, 3, 5, 4, 6};
-  static const uint8_t hl[19] = {2, 3, 4, 5, 6, 3, 2, 4, 3, 5, 4, 6, 5, 4, 2, 5, 3, 6, 4};
-  const int W = 1 << wl[tx_size], H = 1 << hl[tx_size];
+  const int wl = r1tx::kTxWLog2[tx_size], hl = r1tx::kTxHLog2[tx_size];
+  const int W = 1 << wl, H = 1 << hl;
   const int NC = 64 / W, FL = 2 * (W + H) + 1;
   const size_t lds = (((size_t)NC * (EDGE_LEN + 4 * FL) * sizeof(uint16_t) + 15) & ~(size_t)15) +
                      (size_t)NC * W * H * src->bytes_per_px;
   unsigned grid = (unsigned)((n / group + NC - 1) / NC) * (unsigned)group;   // (block group, member)
   // the pre-screen's sizes (luma transform blocks 8x8 .. 32x32) with the block size as a constant; at 8x8 a
   // wave walks the members of its blocks' groups itself
-  const int sq = wl[tx_size] == hl[tx_size] ? wl[tx_size] : 0;
+  const int sq = wl == hl ? wl : 0;
   if (sq == 3) grid /= (unsigned)group;
   hipStream_t st = (hipStream_t)stream;
-#define R1_SATD_LAUNCH(B, ...)                                                                            \
-  hipLaunchKernelGGL((k_intra_predict<B, true, ##__VA_ARGS__>), dim3(grid), dim3(64), lds, st,            \
-                     (int)wl[tx_size], (int)hl[tx_size], cands, n, edges, edge_stride, lens, ac,          \
-                     src->bit_depth, (void *)nullptr, *src, pos_xy, group, satd_out)
-  if (src->bytes_per_px == 1) {
-    if (sq == 3) R1_SATD_LAUNCH(1, 3, 3);
-    else if (sq == 4) R1_SATD_LAUNCH(1, 4, 4);
-    else if (sq == 5) R1_SATD_LAUNCH(1, 5, 5);
-    else R1_SATD_LAUNCH(1);
-  } else {
-    if (sq == 3) R1_SATD_LAUNCH(2, 3, 3);
-    else if (sq == 4) R1_SATD_LAUNCH(2, 4, 4);
-    else if (sq == 5) R1_SATD_LAUNCH(2, 5, 5);
-    else R1_SATD_LAUNCH(2);
-  }
-#undef R1_SATD_LAUNCH
+  r1_by_bpp(src->bytes_per_px, [&](auto B) {
+    r1_by_value<-1, 3, 4, 5>(sq, [&](auto S) {
+      hipLaunchKernelGGL((k_intra_predict<B.value, true, S.value, S.value>), dim3(grid), dim3(64), lds, st, wl, hl,
+                         cands, n, edges, edge_stride, lens, ac, src->bit_depth, (void *)nullptr, *src, pos_xy, group,
+                         satd_out);
+    });
+  });
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }
@@ -855,16 +828,15 @@ extern "C" int r1_cfl_ac_batch(r1_ctx *ctx, const R1Plane *luma, int bw, int bh,
                                int ydec, const R1CflAcCand *cands, int n, int16_t *ac,
                                void *stream) {
   R1_REQUIRE(ctx && luma);
-  R1_REQUIRE(luma->bytes_per_px == 1 || luma->bytes_per_px == 2);
+  R1_REQUIRE(r1_px_ok(*luma));
   R1_REQUIRE(r1_is_pow2(bw) && r1_is_pow2(bh) && bw >= 4 && bh >= 4 && bw <= 64 && bh <= 64);
-  R1_REQUIRE(xdec >= 0 && xdec <= 1 && ydec >= 0 && ydec <= 1 && (ydec == 0 || xdec == 1));
+  R1_REQUIRE(r1_dec_ok(xdec, ydec) && (ydec == 0 || xdec == 1));
   if (n <= 0) return R1_OK;
   R1_REQUIRE(cands && ac);
   hipStream_t st = (hipStream_t)stream;
-  if (luma->bytes_per_px == 1)
-    hipLaunchKernelGGL((k_cfl_ac<1>), dim3(n), dim3(64), 0, st, *luma, bw, bh, xdec, ydec, cands, n, ac);
-  else
-    hipLaunchKernelGGL((k_cfl_ac<2>), dim3(n), dim3(64), 0, st, *luma, bw, bh, xdec, ydec, cands, n, ac);
+  r1_by_bpp(luma->bytes_per_px, [&](auto B) {
+    hipLaunchKernelGGL((k_cfl_ac<B.value>), dim3(n), dim3(64), 0, st, *luma, bw, bh, xdec, ydec, cands, n, ac);
+  });
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }
@@ -874,24 +846,19 @@ extern "C" int r1_cfl_alpha_search_batch(r1_ctx *ctx, const R1Plane *src, int tx
                                          int edge_stride, const uint8_t *lens, const int16_t *ac,
                                          int16_t *alpha_out, uint64_t *cost_out, void *stream) {
   R1_REQUIRE(ctx && src);
-  R1_REQUIRE(tx_size >= 0 && tx_size < 19);
-  R1_REQUIRE(src->bytes_per_px == 1 || src->bytes_per_px == 2);
-  R1_REQUIRE((src->bytes_per_px == 1) == (src->bit_depth == 8));
+  R1_REQUIRE(r1_tx_size_ok(tx_size));
+  R1_REQUIRE(r1_px_ok(*src));
+  R1_REQUIRE(r1_px_fits_depth(*src));
   R1_REQUIRE(edge_stride >= EDGE_LEN);
-  static const uint8_t wl[19] = {2, 3, 4, 5, 6, 2, 3, 3, 4, 4, 5, 5, 6, 2, 4, 3, 5, 4, 6};
-  static const uint8_t hl[19] = {2, 3, 4, 5, 6, 3, 2, 4, 3, 5, 4, 6, 5, 4, 2, 5, 3, 6, 4};
-  R1_REQUIRE(wl[tx_size] <= 5 && hl[tx_size] <= 5);   // CFL: chroma transforms up to 32x32
+  const int wl = r1tx::kTxWLog2[tx_size], hl = r1tx::kTxHLog2[tx_size];
+  R1_REQUIRE(wl <= 5 && hl <= 5);   // CFL: chroma transforms up to 32x32
   if (n <= 0) return R1_OK;
   R1_REQUIRE(cands && edges && lens && ac && alpha_out);
   hipStream_t st = (hipStream_t)stream;
-  if (src->bytes_per_px == 1)
-    hipLaunchKernelGGL((k_cfl_alpha<1>), dim3(n), dim3(64), 0, st, *src, (int)wl[tx_size],
-                       (int)hl[tx_size], cands, n, edges, edge_stride, lens, ac, src->bit_depth,
-                       alpha_out, (unsigned long long *)cost_out);
-  else
-    hipLaunchKernelGGL((k_cfl_alpha<2>), dim3(n), dim3(64), 0, st, *src, (int)wl[tx_size],
-                       (int)hl[tx_size], cands, n, edges, edge_stride, lens, ac, src->bit_depth,
-                       alpha_out, (unsigned long long *)cost_out);
+  r1_by_bpp(src->bytes_per_px, [&](auto B) {
+    hipLaunchKernelGGL((k_cfl_alpha<B.value>), dim3(n), dim3(64), 0, st, *src, wl, hl, cands, n, edges, edge_stride,
+                       lens, ac, src->bit_depth, alpha_out, (unsigned long long *)cost_out);
+  });
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }

@@ -198,7 +198,7 @@ int quantize_common(r1_ctx *ctx, const void *coeffs, int coeff_stride, int n, in
   R1_REQUIRE(ctx && p);
   // av1_scan_orders has TX_TYPES = 16 columns: WHT_WHT would index out of it
   R1_REQUIRE(r1tx::valid_av1_transform(tx_size, tx_type) && tx_type < 16);
-  R1_REQUIRE(p->bit_depth == 8 || p->bit_depth == 10 || p->bit_depth == 12);
+  R1_REQUIRE(r1_depth_ok(p->bit_depth));
   R1_REQUIRE(coeff_bytes == 2 || coeff_bytes == 4);
   const int area = coded_dim(r1tx::kTxWLog2[tx_size]) * coded_dim(r1tx::kTxHLog2[tx_size]);
   const int full_area = 1 << (r1tx::kTxWLog2[tx_size] + r1tx::kTxHLog2[tx_size]);
@@ -245,8 +245,8 @@ extern "C" int r1_dequantize_batch(r1_ctx *ctx, const void *qcoeffs, int n, int 
                                    const R1QuantParams *p, int coeff_bytes, void *rcoeffs,
                                    void *stream) {
   R1_REQUIRE(ctx && p);
-  R1_REQUIRE(tx_size >= 0 && tx_size < 19);
-  R1_REQUIRE(p->bit_depth == 8 || p->bit_depth == 10 || p->bit_depth == 12);
+  R1_REQUIRE(r1_tx_size_ok(tx_size));
+  R1_REQUIRE(r1_depth_ok(p->bit_depth));
   R1_REQUIRE(coeff_bytes == 2 || coeff_bytes == 4);
   if (n <= 0) return R1_OK;
   R1_REQUIRE(qcoeffs && rcoeffs);

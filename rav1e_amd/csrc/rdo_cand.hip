@@ -8,9 +8,9 @@
 namespace {
 // The source plane and the block of every entry point: pixel format against bit depth, w x h against tx_size.
 int rdo_plane_checks(const R1Plane *org, int w, int h, int tx_size) {
-  R1_REQUIRE(org->bytes_per_px == 1 || org->bytes_per_px == 2);
-  R1_REQUIRE((org->bytes_per_px == 1) == (org->bit_depth == 8));
-  R1_REQUIRE(tx_size >= 0 && tx_size < 19);
+  R1_REQUIRE(r1_px_ok(*org));
+  R1_REQUIRE(r1_px_fits_depth(*org));
+  R1_REQUIRE(r1_tx_size_ok(tx_size));
   R1_REQUIRE((1 << r1tx::kTxWLog2[tx_size]) == w && (1 << r1tx::kTxHLog2[tx_size]) == h);
   return R1_OK;
 }
@@ -22,8 +22,8 @@ int rdo_dispatch(r1_ctx *ctx, const R1Plane *org, const R1Plane *ref, int w, int
   R1_REQUIRE(ctx && org && (ref || from_pred));
   const R1Plane no_ref = {};
   if (from_pred) ref = &no_ref;
-  R1_REQUIRE(from_pred || org->bytes_per_px == ref->bytes_per_px);
-  R1_REQUIRE(from_pred || org->bit_depth == ref->bit_depth);
+  R1_REQUIRE(from_pred || r1_same_px(*org, *ref));
+  R1_REQUIRE(from_pred || r1_same_depth(*org, *ref));
   if (const int rc = rdo_plane_checks(org, w, h, tx_size); rc != R1_OK) return rc;
   if (n <= 0) return R1_OK;
   R1_REQUIRE(cands);
@@ -32,7 +32,7 @@ int rdo_dispatch(r1_ctx *ctx, const R1Plane *org, const R1Plane *ref, int w, int
   // shifts depend only on (tx_size, bit depth) for every non-WHT type and are
   // compile-time constants of the instantiation
   const int bd = org->bit_depth;
-  R1_REQUIRE(bd == 8 || bd == 10 || bd == 12);
+  R1_REQUIRE(r1_depth_ok(bd));
   const int qm = !qa ? 0 : (qa->pix_dist ? 2 : 1);
   typedef int (*SliceFn)(R1_SLICE_ARGS);
 #define R1_RDO_SLICE_ENTRY(B, Q) r1_rdo_slice_b##B##_q##Q,
@@ -52,10 +52,10 @@ int rdo_quant_args(const r1_ctx *ctx, const R1Plane *org, int tx_size, const R1Q
                    const uint32_t *scales, int scale_stride, int xdec, int ydec, uint16_t *eob_out,
                    uint64_t *dist_out, void *qcoeffs_out, void *rec_out, RdoQuantArgs &qa) {
   R1_REQUIRE(ctx && org && params && eob_out && dist_out);
-  R1_REQUIRE(tx_size >= 0 && tx_size < 19);
+  R1_REQUIRE(r1_tx_size_ok(tx_size));
   R1_REQUIRE(params->bit_depth == org->bit_depth);
   R1_REQUIRE(dist_kind == 0 || dist_kind == R1_DIST_WSSE || dist_kind == R1_DIST_CDEF);
-  R1_REQUIRE(xdec >= 0 && xdec <= 1 && ydec >= 0 && ydec <= 1);
+  R1_REQUIRE(r1_dec_ok(xdec, ydec));
   R1_REQUIRE(dist_kind != R1_DIST_CDEF || (xdec == 0 && ydec == 0));   // cdef_dist is luma-only
   R1_REQUIRE(!scales || scale_stride > 0);
   R1_REQUIRE(dist_kind != 0 || !rec_out);
@@ -173,7 +173,7 @@ extern "C" int r1_rdo_pred_cand_batch(r1_ctx *ctx, const R1Plane *org, const voi
 // 123-148) as a bit mask over TxType, optionally cut down to RAV1E_TX_TYPES (src/transform/mod.rs:28-44):
 // the types the loop of rdo_tx_type_decision (src/rdo.rs:1732-1736) does not skip.
 extern "C" uint32_t r1_tx_type_mask(int tx_size, int is_inter, int use_reduced_set, int rav1e_types_only) {
-  if (tx_size < 0 || tx_size >= 19) return 0;
+  if (!r1_tx_size_ok(tx_size)) return 0;
   const int wl = r1tx::kTxWLog2[tx_size], hl = r1tx::kTxHLog2[tx_size];
   const int up = wl > hl ? wl : hl, dn = wl < hl ? wl : hl;   // sqr_up / sqr as log2 of the side
   // TxSet rows of av1_tx_used
@@ -210,16 +210,6 @@ extern "C" int r1_rdo_txsearch_batch(r1_ctx *ctx, const R1Plane *org, const R1Pl
 }
 
 // ---- the intra candidate in one launch: the prediction is made inside the chain (k_rdo_cand with PS = 1) ----
-void r1_intra_scratch_free(r1_ctx *c) {
-  for (int k = 0; k < r1_ctx::kIntraSlots; k++) {
-    if (c->intra_done[k]) {
-      (void)hipEventSynchronize(c->intra_done[k]);
-      (void)hipEventDestroy(c->intra_done[k]);
-    }
-    if (c->intra_scratch[k]) (void)hipFree(c->intra_scratch[k]);
-  }
-}
-
 extern "C" int r1_rdo_intra_cand_batch(r1_ctx *ctx, const R1Plane *org, int w, int h, int tx_size,
                                        const R1IntraCand *cands, int n, int edge_group, const int16_t *pos_xy,
                                        const void *edges, int edge_stride, const uint8_t *lens, const int16_t *ac,
@@ -236,7 +226,7 @@ extern "C" int r1_rdo_intra_cand_batch(r1_ctx *ctx, const R1Plane *org, int w, i
   if (rc != R1_OK) return rc;
   rc = rdo_plane_checks(org, w, h, tx_size);
   if (rc != R1_OK) return rc;
-  R1_REQUIRE(org->bit_depth == 8 || org->bit_depth == 10 || org->bit_depth == 12);
+  R1_REQUIRE(r1_depth_ok(org->bit_depth));
   // the intra source
   R1_REQUIRE(edge_stride >= R1_INTRA_EDGE_LEN && edge_group >= 1);
   if (n <= 0) return R1_OK;
@@ -274,28 +264,19 @@ extern "C" int r1_rdo_intra_cand_batch(r1_ctx *ctx, const R1Plane *org, int w, i
     R1DeviceGuard guard(ctx);
     const size_t cand_bytes = ((size_t)n * sizeof(R1RdoCand) + 255) & ~(size_t)255;
     const size_t need = cand_bytes + (pred_out ? 0 : (size_t)n * w * h * org->bytes_per_px);
-    std::lock_guard<std::mutex> lock(ctx->intra_mu);
-    const int slot = ctx->intra_next;
-    ctx->intra_next = (slot + 1) % r1_ctx::kIntraSlots;
-    if (!ctx->intra_done[slot]) R1_HIP_CHECK(hipEventCreateWithFlags(&ctx->intra_done[slot], hipEventDisableTiming));
-    else R1_HIP_CHECK(hipEventSynchronize(ctx->intra_done[slot]));
-    if (ctx->intra_scratch_bytes[slot] < need) {
-      if (ctx->intra_scratch[slot]) R1_HIP_CHECK(hipFree(ctx->intra_scratch[slot]));
-      ctx->intra_scratch[slot] = nullptr;
-      ctx->intra_scratch_bytes[slot] = 0;
-      R1_HIP_CHECK(hipMalloc(&ctx->intra_scratch[slot], need));
-      ctx->intra_scratch_bytes[slot] = need;
-    }
-    R1RdoCand *rc_dev = (R1RdoCand *)ctx->intra_scratch[slot];
-    void *pred = pred_out ? pred_out : (void *)((uint8_t *)ctx->intra_scratch[slot] + cand_bytes);
+    void *scratch;
+    rc = ctx->intra_ring.acquire(need, &scratch);
+    if (rc != R1_OK) return rc;
+    R1RdoCand *rc_dev = (R1RdoCand *)scratch;
+    void *pred = pred_out ? pred_out : (void *)((uint8_t *)scratch + cand_bytes);
     rc = r1_predict_intra_route_launch(tx_size, cands, n, edges, edge_stride, lens, edge_group, pos_xy, rc_dev, ac,
                                        org->bit_depth, org->bytes_per_px, pred, st);
     if (rc == R1_OK)
       rc = r1_rdo_txsearch_batch(ctx, org, nullptr, pred, w, h, tx_size, rc_dev, n, tx_type_mask, params, dist_kind,
                                  scales, scale_stride, xdec, ydec, sad_out, satd_out, eob_out, dist_out, est_rate_out,
                                  qcoeffs_out, rec_out, stream);
-    R1_HIP_CHECK(hipEventRecord(ctx->intra_done[slot], st));
-    return rc;
+    const int rel = ctx->intra_ring.release(st);
+    return rel != R1_OK ? rel : rc;
   }
   if (route == RDO_INTRA_FANOUT)   // slices 3 / 4
     return row[qm + 1](tx_size, *org, n, sad_out, satd_out, pred_out, &qa, &ia, st);

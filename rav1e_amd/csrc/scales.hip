@@ -315,7 +315,7 @@ extern "C" int r1_segmentation_from_centroids(const int16_t *centroids, int base
                                               R1SegmentationData *out) {
   R1_REQUIRE(centroids && out);
   R1_REQUIRE(base_q_idx >= 0 && base_q_idx <= 255);
-  R1_REQUIRE(bit_depth == 8 || bit_depth == 10 || bit_depth == 12);
+  R1_REQUIRE(r1_depth_ok(bit_depth));
   // variance in spacing between successive centroids, per k; the LAST k of minimal variance (rposition)
   uint64_t variance[6];
   for (int r = 0; r < 6; r++) {

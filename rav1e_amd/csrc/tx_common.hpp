@@ -85,24 +85,12 @@ __host__ __device__ inline bool lr_flip(int tx_type) {
   return ((1u << 5 | 1u << 7 | 1u << 15 | 1u << 6) >> tx_type) & 1u;
 }
 
-// The 19 transform sizes, written once: X(TxSize id, log2 width, log2 height).  The tables below and every
-// tx_size -> instantiation switch (fwd_tx.hip, inv_tx.hip, mc.hip, rdo_cand_kernel.hpp) expand this list.
-#define R1_TX_SIZES(X)                                                     \
-  X(0, 2, 2) X(1, 3, 3) X(2, 4, 4) X(3, 5, 5) X(4, 6, 6) X(5, 2, 3)        \
-  X(6, 3, 2) X(7, 3, 4) X(8, 4, 3) X(9, 4, 5) X(10, 5, 4) X(11, 5, 6)      \
-  X(12, 6, 5) X(13, 2, 4) X(14, 4, 2) X(15, 3, 5) X(16, 5, 3) X(17, 4, 6)  \
-  X(18, 6, 4)
+// (the 19 transform sizes, R1_TX_SIZES(X) and kTxWLog2 / kTxHLog2: entry.hpp)
 // the sizes of the headline ladder: all that experiment builds of the fused candidate kernel instantiate (slice<>)
 #define R1_TX_SIZES_HEADLINE(X) X(1, 3, 3) X(2, 4, 4) X(3, 5, 5) X(4, 6, 6)
-#define R1_TX_WL(ID, WL, HL) WL,
-#define R1_TX_HL(ID, WL, HL) HL,
-static const uint8_t kTxWLog2[19] = {R1_TX_SIZES(R1_TX_WL)};
-static const uint8_t kTxHLog2[19] = {R1_TX_SIZES(R1_TX_HL)};
-#undef R1_TX_WL
-#undef R1_TX_HL
 
 inline bool valid_av1_transform(int tx_size, int tx_type) {
-  if (tx_size < 0 || tx_size >= 19 || tx_type < 0 || tx_type >= 17) return false;
+  if (!r1_tx_size_ok(tx_size) || tx_type < 0 || tx_type >= 17) return false;
   const int wl = kTxWLog2[tx_size], hl = kTxHLog2[tx_size];
   const int m = wl > hl ? wl : hl;
   if (tx_type == 16) return wl == 2 && hl == 2;

@@ -714,6 +714,41 @@ def test_cdef_frames_spec_model(ctx, fixture, ncases):
             assert np.array_equal(got.astype(np.uint16), G[k + "_out%d" % p]), (c, p, "dirs")
 
 
+def test_cdef_frame_plane_scratch_ring_reuse_and_regrowth():
+    """r1_cdef_filter_frame_plane keeps its own analysis in a ring of four scratch slots of the context: nine calls
+    on ONE fresh context, enqueued back to back, the picture alternating 64x64 -> 192x128 -> 64x64 ... (every second
+    call finds its slot too small and regrows it, every call from the fifth on reuses a slot).  Each output equals
+    cdef_analyze_frame + cdef_filter_frame_plane_dirs on the same inputs over the whole plane allocation."""
+    import torch
+    from rav1e_amd.api import Context
+    own = Context(0)
+    try:
+        rng = np.random.default_rng(4242)
+        ystr, uvstr = rng.integers(1, 64, 8), rng.integers(1, 64, 8)
+        calls = []
+        for i in range(9):
+            W, H = (64, 64) if i % 2 == 0 else (192, 128)
+            _, src = _plane_from(rng.integers(0, 256, (H, W)).astype(np.uint8), 8)
+            skip = rng.integers(0, 2, (H // 4, W // 4)).astype(np.uint8)
+            skip[0:2, 0:2], skip[2:4, 0:2] = 1, 0                # a skipped and an unskipped 8x8 block
+            ci = rng.integers(0, 2, ((H + 63) // 64, (W + 63) // 64)).astype(np.uint8) * 5
+            ci.flat[0] = 5 * (i % 2)                             # two cdef_index values over the calls (0 and 5) ...
+            if ci.size > 1:
+                ci.flat[1] = 5 - ci.flat[0]                      # ... and inside the larger picture
+            _, dst = _plane_from(np.zeros((H, W), np.uint8), 8)
+            calls.append((W, H, src, _t(skip), _t(ci), dst))
+        for (W, H, src, skip, ci, dst) in calls:
+            own.cdef_filter_frame_plane(src, src, dst, 0, 0, 0, W, H, skip, ci, ystr, uvstr, 5, 8)
+        for i, (W, H, src, skip, ci, dst) in enumerate(calls):
+            d, v = own.cdef_analyze_frame(src, W, H, skip.shape[1], skip.shape[0])
+            _, want = _plane_from(np.zeros((H, W), np.uint8), 8)
+            own.cdef_filter_frame_plane_dirs(d, v, src, want, 0, 0, 0, W, H, skip, ci, ystr, uvstr, 5, 8)
+            assert torch.equal(dst.data, want.data), i
+            assert not torch.equal(dst.data[16:16 + H], src.data[16:16 + H]), i      # and it is no plain copy
+    finally:
+        own.close()
+
+
 @pytest.mark.parametrize("bd", [8, 10])
 def test_cdef_filter_block_vs_oracle(ctx, oracle, bd):
     """cdef_filter_block with every edge-flag combination, direction and tap parity."""

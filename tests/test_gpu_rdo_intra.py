@@ -236,6 +236,37 @@ def test_intra_cand_cfl_on_a_420_chroma_plane(ctx, oracle, bd):
                    1, 1, step != 2, ("cfl", bd, n, group, kind))
 
 
+def test_two_launch_route_scratch_ring_reuse_and_regrowth():
+    """the two-launch route (16x16, 8-bit, dist_kind 0) keeps its R1RdoCand list and, without pred_out, its dense
+    predictions in a ring of four scratch slots of the context: nine calls on ONE fresh context, enqueued back to
+    back, n alternating between one edge group of 5 and forty (every second call regrows its slot, every call from
+    the fifth on reuses one).  Each equals predict_intra_batch -> rdo_txsearch_batch(pred) on the same candidates."""
+    import torch
+    from rav1e_amd.api import Context
+    ts, bd, group = 2, 8, 5
+    w, h = TX_DIMS[ts]
+    rec, org = _planes(bd, 8800)
+    drec, dorg = _dev_plane(rec), _dev_plane(org)
+    rng = np.random.default_rng(8801)
+    own = Context(0)
+    try:
+        mask = own.tx_type_mask(ts, False)
+        calls = [make_case(rng, own, rec, drec, ts, group * (1 if i % 2 == 0 else 40), group) for i in range(9)]
+        got = [own.rdo_intra_cand_batch(dorg, w, h, cs["ic"], cs["pos"], cs["edges"], cs["lens"], mask, 90, 0,
+                                        edge_group=group, want_est_rate=True, want_qcoeffs=True) for cs in calls]
+        for i, (cs, o) in enumerate(zip(calls, got)):
+            assert "pred" not in o
+            dsets = torch.from_numpy(cs["sets"]).cuda()
+            pred = own.predict_intra_batch(ts, cs["ic"], cs["edges"][dsets].contiguous(), cs["lens"][dsets].contiguous(), bd)
+            r = own.rdo_txsearch_batch(dorg, None, w, h, cs["rc"], mask, 90, 0, is_intra=1, want_est_rate=True,
+                                       want_qcoeffs=True, pred=pred)
+            for k in ("eob", "dist", "est_rate", "qcoeffs"):
+                assert torch.equal(o[k], r[k]), (i, k)
+            assert int((o["eob"] != 0).sum()) > 0, i
+    finally:
+        own.close()
+
+
 def test_intra_cand_rejects_bad_arguments(ctx):
     """the refusals that need a context: every one leaves without a launch"""
     from rav1e_amd.api import R1Error

@@ -1,9 +1,11 @@
 // intra_pred_common.hpp -- the arithmetic of dispatch_predict_intra (src/predict.rs:705-784 and the kernels it
-// selects, 786-1505) as device functions, for the intra prediction source of the fused candidate kernel
-// (rdo_cand_kernel.hpp, PS == 1).
-// THE SAME ARITHMETIC EXISTS TWICE: k_intra_predict (predict.hip) keeps its own inline copy of these predictors --
-// calling this header from it moved its registers (47 -> 73 VGPRs at 8-bit 32x32, tools/kres.py).  A change to a
-// predictor here must be made there too; tests/test_gpu_rdo_intra.py compares the two bit for bit on every mode.
+// selects, 786-1505) as device functions, called by k_intra_predict (predict.hip) and by the intra prediction source
+// of the fused candidate kernel (rdo_cand_kernel.hpp, PS == 1).
+// edge_filter_upsample'S ARITHMETIC STILL EXISTS A SECOND TIME in one place: k_intra_predict's 8-bit 16x16 pre-screen
+// instantiation keeps an inline copy of it (INLINE_FORM in predict.hip), because with both functions from here its
+// launch was 0.4 .. 0.7 % slower and the cause was not found.  A change to the edge filter here must be made there
+// too; until that copy goes, test_intra_prescreen_vs_oracle (tests/test_gpu_parity.py) and tests/test_gpu_intra_partial_wave.py are
+// what hold it against the oracle.
 //
 // Two parts.  edge_filter_upsample is COOPERATIVE: the `lanes` lanes of a candidate build the filtered /
 // upsampled edges of a directional mode in LDS (ping-pong, every tap reads the unfiltered copy exactly like
@@ -11,13 +13,28 @@
 // predict_column is per lane: column `c` of the block, rows 0 .. H-1 through `put(row, value)`.  It does not care
 // how many lanes a candidate has.
 //
-// Edge addressing is relative to the top-left entry `tl` of a candidate's raw edge (index 2 * MAX_TX_SIZE of the
-// reference's IntraEdgeBuffer): tl[-1 - r] = the left pixel beside row r, tl[1 + i] = above[i].  A caller may keep
-// all 257 entries or only the 2 (W + H) + 1 around tl that a W x H block can reach.
+// Edge addressing: a candidate's raw edge is a base `e` and the index `tli` of its top-left entry (index
+// 2 * MAX_TX_SIZE of the reference's IntraEdgeBuffer): e[tli - 1 - r] = the left pixel beside row r,
+// e[tli + 1 + i] = above[i], and every access is written e[tli + ...].  The base is separate from the top-left entry
+// because the offset field of an LDS read is unsigned: with a constant tli at or above the window's reach the left
+// edge's indices are non-negative constants that fold into the instruction, where a negative index off a pointer to
+// the top-left entry takes an address register of its own, one per read of an unrolled row loop.  So a caller
+// whose window starts below the top-left entry passes its window's start (k_intra_predict: all 257 entries,
+// tli = 2 * MAXTX); one that holds a pointer to the top-left entry passes it with tli = 0 (the fused kernel, which
+// keeps only the 2 (W + H) + 1 entries around it that a W x H block can reach).
+//
+// The candidate record `cd` is R1IntraCand or const R1IntraCand &, and every caller has to say which (`Cand` is not
+// deduced: a call without it does not compile).  The choice is visible in the code: by value the fields are unpacked
+// once and compared as 32-bit integers, by reference every compare extracts its field (16-bit SDWA compares, a v_mov
+// per constant).  k_intra_predict's 16x16 pre-screen launch is 1.3 % faster by value; the fused kernel's
+// instantiations were tuned by reference and stay so.
 #pragma once
 #include "common.hpp"
 
 namespace r1ip {
+
+template <typename T>
+struct as_stated { using type = T; };   // a parameter of this type takes no part in template argument deduction
 
 #define R1_TABLE_QUAL static __constant__
 #include "intra_tables.inc"
@@ -77,13 +94,14 @@ __device__ __forceinline__ bool is_directional(int mode, int angle) {
 // ---- edge filter / upsample in LDS (wave-uniform barriers, per-lane predicates).  `work` = the candidate's four
 // arrays of FL = 2 (W + H) + 1 entries: af0 af1 lf0 lf1; the final edges are af0 / lf0.  Lane c of the candidate's
 // `lanes` walks the entries c, c + lanes, ...  `enable` = this lane's candidate is directional with an edge filter.
-__device__ __forceinline__ void edge_filter_upsample(const uint16_t *tl, uint16_t *work, int W, int H, int lanes, int c,
-                                                     const R1IntraCand &cd, bool enable, int left_len, int above_len,
-                                                     int32_t smax, int &up_a, int &up_l) {
+template <typename Cand>
+__device__ __forceinline__ void edge_filter_upsample(const uint16_t *e, int tli, uint16_t *work, int W, int H, int lanes,
+                                                     int c, typename as_stated<Cand>::type cd, bool enable,
+                                                     int left_len, int above_len, int32_t smax, int &up_a, int &up_l) {
   const int FL = 2 * (W + H) + 1;
   const int angle = cd.angle;
-  const uint16_t *above = tl + 1;
-  const int32_t top_left = tl[0];
+  const uint16_t *above = e + tli + 1;
+  const int32_t top_left = e[tli];
   uint16_t *af0 = work, *af1 = work + FL, *lf0 = work + 2 * FL, *lf1 = work + 3 * FL;
   const int lb_len = left_len < W + H ? left_len : W + H;
   if (__any(enable)) {
@@ -95,7 +113,7 @@ __device__ __forceinline__ void edge_filter_upsample(const uint16_t *tl, uint16_
       for (int k = c; k < FL; k += lanes) {
         af0[k] = k == 0 ? 0 : (k - 1 < al ? above[k - 1] : 0);
         // left_filtered[i] = left[left.len() - i]: i-th pixel downwards from the top
-        lf0[k] = k == 0 ? 0 : (k <= ll ? tl[-k] : 0);
+        lf0[k] = k == 0 ? 0 : (k <= ll ? e[tli - k] : 0);
       }
     }
     __syncthreads();
@@ -145,17 +163,18 @@ __device__ __forceinline__ void edge_filter_upsample(const uint16_t *tl, uint16_
 // ---- one column of the prediction: put(row, value) for rows 0 .. H-1 of column c.  `directional` / `enable` as
 // above; work / up_a / up_l as edge_filter_upsample left them.  acb: the candidate's AC block (UV_CFL_PRED), else
 // unused.
-template <typename Put>
-__device__ __forceinline__ void predict_column(int W, int H, int c, const R1IntraCand &cd, bool directional, bool enable,
-                                               int up_a, int up_l, const uint16_t *tl, const uint16_t *work,
+template <typename Cand, typename Put>
+__device__ __forceinline__ void predict_column(int W, int H, int c, typename as_stated<Cand>::type cd, bool directional,
+                                               bool enable, int up_a, int up_l, const uint16_t *e, int tli,
+                                               const uint16_t *work,
                                                int left_len, int bit_depth, const int16_t *acb, Put put) {
   const int FL = 2 * (W + H) + 1;
   const int mode = cd.mode, variant = cd.variant, angle = cd.angle;
   const int32_t smax = (1 << bit_depth) - 1;
-  const uint16_t *above = tl + 1;
-  const int32_t top_left = tl[0];
+  const uint16_t *above = e + tli + 1;
+  const int32_t top_left = e[tli];
   // left pixel beside row r (left_slice[height-1-r])
-  auto left_row = [&](int r) -> int32_t { return tl[-1 - r]; };
+  auto left_row = [&](int r) -> int32_t { return e[tli - 1 - r]; };
   const uint16_t *af0 = work, *lf0 = work + 2 * FL;
   const uint16_t *aedge = enable ? af0 : above;   // !enable: raw above, index 0 = above[0]
   const int lb_len = left_len < W + H ? left_len : W + H;
@@ -163,7 +182,7 @@ __device__ __forceinline__ void predict_column(int W, int H, int c, const R1Intr
   // raw case: left_and_left_below_slice[k] = raw[128 - lb_len + k]
   const int l = enable ? FL - 1 : lb_len - 1;
   auto ledge = [&](int k) -> int32_t {
-    return enable ? (int32_t)lf0[FL - 1 - k] : (int32_t)tl[k - lb_len];
+    return enable ? (int32_t)lf0[FL - 1 - k] : (int32_t)e[tli - lb_len + k];
   };
 
   if (directional) {
@@ -238,7 +257,7 @@ __device__ __forceinline__ void predict_column(int W, int H, int c, const R1Intr
       put(r, (pl <= pt && pl <= ptl) ? rl : (pt <= ptl ? rt : top_left));
     }
   } else if (mode == SMOOTH_PRED || mode == SMOOTH_V_PRED || mode == SMOOTH_H_PRED) {
-    const uint32_t below_pred = tl[-ls_len], right_pred = above[W - 1];
+    const uint32_t below_pred = e[tli - ls_len], right_pred = above[W - 1];
     const uint32_t a = above[c], wc = kR1SmWeights[W + c];
 #pragma unroll
     for (int r = 0; r < H; r++) {
@@ -258,7 +277,7 @@ __device__ __forceinline__ void predict_column(int W, int H, int c, const R1Intr
       avg = 128u << (bit_depth - 8);
     } else if (variant == 1) {
       uint32_t s = 0;
-      for (int i = 0; i < ls_len; i++) s += tl[-ls_len + i];
+      for (int i = 0; i < ls_len; i++) s += e[tli - ls_len + i];
       avg = (s + (uint32_t)(H >> 1)) / (uint32_t)H;
     } else if (variant == 2) {
       uint32_t s = 0;
@@ -266,7 +285,7 @@ __device__ __forceinline__ void predict_column(int W, int H, int c, const R1Intr
       avg = (s + (uint32_t)(W >> 1)) / (uint32_t)W;
     } else {
       uint32_t s = 0;
-      for (int i = 0; i < H; i++) s += tl[-ls_len + i];
+      for (int i = 0; i < H; i++) s += e[tli - ls_len + i];
       for (int i = 0; i < W; i++) s += above[i];
       avg = (s + (uint32_t)((W + H) >> 1)) / (uint32_t)(W + H);
     }

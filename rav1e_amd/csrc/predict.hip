@@ -18,49 +18,18 @@
 // array), then every lane walks its column with the reference's index
 // arithmetic.  Rows are stored as W consecutive pixels per candidate
 // (coalesced).
-// Its mode arithmetic has a TWIN: intra_pred_common.hpp states the same predictors as device functions for the fused
-// candidate kernel (rdo_cand_kernel.hpp, PS == 1).  This kernel keeps its inline form because calling the header
-// moved its registers; a change to a predictor here must be made there too.
+// The predictors themselves (edge filter / upsampler, the directional walks, DC, V, H, Paeth, the smooths, CFL) are
+// stated once, in intra_pred_common.hpp, and shared with the fused candidate kernel (rdo_cand_kernel.hpp, PS == 1);
+// this kernel owns the staging, the grouping of candidates into waves, where a column goes and the SATD tail.
+// ONE instantiation, the 8-bit 16x16 pre-screen, still carries the edge filter / upsampler inline (INLINE_FORM below):
+// a change to r1ip::edge_filter_upsample must be made there too.
 #include "common.hpp"
 #include "dist_common.hpp"
+#include "intra_pred_common.hpp"
 
-#define R1_TABLE_QUAL __constant__
-#include "intra_tables.inc"
+using namespace r1ip;
 
 namespace {
-
-enum { DC_PRED = 0, V_PRED, H_PRED, D45_PRED, D135_PRED, D113_PRED, D157_PRED,
-       D203_PRED, D67_PRED, SMOOTH_PRED, SMOOTH_V_PRED, SMOOTH_H_PRED, PAETH_PRED,
-       UV_CFL_PRED };
-constexpr int MAXTX = 64;
-constexpr int EDGE_LEN = 4 * MAXTX + 1;
-
-__device__ __forceinline__ int mode_angle(int mode) {
-  constexpr int16_t a[9] = {0, 90, 180, 45, 135, 113, 157, 203, 67};
-  return mode >= 0 && mode < 9 ? a[mode] : 0;
-}
-__device__ __forceinline__ int iabs(int v) { return v < 0 ? -v : v; }
-
-// select_ief_strength / select_ief_upsample (predict.rs:1133-1201)
-__device__ __forceinline__ int ief_strength(int wh, bool smooth, int delta) {
-  const int d = iabs(delta);
-  if (smooth) {
-    if (wh <= 8) return d >= 64 ? 2 : (d >= 40 ? 1 : 0);
-    if (wh <= 16) return d >= 48 ? 2 : (d >= 20 ? 1 : 0);
-    if (wh <= 24) return d >= 4 ? 3 : 0;
-    return 3;
-  }
-  if (wh <= 8) return d >= 56 ? 1 : 0;
-  if (wh <= 16) return d >= 40 ? 1 : 0;
-  if (wh <= 24) return d >= 32 ? 3 : (d >= 16 ? 2 : (d >= 8 ? 1 : 0));
-  if (wh <= 32) return d >= 32 ? 3 : (d >= 4 ? 2 : 1);
-  return 3;
-}
-__device__ __forceinline__ bool ief_upsample(int wh, bool smooth, int delta) {
-  const int d = iabs(delta);
-  if (d == 0 || d >= 40) return false;
-  return smooth ? wh <= 8 : wh <= 16;
-}
 
 template <int BPP>
 __device__ __forceinline__ int32_t ldp(const void *p, size_t i) {
@@ -177,19 +146,6 @@ __global__ __launch_bounds__(64) void k_intra_edges(
 }
 
 // ---------------------------------------------------------------- predict
-// filter_edge (predict.rs:1203-1233): dst[i] for 1 <= i < size from src
-__device__ __forceinline__ int32_t filt5(const uint16_t *src, int i, int size, int strength) {
-  constexpr uint8_t K[3][5] = {{0, 4, 8, 4, 0}, {0, 5, 6, 5, 0}, {2, 4, 4, 4, 2}};
-  int32_t s = 0;
-#pragma unroll
-  for (int j = 0; j < 5; j++) {
-    int k = i + j - 2;
-    k = k < 0 ? 0 : (k > size - 1 ? size - 1 : k);
-    s += K[strength - 1][j] * (int32_t)src[k];
-  }
-  return (s + 8) >> 4;
-}
-
 // SATD_OUT: the intra mode pre-screen of src/rdo.rs:1434-1506 in one launch --
 // `group` consecutive candidates (the modes of one block) share one edge set
 // and one source position; the prediction goes to LDS and only get_satd of it
@@ -199,10 +155,12 @@ __device__ __forceinline__ int32_t filt5(const uint16_t *src, int i, int size, i
 // through LDS and back: one ds_write + one ds_read per pixel, plus the address arithmetic of loops
 // with a runtime trip count).
 // waves per SIMD the register allocator is asked to make room for in the fixed-size pre-screen
-// instantiations: left alone it takes 79 / 113 VGPRs (16x16 / 32x32); asked, 44 / 68 without a spill
-// (tools/kres.py): launches 0.136 -> 0.133 and 0.126 -> 0.103 ms
+// instantiations: left alone it took 79 / 113 VGPRs (16x16 / 32x32); asked, 44 / 68 without a spill
+// (tools/kres.py): launches 0.136 -> 0.133 and 0.126 -> 0.103 ms.  Those figures are the inline predictors'; with the
+// shared ones (intra_pred_common.hpp) the same requests give 43 / 74 at 8 bits and 56 / 74 at 10, still without a
+// spill, and the 8x8 kernel, asked nothing, takes 79 and runs 6 waves (profiles/HISTORY.md has the timings).
 constexpr int intra_waves_hint(bool satd, int wlt) {
-  return !satd ? 1 : (wlt == 4 ? 7 : (wlt == 5 ? 5 : 1));   // 8x8 at 6 waves (79 VGPRs): +1.7 % on the launch, left alone
+  return !satd ? 1 : (wlt == 4 ? 7 : (wlt == 5 ? 5 : 1));   // 8x8: a request for 6 once measured +1.7 %, so none is made
 }
 
 // EGRP (the dense form only; the two-launch route of r1_rdo_intra_cand_batch): `group` consecutive candidates share
@@ -222,6 +180,13 @@ __global__ __launch_bounds__(64, intra_waves_hint(SATD_OUT, WLT)) void k_intra_p
   const int W = 1 << wl, H = 1 << hl;
   const int NC = 64 >> wl;
   constexpr bool IN_REGS = SATD_OUT && FIXED;
+  // The 8-bit 16x16 pre-screen keeps the EDGE FILTER / UPSAMPLER inline (r1ip::edge_filter_upsample's arithmetic a
+  // second time), as every instantiation had it before the predictors moved to intra_pred_common.hpp.  With both
+  // halves from the header its launch measured 0.4 .. 0.7 % above the inline form's run-to-run band; with either
+  // half inline it is inside (profiles/HISTORY.md).  Why the pair costs what neither half does was not found.  A
+  // change to the edge filter in the header must be made in that block too; test_intra_prescreen_vs_oracle (tests/test_gpu_parity.py) and
+  // tests/test_gpu_intra_partial_wave.py hold this instantiation against the oracle.
+  constexpr bool INLINE_FORM = BPP == 1 && SATD_OUT && WLT == 4 && HLT == 4;
   int32_t pv[IN_REGS ? (1 << (HLT < 0 ? 0 : HLT)) : 1];   // IN_REGS: the lane's prediction column
   const int FL = 2 * (W + H) + 1;
   const int lane = threadIdx.x;
@@ -288,216 +253,89 @@ __global__ __launch_bounds__(64, intra_waves_hint(SATD_OUT, WLT)) void k_intra_p
   }
   R1IntraCand cd = {};
   if (live) cd = cands[cand];
-  const int mode = cd.mode, variant = cd.variant, angle = cd.angle;
-  const int32_t smax = (1 << bit_depth) - 1;
-  const uint16_t *above = raw + 2 * MAXTX + 1;
-  const int32_t top_left = raw[2 * MAXTX];
-  // left pixel beside row r (left_slice[height-1-r])
-  auto left_row = [&](int r) -> int32_t { return raw[2 * MAXTX - 1 - r]; };
   void *out = SATD_OUT ? (void *)((uint8_t *)smem + ((NC * (EDGE_LEN + 4 * FL) * 2 + 15) & ~15) +
                                   (size_t)cl * W * H * BPP)
                        : (void *)((uint8_t *)dst + (size_t)cand * W * H * BPP);
-
-  // one predicted pixel of this lane's column (row `i_`)
-#define R1_PUT(i_, v_)                                                   \
-  do {                                                                   \
-    if constexpr (IN_REGS) pv[i_] = (v_);                                \
-    else stp<BPP>(out, (size_t)(i_) * W + c, (v_));                      \
-  } while (0)
-  const bool directional = live && mode >= V_PRED && mode <= D67_PRED &&
-                           !(mode == V_PRED && angle == 90) && !(mode == H_PRED && angle == 180);
+  const bool directional = live && is_directional(cd.mode, cd.angle);
   const bool enable = directional && cd.ief != 0;
-  // ---- edge filter / upsample in LDS (wave-uniform barriers, per-lane predicates)
+  // the cooperative part holds the workgroup's barriers: dead lanes go through it too (cd by value: see the header)
   int up_a = 0, up_l = 0;
-  const uint16_t *aedge = above;      // !enable: raw above, index 0 = above[0]
-  uint16_t *af0 = work, *af1 = work + FL, *lf0 = work + 2 * FL, *lf1 = work + 3 * FL;
-  const int lb_len = left_len < W + H ? left_len : W + H;
-  if (__any(enable)) {
-    const bool smooth = cd.ief == 2;
-    const int wh = W + H;
-    if (enable) {
-      const int al = above_len < FL - 1 ? above_len : FL - 1;
-      const int ll = lb_len < FL - 1 ? lb_len : FL - 1;
-      for (int k = c; k < FL; k += W) {
-        af0[k] = k == 0 ? 0 : (k - 1 < al ? above[k - 1] : 0);
-        // left_filtered[i] = left[left.len() - i]: i-th pixel downwards from the top
-        lf0[k] = k == 0 ? 0 : (k <= ll ? raw[2 * MAXTX - k] : 0);
-      }
-    }
-    __syncthreads();
-    int npa = 0, npl = 0, sa = 0, sl = 0;
-    if (enable && angle != 90 && angle != 180) {
-      if (c == 0) { af0[0] = (uint16_t)top_left; lf0[0] = (uint16_t)top_left; }
-      npa = (W < cd.avail_w ? W : cd.avail_w) + (angle < 90 ? H : 0) + 1;
-      npl = (H < cd.avail_h ? H : cd.avail_h) + (angle > 180 ? W : 0) + 1;
-      sa = ief_strength(wh, smooth, angle - 90);
-      sl = ief_strength(wh, smooth, angle - 180);
-    }
-    __syncthreads();
-    if (enable)
-      for (int k = c; k < FL; k += W) {
-        af1[k] = (sa && k >= 1 && k < npa) ? (uint16_t)filt5(af0, k, npa, sa) : af0[k];
-        lf1[k] = (sl && k >= 1 && k < npl) ? (uint16_t)filt5(lf0, k, npl, sl) : lf0[k];
-      }
-    __syncthreads();
-    // upsample_edge (predict.rs:1235-1266): af1/lf1 (filtered) -> af0/lf0 (final)
-    if (enable) {
-      up_a = ief_upsample(wh, smooth, angle - 90);
-      up_l = ief_upsample(wh, smooth, angle - 180);
-      const int na = W + (angle < 90 ? H : 0), nl = H + (angle > 180 ? W : 0);
-      auto ups = [&](const uint16_t *s, uint16_t *d, int size) {
-        auto dup = [&](int i) -> int32_t {
-          return i == 0 ? s[0] : (i <= size + 1 ? s[i - 1] : s[size]);
-        };
-        for (int k = c; k < FL; k += W)     // entries outside [1, 2*size] keep s
-          if (k == 0 || k > 2 * size) d[k] = s[k];
-        for (int i = c; i < size; i += W) {
-          int32_t v = -dup(i) + 9 * dup(i + 1) + 9 * dup(i + 2) - dup(i + 3);
-          v = (v + 8) / 16;
-          v = v < 0 ? 0 : (v > smax ? smax : v);
-          d[2 * i + 1] = (uint16_t)v;
-          d[2 * i + 2] = (uint16_t)dup(i + 2);
+  if constexpr (INLINE_FORM) {
+    const int angle = cd.angle;
+    const int32_t smax = (1 << bit_depth) - 1;
+    const uint16_t *above = raw + 2 * MAXTX + 1;
+    const int32_t top_left = raw[2 * MAXTX];
+    // ---- edge filter / upsample in LDS (wave-uniform barriers, per-lane predicates)
+    uint16_t *af0 = work, *af1 = work + FL, *lf0 = work + 2 * FL, *lf1 = work + 3 * FL;
+    const int lb_len = left_len < W + H ? left_len : W + H;
+    if (__any(enable)) {
+      const bool smooth = cd.ief == 2;
+      const int wh = W + H;
+      if (enable) {
+        const int al = above_len < FL - 1 ? above_len : FL - 1;
+        const int ll = lb_len < FL - 1 ? lb_len : FL - 1;
+        for (int k = c; k < FL; k += W) {
+          af0[k] = k == 0 ? 0 : (k - 1 < al ? above[k - 1] : 0);
+          // left_filtered[i] = left[left.len() - i]: i-th pixel downwards from the top
+          lf0[k] = k == 0 ? 0 : (k <= ll ? raw[2 * MAXTX - k] : 0);
         }
-      };
-      if (up_a) ups(af1, af0, na);
-      else for (int k = c; k < FL; k += W) af0[k] = af1[k];
-      if (up_l) ups(lf1, lf0, nl);
-      else for (int k = c; k < FL; k += W) lf0[k] = lf1[k];
+      }
+      __syncthreads();
+      int npa = 0, npl = 0, sa = 0, sl = 0;
+      if (enable && angle != 90 && angle != 180) {
+        if (c == 0) { af0[0] = (uint16_t)top_left; lf0[0] = (uint16_t)top_left; }
+        npa = (W < cd.avail_w ? W : cd.avail_w) + (angle < 90 ? H : 0) + 1;
+        npl = (H < cd.avail_h ? H : cd.avail_h) + (angle > 180 ? W : 0) + 1;
+        sa = ief_strength(wh, smooth, angle - 90);
+        sl = ief_strength(wh, smooth, angle - 180);
+      }
+      __syncthreads();
+      if (enable)
+        for (int k = c; k < FL; k += W) {
+          af1[k] = (sa && k >= 1 && k < npa) ? (uint16_t)filt5(af0, k, npa, sa) : af0[k];
+          lf1[k] = (sl && k >= 1 && k < npl) ? (uint16_t)filt5(lf0, k, npl, sl) : lf0[k];
+        }
+      __syncthreads();
+      // upsample_edge (predict.rs:1235-1266): af1/lf1 (filtered) -> af0/lf0 (final)
+      if (enable) {
+        up_a = ief_upsample(wh, smooth, angle - 90);
+        up_l = ief_upsample(wh, smooth, angle - 180);
+        const int na = W + (angle < 90 ? H : 0), nl = H + (angle > 180 ? W : 0);
+        auto ups = [&](const uint16_t *s, uint16_t *d, int size) {
+          auto dup = [&](int i) -> int32_t {
+            return i == 0 ? s[0] : (i <= size + 1 ? s[i - 1] : s[size]);
+          };
+          for (int k = c; k < FL; k += W)     // entries outside [1, 2*size] keep s
+            if (k == 0 || k > 2 * size) d[k] = s[k];
+          for (int i = c; i < size; i += W) {
+            int32_t v = -dup(i) + 9 * dup(i + 1) + 9 * dup(i + 2) - dup(i + 3);
+            v = (v + 8) / 16;
+            v = v < 0 ? 0 : (v > smax ? smax : v);
+            d[2 * i + 1] = (uint16_t)v;
+            d[2 * i + 2] = (uint16_t)dup(i + 2);
+          }
+        };
+        if (up_a) ups(af1, af0, na);
+        else for (int k = c; k < FL; k += W) af0[k] = af1[k];
+        if (up_l) ups(lf1, lf0, nl);
+        else for (int k = c; k < FL; k += W) lf0[k] = lf1[k];
+      }
+      __syncthreads();
     }
-    __syncthreads();
-    if (enable) aedge = af0;
+  } else {
+    edge_filter_upsample<R1IntraCand>(raw, 2 * MAXTX, work, W, H, W, c, cd, enable, left_len, above_len,
+                                      (1 << bit_depth) - 1, up_a, up_l);
   }
   if (!live) {
     if constexpr (LOOPED) continue;
     else return;
   }
-
-  // left_edge[k] of the reference (after left_filtered.reverse()) = lf0[FL-1-k];
-  // raw case: left_and_left_below_slice[k] = raw[128 - lb_len + k]
-  const int l = enable ? FL - 1 : lb_len - 1;
-  auto ledge = [&](int k) -> int32_t {
-    return enable ? (int32_t)lf0[FL - 1 - k] : (int32_t)raw[2 * MAXTX - lb_len + k];
-  };
-
-  if (directional) {
-    int dx = 0, dy = 0;
-    if (angle < 90) dx = kR1DrIntraDerivative[angle];
-    else if (angle > 90 && angle < 180) dx = kR1DrIntraDerivative[180 - angle];
-    if (angle > 90 && angle < 180) dy = kR1DrIntraDerivative[angle - 90];
-    else if (angle > 180) dy = kR1DrIntraDerivative[270 - angle];
-    const int oa = (enable ? 1 : 0) << up_a, ol = (enable ? 1 : 0) << up_l;
-    const int j = c;
-#pragma unroll
-    for (int i = 0; i < H; i++) {
-      int32_t v;
-      if (angle < 90) {
-        const int idx = (i + 1) * dx;
-        const int base = (idx >> (6 - up_a)) + (j << up_a);
-        const int shift = ((idx << up_a) >> 1) & 31;
-        const int mb = (H + W - 1) << up_a;
-        if (base < mb)
-          v = ((int32_t)aedge[base + oa] * (32 - shift) + (int32_t)aedge[base + 1 + oa] * shift + 16) >> 5;
-        else
-          v = aedge[mb + oa];
-      } else if (angle < 180) {
-        int idx = (j << 6) - (i + 1) * dx;
-        int base = idx >> (6 - up_a);
-        if (base >= -(1 << up_a)) {
-          const int shift = ((idx << up_a) >> 1) & 31;
-          const int32_t a = (!enable && base < 0) ? top_left : (int32_t)aedge[base + oa];
-          const int32_t b = aedge[base + 1 + oa];
-          v = (a * (32 - shift) + b * shift + 16) >> 5;
-        } else {
-          idx = (i << 6) - (j + 1) * dy;
-          base = idx >> (6 - up_l);
-          const int shift = ((idx << up_l) >> 1) & 31;
-          int32_t a, b;
-          if (!enable && base < 0) a = top_left;
-          else if (base + ol == -2) a = ledge(0);
-          else a = ledge(l - (base + ol));
-          if (base + ol == -2) b = ledge(1);
-          else b = ledge(l - (base + ol + 1));
-          v = (a * (32 - shift) + b * shift + 16) >> 5;
-        }
-      } else {
-        const int idx = (j + 1) * dy;
-        const int base = (idx >> (6 - up_l)) + (i << up_l);
-        const int shift = ((idx << up_l) >> 1) & 31;
-        int ia = l - (base + ol), ib = l - (base + ol + 1);
-        ia = ia < 0 ? 0 : ia;
-        ib = ib < 0 ? 0 : ib;
-        v = (ledge(ia) * (32 - shift) + ledge(ib) * shift + 16) >> 5;
-      }
-      R1_PUT(i, v < 0 ? 0 : (v > smax ? smax : v));
-    }
-  }
-  // ---- non-directional ----
-  const int ls_len = left_len < H ? left_len : H;
-  if (directional) {
-  } else if (mode == V_PRED) {
-    const int32_t a = above[c];
-#pragma unroll
-    for (int r = 0; r < H; r++) R1_PUT(r, a);
-  } else if (mode == H_PRED) {
-#pragma unroll
-    for (int r = 0; r < H; r++) R1_PUT(r, left_row(r));
-  } else if (mode == PAETH_PRED) {
-    const int32_t rt = above[c];
-#pragma unroll
-    for (int r = 0; r < H; r++) {
-      const int32_t rl = left_row(r);
-      const int32_t base = rt + rl - top_left;
-      const int32_t pl = iabs(base - rl), pt = iabs(base - rt), ptl = iabs(base - top_left);
-      R1_PUT(r, (pl <= pt && pl <= ptl) ? rl : (pt <= ptl ? rt : top_left));
-    }
-  } else if (mode == SMOOTH_PRED || mode == SMOOTH_V_PRED || mode == SMOOTH_H_PRED) {
-    const uint32_t below_pred = raw[2 * MAXTX - ls_len], right_pred = above[W - 1];
-    const uint32_t a = above[c], wc = kR1SmWeights[W + c];
-#pragma unroll
-    for (int r = 0; r < H; r++) {
-      const uint32_t lft = (uint32_t)left_row(r), wr = kR1SmWeights[H + r];
-      uint32_t p;
-      if (mode == SMOOTH_PRED)
-        p = (wr * a + (256 - wr) * below_pred + wc * lft + (256 - wc) * right_pred + 256) >> 9;
-      else if (mode == SMOOTH_H_PRED)
-        p = (wc * lft + (256 - wc) * right_pred + 128) >> 8;
-      else
-        p = (wr * a + (256 - wr) * below_pred + 128) >> 8;
-      R1_PUT(r, (int32_t)p);
-    }
-  } else {   // DC_PRED / UV_CFL_PRED
-    uint32_t avg;
-    if (variant == 0) {
-      avg = 128u << (bit_depth - 8);
-    } else if (variant == 1) {
-      uint32_t s = 0;
-      for (int i = 0; i < ls_len; i++) s += raw[2 * MAXTX - ls_len + i];
-      avg = (s + (uint32_t)(H >> 1)) / (uint32_t)H;
-    } else if (variant == 2) {
-      uint32_t s = 0;
-      for (int i = 0; i < W; i++) s += above[i];
-      avg = (s + (uint32_t)(W >> 1)) / (uint32_t)W;
-    } else {
-      uint32_t s = 0;
-      for (int i = 0; i < H; i++) s += raw[2 * MAXTX - ls_len + i];
-      for (int i = 0; i < W; i++) s += above[i];
-      avg = (s + (uint32_t)((W + H) >> 1)) / (uint32_t)(W + H);
-    }
-    if (mode == UV_CFL_PRED && angle != 0) {
-      const int16_t *acb = ac + cand * (W * H);
-#pragma unroll
-      for (int r = 0; r < H; r++) {
-        const int32_t q6 = (int32_t)(int16_t)angle * (int32_t)acb[r * W + c];
-        const int32_t q0 = (iabs(q6) + 32) >> 6;
-        const int32_t v = (int32_t)avg + (q6 < 0 ? -q0 : q0);
-        R1_PUT(r, v < 0 ? 0 : (v > smax ? smax : v));
-      }
-    } else {
-#pragma unroll
-      for (int r = 0; r < H; r++) R1_PUT(r, (int32_t)avg);
-    }
-  }
-#undef R1_PUT
+  // one predicted pixel of this lane's column: a register (IN_REGS) or row i of `out`
+  predict_column<R1IntraCand>(W, H, c, cd, directional, enable, up_a, up_l, raw, 2 * MAXTX, work, left_len, bit_depth,
+                              ac ? ac + cand * (W * H) : nullptr, [&](int i, int32_t v) {
+                                if constexpr (IN_REGS) pv[i] = v;
+                                else stp<BPP>(out, (size_t)i * W + c, v);
+                              });
   if constexpr (SATD_OUT) {
     __builtin_amdgcn_wave_barrier();
     const bool small = (W < H ? W : H) == 4;

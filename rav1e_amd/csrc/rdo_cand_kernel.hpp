@@ -270,14 +270,15 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
     const uint16_t *tl = eraw + (W + H);
     uint16_t *work = eraw + FL;
     int up_a = 0, up_l = 0;
-    r1ip::edge_filter_upsample(tl, work, W, H, P, c, ic, enable, left_len, above_len, (1 << BD) - 1, up_a, up_l);
+    r1ip::edge_filter_upsample<const R1IntraCand &>(tl, 0, work, W, H, P, c, ic, enable, left_len, above_len,
+                                                     (1 << BD) - 1, up_a, up_l);
     int32_t pred[H];
     if (col_live) {
       // (a CFL candidate without an AC buffer -- the entry point refuses the ones it can see -- predicts its DC)
       if (ic.mode == r1ip::UV_CFL_PRED && !ia.ac) ic.angle = 0;
       const int16_t *acb = ic.mode == r1ip::UV_CFL_PRED && ia.ac ? ia.ac + (size_t)cand_ld * (W * H) : nullptr;
-      r1ip::predict_column(W, H, c, ic, directional, enable, up_a, up_l, tl, work, left_len, BD, acb,
-                           [&](int i, int32_t pv) { pred[i] = pv; });
+      r1ip::predict_column<const R1IntraCand &>(W, H, c, ic, directional, enable, up_a, up_l, tl, 0, work, left_len, BD,
+                                                 acb, [&](int i, int32_t pv) { pred[i] = pv; });
       if (pred_out && live_st) {
         if constexpr (BPP == 1) {
           uint8_t *pp = (uint8_t *)pred_out + (size_t)cand * W * H + c;

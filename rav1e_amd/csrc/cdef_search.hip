@@ -17,6 +17,7 @@
 // scratch copy (rdo.rs:2277-2284).  Integer arithmetic throughout.
 #include "cdef_common.hpp"
 #include "dist_common.hpp"
+#include "sgr_trial.hpp"
 
 namespace {
 using namespace r1cdef;
@@ -115,7 +116,7 @@ __device__ __forceinline__ uint32_t swz_xor4(uint32_t v) {
 }
 
 // MODE 0: the search (first pass).  MODE 1: a later pass -- planes of a superblock whose restoration unit has a
-// self-guided choice get their filtered pixels STORED per index (the restoration trial reads them, lrf.hip), the
+// self-guided choice get their filtered pixels STORED per index (the restoration trial reads them, lrf_search.hip), the
 // others are measured as in MODE 0.  MODE 2: cdef_filter_superblock with the superblock's chosen index into `out`
 // (rdo.rs:2546-2560 "keep cdef output up to date"), everything else copied through: the CDEF working copy.
 template <int BPP, int XD, int YD, bool LUMA, int MODE = 0>
@@ -517,12 +518,6 @@ ScratchMap scratch_map(int mi_cols, int mi_rows, int xdec, int ydec, int bpp, in
 
 }  // namespace
 
-// lrf.hip: the restoration trial of one plane (sgr_tile lives there)
-__attribute__((visibility("hidden")))
-int r1i_sgr_trial_err_launch(const R1Plane &trial, size_t trial_idx_bytes, const R1Plane &cdef_cur, const R1Plane &src,
-                             const R1TrialUnit *units, int n_units, int n_idx, int pli, int xdec, int ydec,
-                             const uint32_t *scales, int scale_stride, unsigned long long *psum, int n_sb, hipStream_t st);
-
 // scratch: the per-superblock sums [n_sb][8][3] u64, then (var i32, dir u8) per 8x8 block of the grid
 extern "C" long long r1_cdef_strength_search_scratch_bytes(int mi_cols, int mi_rows) {
   const long long n_sb = (long long)((mi_cols + 15) / 16) * ((mi_rows + 15) / 16);
@@ -587,7 +582,7 @@ extern "C" int r1_cdef_lrf_trial_batch(r1_ctx *ctx, const R1Plane *rec, const R1
       R1_REQUIRE(cdef_cur[k].width >= rec[k].width && cdef_cur[k].height >= rec[k].height);
     }
   const ScratchMap m = scratch_map(mi_cols, mi_rows, np == 1 ? 0 : a.p.xdec, np == 1 ? 0 : a.p.ydec, bpp, a.p.n_idx, np);
-  for (int k = 0; k < np; k++) R1_REQUIRE(m.plane_bytes[k] < (1ull << 32));   // 32-bit byte offsets in lrf.hip's tile loads
+  for (int k = 0; k < np; k++) R1_REQUIRE(m.plane_bytes[k] < (1ull << 32));   // 32-bit byte offsets in lrf_search.hip's tile loads
   R1DeviceGuard guard(ctx);
   hipStream_t st = (hipStream_t)stream;
   uint8_t *sc = (uint8_t *)scratch;

@@ -2,7 +2,7 @@
 // (candidates from HBM) and me_blocks.hip (sub-pel candidates predicted into LDS), and
 // the reference's pixel-domain distortion arithmetic, each rule stated once for
 // every kernel that needs it (dist_scaled.hip, the fused candidate kernel,
-// lrf.hip, cdef_search.hip):
+// lrf_search.hip, cdef_search.hip):
 //   CdefMoments       cdef_dist_kernel's five sums: add / xor_sum / store / load
 //   cdef_tile_vars    its fixed-point tail -> (svar, dvar, sse)
 //   cdef_tile_tail    ... + apply_ssim_boost + the block's DistortionScale

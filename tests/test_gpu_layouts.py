@@ -474,7 +474,7 @@ def test_deblock(ctx, oracle, bd, kinds):
 @pytest.mark.parametrize("bd", [8, 10])
 def test_lrf(ctx, oracle, bd, w, kinds):
     """r1_lrf_sgrproj_plane, r1_sgrproj_solve_batch and r1_lrf_search_batch on one and on two 64-pixel units.
-    luma_block_moments (csrc/lrf.hip) loads eight source pixels at once where po = data + ((yorigin + y) * stride +
+    luma_block_moments (csrc/lrf_search.hip) loads eight source pixels at once where po = data + ((yorigin + y) * stride +
     xorigin + x) * BPP is a multiple of 8 * BPP, x a multiple of 8.  "tight" with 8 pixels of padding keeps that for
     every row at both depths (base aligned, xorigin 8, stride 80 or 144).  "odd" (base one element past the
     boundary, xorigin 9, stride 81 or 145: 1 + 9 + row * 81 elements) leaves one row in eight aligned, at 8 and at

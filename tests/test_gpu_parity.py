@@ -1740,7 +1740,7 @@ def test_lrf_search_ref(ctx, case):
 
 def test_lrf_entry_points_reject_planes_their_32_bit_offsets_cannot_address(ctx):
     """the restoration kernels address pixels with 32-bit byte offsets and 24-bit row / stride factors
-    (csrc/lrf.hip, px_off): a descriptor beyond that is R1_EINVAL before anything is launched"""
+    (csrc/sgr_common.hpp, px_off): a descriptor beyond that is R1_EINVAL before anything is launched"""
     from rav1e_amd.api import SGR_SOLVE_UNIT
     a, b = planes(8, seed=3)
     da, db = dev_plane(a), dev_plane(b)
@@ -1765,16 +1765,17 @@ def test_lrf_entry_points_reject_planes_their_32_bit_offsets_cannot_address(ctx)
         da.stride, da.alloc_height = keep
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 def test_lrf_search_vs_oracle_frame_units(ctx, oracle, bd):
     """every 64x64 luma unit (and the 32x32 units of a 4:2:0 chroma plane) of a 520x264 frame -- the last
     column of units 8 wide, the last row 8 high -- x {no filter, four parameter sets}, against
-    oracle/lrf.c::r1o_lrf_search_unit"""
+    oracle/lrf.c::r1o_lrf_search_unit.  12 bits (the one-launch kernel's unpacked instantiation) on a 136x72
+    frame: luma units 64, 64 and 8 wide, 64 and 8 high; chroma 32, 32 and 4 wide, 32 and 4 high"""
     import ctypes as C
     import torch
     from rav1e_amd.api import SGR_SOLVE_UNIT
     rng = np.random.default_rng(77 + bd)
-    W, H = 520, 264
+    W, H = (136, 72) if bd == 12 else (520, 264)
     yy, xx = np.mgrid[0:H, 0:W]
     srcY = np.clip((np.sin(xx / 7.0) + np.cos(yy / 5.0) + 2) / 4 * ((1 << bd) - 1), 0, (1 << bd) - 1).astype(np.int64)
     inY = np.clip(srcY + rng.integers(-8, 9, (H, W)) * (1 << (bd - 8)), 0, (1 << bd) - 1)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Instruction histogram of the gfx950 code of one .hip file, per kernel.
 
-  python tools/isa_hist.py rav1e_amd/csrc/lrf.hip [kernel-name-substring ...]
+  python tools/isa_hist.py rav1e_amd/csrc/lrf_search.hip [kernel-name-substring ...]
   python tools/isa_hist.py --json OUT.json -DR1_RDO_TU_BD=8 -DR1_RDO_TU_QM=0 -DR1_HEADLINE_ONLY
       rav1e_amd/csrc/rdo_cand_slice.hip k_rdo_cand
       (one slice of the fused kernel; the 8- and 10-bit slices 0 together are the per-kernel VALU mix of

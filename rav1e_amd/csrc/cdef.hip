@@ -1,22 +1,18 @@
-// cdef.hip -- CDEF direction search and filter
+// cdef.hip -- CDEF direction search and filter: the entry points of the filter
 // (reference: cdef_find_dir src/cdef.rs:84-143, constrain 146-159,
 // cdef_filter_block 198-298, adjust_strength 313-321,
 // cdef_analyze_superblock 340-373, cdef_filter_superblock / cdef_filter_tile
-// 405-625; x86 dispatch src/asm/x86/cdef.rs).
-//
-// Mapping: one wave per 8x8 luma block position, lane = pixel.
-//  direction  every lane adds its pixel (>> coeff_shift, - 128) into the 8x15
-//             partial-sum table in LDS (ds_add: integer adds, order-free), the
-//             eight direction costs are formed by lanes 0..7 and the first
-//             maximum (cdef.rs:64-73) is taken across them.
-//  filter     lane = pixel of the (8>>xdec)x(8>>ydec) block of the plane; the
-//             twelve taps are read straight from the deblocked input plane
-//             (L1/L2 resident: neighbouring blocks share their halos); taps in
-//             a halo the `edges` flags do not grant read as CDEF_VERY_LARGE,
-//             exactly like the reference's padded u16 tile (cdef.rs:161-196).
-// The frame kernel fuses cdef_analyze_superblock + cdef_filter_superblock for
-// one plane: skip test, direction, strength adjustment, edge flags, filter or
-// copy.  Integer arithmetic throughout.
+// 405-625; x86 dispatch src/asm/x86/cdef.rs).  Two families of kernels, integer arithmetic throughout:
+//  per-block batches  k_cdef_find_dir, k_cdef_filter: one wave per 8x8 luma block position of a candidate
+//             list, lane = pixel.  Direction: find_dir_wave (cdef_common.hpp).  Filter: lane = pixel of the
+//             (8>>xdec)x(8>>ydec) block of the plane; the twelve taps are read straight from the deblocked
+//             input plane (L1/L2 resident: neighbouring blocks share their halos); taps in a halo the `edges`
+//             flags do not grant read as CDEF_VERY_LARGE, like the reference's padded u16 tile (cdef.rs:161-196).
+//  the frame filter   k_cdef_analyze (cdef_common.hpp: a thread per 8x8 block) + k_cdef_frame:
+//             cdef_filter_superblock for one plane of the frame on packed pixel pairs.  Its steps -- tap offsets,
+//             block records, tile staging, tap reads, rounding, stores -- are the shared ones of cdef_common.hpp,
+//             which the strength search (cdef_search.hip) runs too; the lane map, the tile stride and the record
+//             layout are this kernel's own.
 #include "cdef_common.hpp"
 
 namespace {
@@ -24,8 +20,7 @@ using namespace r1cdef;
 
 __device__ __forceinline__ int32_t constrain(int32_t diff, int32_t threshold, int32_t damping) {
   if (!threshold) return 0;
-  int shift = damping - (31 - __clz(threshold));
-  shift = shift < 0 ? 0 : shift;
+  const int shift = constrain_shift(threshold, damping);
   const int32_t ad = diff < 0 ? -diff : diff;
   int32_t mag = threshold - (ad >> shift);
   mag = mag < 0 ? 0 : (mag > ad ? ad : mag);
@@ -37,14 +32,6 @@ __device__ __forceinline__ int32_t constrain(int32_t diff, int32_t threshold, in
 template <typename RD>
 __device__ __forceinline__ int32_t filter_pixel_rd(RD rd, int i, int j, int pri, int sec, int dir,
                                                    int damping, int coeff_shift) {
-  // cdef_directions (cdef.rs:225-234) packed as nibbles (value + 2) so that the
-  // lookup is two shifts instead of a dependent table load
-  constexpr uint32_t DY0 = 0x33332221u, DX0 = 0x22233333u, DY1 = 0x44443210u, DX1 = 0x12344444u;
-  auto dyx = [&](int d, int k, int &dy, int &dx) {
-    const int sh = 4 * d;
-    dy = (int)(((k == 0 ? DY0 : DY1) >> sh) & 0xf) - 2;
-    dx = (int)(((k == 0 ? DX0 : DX1) >> sh) & 0xf) - 2;
-  };
   const int32_t x = rd(i, j);
   int32_t sum = 0, mx = x, mn = x;
   const int odd = (pri >> coeff_shift) & 1;
@@ -53,9 +40,9 @@ __device__ __forceinline__ int32_t filter_pixel_rd(RD rd, int i, int j, int pri,
     const int pri_tap = odd ? 3 : (k == 0 ? 4 : 2);
     const int sec_tap = k == 0 ? 2 : 1;
     int d0y, d0x, d1y, d1x, d2y, d2x;
-    dyx(dir, k, d0y, d0x);
-    dyx((dir + 2) & 7, k, d1y, d1x);
-    dyx((dir + 6) & 7, k, d2y, d2x);
+    dir_dyx(dir, k, d0y, d0x);
+    dir_dyx((dir + 2) & 7, k, d1y, d1x);
+    dir_dyx((dir + 6) & 7, k, d2y, d2x);
     const int32_t p[2] = {rd(i + d0y, j + d0x), rd(i - d0y, j - d0x)};
 #pragma unroll
     for (int t = 0; t < 2; t++) {
@@ -114,9 +101,8 @@ struct CdefFrameArgs {
 // horizontally adjacent pixels held as one packed i16 pair: all of constrain(), the tap sum and
 // the min / max tracking run on v_pk_* instructions, 12 (+ 1 to pair the two reads) per tap for
 // two pixels.
-//  * the region plus its halo (2 rows above / below, 4 columns left / right so that every global
-//    load is one aligned 4-pixel group) is staged once in LDS as u16 with CDEF_VERY_LARGE where
-//    the picture ends -- a halo pixel is missing exactly when it lies outside
+//  * the region plus its halo (Tile, cdef_common.hpp) is staged once in LDS as u16 with
+//    CDEF_VERY_LARGE where the picture ends -- a halo pixel is missing exactly when it lies outside
 //    [0, 8*floor(W/8)) x [0, 8*floor(H/8)) in luma units, which is what the reference's edge flags
 //    say block by block (`bx + 1 >= xavail >> 3`, first row / column; cdef.rs:441-459);
 //  * what depends on the 8x8 block only (skip, strengths after adjust_strength, damping shifts,
@@ -128,13 +114,12 @@ struct CdefFrameArgs {
 //  * 0x8000 is the smallest i16: the signed maximum ignores it, the unsigned minimum sees it as
 //    large, and constrain() of it is 0 because (0x8000 >> shift) >= threshold for every legal
 //    strength / damping -- the three things the reference does with CDEF_VERY_LARGE.
-constexpr int CT_STRIDE = 48;           // u16 per tile row (40 used)
-constexpr int CT_ROWS = 20, CT_X0 = 4, CT_Y0 = 2;
+typedef Tile<48> CT;                    // u16 per tile row (40 used)
 constexpr int CT_REC = 16;              // dwords per block record
 
 template <int BPP, int XD, int YD>
 __global__ __launch_bounds__(256) void k_cdef_frame(CdefFrameArgs a) {
-  __shared__ __attribute__((aligned(16))) uint16_t tile[CT_ROWS * CT_STRIDE];
+  __shared__ __attribute__((aligned(16))) uint16_t tile[CT::SIZE];
   __shared__ __attribute__((aligned(16))) uint32_t rec[32 * CT_REC];
   constexpr int xs = 8 >> XD, ys = 8 >> YD;
   constexpr int NBX = 32 / xs, NBY = 16 / ys, NB = NBX * NBY;     // blocks of the workgroup
@@ -149,12 +134,11 @@ __global__ __launch_bounds__(256) void k_cdef_frame(CdefFrameArgs a) {
     // every load of the record is issued here, together (one round trip for wave 0)
     int skip = 1, ci = 0, dir = 0, var = 0;
     if (in_grid) {
-      const uint8_t *sk = a.skip_mi + (size_t)my * a.mi_stride + mx;
-      const uint32_t s0 = *(const uint16_t *)sk, s1 = *(const uint16_t *)(sk + a.mi_stride);   // mx is even
+      const uint2 sk = block_skip_rows(a.skip_mi, a.mi_stride, mx, my);
       ci = a.cdef_index_sb[(gby >> 3) * a.sb_stride + (gbx >> 3)];
       dir = a.dirs[(size_t)gby * a.nbx + gbx];
       var = a.vars[(size_t)gby * a.nbx + gbx];
-      skip = r1cdef::skip4(s0, s1);
+      skip = block_skip(sk);
     }
     // strengths of the superblock's cdef_index out of the argument registers (no dependent load)
     uint32_t st8[2];
@@ -169,69 +153,27 @@ __global__ __launch_bounds__(256) void k_cdef_frame(CdefFrameArgs a) {
       lsec = sec_s << cs;
       if (a.p == 0) {
         lpri = adjust_strength(pri_s << cs, var);
-        ldir = pri_s != 0 ? dir : 0;
+        ldir = filter_dir<true, XD, YD>(dir, pri_s);
       } else {
-        // Cdef_Uv_Dir for 4:2:2: {7, 0, 2, 4, 5, 6, 6, 6} packed as nibbles
-        const int uvdir = (int)((0x66654207u >> (4 * dir)) & 0xf);
         lpri = pri_s << cs;
-        ldir = pri_s != 0 ? (XD != YD ? uvdir : dir) : 0;
+        ldir = filter_dir<false, XD, YD>(dir, pri_s);
       }
     }
-    auto shift_of = [&](int thr) {
-      const int sft = thr ? ldamp - (31 - __clz(thr)) : 0;
-      return sft < 0 ? 0 : sft;
-    };
-    const uint32_t psh = shift_of(lpri), ssh = shift_of(lsec);
-    const int odd = (lpri >> cs) & 1;
-    // cdef_directions (cdef.rs:225-234) packed as nibbles (value + 2)
-    constexpr uint32_t DY0 = 0x33332221u, DX0 = 0x22233333u, DY1 = 0x44443210u, DX1 = 0x12344444u;
-    auto off = [&](int d, int k) -> uint32_t {
-      const int sh4 = 4 * (d & 7);
-      const int dy = (int)(((k == 0 ? DY0 : DY1) >> sh4) & 0xf) - 2;
-      const int dx = (int)(((k == 0 ? DX0 : DX1) >> sh4) & 0xf) - 2;
-      return (uint32_t)((dy * CT_STRIDE + dx) * 2);
-    };
+    const uint4 pr = pri_record(lpri, cs, ldamp);
     uint32_t *r = rec + tid * CT_REC;
-    r[0] = (uint32_t)lpri * 0x10001u;
+    r[0] = pr.x;
     r[1] = (uint32_t)lsec * 0x10001u;
-    r[2] = psh * 0x10001u;
-    r[3] = ssh * 0x10001u;
-    r[4] = (odd ? 3u : 4u) * 0x10001u;
-    r[5] = (odd ? 3u : 2u) * 0x10001u;
+    r[2] = pr.y;
+    r[3] = (uint32_t)constrain_shift(lsec, ldamp) * 0x10001u;
+    r[4] = pr.z;
+    r[5] = pr.w;
     r[6] = (in_grid ? 1u : 0u) | (skip ? 0u : 2u);
-    r[7] = 0;
-    r[8] = off(ldir, 0);
-    r[9] = off(ldir, 1);
-    r[10] = off(ldir + 2, 0);
-    r[11] = off(ldir + 2, 1);
-    r[12] = off(ldir + 6, 0);
-    r[13] = off(ldir + 6, 1);
-    r[14] = 0;
-    r[15] = 0;
+    r[7] = r[14] = r[15] = 0;
+    dir_offsets<CT::STRIDE>(ldir, r + 8);
   }
-  // ---- the tile: 20 rows x 10 groups of 4 pixels, one per thread
-  {
-    const int lim_x = ((a.luma.width >> 3) << 3) >> XD, lim_y = ((a.luma.height >> 3) << 3) >> YD;
-    if (tid < CT_ROWS * 10) {
-      const int ty = tid / 10, tq = tid - ty * 10;
-      const int py = ry0 - CT_Y0 + ty, px = rx0 - CT_X0 + 4 * tq;
-      uint32_t lo = 0x80008000u, hi = 0x80008000u;
-      if (py >= 0 && py < lim_y && px >= 0 && px < lim_x) {
-        const uint8_t *g = (const uint8_t *)a.in.data +
-                           ((size_t)(a.in.yorigin + py) * a.in.stride + a.in.xorigin + px) * BPP;
-        if constexpr (BPP == 1) {
-          const uint32_t q = ld_u32(g);
-          lo = __builtin_amdgcn_perm(0, q, 0x0c010c00u);
-          hi = __builtin_amdgcn_perm(0, q, 0x0c030c02u);
-        } else {
-          const U32x2 q = ld_u32x2(g);
-          lo = q.a;
-          hi = q.b;
-        }
-      }
-      *(uint2 *)(tile + ty * CT_STRIDE + 4 * tq) = make_uint2(lo, hi);
-    }
-  }
+  // ---- the tile: CDEF_VERY_LARGE outside the picture
+  stage_tile<BPP, CT::STRIDE>(tile, a.in, rx0, ry0, 0, 0, ((a.luma.width >> 3) << 3) >> XD,
+                              ((a.luma.height >> 3) << 3) >> YD);
   __syncthreads();
   // ---- lane -> pixel pair
   const int r = lane >> 3, pc = lane & 7;
@@ -239,20 +181,13 @@ __global__ __launch_bounds__(256) void k_cdef_frame(CdefFrameArgs a) {
   const int blk = (ly / ys) * NBX + lx / xs;
   const uint4 q0 = *(const uint4 *)(rec + blk * CT_REC);
   const uint32_t flags = rec[blk * CT_REC + 6];
-  const uint32_t base = (uint32_t)(((ly + CT_Y0) * CT_STRIDE + lx + CT_X0) * 2);
+  const uint32_t base = CT::pair_at(lx, ly);
   Pk x;
   x.u = *(const uint32_t *)((const uint8_t *)tile + base);
-  // lds_pair takes LDS byte addresses, not offsets into the tile
-  typedef __attribute__((address_space(3))) uint16_t LdsU16;
-  const uint32_t tbase = (uint32_t)(uintptr_t)(LdsU16 *)tile + base;
   if (!(flags & 1)) return;
   uint8_t *dst = (uint8_t *)px_addr<BPP>(a.out, rx0 + lx, ry0 + ly);
-  auto store = [&](Pk v) {
-    if constexpr (BPP == 1) *(uint16_t *)dst = (uint16_t)__builtin_amdgcn_perm(0, v.u, 0x0c0c0200u);
-    else *(uint32_t *)dst = v.u;
-  };
   if (!__any((int)(flags & 2))) {   // every block of the wave is skipped: copy
-    store(x);
+    store_pair<BPP>(dst, x);
     return;
   }
   const uint4 q1 = *(const uint4 *)(rec + blk * CT_REC + 4);
@@ -262,16 +197,8 @@ __global__ __launch_bounds__(256) void k_cdef_frame(CdefFrameArgs a) {
   pri.u = q0.x; sec.u = q0.y; psh.u = q0.z; ssh.u = q0.w;
   pt0.u = q1.x; pt1.u = q1.y;
   const uint32_t offs[6] = {q2.x, q2.y, q2.z, q2.w, q3.x, q3.y};
-  // all 24 reads are issued before the first is used
-  uint32_t tlo[12], thi[12], tp[12];
-#pragma unroll
-  for (int t = 0; t < 6; t++) {
-    lds_two(tbase + offs[t], tlo[2 * t], thi[2 * t]);
-    lds_two(tbase - offs[t], tlo[2 * t + 1], thi[2 * t + 1]);
-  }
-  lds_wait(tlo, thi);
-#pragma unroll
-  for (int t = 0; t < 12; t++) tp[t] = tlo[t] | (thi[t] << 16);
+  uint32_t tp[12];
+  load_taps(lds_addr(tile) + base, offs, tp);
   i16x2 sum = (i16x2)0, mx = x.s;
   u16x2 mn = x.v;
 #pragma unroll
@@ -290,11 +217,9 @@ __global__ __launch_bounds__(256) void k_cdef_frame(CdefFrameArgs a) {
       sum += k == 0 ? c * (i16x2)2 : c;
     }
   }
-  // x + ((8 + sum - (sum < 0)) >> 4), clamped to the taps' range
   Pk v;
-  v.s = x.s + ((sum + (sum >> (i16x2)15) + (i16x2)8) >> (i16x2)4);
-  v.s = __builtin_elementwise_min(__builtin_elementwise_max(v.s, (i16x2)mn), mx);
-  store(v);
+  v.s = round_clamp(x.s, sum, mn, mx);
+  store_pair<BPP>(dst, v);
 }
 
 template <int BPP>

@@ -219,6 +219,138 @@ __device__ __forceinline__ i16x2 constrain2(i16x2 d, i16x2 thr, u16x2 sh) {
   return __builtin_elementwise_max(__builtin_elementwise_min(d, m), -m);
 }
 
+// ---- the steps of the packed-pair filter that k_cdef_frame (cdef.hip) and k_cdef_search_pk (cdef_search.hip) share.
+// Both filter a 32 x 16 region of a plane out of a 20-row u16 tile in LDS; the row stride (48 u16 = 24 dwords,
+// conflict-free for the frame kernel's 8 rows x 8 pairs; 40 = 20 dwords for the search's 8 rows x 4 pairs) and the
+// lane -> pixel map were chosen and measured per kernel and are parameters here.
+// cdef_directions (cdef.rs:225-234) packed as nibbles (value + 2) so that the lookup is two shifts instead of a
+// dependent table load: tap k of direction d (0 .. 7) lies at (dy, dx)
+__device__ __forceinline__ void dir_dyx(int d, int k, int &dy, int &dx) {
+  constexpr uint32_t DY0 = 0x33332221u, DX0 = 0x22233333u, DY1 = 0x44443210u, DX1 = 0x12344444u;
+  const int sh = 4 * d;
+  dy = (int)(((k == 0 ? DY0 : DY1) >> sh) & 0xf) - 2;
+  dx = (int)(((k == 0 ? DX0 : DX1) >> sh) & 0xf) - 2;
+}
+// ... as a byte offset in a tile of STRIDE u16 per row (any d: taken mod 8)
+template <int STRIDE>
+__device__ __forceinline__ uint32_t tap_offset(int d, int k) {
+  int dy, dx;
+  dir_dyx(d & 7, k, dy, dx);
+  return (uint32_t)((dy * STRIDE + dx) * 2);
+}
+// the six offsets of a block filtered along `dir`, in the order load_taps reads them: primary (dir) k = 0, 1, then
+// the secondaries dir + 2 and dir + 6
+template <int STRIDE>
+__device__ __forceinline__ void dir_offsets(int dir, uint32_t *offs /* [6] */) {
+#pragma unroll
+  for (int k = 0; k < 2; k++) {
+    offs[k] = tap_offset<STRIDE>(dir, k);
+    offs[2 + k] = tap_offset<STRIDE>(dir + 2, k);
+    offs[4 + k] = tap_offset<STRIDE>(dir + 6, k);
+  }
+}
+// constrain's shift (cdef.rs:146-159): max(0, damping - msb(threshold)); a threshold of 0 constrains to 0 anyway
+__device__ __forceinline__ int constrain_shift(int threshold, int damping) {
+  if (!threshold) return 0;
+  const int s = damping - (31 - __clz(threshold));
+  return s < 0 ? 0 : s;
+}
+// Cdef_Uv_Dir for 4:2:2: {7, 0, 2, 4, 5, 6, 6, 6} packed as nibbles
+__device__ __forceinline__ int uv_dir_422(int dir) { return (int)((0x66654207u >> (4 * dir)) & 0xf); }
+// the direction a plane's block is filtered along (cdef.rs:492-512): its luma direction, mapped for 4:2:2 chroma ...
+template <bool LUMA, int XD, int YD>
+__device__ __forceinline__ int plane_dir(int dir) {
+  return !LUMA && XD != YD ? uv_dir_422(dir) : dir;
+}
+// ... and direction 0 when the primary strength is 0
+template <bool LUMA, int XD, int YD>
+__device__ __forceinline__ int filter_dir(int dir, int pri_raw) {
+  return pri_raw != 0 ? plane_dir<LUMA, XD, YD>(dir) : 0;
+}
+// Block::skip of the 8x8 block whose first 4x4 unit is (mx, my), mx even, in two steps: the loads (its two rows of two
+// skip bytes), which a kernel issues FIRST among its block record's loads, and the test, which it takes after the
+// last of them -- one round trip.  With the test right behind the loads the record's other loads waited for it, and
+// with both steps behind them the search launch measured 0.3 .. 0.8 % above the band of the form it had.
+__device__ __forceinline__ uint2 block_skip_rows(const uint8_t *skip_mi, int mi_stride, int mx, int my) {
+  const uint8_t *sk = skip_mi + (size_t)my * mi_stride + mx;
+  return make_uint2(*(const uint16_t *)sk, *(const uint16_t *)(sk + mi_stride));
+}
+__device__ __forceinline__ int block_skip(uint2 rows) { return skip4(rows.x, rows.y); }
+// what a block's record holds per primary strength, each as a packed pair: the strength (after adjust_strength for
+// luma), its constrain shift, and the weights of the primary taps k = 0, 1 (cdef.rs:236-239: 3 / 3 or 4 / 2)
+__device__ __forceinline__ uint4 pri_record(int pri, int cs, int damping) {
+  const uint32_t psh = (uint32_t)constrain_shift(pri, damping);
+  const int odd = (pri >> cs) & 1;
+  return make_uint4((uint32_t)pri * 0x10001u, psh * 0x10001u, (odd ? 3u : 4u) * 0x10001u, (odd ? 3u : 2u) * 0x10001u);
+}
+
+// The tile: region (x, y) is at row Y0 + y, column X0 + x; 2 halo rows above / below, 4 columns left / right so that
+// every global load is one aligned 4-pixel group.
+template <int STRIDE_>
+struct Tile {
+  static constexpr int STRIDE = STRIDE_, ROWS = 20, X0 = 4, Y0 = 2, SIZE = ROWS * STRIDE_;
+  // byte offset of the pixel pair at (lx, ly) of the region
+  static __device__ __forceinline__ uint32_t pair_at(int lx, int ly) { return (uint32_t)(((ly + Y0) * STRIDE + lx + X0) * 2); }
+};
+// lds_two takes LDS byte addresses, not offsets into the tile
+__device__ __forceinline__ uint32_t lds_addr(const uint16_t *tile) {
+  typedef __attribute__((address_space(3))) uint16_t LdsU16;
+  return (uint32_t)(uintptr_t)(LdsU16 *)tile;
+}
+// Stages the tile of the region at (rx0, ry0) of `plane`: 20 rows x 10 groups of 4 pixels, one per thread (the first
+// 200 of the workgroup), 8-bit pixels widened; CDEF_VERY_LARGE outside [x_lo, x_hi) x [y_lo, y_hi) -- the rectangle
+// whose borders count as picture edges (a multiple of 4 pixels on every side).  The caller synchronises.
+template <int BPP, int STRIDE>
+__device__ __forceinline__ void stage_tile(uint16_t *tile, const R1Plane &plane, int rx0, int ry0, int x_lo, int y_lo,
+                                           int x_hi, int y_hi) {
+  typedef Tile<STRIDE> T;
+  const int tid = threadIdx.x;
+  if (tid < T::ROWS * 10) {
+    const int ty = tid / 10, tq = tid - ty * 10;
+    const int py = ry0 - T::Y0 + ty, px = rx0 - T::X0 + 4 * tq;
+    uint32_t lo = 0x80008000u, hi = 0x80008000u;
+    if (py >= y_lo && py < y_hi && px >= x_lo && px < x_hi) {
+      const uint8_t *g = px_addr<BPP>(plane, px, py);
+      if constexpr (BPP == 1) {
+        const uint32_t q = ld_u32(g);
+        lo = __builtin_amdgcn_perm(0, q, 0x0c010c00u);
+        hi = __builtin_amdgcn_perm(0, q, 0x0c030c02u);
+      } else {
+        const U32x2 q = ld_u32x2(g);
+        lo = q.a;
+        hi = q.b;
+      }
+    }
+    *(uint2 *)(tile + ty * STRIDE + 4 * tq) = make_uint2(lo, hi);
+  }
+}
+
+// the twelve taps of the pair at LDS byte address tbase: (+off, -off) of the six offsets; all 24 reads are issued
+// before the first is used
+__device__ __forceinline__ void load_taps(uint32_t tbase, const uint32_t (&offs)[6], uint32_t (&tp)[12]) {
+  uint32_t tlo[12], thi[12];
+#pragma unroll
+  for (int t = 0; t < 6; t++) {
+    lds_two(tbase + offs[t], tlo[2 * t], thi[2 * t]);
+    lds_two(tbase - offs[t], tlo[2 * t + 1], thi[2 * t + 1]);
+  }
+  lds_wait(tlo, thi);
+#pragma unroll
+  for (int t = 0; t < 12; t++) tp[t] = tlo[t] | (thi[t] << 16);
+}
+// x + ((8 + sum - (sum < 0)) >> 4), clamped to the taps' range (cdef.rs:293-294)
+__device__ __forceinline__ i16x2 round_clamp(i16x2 x, i16x2 sum, u16x2 mn, i16x2 mx) {
+  const i16x2 v = x + ((sum + (sum >> (i16x2)15) + (i16x2)8) >> (i16x2)4);
+  return __builtin_elementwise_min(__builtin_elementwise_max(v, (i16x2)mn), mx);
+}
+
+// a pixel pair to its place in a plane (dst: the address of the left pixel)
+template <int BPP>
+__device__ __forceinline__ void store_pair(uint8_t *dst, Pk v) {
+  if constexpr (BPP == 1) *(uint16_t *)dst = (uint16_t)__builtin_amdgcn_perm(0, v.u, 0x0c0c0200u);
+  else *(uint32_t *)dst = v.u;
+}
+
 inline int cdef_analyze_launch(const R1Plane *luma, int nbx, int nby, int mi_cols, int mi_rows,
                         uint8_t *dirs, int32_t *vars, hipStream_t st) {
   const dim3 grid((nbx + 63) / 64, nby);

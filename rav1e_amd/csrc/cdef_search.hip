@@ -22,12 +22,6 @@
 namespace {
 using namespace r1cdef;
 
-__device__ __forceinline__ int constrain_shift(int threshold, int damping) {
-  if (!threshold) return 0;
-  const int s = damping - (31 - __clz(threshold));
-  return s < 0 ? 0 : s;
-}
-
 struct SearchArgs {
   R1Plane rec[3], src[3];
   const uint8_t *skip_mi;
@@ -81,11 +75,11 @@ __device__ __forceinline__ bool sb_all_skip(const SearchArgs &a, const AreaGeo &
 }
 
 // ---- the search for one plane (LUMA) or both chroma planes (blockIdx.z), packed pairs.
-// Geometry as k_cdef_frame's (cdef.hip): workgroup = 32 x 16 pixels of the plane (always inside one
-// superblock), wave = 16 x 8, lane = two horizontally adjacent pixels; here lane = hb*32 + row*4 +
-// pair, so that the 32 lanes of an 8-pixel-wide half are one luma block and DPP sums stay inside
-// it.  The tile in LDS holds CDEF_VERY_LARGE outside the ANALYSIS AREA's rectangle: that is what
-// the reference's edge flags on its scratch copy of the area say block by block.
+// Geometry and filter steps as k_cdef_frame's (cdef.hip), both from cdef_common.hpp: workgroup = 32 x 16
+// pixels of the plane (always inside one superblock), wave = 16 x 8, lane = two horizontally adjacent
+// pixels; here lane = hb*32 + row*4 + pair, so that the 32 lanes of an 8-pixel-wide half are one luma
+// block and DPP sums stay inside it.  The tile in LDS holds CDEF_VERY_LARGE outside the ANALYSIS AREA's
+// rectangle: that is what the reference's edge flags on its scratch copy of the area say block by block.
 //  * per block (first lanes of wave 0, once): skip, bias, the six tap offsets of its direction,
 //    and for every cdef_index the primary strength after adjust_strength, its shift and taps;
 //    the secondary strength / shift of an index do not depend on the block (scalar registers);
@@ -97,7 +91,7 @@ __device__ __forceinline__ bool sb_all_skip(const SearchArgs &a, const AreaGeo &
 //    ONE pass of the workgroup does all tails (cdef_dist_kernel's fixed point, the weighted-SSE
 //    scaling) and the 64-bit atomics, a (block, index) pair per thread.
 constexpr int SR_REC = 48;   // dwords per block record
-constexpr int ST_STRIDE = 40, ST_ROWS = 20, ST_X0 = 4, ST_Y0 = 2;   // tile: 20 dwords per row, conflict-free for 8 rows x 4 pairs
+typedef Tile<40> ST;         // 20 dwords per row, conflict-free for 8 rows x 4 pairs
 
 template <int CTRL, int ROW_MASK = 0xf>
 __device__ __forceinline__ uint32_t add_dpp_m(uint32_t v) {
@@ -121,7 +115,7 @@ __device__ __forceinline__ uint32_t swz_xor4(uint32_t v) {
 // (rdo.rs:2546-2560 "keep cdef output up to date"), everything else copied through: the CDEF working copy.
 template <int BPP, int XD, int YD, bool LUMA, int MODE = 0>
 __global__ __launch_bounds__(256) void k_cdef_search_pk(SearchArgs a) {
-  __shared__ __attribute__((aligned(16))) uint16_t tile[ST_ROWS * ST_STRIDE];
+  __shared__ __attribute__((aligned(16))) uint16_t tile[ST::SIZE];
   __shared__ __attribute__((aligned(16))) uint32_t rec[32 * SR_REC];
   __shared__ uint32_t acc[32 * 8 * 3 + 16];   // luma: [8 blocks][8 idx][d, d2, sd] + [8][s, s2]; chroma: [32 cells][8 idx]
   constexpr int xs = 8 >> XD, ys = 8 >> YD;
@@ -145,14 +139,6 @@ __global__ __launch_bounds__(256) void k_cdef_search_pk(SearchArgs a) {
   const int n_idx = a.p.n_idx;
   const uint8_t *strengths = LUMA ? a.p.y_strengths : a.p.uv_strengths;
   const int damping = a.p.damping + cs - (LUMA ? 0 : 1);
-  // cdef_directions (cdef.rs:225-234) packed as nibbles (value + 2)
-  constexpr uint32_t DY0 = 0x33332221u, DX0 = 0x22233333u, DY1 = 0x44443210u, DX1 = 0x12344444u;
-  auto off = [&](int d, int k) -> uint32_t {
-    const int sh4 = 4 * (d & 7);
-    const int dy = (int)(((k == 0 ? DY0 : DY1) >> sh4) & 0xf) - 2;
-    const int dx = (int)(((k == 0 ? DX0 : DX1) >> sh4) & 0xf) - 2;
-    return (uint32_t)((dy * ST_STRIDE + dx) * 2);
-  };
   // ---- per-block records
   if (tid < NB) {
     const int gbx = blockIdx.x * NBX + tid % NBX, gby = blockIdx.y * NBY + tid / NBX;   // frame 8x8 grid
@@ -162,58 +148,25 @@ __global__ __launch_bounds__(256) void k_cdef_search_pk(SearchArgs a) {
     int skip = 1, dir = 0, var = 0;
     uint32_t bias = 1u << 14;
     if (in_grid) {
-      const uint8_t *sk = a.skip_mi + (size_t)(g.ay0 * 16 + my) * a.mi_stride + g.ax0 * 16 + mx;
-      const uint32_t s0 = *(const uint16_t *)sk, s1 = *(const uint16_t *)(sk + a.mi_stride);
+      const uint2 sk = block_skip_rows(a.skip_mi, a.mi_stride, g.ax0 * 16 + mx, g.ay0 * 16 + my);
       dir = a.dirs[(size_t)gby * a.nbx + gbx];
       var = a.vars[(size_t)gby * a.nbx + gbx];
       if (a.scales) bias = a.scales[(size_t)gby * a.scale_stride + gbx];
-      skip = r1cdef::skip4(s0, s1);
+      skip = block_skip(sk);
     }
-    const int own = LUMA ? dir : (XD != YD ? (int)((0x66654207u >> (4 * dir)) & 0xf) : dir);
+    // the block's own direction; an index whose primary strength is 0 (filter_dir: direction 0) reads the zero set
     uint32_t *r = rec + tid * SR_REC;
     r[0] = (in_grid ? 1u : 0u) | (skip ? 0u : 2u);
     r[1] = bias;
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-      r[2 + k] = off(own, k);
-      r[4 + k] = off(own + 2, k);
-      r[6 + k] = off(own + 6, k);
-    }
+    dir_offsets<ST::STRIDE>(plane_dir<LUMA, XD, YD>(dir), r + 2);
     for (int idx = 0; idx < 8; idx++) {
-      const int st = idx < n_idx ? strengths[idx] : 0;
-      const int pri_raw = st >> 2;
-      const int pri = LUMA ? adjust_strength(pri_raw << cs, var) : pri_raw << cs;
-      const uint32_t psh = (uint32_t)constrain_shift(pri, damping);
-      const int odd = (pri >> cs) & 1;
-      r[16 + 4 * idx + 0] = (uint32_t)pri * 0x10001u;
-      r[16 + 4 * idx + 1] = psh * 0x10001u;
-      r[16 + 4 * idx + 2] = (odd ? 3u : 4u) * 0x10001u;
-      r[16 + 4 * idx + 3] = (odd ? 3u : 2u) * 0x10001u;
+      const int pri_raw = (idx < n_idx ? strengths[idx] : 0) >> 2;
+      *(uint4 *)(r + 16 + 4 * idx) = pri_record(LUMA ? adjust_strength(pri_raw << cs, var) : pri_raw << cs, cs, damping);
     }
   }
   // ---- the tile: the area's rectangle in plane pixels, CDEF_VERY_LARGE outside
-  {
-    const int ax = (g.ax0 * 64) >> XD, ay = (g.ay0 * 64) >> YD;
-    const int ax1 = (g.ax0 * 64 + g.area_w) >> XD, ay1 = (g.ay0 * 64 + g.area_h) >> YD;
-    if (tid < ST_ROWS * 10) {
-      const int ty = tid / 10, tq = tid - ty * 10;
-      const int py = ry0 - ST_Y0 + ty, px = rx0 - ST_X0 + 4 * tq;
-      uint32_t lo = 0x80008000u, hi = 0x80008000u;
-      if (py >= ay && py < ay1 && px >= ax && px < ax1) {
-        const uint8_t *gp = px_addr<BPP>(rp, px, py);
-        if constexpr (BPP == 1) {
-          const uint32_t q = ld_u32(gp);
-          lo = __builtin_amdgcn_perm(0, q, 0x0c010c00u);
-          hi = __builtin_amdgcn_perm(0, q, 0x0c030c02u);
-        } else {
-          const U32x2 q = ld_u32x2(gp);
-          lo = q.a;
-          hi = q.b;
-        }
-      }
-      *(uint2 *)(tile + ty * ST_STRIDE + 4 * tq) = make_uint2(lo, hi);
-    }
-  }
+  stage_tile<BPP, ST::STRIDE>(tile, rp, rx0, ry0, (g.ax0 * 64) >> XD, (g.ay0 * 64) >> YD, (g.ax0 * 64 + g.area_w) >> XD,
+                              (g.ay0 * 64 + g.area_h) >> YD);
   __syncthreads();
   // ---- lane -> pixel pair: half-wave hb = 8 columns, row, pair
   const int hb = lane >> 5, row = (lane >> 2) & 7, pq = lane & 3;
@@ -222,7 +175,7 @@ __global__ __launch_bounds__(256) void k_cdef_search_pk(SearchArgs a) {
   const uint32_t *rb = rec + blk * SR_REC;
   const uint32_t flags = rb[0];
   const bool in_grid = flags & 1, filt = (flags & 2) != 0 && (MODE != 2 || apply_idx >= 0);
-  const uint32_t base = (uint32_t)(((ly + ST_Y0) * ST_STRIDE + lx + ST_X0) * 2);
+  const uint32_t base = ST::pair_at(lx, ly);
   Pk x, s;
   x.u = *(const uint32_t *)((const uint8_t *)tile + base);
   s.u = 0;
@@ -231,8 +184,7 @@ __global__ __launch_bounds__(256) void k_cdef_search_pk(SearchArgs a) {
     if constexpr (BPP == 1) s.u = __builtin_amdgcn_perm(0, (uint32_t) * (const uint16_t *)gp, 0x0c010c00u);
     else s.u = ld_u32(gp);
   }
-  typedef __attribute__((address_space(3))) uint16_t LdsU16;
-  const uint32_t tbase = (uint32_t)(uintptr_t)(LdsU16 *)tile + base;
+  const uint32_t tbase = lds_addr(tile) + base;
   // which direction sets the index set asks for (scalar)
   bool need_own = false, need_zero = false;
   const int idx_lo = MODE == 2 ? (apply_idx < 0 ? 0 : apply_idx) : 0, idx_hi = MODE == 2 ? idx_lo + 1 : n_idx;
@@ -244,20 +196,14 @@ __global__ __launch_bounds__(256) void k_cdef_search_pk(SearchArgs a) {
   struct TapSet { uint32_t tp[12]; i16x2 mx; u16x2 mn; };
   auto load_set = [&](const uint32_t (&offs)[6]) {
     TapSet ts;
-    uint32_t tlo[12], thi[12];
-#pragma unroll
-    for (int t = 0; t < 6; t++) {
-      lds_two(tbase + offs[t], tlo[2 * t], thi[2 * t]);
-      lds_two(tbase - offs[t], tlo[2 * t + 1], thi[2 * t + 1]);
-    }
-    lds_wait(tlo, thi);
+    load_taps(tbase, offs, ts.tp);
     ts.mx = x.s;
     ts.mn = x.v;
 #pragma unroll
     for (int t = 0; t < 12; t++) {
       // a skipped block is not filtered: all its taps read as the centre (every term 0, clamp = x)
       Pk p;
-      p.u = filt ? (tlo[t] | (thi[t] << 16)) : x.u;
+      p.u = filt ? ts.tp[t] : x.u;
       ts.tp[t] = p.u;
       ts.mx = __builtin_elementwise_max(ts.mx, p.s);
       ts.mn = __builtin_elementwise_min(ts.mn, p.v);
@@ -270,7 +216,8 @@ __global__ __launch_bounds__(256) void k_cdef_search_pk(SearchArgs a) {
     own = load_set(offs);
   }
   if (need_zero) {
-    const uint32_t offs[6] = {off(0, 0), off(0, 1), off(2, 0), off(2, 1), off(6, 0), off(6, 1)};
+    uint32_t offs[6];
+    dir_offsets<ST::STRIDE>(0, offs);
     zero = load_set(offs);
   }
   // the source's two moments of a luma block do not depend on the index
@@ -325,16 +272,14 @@ __global__ __launch_bounds__(256) void k_cdef_search_pk(SearchArgs a) {
         sum += (constrain2(p0.s - x.s, pri2.s, psh2.v) + constrain2(p1.s - x.s, pri2.s, psh2.v)) * pt0.s;
         sum += (constrain2(p2.s - x.s, pri2.s, psh2.v) + constrain2(p3.s - x.s, pri2.s, psh2.v)) * pt1.s;
       }
-      v.s = x.s + ((sum + (sum >> (i16x2)15) + (i16x2)8) >> (i16x2)4);
-      v.s = __builtin_elementwise_min(__builtin_elementwise_max(v.s, (i16x2)ts.mn), ts.mx);
+      v.s = round_clamp(x.s, sum, ts.mn, ts.mx);
     }
     if (MODE != 0 && store) {
       // the filtered pair itself: the trial plane of this index / the working copy
       if (in_grid) {
         const R1Plane &dp = MODE == 2 ? a.out[pli] : a.trial[pli];
         uint8_t *d = (uint8_t *)px_addr<BPP>(dp, rx0 + lx, ry0 + ly) + (MODE == 2 ? (size_t)0 : (size_t)idx * a.trial_idx_bytes);
-        if constexpr (BPP == 1) *(uint16_t *)d = (uint16_t)((v.u & 0xffu) | ((v.u >> 8) & 0xff00u));
-        else *(uint32_t *)d = v.u;
+        store_pair<BPP>(d, v);
       }
     } else if constexpr (LUMA) {
       // cdef_dist_kernel's moments of the filtered block (dist.rs:316-345)
@@ -494,11 +439,12 @@ int search_launch(const SearchArgs &a, hipStream_t st) {
 }
 
 // scratch layout: per-superblock sums [n_sb][8][3] u64 | var i32 per 8x8 block | dir u8 per 8x8 block |
-// (trial only) plane mask u8 per superblock, padded to 256 B | trial planes [n_idx][Y | U | V]
+// (trial only) plane mask u8 per superblock, padded to 256 B | trial planes [n_idx][Y | U | V].
+// The search and the working copy use the first three regions: they end where `mask` begins, whatever the rest is.
 struct ScratchMap {
   size_t n_sb, psum, vars, dirs, mask, planes, plane_bytes[3], idx_bytes, total;
 };
-ScratchMap scratch_map(int mi_cols, int mi_rows, int xdec, int ydec, int bpp, int n_idx, int planes) {
+ScratchMap scratch_map(int mi_cols, int mi_rows, int xdec = 0, int ydec = 0, int bpp = 0, int n_idx = 0, int planes = 0) {
   ScratchMap m = {};
   const size_t n_sbx = (mi_cols + 15) / 16, n_sby = (mi_rows + 15) / 16;
   m.n_sb = n_sbx * n_sby;
@@ -516,12 +462,20 @@ ScratchMap scratch_map(int mi_cols, int mi_rows, int xdec, int ydec, int bpp, in
   return m;
 }
 
+// psum / vars / dirs of the launch arguments from the map, and cdef_analyze_superblock once for the frame (a thread
+// per 8x8 block), shared by the planes
+int analyze_into_scratch(SearchArgs &a, const ScratchMap &m, void *scratch, hipStream_t st) {
+  uint8_t *sc = (uint8_t *)scratch;
+  a.psum = (unsigned long long *)(sc + m.psum);
+  a.vars = (const int32_t *)(sc + m.vars);
+  a.dirs = sc + m.dirs;
+  return cdef_analyze_launch(&a.rec[0], a.nbx, a.n_sby * 8, a.mi_cols, a.mi_rows, sc + m.dirs, (int32_t *)(sc + m.vars), st);
+}
+
 }  // namespace
 
-// scratch: the per-superblock sums [n_sb][8][3] u64, then (var i32, dir u8) per 8x8 block of the grid
 extern "C" long long r1_cdef_strength_search_scratch_bytes(int mi_cols, int mi_rows) {
-  const long long n_sb = (long long)((mi_cols + 15) / 16) * ((mi_rows + 15) / 16);
-  return n_sb * 24 * 8 + n_sb * 64 * 5;
+  return (long long)scratch_map(mi_cols, mi_rows).mask;
 }
 
 extern "C" int r1_cdef_strength_search(r1_ctx *ctx, const R1Plane *rec, const R1Plane *src,
@@ -534,16 +488,10 @@ extern "C" int r1_cdef_strength_search(r1_ctx *ctx, const R1Plane *rec, const R1
   int rc = search_args(ctx, rec, src, skip_mi, mi_stride, mi_cols, mi_rows, scales, scale_stride, params, a);
   if (rc != R1_OK) return rc;
   R1DeviceGuard guard(ctx);
-  a.psum = (unsigned long long *)scratch;
   hipStream_t st = (hipStream_t)stream;
-  const size_t n_sb = (size_t)a.n_sbx * a.n_sby;
-  R1_HIP_CHECK(hipMemsetAsync(scratch, 0, n_sb * 24 * 8, st));
-  // cdef_analyze_superblock once for the frame (a thread per 8x8 block), shared by the planes
-  int32_t *vars = (int32_t *)((uint8_t *)scratch + n_sb * 24 * 8);
-  uint8_t *dirs = (uint8_t *)(vars + n_sb * 64);
-  a.dirs = dirs;
-  a.vars = vars;
-  rc = cdef_analyze_launch(&rec[0], a.nbx, a.n_sby * 8, mi_cols, mi_rows, dirs, vars, st);
+  const ScratchMap m = scratch_map(mi_cols, mi_rows);
+  R1_HIP_CHECK(hipMemsetAsync((uint8_t *)scratch + m.psum, 0, m.vars - m.psum, st));
+  rc = analyze_into_scratch(a, m, scratch, st);
   if (rc != R1_OK) return rc;
   rc = search_launch<0>(a, st);
   if (rc != R1_OK) return rc;
@@ -586,11 +534,8 @@ extern "C" int r1_cdef_lrf_trial_batch(r1_ctx *ctx, const R1Plane *rec, const R1
   R1DeviceGuard guard(ctx);
   hipStream_t st = (hipStream_t)stream;
   uint8_t *sc = (uint8_t *)scratch;
-  a.psum = (unsigned long long *)(sc + m.psum);
-  R1_HIP_CHECK(hipMemsetAsync(sc, 0, m.n_sb * 24 * 8, st));
+  R1_HIP_CHECK(hipMemsetAsync(sc + m.psum, 0, m.vars - m.psum, st));
   R1_HIP_CHECK(hipMemsetAsync(sc + m.mask, 0, m.planes - m.mask, st));
-  a.vars = (const int32_t *)(sc + m.vars);
-  a.dirs = sc + m.dirs;
   a.sb_lrf = sc + m.mask;
   a.sb_sel = sb_sel;
   size_t off = m.planes;
@@ -607,7 +552,7 @@ extern "C" int r1_cdef_lrf_trial_batch(r1_ctx *ctx, const R1Plane *rec, const R1
     off += m.plane_bytes[k];
   }
   a.trial_idx_bytes = m.idx_bytes;
-  rc = cdef_analyze_launch(&rec[0], a.nbx, a.n_sby * 8, mi_cols, mi_rows, (uint8_t *)(sc + m.dirs), (int32_t *)(sc + m.vars), st);
+  rc = analyze_into_scratch(a, m, scratch, st);
   if (rc != R1_OK) return rc;
   if (n_tot)
     hipLaunchKernelGGL(k_trial_mark, dim3((n_tot + 255) / 256), dim3(256), 0, st, units, n_units[0], n_units[1],
@@ -643,13 +588,8 @@ extern "C" int r1_cdef_apply_area(r1_ctx *ctx, const R1Plane *rec, const R1Plane
   }
   R1DeviceGuard guard(ctx);
   hipStream_t st = (hipStream_t)stream;
-  const size_t n_sb = (size_t)a.n_sbx * a.n_sby;
-  int32_t *vars = (int32_t *)((uint8_t *)scratch + n_sb * 24 * 8);
-  uint8_t *dirs = (uint8_t *)(vars + n_sb * 64);
-  a.dirs = dirs;
-  a.vars = vars;
   a.index_sb = index_sb;
-  rc = cdef_analyze_launch(&rec[0], a.nbx, a.n_sby * 8, mi_cols, mi_rows, dirs, vars, st);
+  rc = analyze_into_scratch(a, scratch_map(mi_cols, mi_rows), scratch, st);
   if (rc != R1_OK) return rc;
   return search_launch<2>(a, st);
 }

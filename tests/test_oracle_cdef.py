@@ -90,3 +90,22 @@ def test_zero_strength_is_identity(oracle):
     blk = np.ascontiguousarray(src[4:12, 4:12])
     oracle.r1o_cdef_filter_block(O.ptr(dst), 8, O.ptr(blk), 8, 0, 0, 3, 5, 8, 0, 0, 0, 0)
     assert np.array_equal(dst, blk)
+
+
+@pytest.mark.parametrize("size", [(136, 72), (200, 136)])
+def test_apply_area_with_one_area_is_the_frame_filter(oracle, size):
+    """r1o_cdef_apply_area with one analysis area over the frame and the frame filter's cdef_index map equals
+    r1o_cdef_filter_tile_plane on every plane, pixel for pixel, when the frame is a multiple of 8 both ways (at other
+    sizes the two differ on what a partly visible block is, as they do in the reference).  Holds, with zero
+    differing pixels, for 4:2:0 at 8 / 10 / 12 bits, 4:2:2 and 4:4:4: all of cdef_pair_util.FORMATS."""
+    import cdef_pair_util as P
+    import layout_util as LU
+    for bd, xdec, ydec in P.FORMATS:
+        c, frame, area = P.oracle_pair(oracle, bd, xdec, ydec, *size)
+        for p in range(3):
+            bad = np.argwhere(frame[p] != area[p])
+            assert len(bad) == 0, (size, bd, xdec, ydec, p, len(bad), bad[:4])
+            assert (frame[p] != LU.window(c["rec"][p])).sum() > 500, (size, bd, xdec, ydec, p)
+        # the superblocks of the two indices with primary strength 0 and a secondary one (direction 0) are filtered
+        assert (frame[0][:64, 64:128] != LU.window(c["rec"][0])[:64, 64:128]).any()
+        assert (frame[1][:64 >> ydec, 128 >> xdec:] != LU.window(c["rec"][1])[:64 >> ydec, 128 >> xdec:]).any()

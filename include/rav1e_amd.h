@@ -121,7 +121,8 @@ const char *r1_last_error(void);
  * r1_comm_push_frame (round 5) were added under versions 4 and 5 respectively, and the compound candidate
  * (r1_rdo_compound_cand_batch, R1CompoundCand) under version 7, as were the frame's scale maps and segmentation
  * inputs (r1_frame_scales, r1_scale_kmeans, r1_segmentation_from_centroids, r1_spatiotemporal_scale_batch) and the
- * intra candidate (r1_rdo_intra_cand_batch) and the coefficient rate (r1_coeff_rate_batch, R1CoeffCdfs, R1TxbCtx). */
+ * intra candidate (r1_rdo_intra_cand_batch), the coefficient rate (r1_coeff_rate_batch, R1CoeffCdfs, R1TxbCtx) and the
+ * intra transform-split candidate (r1_rdo_intra_split_batch, R1IntraSplitCand). */
 int r1_abi_version(void);
 
 /* ---- dist:: (reference: src/dist.rs get_sad 31, get_satd 156; dispatch
@@ -1069,6 +1070,74 @@ int r1_rdo_intra_cand_batch(r1_ctx *ctx, const R1Plane *org, int w, int h, int t
                             const uint32_t *scales, int scale_stride, int xdec, int ydec,
                             uint32_t *sad_out, uint32_t *satd_out, uint16_t *eob_out, uint64_t *dist_out,
                             uint64_t *est_rate_out, void *qcoeffs_out, void *rec_out, void *pred_out, void *stream);
+/* ---- the intra transform-split candidate in ONE launch (added under ABI 7): rdo_tx_size_type (src/rdo.rs:725-802)
+ * tries an intra block's largest transform, then one split, then two, each through rdo_tx_type_decision ->
+ * write_tx_blocks (src/encoder.rs:2243-2311), which walks the block's transform blocks in raster order; each is
+ * predicted from a reconstruction that already holds the ones before it (need_recon_pixel, rdo.rs:1729).  This call
+ * runs that loop on the device for n blocks of bw x bh pixels coded with square tx_size transforms: the block's working
+ * reconstruction stays in LDS between the steps, and `rec` is never written.
+ *   cands:   one R1IntraSplitCand per block.  tr_mask / bl_mask are has_top_right / has_bottom_left per transform
+ *            block -- decisions on the partition tree, which stay on the host as for R1IntraEdgeCand.flags.
+ *   tile:    (tile_x, tile_y, tile_w, tile_h) in plane pixels, inside `rec`; block i lies at (tile_x + x, tile_y + y)
+ *            of both planes.
+ * A trial is (block i, slot j), slot j = the j-th set bit of tx_type_mask, nt = popcount (r1_rdo_txsearch_batch's
+ * slots); its index is i * nt + j, and ntx = (bw / tw) * (bh / th) is the transform-block grid.  Let R be a private
+ * copy of `rec`.  For each transform block k in raster order over the grid, at (x_k, y_k) relative to the tile --
+ * skipped when its 4x4-unit origin is at or beyond (tile_w + 3) >> 2 or (tile_h + 3) >> 2 (encoder.rs:1441, 2282) --
+ * the results are, bit for bit, those of
+ *   r1_intra_edges_batch(R, tile, tx_size, {x_k, y_k, mode, angle_delta,
+ *                        flags = enable_intra_edge_filter | tr_mask[k] << 1 | bl_mask[k] << 2})
+ *   -> r1_predict_intra_batch with the R1IntraCand predict_intra (src/predict.rs:205-249) implies: the Paeth remap
+ *      and `variant` by x_k == 0 / y_k == 0, angle = mode angle + 3 * angle_delta, the block's ief, avail_w / avail_h
+ *      = min(transform side, plane size - position), at least 1
+ *   -> r1_rdo_txsearch_batch(pred = that, tx_type_mask = 1 << t_j, is_intra quantizer) at (x_k, y_k)
+ *   -> its reconstruction (rec_out of a pixel-domain kind; the prediction itself when eob == 0) stored into R.
+ * Transform block k + 1 sees the results of 0 .. k; every trial starts from the same `rec`.
+ * Outputs:
+ *   eob_out[trial * ntx + k]          0 for a skipped transform block
+ *   qcoeffs_out (optional)            coded-area blocks at [trial * ntx + k] (int16 at 8 bits, else int32); zeros for
+ *                                     a skipped transform block
+ *   rec_out (optional)                one dense bw x bh block per trial: R over the block behind the last step.  What
+ *                                     no step wrote is `rec` inside the tile and 0 outside it.
+ *   dist_kind 0                       dist_out[trial * ntx + k] (, est_rate_out[..], optional): the raw transform-
+ *                                     domain distortion and table rate per transform block (0 when skipped);
+ *                                     distortion_scale differs per transform block (encoder.rs:1654), so the host
+ *                                     applies it, as it does for r1_rdo_full_cand_batch.  rec_out must be NULL.
+ *   R1_DIST_WSSE / R1_DIST_CDEF       dist_out[trial]: what r1_dist_scaled_batch returns for `org` against that final
+ *                                     block over bw x bh with the `scales` grid (xdec = ydec = 0).  est_rate_out must
+ *                                     be NULL.
+ * As with r1_rdo_intra_cand_batch a block cut by the frame edge is evaluated whole -- `org` must hold every transform
+ * block that is not skipped, and for a pixel-domain kind the whole block, padding included -- and the caller gets the
+ * reference's visible-part distortion (clip_visible_bsize) from rec_out through r1_dist_scaled_batch.
+ * Built: square transforms 4x4, 8x8, 16x16, 32x32 on blocks up to 64x64 that they divide with 2 <= ntx <= 16 (both
+ * split depths of every square and 2:1 block, depth 2 of the 4:1 blocks), bit depths 8 / 10 / 12, luma modes 0 .. 12
+ * as write_tx_blocks receives them (NO Paeth remap by the caller).
+ * NOT built: the 2:1 transform sizes (depth 1 of the 4:1 blocks) -- they stay on the host loop over the three calls
+ * above; the real coefficient rate across several transform blocks (its context chain between transform blocks
+ * stays on the host, which gets qcoeffs_out / eob_out for r1_coeff_rate_batch); chroma (write_tx_blocks never splits
+ * it); a routing to a multi-launch fallback (every point runs the one kernel).
+ * R1_EINVAL: everything r1_rdo_txsearch_batch rejects for the size, mask and kind; a tx_size that is not one of the
+ * four; bw / bh that the transform does not divide, that is no block size, or ntx of 1 or above 16; a tile that is not
+ * inside `rec`; planes of different pixel formats; a NULL plane, cands, params, eob_out or dist_out; est_rate_out or
+ * rec_out with the wrong kind; and, where the host can read the descriptors (host or pinned memory; the Python
+ * wrapper checks NumPy descriptors before it uploads them), a mode above 12 or an x / y that is negative or no
+ * multiple of 4.  Descriptors in device memory are not read by the host: there a mode above 12 predicts DC and a
+ * negative position skips every transform block of the trial. */
+typedef struct R1IntraSplitCand {
+  int16_t x, y;          /* block position relative to the tile, multiples of 4 */
+  uint8_t mode;          /* luma PredictionMode 0..12 as write_tx_blocks receives it: NO Paeth remap */
+  int8_t  angle_delta;
+  uint8_t ief;           /* as R1IntraCand.ief: one value per BLOCK (encoder.rs:1458-1469 uses tile_partition_bo) */
+  uint8_t reserved;
+  uint16_t tr_mask;      /* bit k: has_top_right(..)  of transform block k (raster index in the bw/tw x bh/th grid) */
+  uint16_t bl_mask;      /* bit k: has_bottom_left(..) of transform block k */
+} R1IntraSplitCand;
+int r1_rdo_intra_split_batch(r1_ctx *ctx, const R1Plane *org, const R1Plane *rec,
+    int tile_x, int tile_y, int tile_w, int tile_h, int bw, int bh, int tx_size,
+    const R1IntraSplitCand *cands, int n, int enable_intra_edge_filter, uint32_t tx_type_mask,
+    const R1QuantParams *params, int dist_kind, const uint32_t *scales, int scale_stride,
+    uint16_t *eob_out, uint64_t *dist_out, uint64_t *est_rate_out,
+    void *qcoeffs_out, void *rec_out, void *stream);
 /* The mask of that loop: bit t set = TxType t is in av1_tx_used[get_tx_set(tx_size, is_inter,
  * use_reduced_set)]; rav1e_types_only != 0 keeps only RAV1E_TX_TYPES (DCT_DCT, ADST_DCT, DCT_ADST,
  * ADST_ADST, IDTX, V_DCT, H_DCT = 0x0E0F).  0 for an invalid tx_size.  Host arithmetic, no device work. */

@@ -166,6 +166,8 @@ SYMBOLS = {
     "r1_rdo_intra_cand_batch": (_i, [_vp, _PP, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, C.c_uint32,
                                      C.POINTER(R1QuantParams), _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                      _vp, _vp]),
+    "r1_rdo_intra_split_batch": (_i, [_vp, _PP, _PP, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, C.c_uint32,
+                                      C.POINTER(R1QuantParams), _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "r1_tx_type_mask": (C.c_uint32, [_i, _i, _i, _i]),
     "r1_coeff_rate_batch": (_i, [_vp, _vp, _i, _vp, _i, C.c_uint32, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "r1_lrf_sgrproj_plane": (_i, [_vp, _PP, _PP, _PP, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),

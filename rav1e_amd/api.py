@@ -22,6 +22,10 @@ INTRA_EDGE_CAND = np.dtype([("x", "<i2"), ("y", "<i2"), ("mode", "i1"), ("angle_
                             ("flags", "u1"), ("reserved", "u1")])
 INTRA_CAND = np.dtype([("mode", "u1"), ("variant", "u1"), ("angle", "<i2"), ("ief", "u1"),
                        ("avail_w", "u1"), ("avail_h", "u1"), ("reserved", "u1")])
+# R1IntraSplitCand: one intra block of r1_rdo_intra_split_batch
+INTRA_SPLIT_CAND = np.dtype([("x", "<i2"), ("y", "<i2"), ("mode", "u1"), ("angle_delta", "i1"), ("ief", "u1"),
+                             ("reserved", "u1"), ("tr_mask", "<u2"), ("bl_mask", "<u2")])
+assert INTRA_SPLIT_CAND.itemsize == 12
 CFL_AC_CAND = np.dtype([("x", "<i2"), ("y", "<i2"), ("w_pad", "u1"), ("h_pad", "u1"),
                         ("reserved", "u1", (2,))])
 CDEF_DIR_CAND = np.dtype([("x", "<i2"), ("y", "<i2")])
@@ -1017,6 +1021,42 @@ class Context:
             C.byref(qp), dist_kind, *_scales_arg(scales), xdec, ydec,
             *_ptrs(o, "sad", "satd", "eob", "dist", "est_rate", "qcoeffs", "rec", "pred"), _stream_ptr()),
             "r1_rdo_intra_cand_batch")
+        return o
+
+    def rdo_intra_split_batch(self, org, rec, tile, bw, bh, tx_size, cands, tx_type_mask, qindex, dist_kind,
+                              enable_intra_edge_filter=True, scales=None, is_intra=1, dc_delta_q=0, ac_delta_q=0,
+                              n=None, want_est_rate=False, want_qcoeffs=False, want_rec=False, outs=None):
+        """r1_rdo_intra_split_batch: write_tx_blocks' loop over the transform blocks of an intra block coded with
+        tx_size < block size (rdo_tx_size_type's split depths), one launch, the working reconstruction on the CU.
+        cands: INTRA_SPLIT_CAND list (rdo_glue.intra_split_cands), positions relative to tile = (x, y, w, h).
+        Outputs, ntx = transform blocks per block, nt = set bits of tx_type_mask: eob (n, nt, ntx); dist (n, nt, ntx)
+        under dist_kind 0 (with est_rate), else (n, nt); qcoeffs (n, nt, ntx, coded area); rec (n, nt, bh, bw)."""
+        tw, th = TxSize(tx_size).dims
+        ntx = max(1, bw // tw) * max(1, bh // th)
+        # the library checks the descriptors only where it can read them: before the upload
+        if isinstance(cands, np.ndarray):
+            c = cands[:n]
+            if (c["mode"] > 12).any() or ((c["x"] | c["y"]) & 3).any() or (c["x"] < 0).any() or (c["y"] < 0).any():
+                raise R1Error("r1_rdo_intra_split_batch: a mode above 12 or a position that is no multiple of 4")
+        dc, n = _dev_cands(cands, INTRA_SPLIT_CAND, n)
+        nt = bin(int(tx_type_mask)).count("1")
+        o = outs if outs is not None else {}
+        spec = {"eob": ((n, nt, ntx), torch.int16), "dist": ((n, nt, ntx) if dist_kind == 0 else (n, nt), torch.int64)}
+        if want_est_rate:
+            spec["est_rate"] = ((n, nt, ntx), torch.int64)
+        if want_qcoeffs:
+            spec["qcoeffs"] = ((n, nt, ntx, min(tw, 32) * min(th, 32)), _coeff_dtype(org.bpp))
+        if want_rec:
+            spec["rec"] = ((n, nt, bh, bw), _pix_dtype(org.bpp))
+        for k, (shape, dtype) in spec.items():
+            if k not in o:
+                o[k] = torch.empty(shape, dtype=dtype, device=_CUDA)
+        po, pr = org.cstruct(), rec.cstruct()
+        qp = self._qparams(qindex, org.bit_depth, is_intra, dc_delta_q, ac_delta_q)
+        self._check(self.lib.r1_rdo_intra_split_batch(
+            self.h, C.byref(po), C.byref(pr), *[int(v) for v in tile], bw, bh, int(tx_size), dc.data_ptr(), n,
+            int(bool(enable_intra_edge_filter)), int(tx_type_mask), C.byref(qp), dist_kind, *_scales_arg(scales),
+            *_ptrs(o, "eob", "dist", "est_rate", "qcoeffs", "rec"), _stream_ptr()), "r1_rdo_intra_split_batch")
         return o
 
     def coeff_rate_batch(self, qcoeffs, eobs, tx_type_mask, tx_size, plane, is_inter, ctxs, cdfs,

@@ -91,6 +91,106 @@ __device__ __forceinline__ bool is_directional(int mode, int angle) {
   return mode >= V_PRED && mode <= D67_PRED && !(mode == V_PRED && angle == 90) && !(mode == H_PRED && angle == 180);
 }
 
+// ---- get_intra_edges (src/partition.rs:639-898) as a rule over a pixel accessor, shared by k_intra_edges
+// (predict.hip: the accessor reads the reconstructed plane) and the transform-split kernel (rdo_intra_split.hip: it
+// answers from the block's working reconstruction in LDS inside the block and from the plane outside).  Every entry of
+// the reference's IntraEdgeBuffer has a closed-form source -- a pixel of the tile, a replicated pixel or a frame-edge
+// base value -- so the entries are produced independently.  (x, y): the transform block relative to the tile;
+// rect_w / rect_h: the tile clipped to the plane; mode < 0 = None (every edge is needed); flags as R1IntraEdgeCand's.
+struct EdgeRule {
+  int x, y, txw, txh, tw, th, tr_avail, bl_avail, init_left, init_above;
+  int32_t base;
+  bool needs_left, needs_topleft, needs_top, tl_filter;
+
+  __device__ __forceinline__ EdgeRule(int x_, int y_, int mode, int angle_delta, int flags, int rect_w, int rect_h,
+                                      int txw_, int txh_, int bd)
+      : x(x_), y(y_), txw(txw_), txh(txh_) {
+    base = 128 << (bd - 8);
+    bool needs_topright = true, needs_bottomleft = true;
+    needs_left = needs_topleft = needs_top = true;
+    tl_filter = false;
+    if (mode >= 0) {
+      if (mode == PAETH_PRED)
+        mode = (x == 0 && y == 0) ? DC_PRED : (x == 0 ? V_PRED : (y == 0 ? H_PRED : PAETH_PRED));
+      const bool directional = mode >= V_PRED && mode <= D67_PRED;
+      const int p_angle = mode_angle(mode) + angle_delta * 3;
+      const bool dc_or_cfl = mode == DC_PRED || mode == UV_CFL_PRED;
+      needs_left = (!dc_or_cfl || x != 0) || (p_angle > 90 && p_angle != 180);
+      needs_topleft = mode == PAETH_PRED || (directional && p_angle != 90 && p_angle != 180);
+      needs_top = (!dc_or_cfl || y != 0) || (p_angle != 90 && p_angle < 180);
+      needs_topright = directional && p_angle < 90;
+      needs_bottomleft = directional && p_angle > 180;
+      tl_filter = (flags & 1) && p_angle > 90 && p_angle < 180;
+    }
+    th = y + txh > rect_h ? rect_h - y : txh;     // visible rows / cols of the block
+    tw = x + txw > rect_w ? rect_w - x : txw;
+    tr_avail = bl_avail = 0;
+    if (needs_topright && y != 0 && (flags & 2)) {
+      tr_avail = rect_w - x - txw;
+      tr_avail = tr_avail > txw ? txw : (tr_avail < 0 ? 0 : tr_avail);
+    }
+    if (needs_bottomleft && x != 0 && (flags & 4)) {
+      bl_avail = rect_h - y - txh;
+      bl_avail = bl_avail > txh ? txh : (bl_avail < 0 ? 0 : bl_avail);
+    }
+    init_left = (needs_left ? txh : 0) + (needs_bottomleft ? txw : 0);
+    init_above = (needs_top ? txw : 0) + (needs_topright ? txh : 0);
+  }
+  // left[i], i = distance below the block's top row (index 127 - i); px(yy, xx) = the tile's pixel
+  template <typename Px>
+  __device__ __forceinline__ int32_t left_at(int i, Px px) const {
+    if (i < txh) {
+      if (x != 0) return px(y + (i < th ? i : th - 1), x - 1);
+      return y != 0 ? px(y - 1, 0) : base + 1;
+    }
+    const int k = i - txh;                                // bottom-left part
+    if (k < bl_avail) return px(y + txh + k, x - 1);
+    // replicate left[2*MAX - txh - num_avail] = the entry just above
+    const int j = txh + bl_avail - 1;
+    if (j >= txh) return px(y + txh + bl_avail - 1, x - 1);
+    if (x != 0) return px(y + (j < th ? j : th - 1), x - 1);
+    return y != 0 ? px(y - 1, 0) : base + 1;
+  }
+  template <typename Px>
+  __device__ __forceinline__ int32_t above_at(int i, Px px) const {
+    if (i < txw) {
+      if (y != 0) return px(y - 1, x + (i < tw ? i : tw - 1));
+      return x != 0 ? px(0, x - 1) : base - 1;
+    }
+    const int k = i - txw;                                // top-right part
+    if (k < tr_avail) return px(y - 1, x + txw + k);
+    const int j = txw + tr_avail - 1;
+    if (j >= txw) return px(y - 1, x + txw + tr_avail - 1);
+    if (y != 0) return px(y - 1, x + (j < tw ? j : tw - 1));
+    return x != 0 ? px(0, x - 1) : base - 1;
+  }
+  // entry k of the IntraEdgeBuffer, 2 * MAXTX - init_left <= k < 2 * MAXTX + 1 + init_above: only that range is
+  // initialised, in the reference as well
+  template <typename Px>
+  __device__ __forceinline__ int32_t entry(int k, Px px) const {
+    int32_t v = 0;
+    if (k < 2 * MAXTX) {
+      const int i = 2 * MAXTX - 1 - k;
+      // bottom-left entries exist only behind a needed left column; the
+      // reference never builds one without the other
+      if (i < init_left && needs_left) v = left_at(i, px);
+    } else if (k == 2 * MAXTX) {
+      if (needs_topleft) {
+        v = (x == 0 && y == 0) ? base
+            : (y == 0 ? px(0, x - 1) : (x == 0 ? px(y - 1, 0) : px(y - 1, x - 1)));
+        if (tl_filter && txw + txh >= 24)
+          v = (int32_t)(((uint32_t)left_at(0, px) * 5 + (uint32_t)v * 6 + (uint32_t)above_at(0, px) * 5 + 8) >> 4);
+      } else {
+        v = base;
+      }
+    } else {
+      const int i = k - 2 * MAXTX - 1;
+      if (i < init_above && needs_top) v = above_at(i, px);
+    }
+    return v;
+  }
+};
+
 // ---- edge filter / upsample in LDS (wave-uniform barriers, per-lane predicates).  `work` = the candidate's four
 // arrays of FL = 2 (W + H) + 1 entries: af0 af1 lf0 lf1; the final edges are af0 / lf0.  Lane c of the candidate's
 // `lanes` walks the entries c, c + lanes, ...  `enable` = this lane's candidate is directional with an edge filter.

@@ -3,11 +3,12 @@
 // kernels it selects, 786-1505; get_intra_edges src/partition.rs:639-898;
 // x86 dispatch src/asm/x86/predict.rs).
 //
-// k_intra_edges: one wave per candidate.  Every entry of the reference's
+// k_intra_edges: eight lanes per candidate.  Every entry of the reference's
 // IntraEdgeBuffer (left right-aligned ending at index 128, bottom->top;
 // top-left at 128; above from 129) has a closed-form source -- a pixel of the
 // reconstructed tile, a replicated pixel or a frame-edge base value -- so the
-// 257 entries are produced independently by the 64 lanes (no serial fill).
+// 257 entries are produced independently by the lanes (no serial fill).  The rule itself
+// is r1ip::EdgeRule (intra_pred_common.hpp), shared with the transform-split kernel.
 // The partition-tree availability answers (has_top_right / has_bottom_left)
 // are encoder state and arrive as flags.
 //
@@ -54,91 +55,15 @@ __global__ __launch_bounds__(64) void k_intra_edges(
   const int l = threadIdx.x & (lpc - 1);
   if (cand >= n) return;
   const R1IntraEdgeCand cd = cands[cand];
-  const int x = cd.x, y = cd.y, bd = rec.bit_depth;
-  const int32_t base = 128 << (bd - 8);
-  bool needs_left = true, needs_topleft = true, needs_top = true, needs_topright = true,
-       needs_bottomleft = true, tl_filter = false;
-  if (cd.mode >= 0) {
-    int mode = cd.mode;
-    if (mode == PAETH_PRED)
-      mode = (x == 0 && y == 0) ? DC_PRED : (x == 0 ? V_PRED : (y == 0 ? H_PRED : PAETH_PRED));
-    const bool directional = mode >= V_PRED && mode <= D67_PRED;
-    const int p_angle = mode_angle(mode) + cd.angle_delta * 3;
-    const bool dc_or_cfl = mode == DC_PRED || mode == UV_CFL_PRED;
-    needs_left = (!dc_or_cfl || x != 0) || (p_angle > 90 && p_angle != 180);
-    needs_topleft = mode == PAETH_PRED || (directional && p_angle != 90 && p_angle != 180);
-    needs_top = (!dc_or_cfl || y != 0) || (p_angle != 90 && p_angle < 180);
-    needs_topright = directional && p_angle < 90;
-    needs_bottomleft = directional && p_angle > 180;
-    tl_filter = (cd.flags & 1) && p_angle > 90 && p_angle < 180;
-  }
+  const EdgeRule er(cd.x, cd.y, cd.mode, cd.angle_delta, cd.flags, rect_w, rect_h, txw, txh, rec.bit_depth);
   const uint8_t *t0 = px_addr<BPP>(rec, tile_x, tile_y);
   const size_t st = (size_t)rec.stride;
   auto DST = [&](int yy, int xx) -> int32_t { return ldp<BPP>(t0, (size_t)yy * st + xx); };
-  const int th = y + txh > rect_h ? rect_h - y : txh;     // visible rows / cols of the block
-  const int tw = x + txw > rect_w ? rect_w - x : txw;
-  int tr_avail = 0, bl_avail = 0;
-  if (needs_topright && y != 0 && (cd.flags & 2)) {
-    tr_avail = rect_w - x - txw;
-    tr_avail = tr_avail > txw ? txw : (tr_avail < 0 ? 0 : tr_avail);
-  }
-  if (needs_bottomleft && x != 0 && (cd.flags & 4)) {
-    bl_avail = rect_h - y - txh;
-    bl_avail = bl_avail > txh ? txh : (bl_avail < 0 ? 0 : bl_avail);
-  }
-  // left[i], i = distance below the block's top row (index 127 - i)
-  auto left_at = [&](int i) -> int32_t {
-    if (i < txh) {
-      if (x != 0) return DST(y + (i < th ? i : th - 1), x - 1);
-      return y != 0 ? DST(y - 1, 0) : base + 1;
-    }
-    const int k = i - txh;                                // bottom-left part
-    if (k < bl_avail) return DST(y + txh + k, x - 1);
-    // replicate left[2*MAX - txh - num_avail] = the entry just above
-    const int j = txh + bl_avail - 1;
-    if (j >= txh) return DST(y + txh + bl_avail - 1, x - 1);
-    if (x != 0) return DST(y + (j < th ? j : th - 1), x - 1);
-    return y != 0 ? DST(y - 1, 0) : base + 1;
-  };
-  auto above_at = [&](int i) -> int32_t {
-    if (i < txw) {
-      if (y != 0) return DST(y - 1, x + (i < tw ? i : tw - 1));
-      return x != 0 ? DST(0, x - 1) : base - 1;
-    }
-    const int k = i - txw;                                // top-right part
-    if (k < tr_avail) return DST(y - 1, x + txw + k);
-    const int j = txw + tr_avail - 1;
-    if (j >= txw) return DST(y - 1, x + txw + tr_avail - 1);
-    if (y != 0) return DST(y - 1, x + (j < tw ? j : tw - 1));
-    return x != 0 ? DST(0, x - 1) : base - 1;
-  };
-  const int init_left = (needs_left ? txh : 0) + (needs_bottomleft ? txw : 0);
-  const int init_above = (needs_top ? txw : 0) + (needs_topright ? txh : 0);
+  const int init_left = er.init_left, init_above = er.init_above;
   void *e = (uint8_t *)edges + (size_t)cand * edge_stride * BPP;
   // only the initialised range [128 - init_left, 129 + init_above) is written;
   // the reference leaves the rest of the buffer uninitialised as well
-  for (int k = 2 * MAXTX - init_left + l; k < 2 * MAXTX + 1 + init_above; k += lpc) {
-    int32_t v = 0;
-    if (k < 2 * MAXTX) {
-      const int i = 2 * MAXTX - 1 - k;
-      // bottom-left entries exist only behind a needed left column; the
-      // reference never builds one without the other
-      if (i < init_left && needs_left) v = left_at(i);
-    } else if (k == 2 * MAXTX) {
-      if (needs_topleft) {
-        v = (x == 0 && y == 0) ? base
-            : (y == 0 ? DST(0, x - 1) : (x == 0 ? DST(y - 1, 0) : DST(y - 1, x - 1)));
-        if (tl_filter && txw + txh >= 24)
-          v = (int32_t)(((uint32_t)left_at(0) * 5 + (uint32_t)v * 6 + (uint32_t)above_at(0) * 5 + 8) >> 4);
-      } else {
-        v = base;
-      }
-    } else {
-      const int i = k - 2 * MAXTX - 1;
-      if (i < init_above && needs_top) v = above_at(i);
-    }
-    stp<BPP>(e, k, v);
-  }
+  for (int k = 2 * MAXTX - init_left + l; k < 2 * MAXTX + 1 + init_above; k += lpc) stp<BPP>(e, k, er.entry(k, DST));
   if (l == 0) {
     lens[2 * cand] = (uint8_t)init_left;
     lens[2 * cand + 1] = (uint8_t)init_above;

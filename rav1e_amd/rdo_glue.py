@@ -17,6 +17,14 @@ the kernels by executing the reference's own text (tests/golden/gen_rdo_glue_ref
                                                       (which slot of r1_rdo_txsearch_batch holds which TxType)
   txb_ctx                    src/context/block_unit.rs:442-526   (BlockContext::get_txb_ctx: the two neighbour
                                                        contexts r1_coeff_rate_batch takes per candidate)
+  sub_tx_size                src/context/transform_unit.rs:85-105  (sub_tx_size_map: the next transform depth)
+  intra_split_cands          src/encoder.rs:2276-2311  (write_tx_blocks' transform-block grid -> the descriptors of
+                                                       r1_rdo_intra_split_batch)
+  has_top_right / has_bottom_left   src/recon_intra.rs:174-243, 374-450   (luma, blocks up to 64x64; the reference's
+                                                       availability tables are replaced by the coding order they
+                                                       encode, computed)
+  intra_split_masks          src/partition.rs:766-848  (the questions get_intra_edges asks per transform block)
+                             pinned by tests/golden/rdo_intra_split_ref.npz / tests/test_rdo_intra_split_ref.py
   pick_tx_type               src/rdo.rs:1801-1818     (the tail of rdo_tx_type_decision's loop on the device's rates)
                              both pinned by tests/golden/coeff_rate_ref.npz / tests/test_coeff_rate_ref.py
 """
@@ -146,6 +154,118 @@ def tx_type_slots(tx_type_mask):
     """slot j of r1_rdo_txsearch_batch's outputs -> TxType: the set bits of the mask in ascending order,
     which is also the order of RAV1E_TX_TYPES (the loop order of rdo_tx_type_decision)"""
     return [t for t in range(16) if (int(tx_type_mask) >> t) & 1]
+
+
+def sub_tx_size(tx_size):
+    """sub_tx_size_map: the transform size one split depth down (rdo_tx_size_type, src/rdo.rs:735, 792).  A square
+    halves both sides (4x4 stays), a 2:1 rectangle becomes the square of its short side, a 4:1 rectangle halves its
+    long side."""
+    w, h = TxSize(tx_size).dims
+    if w == h:
+        return TxSize.by_dims(max(4, w // 2), max(4, h // 2))
+    if max(w, h) == 2 * min(w, h):
+        return TxSize.by_dims(min(w, h), min(w, h))
+    return TxSize.by_dims(w // 2, h) if w > h else TxSize.by_dims(w, h // 2)
+
+
+SB_MI = 16   # a 64x64 superblock in 4x4 units
+
+
+def _coding_rank(r, c, w_mi, h_mi):
+    """The place of block (row r, column c) of a superblock cut into uniform w_mi x h_mi blocks, in coding order:
+    the z-order of the square of side max(w, h) that holds it, then its place inside that square (halves or quarters
+    of a HORZ / VERT / HORZ_4 / VERT_4 partition, top to bottom or left to right).  This is what the reference's
+    has_tr_* / has_bl_* tables (src/recon_intra.rs) tabulate: `the neighbour is coded before this block`."""
+    s = max(w_mi, h_mi)
+    rs, cs = r * h_mi // s, c * w_mi // s
+    z = 0
+    for bit in range(5):
+        z |= ((cs >> bit) & 1) << (2 * bit) | ((rs >> bit) & 1) << (2 * bit + 1)
+    return z * 4 + (c * w_mi % s) // w_mi + (r * h_mi % s) // h_mi
+
+
+def has_top_right(bw, bh, mi_col, mi_row, top_available, right_available, tx_w, row_off, col_off):
+    """has_top_right (src/recon_intra.rs:174-243) for a luma block of bw x bh pixels (<= 64) at 4x4-unit position
+    (mi_col, mi_row) and the transform block of width tx_w at (row_off, col_off) 4x4 units inside it."""
+    if not top_available or not right_available:
+        return False
+    bw_unit, count = bw >> 2, tx_w >> 2
+    if row_off > 0:
+        return col_off + count < bw_unit             # just: enough pixels on the right, inside the block
+    if col_off + count < bw_unit:
+        return True                                  # all in the block above
+    w_mi, h_mi = bw >> 2, bh >> 2
+    r, c = (mi_row & (SB_MI - 1)) // h_mi, (mi_col & (SB_MI - 1)) // w_mi
+    if r == 0:
+        return True                                  # top row of the superblock: the superblocks above are coded
+    if (c + 1) * w_mi >= SB_MI:
+        return False                                 # rightmost column: the superblock to the right is not
+    return _coding_rank(r - 1, c + 1, w_mi, h_mi) < _coding_rank(r, c, w_mi, h_mi)
+
+
+def has_bottom_left(bw, bh, mi_col, mi_row, bottom_available, left_available, tx_h, row_off, col_off):
+    """has_bottom_left (src/recon_intra.rs:374-450), as has_top_right"""
+    if not bottom_available or not left_available:
+        return False
+    if col_off > 0:
+        return False                                 # inside the block: that transform block is not coded yet
+    bh_unit, count = bh >> 2, tx_h >> 2
+    if row_off + count < bh_unit:
+        return True                                  # all in the block to the left
+    w_mi, h_mi = bw >> 2, bh >> 2
+    r, c = (mi_row & (SB_MI - 1)) // h_mi, (mi_col & (SB_MI - 1)) // w_mi
+    if c == 0:
+        return r * h_mi + row_off + count < SB_MI    # leftmost column: only the left superblock is coded
+    if (r + 1) * h_mi >= SB_MI:
+        return False                                 # bottom row: the superblock below is not coded
+    # the block that holds the pixel below-left of this block's bottom-left corner
+    return _coding_rank((r + 1), c - 1, w_mi, h_mi) < _coding_rank(r, c, w_mi, h_mi)
+
+
+def intra_split_masks(bw, bh, tx_size, mi_col, mi_row, x, y, rect_w, rect_h):
+    """(tr_mask, bl_mask) of R1IntraSplitCand for the block at tile position (x, y) pixels / (mi_col, mi_row) 4x4 units:
+    bit k = has_top_right / has_bottom_left as get_intra_edges asks them for transform block k (src/partition.rs:766-848:
+    have_top = by4 != 0 || the block is not in the tile's first row, right_available = x_k + tw < rect_w, ...).
+    rect_w / rect_h: the tile clipped to the plane."""
+    tw, th = TxSize(tx_size).dims
+    gw, gh = bw // tw, bh // th
+    tr = bl = 0
+    for by in range(gh):
+        for bx in range(gw):
+            k, xk, yk, bx4, by4 = by * gw + bx, x + bx * tw, y + by * th, bx * (tw >> 2), by * (th >> 2)
+            if has_top_right(bw, bh, mi_col, mi_row, by4 != 0 or mi_row > 0, xk + tw < rect_w, tw, by4, bx4):
+                tr |= 1 << k
+            if has_bottom_left(bw, bh, mi_col, mi_row, yk + th < rect_h, bx4 != 0 or mi_col > 0, th, by4, bx4):
+                bl |= 1 << k
+    return tr, bl
+
+
+def intra_split_cands(blocks, bw, bh, tx_size):
+    """The descriptors of r1_rdo_intra_split_batch for intra blocks of bw x bh pixels coded with tx_size transforms.
+    blocks: one (x, y, mode, angle_delta, ief, has_tr, has_bl) per block -- the position relative to the tile, the luma
+    mode as write_tx_blocks receives it (no Paeth remap), the block's ief (0 none, 1 plain, 2 smooth neighbour; it is
+    taken as 0 for a mode that is not directional, as encode_tx_block does, src/encoder.rs:1458) and has_tr / has_bl:
+    the answers of has_top_right / has_bottom_left per transform block, indexed by the block's raster index in the
+    bw/tw x bh/th grid (sequences of ntx truth values, or ready bit masks).  -> numpy array of api.INTRA_SPLIT_CAND"""
+    import numpy as np
+    from .api import INTRA_SPLIT_CAND
+    tw, th = TxSize(tx_size).dims
+    assert bw % tw == 0 and bh % th == 0
+    ntx = (bw // tw) * (bh // th)
+    assert 2 <= ntx <= 16
+
+    def mask(v):
+        if isinstance(v, (int, np.integer)):
+            assert 0 <= int(v) < (1 << ntx)
+            return int(v)
+        assert len(v) == ntx
+        return sum(1 << k for k, b in enumerate(v) if b)
+    c = np.zeros(len(blocks), INTRA_SPLIT_CAND)
+    for i, (x, y, mode, delta, ief, tr, bl) in enumerate(blocks):
+        assert x >= 0 and y >= 0 and x % 4 == 0 and y % 4 == 0 and 0 <= mode <= 12
+        directional = 1 <= mode <= 8
+        c[i] = (x, y, mode, delta if directional else 0, ief if directional else 0, 0, mask(tr), mask(bl))
+    return c
 
 
 RESTORATION_TILESIZE_MAX_LOG2 = 8

@@ -1,0 +1,287 @@
+"""r1_rdo_intra_split_batch on the GPU: the transform blocks of an intra block in one launch (the block's working
+reconstruction in LDS) against the composition its header states -- r1_intra_edges_batch -> r1_predict_intra_batch ->
+r1_rdo_txsearch_batch -> scatter, per transform block in raster order on a private copy of `rec` -- run on the device
+and on the CPU oracle (tests/intra_split_util.py), bit for bit, on seeded inputs at the smallest shapes that reach
+each path of the kernel."""
+import numpy as np
+import pytest
+
+import intra_split_util as SU
+import layout_util as LU
+import oracle_lib as O
+
+pytestmark = pytest.mark.gpu
+
+GUARD = 0x5A
+W, H = 204, 140     # multiples of 4, not of 8: the last column / row of 4x4 units is half an 8x8
+
+
+def _t(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _dev_plane(hp):
+    from rav1e_amd.api import Plane
+    return Plane.from_numpy(hp.data, hp.width, hp.height, hp.bit_depth, hp.xpad, hp.ypad)
+
+
+def _planes(bd, seed, width=W, height=H):
+    """a reconstructed plane and a source plane near it (so that some transform blocks quantize to nothing and
+    others do not)"""
+    rng = np.random.default_rng(seed)
+    rec = O.HostPlane(width, height, bd, rng=rng)
+    # smooth-ish content: directional predictions then leave residuals of a few levels
+    yy, xx = np.mgrid[0:rec.alloc_height, 0:rec.stride]
+    base = ((xx * 3 + yy * 5) % 97 + (xx // 7) * 2) * (1 << (bd - 8)) + rng.integers(0, 24 << (bd - 8), rec.data.shape)
+    rec.data[...] = np.clip(base, 0, (1 << bd) - 1).astype(rec.data.dtype)
+    org = O.HostPlane(width, height, bd)
+    nz = rng.integers(-14, 15, org.data.shape) * (1 << (bd - 8))
+    org.data[...] = np.clip(rec.data.astype(np.int64) + nz, 0, (1 << bd) - 1).astype(org.data.dtype)
+    return rec, org
+
+
+def _guarded(shape, dtype):
+    import torch
+    n = int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
+    raw = torch.full((n + 128,), GUARD, dtype=torch.uint8, device="cuda")
+    return raw, raw[64:64 + n].view(dtype).view(*shape)
+
+
+def _guards_intact(raw):
+    g = raw.cpu().numpy()
+    return bool((g[:64] == GUARD).all() and (g[-64:] == GUARD).all())
+
+
+def make_cands(rng, n, bw, bh, t, tile_w, tile_h, inside_only=False):
+    """n blocks on the 4-pixel grid.  The first seven: the tile origin, the first row, the first column, inside, cut by
+    the right edge with its last transform-block column skipped, the same partly visible, cut by the bottom edge.  All 13
+    modes, deltas -3 .. 3 with the extremes first, every ief value, random has_top_right / has_bottom_left masks."""
+    c = np.zeros(n, SU.SPLIT_CAND)
+    mx, my = (tile_w - bw) // 4, (tile_h - bh) // 4
+    c["x"], c["y"] = rng.integers(0, mx + 1, n) * 4, rng.integers(0, my + 1, n) * 4
+    if not inside_only:
+        gw = bw // t
+        # the last transform-block column starts on the tile's right edge (skipped), or half a transform before it
+        # (partly visible; a 4x4 cannot be: the tile is a multiple of 4)
+        skip_x = tile_w - (gw - 1) * t if gw > 1 else tile_w - t // 2
+        part_x = tile_w - (gw - 1) * t - t // 2 if t > 4 else tile_w - 4
+        fixed = [(0, 0), (max(4, bw), 0), (0, max(4, bh)), (bw + 4, bh + 4), (skip_x, 8), (part_x, 4),
+                 (12, tile_h - bh // 2)]
+        for k, (x, y) in enumerate(fixed[:n]):
+            c["x"][k], c["y"][k] = x, y
+    c["mode"] = rng.permutation(np.arange(n) % 13)
+    c["angle_delta"] = np.where((c["mode"] >= 1) & (c["mode"] <= 8), rng.choice([-3, 3, 0, -1, 2], n), 0)
+    c["ief"] = np.where((c["mode"] >= 1) & (c["mode"] <= 8), rng.integers(0, 3, n), 0)
+    ntx = (bw // t) * (bh // t)
+    c["tr_mask"], c["bl_mask"] = rng.integers(0, 1 << ntx, n), rng.integers(0, 1 << ntx, n)
+    return c
+
+
+def one_launch(ctx, dorg, drec, tile, bw, bh, ts, cands, enable, mask, qi, kind, dscales, full=True):
+    """the call with every output it can give inside guard bytes -> host arrays"""
+    import torch
+    t = SU.TX_SIDE[ts]
+    n, nt, ntx = len(cands), bin(mask).count("1"), (bw // t) * (bh // t)
+    pt, cdt = (torch.uint8, torch.int16) if dorg.bit_depth == 8 else (torch.int16, torch.int32)
+    spec = {"eob": ((n, nt, ntx), torch.int16), "dist": ((n, nt, ntx) if kind == 0 else (n, nt), torch.int64)}
+    if full:
+        spec["qcoeffs"] = ((n, nt, ntx, t * t), cdt)
+        if kind:
+            spec["rec"] = ((n, nt, bh, bw), pt)
+        else:
+            spec["est_rate"] = ((n, nt, ntx), torch.int64)
+    raws, outs = {}, {}
+    for k, (shape, dtype) in spec.items():
+        raws[k], outs[k] = _guarded(shape, dtype)
+    o = ctx.rdo_intra_split_batch(dorg, drec, tile, bw, bh, ts, cands, mask, qi, kind, enable_intra_edge_filter=enable,
+                                  scales=dscales, outs=outs)
+    assert set(o) == set(spec)
+    torch.cuda.synchronize()
+    for k in raws:
+        assert _guards_intact(raws[k]), (k, "guard bytes")
+    return {k: v.cpu().numpy() for k, v in o.items()}
+
+
+def _same(got, want, keys, key, what):
+    for k in keys:
+        w = want[k].cpu().numpy() if hasattr(want[k], "cpu") else want[k]
+        g = got[k]
+        assert g.shape == w.shape, (key, k, what, g.shape, w.shape)
+        assert np.array_equal(g.view(w.dtype) if g.dtype != w.dtype else g, w), (key, k, what)
+
+
+# (block w, block h, TxSize, bit depth): 8x8/4x4; 16x16/4x4, the smallest grid in which every inner top-right pattern
+# occurs; 16x16/8x8; 32x32/8x8 (16 steps of 8x8); 64x64/32x32 (two trials a wave, 16 KB of reconstructions at 10 bits);
+# 64x64/16x16 (trials per wave cut to fit the LDS budget); 16x8/4x4 and 8x16/8x8 (grids that are not square)
+SHAPES = [(8, 8, 0), (16, 16, 0), (16, 16, 1), (32, 32, 1), (64, 64, 3), (64, 64, 2), (16, 8, 0), (8, 16, 1)]
+CASES = [s + (bd,) for s in SHAPES for bd in (8, 10)] + [(16, 16, 1, 12)]
+
+
+@pytest.mark.parametrize("bw,bh,ts,bd", CASES)
+def test_one_launch_equals_device_and_oracle_compositions(ctx, oracle, bw, bh, ts, bd):
+    """three calls per shape: the three distortion kinds, the edge filter on and off, a multi-type mask (up to
+    16x16), a single type and the two types of 32x32; n = trials per wave + 1 and 2 x that + 1 (ragged last wave);
+    blocks at the seven positions; every optional output and the minimal set; a tile that is the frame and one that
+    starts inside it"""
+    import torch
+    t = SU.TX_SIDE[ts]
+    nc = 64 // t
+    rec, org = _planes(bd, 6100 + 100 * ts + bw + bd)
+    drec, dorg = _dev_plane(rec), _dev_plane(org)
+    rng = np.random.default_rng(31 * bw + 7 * bh + ts + bd)
+    scales = rng.integers(1 << 12, 1 << 16, ((H + 64 + 7) // 8, (W + 64 + 7) // 8)).astype(np.uint32)
+    dscales = _t(scales.view(np.int32))
+    full_mask = ctx.tx_type_mask(ts, False)
+    masks = [full_mask & 0x20B, 1 << 9, full_mask] if t <= 16 else [1, 0x201, 1 << 9]
+    before = drec.data.clone()
+    for step, kind in enumerate((3, 0, 2)):
+        n = max(7, nc + 1) if step != 1 else max(7, min(2 * nc + 1, 13))
+        tile = (0, 0, W, H) if step != 2 else (8, 4, W - 8, H - 4)
+        cands = make_cands(rng, n, bw, bh, t, tile[2], tile[3])
+        enable, mask, qi = step != 1, masks[step], (60, 120, 200)[step]
+        use_sc = step != 1
+        key = (bw, bh, ts, bd, kind, hex(mask), n)
+        got = one_launch(ctx, dorg, drec, tile, bw, bh, ts, cands, enable, mask, qi, kind,
+                         dscales if use_sc else None, full=step != 2)
+        keys = list(got)
+        want = SU.oracle_split(oracle, org, rec, tile, bw, bh, ts, cands, enable, mask, qi, kind,
+                               scales if use_sc else None)
+        _same(got, want, keys, key, "oracle composition")
+        dev = SU.device_split(ctx, dorg, drec, tile, bw, bh, ts, cands, enable, mask, qi, kind,
+                              dscales if use_sc else None)
+        _same(got, dev, keys, key, "device composition")
+        assert int((got["eob"] != 0).sum()) > 0 and int((got["eob"] == 0).sum()) > 0, key
+    assert torch.equal(drec.data, before), "rec was written"
+
+
+def test_reference_fixture_through_the_one_launch(ctx):
+    """every case of rdo_intra_split_ref.npz (the reference's encode_tx_block executed over the transform blocks of an
+    intra block): the recorded neighbourhood and source block, the descriptors from rdo_glue.intra_split_cands with the
+    has_top_right / has_bottom_left answers as executed -> eob, qcoeffs, the reconstruction over the transform blocks
+    that are not skipped, the transform-domain distortion per transform block, and the four pixel-domain distortions:
+    the call's own where the block lies inside the frame, and for every case the visible part of rec_out through
+    r1_dist_scaled_batch, as the header tells the caller to do at a frame edge"""
+    import rdo_intra_split_cases as SC
+    from rav1e_amd.api import DIST_CAND, Plane
+    from rav1e_amd.rdo_glue import intra_split_cands
+    cases = SC.load()
+    for c in cases:
+        key = (c.i, c.bd, c.bw, c.bh, c.t, c.mode, c.angle_delta)
+        drec, dorg = _dev_plane(c.rec_plane()), _dev_plane(c.org_plane())
+        grid = _t(c.scales.view(np.int32))
+        cands = intra_split_cands(c.blocks(), c.bw, c.bh, c.ts)
+
+        def run(kind, scaled, **kw):
+            return ctx.rdo_intra_split_batch(dorg, drec, c.tile, c.bw, c.bh, c.ts, cands, 1 << c.tx_type, c.qidx, kind,
+                                             enable_intra_edge_filter=c.enable_ief, scales=grid if scaled else None,
+                                             want_qcoeffs=True, **kw)
+
+        def check(o, what):
+            assert np.array_equal(o["eob"].cpu().numpy().view(np.uint16)[0, 0], c.eob), (key, what, "eob")
+            assert np.array_equal(o["qcoeffs"].cpu().numpy()[0, 0].astype(np.int64), c.qc.astype(np.int64)), (key, what, "qc")
+        o = run(0, False, want_est_rate=True)
+        check(o, "tx")
+        assert np.array_equal(o["dist"].cpu().numpy().view(np.uint64)[0, 0], c.txd), (key, "transform-domain distortion")
+        for j, (kind, scaled) in enumerate(SC.DIST_RUNS):
+            o = run(kind, scaled, want_rec=True)
+            check(o, (kind, scaled))
+            rec = o["rec"].cpu().numpy().view(c.dt)[0, 0]
+            assert np.array_equal(rec[c.coded_mask], c.rec[c.coded_mask]), (key, kind, "rec")
+            if c.inside:
+                assert int(o["dist"].cpu().numpy().view(np.uint64)[0, 0]) == int(c.dist[j]), (key, "dist", j)
+            bp = Plane(c.bw, c.bh, c.bd, 0, 0)
+            bp.data[:c.bh, :c.bw] = o["rec"][0, 0]
+            dc = np.zeros(1, DIST_CAND)
+            dc["ox"], dc["oy"] = c.x, c.y
+            d = ctx.dist_scaled_batch(kind, dorg, bp, c.vis_w, c.vis_h, dc, scales=grid if scaled else None)
+            assert int(d.cpu().numpy().view(np.uint64)[0]) == int(c.dist[j]), (key, "visible dist", j)
+
+
+@pytest.mark.parametrize("kind_of_layout", LU.KINDS)
+@pytest.mark.parametrize("bd", [8, 10])
+def test_odd_and_tight_plane_layouts(ctx, oracle, kind_of_layout, bd):
+    """planes whose rows start at odd element offsets / planes without a spare byte, `org` and `rec` in different
+    layouts, 8 pixels of padding, blocks whole inside the frame (a tight plane has nothing behind its last row):
+    outputs inside guard bytes, guard bytes around both planes intact, `rec` unchanged"""
+    bw, bh, ts = 16, 16, 1
+    rec0, org0 = _planes(bd, 7300 + bd, 76, 52)
+    other = LU.KINDS[1 - LU.KINDS.index(kind_of_layout)]
+    rec, drec = LU.relayout(rec0, kind_of_layout, 8, 8)
+    org, dorg = LU.relayout(org0, other, 8, 8)
+    rng = np.random.default_rng(88 + bd)
+    scales = rng.integers(1 << 12, 1 << 16, (8, 11)).astype(np.uint32)
+    dscales = _t(scales.view(np.int32))
+    before = drec.host().copy()
+    for kind, tile in ((3, (0, 0, 76, 52)), (0, (4, 8, 72, 44))):
+        cands = make_cands(rng, 9, bw, bh, 8, tile[2], tile[3], inside_only=True)
+        got = one_launch(ctx, dorg, drec, tile, bw, bh, ts, cands, True, 0x203, 90, kind, dscales)
+        want = SU.oracle_split(oracle, org, rec, tile, bw, bh, ts, cands, True, 0x203, 90, kind, scales)
+        _same(got, want, list(got), (kind_of_layout, bd, kind), "oracle composition")
+    assert LU.guards_intact(drec, dorg)
+    assert np.array_equal(drec.host(), before), "rec was written"
+
+
+def test_rejects_bad_arguments(ctx):
+    """every R1_EINVAL the header names; each leaves without a launch"""
+    from rav1e_amd.api import R1Error
+    rec, org = _planes(8, 5)
+    drec, dorg = _dev_plane(rec), _dev_plane(org)
+    rec10, _ = _planes(10, 5)
+    drec10 = _dev_plane(rec10)
+    rng = np.random.default_rng(2)
+    tile = (0, 0, W, H)
+    cands = make_cands(rng, 5, 16, 16, 8, W, H)
+
+    def call(bw=16, bh=16, ts=1, c=cands, mask=0x20B, kind=3, tile=tile, rec=drec, **kw):
+        return ctx.rdo_intra_split_batch(dorg, rec, tile, bw, bh, ts, c, mask, 60, kind, **kw)
+
+    call()                                                        # fine
+    call(kind=0, want_est_rate=True)                              # fine
+    call(kind=2, want_rec=True)                                   # fine
+    bad = [dict(ts=5), dict(ts=7, bw=16, bh=32),                  # 4x8, 8x16: not square
+           dict(ts=4, bw=64, bh=64),                              # 64x64: a single transform block
+           dict(bw=8, bh=8),                                      # ntx = 1
+           dict(bw=64, bh=64, ts=0),                              # ntx = 256
+           dict(bw=32, bh=32, ts=0),                              # ntx = 64
+           dict(bw=64, bh=8, ts=1),                               # 8:1 is no block size
+           dict(bw=24, bh=16),                                    # not a power of two
+           dict(bw=16, bh=8, ts=2),                               # the transform does not divide the block
+           dict(mask=0), dict(mask=1 << 16),                      # empty mask, beyond the 16 types
+           dict(bw=64, bh=64, ts=3, mask=0x3),                    # ADST has no 32-point kernel
+           dict(kind=1), dict(kind=4),                            # not a kind
+           dict(kind=3, want_est_rate=True),                      # est_rate with a pixel-domain kind
+           dict(kind=0, want_rec=True),                           # rec with kind 0
+           dict(tile=(0, 0, W + 4, H)), dict(tile=(-4, 0, W, H)), dict(tile=(0, 0, 0, H)),   # tile not inside rec
+           dict(rec=drec10)]                                      # planes of different pixel formats
+    for kw in bad:
+        with pytest.raises(R1Error):
+            call(**kw)
+    for field, value in (("mode", 13), ("x", 6), ("y", 2), ("x", -4)):
+        c = cands.copy()
+        c[field][3] = value
+        with pytest.raises(R1Error):
+            call(c=c)
+    # NULL planes / cands / params: the C entry point itself
+    import ctypes as C
+    from rav1e_amd import _lib
+    lib = ctx.lib
+    po, pr = dorg.cstruct(), drec.cstruct()
+    qp = ctx._qparams(60, 8, 1)
+    dc = _t(cands.view(np.uint8).reshape(-1))
+    eob, dist = _t(np.zeros(5 * 4 * 4, np.int16)), _t(np.zeros(5 * 4, np.int64))
+
+    def raw(org_p, rec_p, cands_p, params_p, eob_p=eob.data_ptr(), dist_p=dist.data_ptr()):
+        return lib.r1_rdo_intra_split_batch(ctx.h, org_p, rec_p, 0, 0, W, H, 16, 16, 1, cands_p, 5, 1, 0x20B, params_p,
+                                            3, None, 0, eob_p, dist_p, None, None, None, None)
+    good = (C.byref(po), C.byref(pr), dc.data_ptr(), C.byref(qp))
+    import torch
+    assert raw(*good) == 0
+    torch.cuda.synchronize()
+    for k in range(4):
+        args = list(good)
+        args[k] = None
+        assert raw(*args) == -1, k
+    assert raw(*good, eob_p=None) == -1 and raw(*good, dist_p=None) == -1
+    wrong_depth = _lib.R1QuantParams(60, 10, 1, 0, 0)
+    assert raw(good[0], good[1], good[2], C.byref(wrong_depth)) == -1

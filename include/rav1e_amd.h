@@ -121,8 +121,9 @@ const char *r1_last_error(void);
  * r1_comm_push_frame (round 5) were added under versions 4 and 5 respectively, and the compound candidate
  * (r1_rdo_compound_cand_batch, R1CompoundCand) under version 7, as were the frame's scale maps and segmentation
  * inputs (r1_frame_scales, r1_scale_kmeans, r1_segmentation_from_centroids, r1_spatiotemporal_scale_batch) and the
- * intra candidate (r1_rdo_intra_cand_batch), the coefficient rate (r1_coeff_rate_batch, R1CoeffCdfs, R1TxbCtx) and the
- * intra transform-split candidate (r1_rdo_intra_split_batch, R1IntraSplitCand). */
+ * intra candidate (r1_rdo_intra_cand_batch), the coefficient rate (r1_coeff_rate_batch, R1CoeffCdfs, R1TxbCtx), the
+ * intra transform-split candidate (r1_rdo_intra_split_batch, R1IntraSplitCand) and the coefficient rate across a
+ * block's transform blocks (r1_coeff_rate_chain_batch, R1TxbChainCtx). */
 int r1_abi_version(void);
 
 /* ---- dist:: (reference: src/dist.rs get_sad 31, get_satd 156; dispatch
@@ -1113,9 +1114,9 @@ int r1_rdo_intra_cand_batch(r1_ctx *ctx, const R1Plane *org, int w, int h, int t
  * split depths of every square and 2:1 block, depth 2 of the 4:1 blocks), bit depths 8 / 10 / 12, luma modes 0 .. 12
  * as write_tx_blocks receives them (NO Paeth remap by the caller).
  * NOT built: the 2:1 transform sizes (depth 1 of the 4:1 blocks) -- they stay on the host loop over the three calls
- * above; the real coefficient rate across several transform blocks (its context chain between transform blocks
- * stays on the host, which gets qcoeffs_out / eob_out for r1_coeff_rate_batch); chroma (write_tx_blocks never splits
- * it); a routing to a multi-launch fallback (every point runs the one kernel).
+ * above; chroma (write_tx_blocks never splits it); a routing to a multi-launch fallback (every point runs the one
+ * kernel).  The real coefficient rate across the transform blocks: r1_coeff_rate_chain_batch (order 0) behind this
+ * call, on qcoeffs_out / eob_out as they lie.
  * R1_EINVAL: everything r1_rdo_txsearch_batch rejects for the size, mask and kind; a tx_size that is not one of the
  * four; bw / bh that the transform does not divide, that is no block size, or ntx of 1 or above 16; a tile that is not
  * inside `rec`; planes of different pixel formats; a NULL plane, cands, params, eob_out or dist_out; est_rate_out or
@@ -1197,13 +1198,62 @@ typedef struct R1TxbCtx { uint8_t txb_skip_ctx, dc_sign_ctx, y_mode, cdf_sel; } 
  * plane outside 0..2.  Device-resident data cannot be checked there: a slot whose eob exceeds the coded area, whose
  * txb_skip_ctx / dc_sign_ctx / y_mode is out of range or whose cdf_sel >= n_cdfs gets rate 0xFFFFFFFF and cul_level 0,
  * and nothing is read out of bounds.  Every loop of the kernel is bounded independently of the data's values.
- * OUT OF SCOPE: blocks that write_tx_tree / write_tx_blocks code as several transform blocks (tx depth > 0, luma and
- * chroma together) -- their CDFs and neighbour contexts carry from one transform block to the next -- and every
- * non-coefficient symbol (modes, motion vectors, partition, count_lrf_switchable). */
+ * Blocks that write_tx_tree / write_tx_blocks code as several transform blocks: r1_coeff_rate_chain_batch below.
+ * OUT OF SCOPE: every non-coefficient symbol (modes, motion vectors, partition, count_lrf_switchable). */
 int r1_coeff_rate_batch(r1_ctx *ctx, const void *qcoeffs, int coeff_bytes, const uint16_t *eobs, int n,
                         uint32_t tx_type_mask, int tx_size, int plane, int is_inter, int use_reduced_tx_set,
                         const R1TxbCtx *ctxs, const R1CoeffCdfs *cdfs, int n_cdfs, uint32_t *rate_out,
                         uint8_t *cul_level_out, void *stream);
+
+/* ---- the real coefficient rate across a block's transform blocks (added under ABI 7): rdo_tx_size_type
+ * (src/rdo.rs:725-802) compares transform depths by compute_rd_cost(rate, distortion) with rate = wr.tell_frac() - tell
+ * around ONE write_tx_blocks (intra) or write_tx_tree (inter) call with luma_only = true (src/rdo.rs:1744-1799): nothing
+ * but write_coeffs_lv_map over the block's luma transform blocks in raster order, on one WriterCounter, with the CDFs
+ * adapted by every symbol of the blocks before and the neighbour contexts set_coeff_context stored for them.  This call
+ * computes that rate for every (block, type) trial behind the launch that made the coefficients, with no copy.
+ *   trial (i, j):   block i with the j-th set bit of tx_type_mask, as the slots of r1_coeff_rate_batch (nt = popcount).
+ *   grid:           ntx = (bw / tw) * (bh / th) transform blocks in raster order, 1 <= ntx <= 16.
+ *   order:          where transform block k of trial (i, j) lies in qcoeffs (dense coded-area blocks) / eobs:
+ *                   0: at (i * nt + j) * ntx + k -- what r1_rdo_intra_split_batch writes;
+ *                   1: at (i * ntx + k) * nt + j -- what r1_rdo_txsearch_batch writes when its candidates are the
+ *                      transform blocks of the blocks, block after block.
+ *   chains[i]:      the block's state in front (R1TxbChainCtx); cdfs[chains[i].cdf_sel] is the snapshot every trial of
+ *                   the block starts from, unadapted.
+ * Per coded transform block, in raster order, what write_coeffs_lv_map does (block_unit.rs:1783-1857): get_txb_ctx
+ * (442-526, luma; txb_skip_ctx is 0 when ntx == 1) over the first frame_clipped_txw >> 2 / txh >> 2 entries; the symbols,
+ * every row they touch adapted for the blocks behind (update_cdf with the row's own length, src/ec.rs:935-955);
+ * set_coeff_context over the FULL tw / 4, th / 4 span with cul_level, or 0 for eob == 0.  A transform block whose origin
+ * lies at or beyond mi_w / mi_h is not coded (encoder.rs:2282, 2446).
+ *   rate_out[i * nt + j]:   tell_frac behind the last block minus the fresh counter's, 1/8 bit.
+ *   txb_rate_out (optional) [trial * ntx + k]: tell_frac behind block k minus tell_frac in front of it; 0 for a block
+ *                   that is not coded; the values of a trial sum to its rate_out.
+ *   cul_level_out (optional) [trial * ntx + k].
+ *   ctx_out (optional): 32 bytes per trial, `above` and `left` behind the last block: what the host stores for the
+ *                   winner.
+ * `cdfs` and the inputs are never written.  With ntx == 1 the numbers are r1_coeff_rate_batch's.
+ * In scope: plane 0, all 19 transform sizes, bw, bh <= 64, coefficient widths 2 and 4.
+ * R1_EINVAL: everything r1_coeff_rate_batch refuses (chains in place of ctxs), a transform that does not divide the
+ * block, ntx outside 1..16, order outside 0..1, bw or bh that is no block size.  Device-resident data the host cannot
+ * see -- an eob above the coded area in any coded transform block, y_mode >= 13, cdf_sel >= n_cdfs, mi_w > clip_w4 or
+ * mi_h > clip_h4 -- gives the trial rate 0xFFFFFFFF and zero side outputs; nothing is read or written out of bounds.
+ * `above` / `left` bytes hold what set_coeff_context stores (below 192); a sign field of 3 counts as no sign.
+ * Every loop is bounded by ntx, the coded area, the four base-range rounds or the Golomb length.
+ * OUT OF SCOPE: the chroma half of write_tx_blocks / write_tx_tree (other R1CoeffCdfs slices, U then V behind luma);
+ * every non-coefficient symbol; exporting the adapted CDFs; making the serial range-coder chain itself faster. */
+typedef struct R1TxbChainCtx {          /* 40 bytes */
+  uint8_t above[16];   /* above_coeff_context[0][bo.x + c], c < bw / 4: the state in front of the block */
+  uint8_t left[16];    /* left_coeff_context[0][bo.y_in_sb() + r], r < bh / 4 */
+  uint8_t mi_w, mi_h;  /* min(255, ts.mi_width - bo.x), min(255, ts.mi_height - bo.y) */
+  uint8_t clip_w4, clip_h4; /* min(255, fi.w_in_b - frame_bo.x), same for h: frame_clipped_txw >> 2 =
+                          min(tw / 4, clip_w4 - x4) for the transform block at 4x4-unit origin (x4, y4) of the block
+                          (encoder.rs:1561-1566) */
+  uint8_t y_mode, cdf_sel, reserved[2];
+} R1TxbChainCtx;
+int r1_coeff_rate_chain_batch(r1_ctx *ctx, const void *qcoeffs, int coeff_bytes, const uint16_t *eobs, int n,
+                              uint32_t tx_type_mask, int bw, int bh, int tx_size, int order, int is_inter,
+                              int use_reduced_tx_set, const R1TxbChainCtx *chains, const R1CoeffCdfs *cdfs, int n_cdfs,
+                              uint32_t *rate_out, uint32_t *txb_rate_out, uint8_t *cul_level_out, uint8_t *ctx_out,
+                              void *stream);
 
 /* ---- multi-GPU: the tile-boundary exchange and the reference-frame all-gather (RCCL over
  * xGMI), SURVEY.md 8(e).  One process (or host thread) per GPU, tile r on rank r.  Rendezvous:

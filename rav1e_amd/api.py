@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .types import COEFF_CDFS, COEFF_RATE_INVALID, TX_DIMS, TXB_CTX, TxSize, valid_av1_transform  # noqa: F401
+from .types import COEFF_CDFS, COEFF_RATE_INVALID, TX_DIMS, TXB_CHAIN_CTX, TXB_CTX, TxSize, valid_av1_transform  # noqa: F401
 
 DIST_CAND = np.dtype([("ox", "<i2"), ("oy", "<i2"), ("rx", "<i2"), ("ry", "<i2")])
 MC_CAND = np.dtype([("rx", "<i2"), ("ry", "<i2"), ("col_frac", "u1"), ("row_frac", "u1"),
@@ -1087,6 +1087,45 @@ class Context:
             int(plane), int(bool(is_inter)), int(bool(use_reduced_tx_set)), dctx.data_ptr(), dcdf.data_ptr(),
             n_cdfs, o["rate"].data_ptr(), cul.data_ptr() if cul is not None else None, _stream_ptr()),
             "r1_coeff_rate_batch")
+        return o
+
+    def coeff_rate_chain_batch(self, qcoeffs, eobs, tx_type_mask, bw, bh, tx_size, order, is_inter, chains, cdfs,
+                               use_reduced_tx_set=False, want_txb_rate=True, want_cul_level=True, want_ctx=True,
+                               outs=None):
+        """r1_coeff_rate_chain_batch: the real luma coefficient rate of every (block, type) trial across the block's
+        ntx = (bw / tw) * (bh / th) transform blocks in raster order -- write_coeffs_lv_map once per coded transform
+        block on one WriterCounter, the CDFs and the neighbour contexts carried, as rdo_tx_size_type measures a
+        transform depth (src/rdo.rs:725-802).
+        qcoeffs / eobs: the int16 / int32 and 2-byte device tensors of n * nt * ntx transform blocks the candidate
+        calls wrote, chained on the current stream, no copy: order 0 = [block][type][transform block]
+        (rdo_intra_split_batch), order 1 = [block][transform block][type] (rdo_txsearch_batch over the blocks'
+        transform blocks).  chains: n TXB_CHAIN_CTX (rdo_glue.txb_chain_ctx; NumPy array or a uint8 device tensor
+        (n, 40)); cdfs: as coeff_rate_batch.
+        -> {"rate": (n, nt) int32 holding uint32 1/8 bits (COEFF_RATE_INVALID for a trial with out-of-range device
+        inputs), "txb_rate": (n, nt, ntx) int32, "cul_level": (n, nt, ntx) uint8, "ctx": (n, nt, 32) uint8 -- above[16],
+        left[16] behind the last transform block}; the three side outputs are optional."""
+        nt = bin(int(tx_type_mask)).count("1")
+        tw, th = TxSize(tx_size).dims
+        ntx = max(1, bw // tw) * max(1, bh // th)
+        assert qcoeffs.is_cuda and qcoeffs.is_contiguous() and qcoeffs.dtype in (torch.int16, torch.int32)
+        assert eobs.is_cuda and eobs.is_contiguous() and eobs.element_size() == 2
+        dch, n = _dev_cands(chains, TXB_CHAIN_CTX)
+        dcdf, n_cdfs = _dev_cands(cdfs, COEFF_CDFS)
+        assert eobs.numel() == n * nt * ntx or nt == 0, (eobs.numel(), n, nt, ntx)
+        dev = qcoeffs.device
+        o = dict(outs) if outs else {}
+        spec = {"rate": (True, (n, nt), torch.int32), "txb_rate": (want_txb_rate, (n, nt, ntx), torch.int32),
+                "cul_level": (want_cul_level, (n, nt, ntx), torch.uint8), "ctx": (want_ctx, (n, nt, 32), torch.uint8)}
+        ptr = {}
+        for k, (want, shape, dtype) in spec.items():
+            if want and k not in o:
+                o[k] = torch.empty(shape, dtype=dtype, device=dev)
+            ptr[k] = o[k].data_ptr() if want else None
+        self._check(self.lib.r1_coeff_rate_chain_batch(
+            self.h, qcoeffs.data_ptr(), qcoeffs.element_size(), eobs.data_ptr(), n, int(tx_type_mask), int(bw), int(bh),
+            int(tx_size), int(order), int(bool(is_inter)), int(bool(use_reduced_tx_set)), dch.data_ptr(),
+            dcdf.data_ptr(), n_cdfs, ptr["rate"], ptr["txb_rate"], ptr["cul_level"], ptr["ctx"], _stream_ptr()),
+            "r1_coeff_rate_chain_batch")
         return o
 
     # ---- lrf:: ----

@@ -2,8 +2,11 @@
 // slot, as rdo_tx_type_decision measures it (src/rdo.rs:1744-1799): a fresh WriterCounter (src/ec.rs:193-201,
 // 317-319), tell_frac, write_coeffs_lv_map (src/context/block_unit.rs:1783-2016), tell_frac, CDFs rolled back.
 // Every slot starts from an unadapted copy of its R1CoeffCdfs snapshot, so the slots are independent.
+// r1_coeff_rate_chain_batch: the same over the luma transform blocks of a block in raster order, as rdo_tx_size_type
+// measures a transform depth (src/rdo.rs:725-802): one counter, one adapting CDF copy and the block's 32 neighbour
+// context bytes carried from transform block to transform block (k_coeff_rate_chain, below the block body).
 //
-// One wave per slot, four slots per workgroup.  Inside a slot:
+// One wave per slot, four slots per workgroup.  Inside a slot, per transform block (txb_rate, stated once):
 //  A  (parallel over the coded area) txb_init_levels: min(|c|, 127), transposed, stride H + TX_PAD_HOR, in LDS.
 //  then, per chunk of 256 scan positions, from eob - 1 down (the order encode_coeffs codes them in):
 //  1  (parallel, four positions per lane) get_nz_map_ctx / the eob context, get_br_ctx and the symbol count of
@@ -11,8 +14,9 @@
 //  2  (parallel over CDF rows) the only rows a slot hits more than once are coeff_base (42) and coeff_br (21):
 //     lane l < 42 keeps coeff_base[l], lane 42 + r keeps coeff_br[r] in registers, walks the chunk's tokens and,
 //     for those of its row, emits (fl, fh, nms) from its adapting copy (update_cdf, src/ec.rs:935-955) at the
-//     symbol's index.  txb_skip, tx_type, eob_flag, eob_extra, coeff_base_eob and dc_sign are hit once per slot
-//     and are read from the snapshot as they stand.
+//     symbol's index.  txb_skip, tx_type, eob_flag, eob_extra, coeff_base_eob and dc_sign are hit once per
+//     transform block: a single-block slot reads them from the snapshot as they stand, the chain from its LDS copy,
+//     which it updates behind every use.
 //  3  (serial) the chain over (fl, fh, nms) through rng and bits (lr_compute + leading_zeros), run by every lane
 //     on the same values: a dozen instructions per symbol, no divergence.
 //  then encode_coeff_signs, in chunks from scan position 0 up: the values gathered in parallel, the sign bits,
@@ -97,48 +101,58 @@ __device__ __forceinline__ uint32_t pack_sym(uint32_t fl, uint32_t fh, uint32_t 
 }
 __device__ __forceinline__ uint32_t min3(uint32_t v) { return v < 3 ? v : 3; }
 
-template <typename CT>
-__global__ __launch_bounds__(256) void k_coeff_rate(const RateArgs a) {
-  __shared__ __attribute__((aligned(16))) uint8_t s_lv[4][kLevelBytes];
-  __shared__ uint16_t s_tok[4][kChunk];
-  __shared__ uint16_t s_off[4][kChunk];
-  __shared__ uint32_t s_sym[4][kSymMax];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int slot = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + wave);
-  if (slot >= a.n_slots) return;
-  const int ci = slot / a.nt, j = slot - ci * a.nt;
-  const R1TxbCtx cx = a.ctxs[ci];
-  const int eob = __builtin_amdgcn_readfirstlane((int)a.eobs[slot]);
-  const int skip_ctx = __builtin_amdgcn_readfirstlane((int)cx.txb_skip_ctx);
-  const int sign_ctx = __builtin_amdgcn_readfirstlane((int)cx.dc_sign_ctx);
-  const int y_mode = __builtin_amdgcn_readfirstlane((int)cx.y_mode);
-  const int sel = __builtin_amdgcn_readfirstlane((int)cx.cdf_sel);
+// The adapting rows, one per lane: coeff_base[lane] / coeff_br[lane - 42], four entries each (the last is the counter)
+struct LaneRow {
+  uint32_t c0, c1, c2, cnt;
+  __device__ __forceinline__ void load(const R1CoeffCdfs *cdf, int lane) {
+    const uint16_t *r = lane < kBaseRows ? cdf->coeff_base[lane] : cdf->coeff_br[lane < 63 ? lane - kBaseRows : 0];
+    c0 = r[0], c1 = r[1], c2 = r[2], cnt = r[3];
+  }
+};
+
+// the LDS of one wave
+struct WaveLds {
+  uint8_t *lv;
+  uint16_t *tok, *off;
+  uint32_t *sym;
+};
+
+// A symbol on one of the rows a transform block hits once.  kChain: `row` lies in the trial's LDS copy and adapts for
+// the transform blocks behind this one -- update_cdf (src/ec.rs:935-955) with the row's own length n, entry i by lane i,
+// the counter by lane n - 1, between two wave barriers: every lane has read the row before it changes, and the next
+// read sees it changed.  Called from wave-uniform control flow only.
+template <bool kChain, typename Row>
+__device__ __forceinline__ void once_symbol(Counter &w, Row *row, int n, int s, int lane) {
+  w.symbol(row, n, s);
+  if constexpr (kChain) {
+    const uint32_t cnt = row[n - 1];
+    const uint32_t mine = row[lane < n ? lane : 0];
+    wave_sync();
+    uint32_t rate = 3 + (n > 3 ? 2 : 1) + (cnt >> 4);     // 3 + (nsymbs >> 1).min(2)
+    rate = rate < 15 ? rate : 15;
+    if (lane < n - 1) row[lane] = (uint16_t)(lane >= s ? mine - (mine >> rate) : mine + ((32768u - mine) >> rate));
+    else if (lane == n - 1) row[lane] = (uint16_t)(cnt + 1 - (cnt >> 5));
+    wave_sync();
+  }
+}
+
+// write_coeffs_lv_map (block_unit.rs:1783-1857) between get_txb_ctx and set_coeff_context, for one transform block on
+// the wave's counter: phases A, 1, 2, 3, the signs and the Golomb tails.  `cdf`: the snapshot (k_coeff_rate) or the
+// trial's adapting LDS copy (kChain); `row`: the lane's adapting row -- loaded here per block from the snapshot, or
+// loaded once per trial by the caller and carried (kChain).  -> false for eob == 0 (only the txb_skip symbol was
+// written); else true and `sum` = the sum of |c| over the coded positions on every lane.
+template <typename CT, bool kChain, typename Cdfs>
+__device__ __forceinline__ bool txb_rate(const RateArgs &a, Counter &w, Cdfs *cdf, LaneRow &row, const CT *qc,
+                                         const int eob, const int skip_ctx, const int sign_ctx, const int y_mode,
+                                         const int j, const int lane, const WaveLds lds, uint32_t &sum) {
   const int area = a.area;
-  if (eob > area || skip_ctx >= R1_TXB_SKIP_CONTEXTS || sign_ctx >= R1_DC_SIGN_CONTEXTS || y_mode >= R1_INTRA_MODES ||
-      sel >= a.n_cdfs) {
-    if (lane == 0) {
-      a.rate[slot] = 0xFFFFFFFFu;
-      if (a.cul) a.cul[slot] = 0;
-    }
-    return;
-  }
-  const R1CoeffCdfs *cdf = a.cdfs + sel;
-  Counter w;
-  const uint32_t tell = w.tell_frac();
-  w.symbol(cdf->txb_skip[skip_ctx], 2, eob == 0);
-  if (eob == 0) {
-    if (lane == 0) {
-      a.rate[slot] = w.tell_frac() - tell;
-      if (a.cul) a.cul[slot] = 0;
-    }
-    return;
-  }
+  once_symbol<kChain>(w, cdf->txb_skip[skip_ctx], 2, eob == 0, lane);
+  if (eob == 0) return false;
   const int tx_type = a.type[j];
   const int cls = tx_type < 10 ? 0 : ((tx_type & 1) ? 1 : 2);   // tx_type_to_class: 2D, HORIZ (H_*), VERT (V_*)
   const uint16_t *scan = a.scan[tx_type < 10 ? 0 : ((tx_type & 1) ? 2 : 1)];
-  const CT *qc = (const CT *)a.qc + (size_t)slot * (size_t)area;
   const int hl = a.hl, H = 1 << hl, stride = H + 4;
-  uint8_t *lv = s_lv[wave];
+  uint8_t *lv = lds.lv;
 
   // A: txb_init_levels (transform_unit.rs:780-792) into zeroed padding
   for (int e = lane; e < kLevelBytes / 4; e += 64) ((uint32_t *)lv)[e] = 0;
@@ -151,25 +165,21 @@ __global__ __launch_bounds__(256) void k_coeff_rate(const RateArgs a) {
   wave_sync();
 
   // write_tx_type (luma only), encode_eob
-  if (a.plane == 0 && a.tx_n > 1) w.symbol(cdf->tx_type[a.is_inter ? 0 : y_mode], a.tx_n, a.tx_sym[j]);
+  if (a.plane == 0 && a.tx_n > 1) once_symbol<kChain>(w, cdf->tx_type[a.is_inter ? 0 : y_mode], a.tx_n, a.tx_sym[j], lane);
   {
     // get_eob_pos_token: eob_to_pos_small / eob_to_pos_large, k_eob_group_start, k_eob_offset_bits
     const int eob_pt = eob < 3 ? eob : (32 - __clz(eob - 1)) + 1;
     const int extra = eob - (eob_pt < 3 ? eob_pt : (1 << (eob_pt - 2)) + 1);
     const int nbits = eob_pt < 3 ? 0 : eob_pt - 2;
-    w.symbol(cdf->eob_flag[cls != 0], a.eob_flag_n, eob_pt - 1);
+    once_symbol<kChain>(w, cdf->eob_flag[cls != 0], a.eob_flag_n, eob_pt - 1, lane);
     if (nbits > 0) {
-      w.symbol(cdf->eob_extra[eob_pt - 3], 2, (extra >> (nbits - 1)) & 1);
+      once_symbol<kChain>(w, cdf->eob_extra[eob_pt - 3], 2, (extra >> (nbits - 1)) & 1, lane);
       for (int i = nbits - 2; i >= 0; i--) w.bit((extra >> i) & 1);
     }
   }
 
-  // the adapting rows: coeff_base[lane] / coeff_br[lane - 42], four entries each (the last is the counter)
-  uint32_t c0, c1, c2, cnt;
-  {
-    const uint16_t *r = lane < kBaseRows ? cdf->coeff_base[lane] : cdf->coeff_br[lane < 63 ? lane - kBaseRows : 0];
-    c0 = r[0], c1 = r[1], c2 = r[2], cnt = r[3];
-  }
+  if constexpr (!kChain) row.load(cdf, lane);
+  uint32_t &c0 = row.c0, &c1 = row.c1, &c2 = row.c2, &cnt = row.cnt;
   // symbol(s) + update_cdf(s) on the lane's row -> the packed (fl, fh, nms)
   auto row_symbol = [&](uint32_t s) -> uint32_t {
     const uint32_t fl = s == 0 ? 32768u : (s == 1 ? c0 : (s == 2 ? c1 : c2));
@@ -251,29 +261,36 @@ __global__ __launch_bounds__(256) void k_coeff_rate(const RateArgs a) {
     for (int q = 0; q < 4; q++) {
       const int idx = lane * 4 + q;
       if (idx < np) {
-        s_tok[wave][idx] = (uint16_t)tok[q];
-        s_off[wave][idx] = (uint16_t)off;
+        lds.tok[idx] = (uint16_t)tok[q];
+        lds.off[idx] = (uint16_t)off;
       }
       off += ns[q];
     }
     wave_sync();
     // 2: every row's lane emits its symbols in coding order
     for (int idx = 0; idx < np; idx++) {
-      const uint32_t t = s_tok[wave][idx], o = s_off[wave][idx];
+      const uint32_t t = lds.tok[idx], o = lds.off[idx];
       const uint32_t ctx = t & 63, br = (t >> 6) & 31, level = (t >> 11) & 15;
       if (t >> 15) {
-        if (lane == 63) {   // coeff_base_eob: one symbol per slot, from the snapshot
-          const uint16_t *r = cdf->coeff_base_eob[ctx];
+        if (lane == 63) {   // coeff_base_eob: one symbol per transform block, from the snapshot or the LDS copy
+          auto *r = cdf->coeff_base_eob[ctx];
           const uint32_t s = (level < 3 ? (level > 1 ? level : 1) : 3) - 1;          // min(level, 3) - 1; level >= 1
-          s_sym[wave][o] = pack_sym(s > 0 ? r[s - 1] : 32768u, r[s], 3 - s);
+          lds.sym[o] = pack_sym(s > 0 ? r[s - 1] : 32768u, r[s], 3 - s);
+          if constexpr (kChain) {   // update_cdf on a three-entry row; lane 63 alone reads and writes these rows
+            const uint32_t n = r[2], rate = 4 + (n >> 4) < 15 ? 4 + (n >> 4) : 15;
+            const uint32_t p0 = r[0], p1 = r[1];
+            r[0] = (uint16_t)(0 >= s ? p0 - (p0 >> rate) : p0 + ((32768u - p0) >> rate));
+            r[1] = (uint16_t)(1 >= s ? p1 - (p1 >> rate) : p1 + ((32768u - p1) >> rate));
+            r[2] = (uint16_t)(n + 1 - (n >> 5));
+          }
         }
       } else if ((uint32_t)lane == ctx) {
-        s_sym[wave][o] = row_symbol(min3(level));
+        lds.sym[o] = row_symbol(min3(level));
       }
       if (level > 2 && (uint32_t)lane == kBaseRows + br) {
         for (uint32_t base = level - 3, k = 0; k < 4; k++) {                        // level 15 stands for >= 15
           const uint32_t s = min3(base - 3 * k);
-          s_sym[wave][o + 1 + k] = row_symbol(s);
+          lds.sym[o + 1 + k] = row_symbol(s);
           if (s < 3) break;
         }
       }
@@ -281,14 +298,14 @@ __global__ __launch_bounds__(256) void k_coeff_rate(const RateArgs a) {
     wave_sync();
     // 3: the chain
     for (int k = 0; k < total; k++) {
-      const uint32_t x = s_sym[wave][k];
+      const uint32_t x = lds.sym[k];
       w.store(x & 1023, (x >> 10) & 1023, x >> 20);
     }
     wave_sync();   // the next chunk rewrites the three buffers
   }
 
   // encode_coeff_signs: scan positions 0 .. eob - 1; cul_level = sum of |c| over them
-  uint32_t sum = 0;
+  sum = 0;
   for (int lo = 0; lo < eob; lo += kChunk) {
     const int np = eob - lo < kChunk ? eob - lo : kChunk;
 #pragma unroll
@@ -298,14 +315,14 @@ __global__ __launch_bounds__(256) void k_coeff_rate(const RateArgs a) {
         const int32_t v = (int32_t)qc[scan[lo + idx]];
         const uint32_t m = (uint32_t)(v < 0 ? -v : v);
         sum += m;
-        s_sym[wave][idx] = (m << 1) | (uint32_t)(v < 0);
+        lds.sym[idx] = (m << 1) | (uint32_t)(v < 0);
       }
     }
     wave_sync();
     for (int idx = 0; idx < np; idx++) {
-      const uint32_t x = s_sym[wave][idx], m = x >> 1;
+      const uint32_t x = lds.sym[idx], m = x >> 1;
       if (m == 0) continue;
-      if (lo + idx == 0) w.symbol(cdf->dc_sign[sign_ctx], 2, x & 1);
+      if (lo + idx == 0) once_symbol<kChain>(w, cdf->dc_sign[sign_ctx], 2, x & 1, lane);
       else w.bit(x & 1);
       if (m > 14) {   // write_golomb(level - COEFF_BASE_RANGE - NUM_BASE_LEVELS - 1)
         const uint32_t g = m - 14;
@@ -318,23 +335,188 @@ __global__ __launch_bounds__(256) void k_coeff_rate(const RateArgs a) {
   }
 #pragma unroll
   for (int m = 1; m < 64; m <<= 1) sum += __shfl_xor(sum, m, WAVE);
+  return true;
+}
+
+// the value write_coeffs_lv_map hands set_coeff_context; dc = coeffs[0]: every scan order starts at coefficient 0
+__device__ __forceinline__ uint32_t cul_level(uint32_t sum, int32_t dc) {
+  uint32_t cul = sum < 63 ? sum : 63;  // COEFF_CONTEXT_MASK, then set_dc_sign (block_unit.rs:325-331)
+  if (dc < 0) cul |= 1u << 6;
+  else if (dc > 0) cul += 2u << 6;
+  return cul;
+}
+
+#define R1_RATE_LDS                                                        \
+  __shared__ __attribute__((aligned(16))) uint8_t s_lv[4][kLevelBytes];    \
+  __shared__ uint16_t s_tok[4][kChunk];                                    \
+  __shared__ uint16_t s_off[4][kChunk];                                    \
+  __shared__ uint32_t s_sym[4][kSymMax]
+
+template <typename CT>
+__global__ __launch_bounds__(256) void k_coeff_rate(const RateArgs a) {
+  R1_RATE_LDS;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int slot = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + wave);
+  if (slot >= a.n_slots) return;
+  const int ci = slot / a.nt, j = slot - ci * a.nt;
+  const R1TxbCtx cx = a.ctxs[ci];
+  const int eob = __builtin_amdgcn_readfirstlane((int)a.eobs[slot]);
+  const int skip_ctx = __builtin_amdgcn_readfirstlane((int)cx.txb_skip_ctx);
+  const int sign_ctx = __builtin_amdgcn_readfirstlane((int)cx.dc_sign_ctx);
+  const int y_mode = __builtin_amdgcn_readfirstlane((int)cx.y_mode);
+  const int sel = __builtin_amdgcn_readfirstlane((int)cx.cdf_sel);
+  if (eob > a.area || skip_ctx >= R1_TXB_SKIP_CONTEXTS || sign_ctx >= R1_DC_SIGN_CONTEXTS || y_mode >= R1_INTRA_MODES ||
+      sel >= a.n_cdfs) {
+    if (lane == 0) {
+      a.rate[slot] = 0xFFFFFFFFu;
+      if (a.cul) a.cul[slot] = 0;
+    }
+    return;
+  }
+  const R1CoeffCdfs *cdf = a.cdfs + sel;
+  const CT *qc = (const CT *)a.qc + (size_t)slot * (size_t)a.area;
+  Counter w;
+  const uint32_t tell = w.tell_frac();
+  LaneRow row;
+  uint32_t sum;
+  if (!txb_rate<CT, false>(a, w, cdf, row, qc, eob, skip_ctx, sign_ctx, y_mode, j, lane,
+                           WaveLds{s_lv[wave], s_tok[wave], s_off[wave], s_sym[wave]}, sum)) {
+    if (lane == 0) {
+      a.rate[slot] = w.tell_frac() - tell;
+      if (a.cul) a.cul[slot] = 0;
+    }
+    return;
+  }
   if (lane == 0) {
     a.rate[slot] = w.tell_frac() - tell;
-    if (a.cul) {
-      const int32_t dc = (int32_t)qc[0];   // coeffs[0]: every scan order starts at coefficient 0
-      uint32_t cul = sum < 63 ? sum : 63;  // COEFF_CONTEXT_MASK, then set_dc_sign (block_unit.rs:325-331)
-      if (dc < 0) cul |= 1u << 6;
-      else if (dc > 0) cul += 2u << 6;
-      a.cul[slot] = (uint8_t)cul;
-    }
+    if (a.cul) a.cul[slot] = (uint8_t)cul_level(sum, (int32_t)qc[0]);
   }
 }
+
+// ---- the chain: a block's luma transform blocks in raster order on one counter (r1_coeff_rate_chain_batch)
+struct ChainArgs {
+  RateArgs r;                  // r.ctxs is unused; r.cul holds ntx bytes per trial; r.n_slots = trials
+  const R1TxbChainCtx *chains;
+  uint32_t *txb_rate;          // optional
+  uint8_t *ctx_out;            // optional
+  int ntx, gw;                 // the grid: transform blocks per trial and per row
+  int tw4, th4;                // the transform in 4x4 units
+  int order;
+};
+static_assert(sizeof(R1TxbChainCtx) == 40, "ABI layout");
+static_assert(sizeof(R1CoeffCdfs) % 4 == 0, "the snapshot is copied to LDS in dwords");
+
+// One wave per trial, four trials per workgroup, as k_coeff_rate.  The trial's R1CoeffCdfs is copied to LDS once and
+// adapts there (the rows a block hits once); the coeff_base / coeff_br rows are loaded into their lanes once and stay
+// there across chunks and transform blocks; the 32 context bytes live in LDS, get_txb_ctx and set_coeff_context run
+// on them wave-uniform.  The loop over k is bounded by ntx <= 16.
+template <typename CT>
+__global__ __launch_bounds__(256) void k_coeff_rate_chain(const ChainArgs c) {
+  R1_RATE_LDS;
+  __shared__ __attribute__((aligned(16))) R1CoeffCdfs s_cdf[4];
+  __shared__ uint8_t s_nb[4][32];      // above[16], left[16]
+  const RateArgs &a = c.r;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int trial = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + wave);
+  if (trial >= a.n_slots) return;
+  const int ci = trial / a.nt, j = trial - ci * a.nt;
+  const int ntx = c.ntx;
+  const uint8_t *chb = (const uint8_t *)(c.chains + ci);
+  const int mi_w = __builtin_amdgcn_readfirstlane((int)chb[32]), mi_h = __builtin_amdgcn_readfirstlane((int)chb[33]);
+  const int clip_w4 = __builtin_amdgcn_readfirstlane((int)chb[34]), clip_h4 = __builtin_amdgcn_readfirstlane((int)chb[35]);
+  const int y_mode = __builtin_amdgcn_readfirstlane((int)chb[36]), sel = __builtin_amdgcn_readfirstlane((int)chb[37]);
+  // where transform block k of this trial lies in qcoeffs / eobs
+  auto at = [&](int k) -> size_t {
+    return c.order == 0 ? (size_t)trial * ntx + k : ((size_t)ci * ntx + k) * a.nt + j;
+  };
+  auto coded = [&](int k) -> bool {      // encoder.rs:2282, 2446
+    const int by = k / c.gw, bx = k - by * c.gw;
+    return bx * c.tw4 < mi_w && by * c.th4 < mi_h;
+  };
+  // device-resident data the host cannot see: lane k looks at transform block k
+  bool bad = y_mode >= R1_INTRA_MODES || sel >= a.n_cdfs || mi_w > clip_w4 || mi_h > clip_h4;
+  if (lane < ntx && coded(lane) && (int)a.eobs[at(lane)] > a.area) bad = true;
+  if (__ballot(bad) != 0) {
+    if (lane == 0) a.rate[trial] = 0xFFFFFFFFu;
+    if (lane < ntx) {
+      if (c.txb_rate) c.txb_rate[(size_t)trial * ntx + lane] = 0;
+      if (a.cul) a.cul[(size_t)trial * ntx + lane] = 0;
+    }
+    if (c.ctx_out && lane < 32) c.ctx_out[(size_t)trial * 32 + lane] = 0;
+    return;
+  }
+  R1CoeffCdfs *cdf = &s_cdf[wave];
+  uint8_t *nb = s_nb[wave];
+  {
+    const uint32_t *src = (const uint32_t *)(a.cdfs + sel);
+    for (int e = lane; e < (int)(sizeof(R1CoeffCdfs) / 4); e += 64) ((uint32_t *)cdf)[e] = src[e];
+    if (lane < 32) nb[lane] = chb[lane];
+  }
+  LaneRow row;
+  row.load(a.cdfs + sel, lane);
+  wave_sync();
+  Counter w;
+  const uint32_t tell0 = w.tell_frac();
+  const WaveLds lds{s_lv[wave], s_tok[wave], s_off[wave], s_sym[wave]};
+  for (int k = 0; k < ntx; k++) {
+    const int by = k / c.gw, bx = k - by * c.gw;
+    const int x4 = bx * c.tw4, y4 = by * c.th4;
+    if (x4 >= mi_w || y4 >= mi_h) {
+      if (lane == 0) {
+        if (c.txb_rate) c.txb_rate[(size_t)trial * ntx + k] = 0;
+        if (a.cul) a.cul[(size_t)trial * ntx + k] = 0;
+      }
+      continue;
+    }
+    const size_t idx = at(k);
+    const int eob = __builtin_amdgcn_readfirstlane((int)a.eobs[idx]);
+    const CT *qc = (const CT *)a.qc + idx * (size_t)a.area;
+    // get_txb_ctx (block_unit.rs:442-526, luma) over the frame-clipped span (encoder.rs:1561-1566); mi_w <= clip_w4
+    // keeps the span of a coded block at 1 or more.  A sign field of 3 is nothing set_dc_sign stores: it counts as 0.
+    const int sw = c.tw4 < clip_w4 - x4 ? c.tw4 : clip_w4 - x4, sh = c.th4 < clip_h4 - y4 ? c.th4 : clip_h4 - y4;
+    int dc_sign = 0;
+    uint32_t top = 0, left = 0;
+    for (int i = 0; i < sw; i++) {
+      const uint32_t v = nb[x4 + i];
+      top |= v;
+      dc_sign += (v >> 6) == 1 ? -1 : ((v >> 6) == 2 ? 1 : 0);
+    }
+    for (int i = 0; i < sh; i++) {
+      const uint32_t v = nb[16 + y4 + i];
+      left |= v;
+      dc_sign += (v >> 6) == 1 ? -1 : ((v >> 6) == 2 ? 1 : 0);
+    }
+    const int sign_ctx = dc_sign == 0 ? 0 : (dc_sign < 0 ? 1 : 2);
+    int skip_ctx = 0;
+    if (ntx > 1) {       // plane_bsize != tx_size.block_size(): skip_contexts[min][max]
+      top &= 63, left &= 63;
+      const uint32_t mx = (top | left) < 4 ? (top | left) : 4, lo = top < left ? top : left, mn = lo < 4 ? lo : 4;
+      skip_ctx = mx == 0 ? 1 : (mn == 0 ? 2 + (mx > 3) : (mx <= 3 ? 4 : (mn <= 3 ? 5 : 6)));
+    }
+    const uint32_t t0 = w.tell_frac();
+    uint32_t sum, cul = 0;
+    if (txb_rate<CT, true>(a, w, cdf, row, qc, eob, skip_ctx, sign_ctx, y_mode, j, lane, lds, sum))
+      cul = cul_level(sum, (int32_t)qc[0]);
+    // set_coeff_context over the full span (block_unit.rs:333-347); the reads above are behind the barriers of txb_rate
+    if (lane < 16 ? (lane >= x4 && lane < x4 + c.tw4) : (lane < 32 && lane - 16 >= y4 && lane - 16 < y4 + c.th4))
+      nb[lane] = (uint8_t)cul;
+    wave_sync();
+    if (lane == 0) {
+      if (c.txb_rate) c.txb_rate[(size_t)trial * ntx + k] = w.tell_frac() - t0;
+      if (a.cul) a.cul[(size_t)trial * ntx + k] = (uint8_t)cul;
+    }
+  }
+  if (lane == 0) a.rate[trial] = w.tell_frac() - tell0;
+  if (c.ctx_out && lane < 32) c.ctx_out[(size_t)trial * 32 + lane] = nb[lane];
+}
+#undef R1_RATE_LDS
 }  // namespace
 
-extern "C" int r1_coeff_rate_batch(r1_ctx *ctx, const void *qcoeffs, int coeff_bytes, const uint16_t *eobs, int n,
-                                   uint32_t tx_type_mask, int tx_size, int plane, int is_inter,
-                                   int use_reduced_tx_set, const R1TxbCtx *ctxs, const R1CoeffCdfs *cdfs, int n_cdfs,
-                                   uint32_t *rate_out, uint8_t *cul_level_out, void *stream) {
+// The checks and the launch arguments both entry points share: what the transform size, the type mask and the set
+// decide.  `per_block`: slots per candidate beyond the types (1, or the chain's ntx) for the 2^31 bound.
+static int rate_args(r1_ctx *ctx, const void *qcoeffs, int coeff_bytes, const uint16_t *eobs, int n, uint32_t tx_type_mask,
+                     int tx_size, int plane, int is_inter, int use_reduced_tx_set, const R1CoeffCdfs *cdfs, int n_cdfs,
+                     uint32_t *rate_out, uint8_t *cul_level_out, int per_block, RateArgs &a) {
   R1_REQUIRE(ctx);
   R1_REQUIRE(coeff_bytes == 2 || coeff_bytes == 4);
   R1_REQUIRE(r1_tx_size_ok(tx_size));
@@ -344,8 +526,7 @@ extern "C" int r1_coeff_rate_batch(r1_ctx *ctx, const void *qcoeffs, int coeff_b
   use_reduced_tx_set = use_reduced_tx_set != 0;
   const uint32_t allowed = r1_tx_type_mask(tx_size, is_inter, use_reduced_tx_set, 0);
   R1_REQUIRE(tx_type_mask != 0 && (tx_type_mask & ~allowed) == 0);
-  R1_REQUIRE(qcoeffs && eobs && ctxs && cdfs && rate_out);
-  if (n <= 0) return R1_OK;
+  R1_REQUIRE(qcoeffs && eobs && cdfs && rate_out);
   // num_tx_set / av1_tx_ind (transform_unit.rs:36, 51-58), rows in TxSet order; the set from the mask of its types
   static const uint8_t kNumTxSet[6] = {1, 2, 5, 7, 12, 16};
   static const uint32_t kSetMask[6] = {0x0001, 0x0201, 0x020F, 0x0E0F, 0x0FFF, 0xFFFF};
@@ -358,12 +539,12 @@ extern "C" int r1_coeff_rate_batch(r1_ctx *ctx, const void *qcoeffs, int coeff_b
   int set = 0;
   while (kSetMask[set] != allowed) set++;
   const int wl = r1tx::kTxWLog2[tx_size], hl = r1tx::kTxHLog2[tx_size];
-  RateArgs a = {};
-  a.qc = qcoeffs, a.eobs = eobs, a.ctxs = ctxs, a.cdfs = cdfs, a.rate = rate_out, a.cul = cul_level_out;
+  a = {};
+  a.qc = qcoeffs, a.eobs = eobs, a.cdfs = cdfs, a.rate = rate_out, a.cul = cul_level_out;
   for (int k = 0; k < 3; k++) a.scan[k] = ctx->scan_dev + ctx->scan_off[tx_size][k];
   a.nt = __builtin_popcount(tx_type_mask);
-  R1_REQUIRE((long long)n * a.nt <= 0x7fffffffLL);
-  a.n_slots = n * a.nt, a.n_cdfs = n_cdfs, a.plane = plane;
+  R1_REQUIRE((long long)(n > 0 ? n : 0) * a.nt * per_block <= 0x7fffffffLL);
+  a.n_slots = (n > 0 ? n : 0) * a.nt, a.n_cdfs = n_cdfs, a.plane = plane;
   a.w_coded = r1q::coded_dim(wl);
   a.hl = r1_ilog2(r1q::coded_dim(hl));
   a.area = a.w_coded << a.hl;
@@ -373,10 +554,53 @@ extern "C" int r1_coeff_rate_batch(r1_ctx *ctx, const void *qcoeffs, int coeff_b
   a.is_inter = is_inter;
   for (int t = 0, j = 0; t < 16; t++)
     if ((tx_type_mask >> t) & 1) a.type[j] = (uint8_t)t, a.tx_sym[j] = kTxInd[set][t], j++;
+  return R1_OK;
+}
+
+extern "C" int r1_coeff_rate_batch(r1_ctx *ctx, const void *qcoeffs, int coeff_bytes, const uint16_t *eobs, int n,
+                                   uint32_t tx_type_mask, int tx_size, int plane, int is_inter,
+                                   int use_reduced_tx_set, const R1TxbCtx *ctxs, const R1CoeffCdfs *cdfs, int n_cdfs,
+                                   uint32_t *rate_out, uint8_t *cul_level_out, void *stream) {
+  RateArgs a;
+  const int rc = rate_args(ctx, qcoeffs, coeff_bytes, eobs, n, tx_type_mask, tx_size, plane, is_inter, use_reduced_tx_set,
+                           cdfs, n_cdfs, rate_out, cul_level_out, 1, a);
+  if (rc != R1_OK) return rc;
+  R1_REQUIRE(ctxs);
+  if (n <= 0) return R1_OK;
+  a.ctxs = ctxs;
   R1DeviceGuard guard(ctx);
   const unsigned grid = (unsigned)((a.n_slots + 3) / 4);
   if (coeff_bytes == 2) hipLaunchKernelGGL(k_coeff_rate<int16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(k_coeff_rate<int32_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+  R1_HIP_CHECK(hipGetLastError());
+  return R1_OK;
+}
+
+extern "C" int r1_coeff_rate_chain_batch(r1_ctx *ctx, const void *qcoeffs, int coeff_bytes, const uint16_t *eobs, int n,
+                                         uint32_t tx_type_mask, int bw, int bh, int tx_size, int order, int is_inter,
+                                         int use_reduced_tx_set, const R1TxbChainCtx *chains, const R1CoeffCdfs *cdfs,
+                                         int n_cdfs, uint32_t *rate_out, uint32_t *txb_rate_out, uint8_t *cul_level_out,
+                                         uint8_t *ctx_out, void *stream) {
+  R1_REQUIRE(r1_tx_size_ok(tx_size));
+  const int tw = 1 << r1tx::kTxWLog2[tx_size], th = 1 << r1tx::kTxHLog2[tx_size];
+  R1_REQUIRE(r1_is_pow2(bw) && r1_is_pow2(bh) && bw >= 4 && bh >= 4 && bw <= 64 && bh <= 64);
+  R1_REQUIRE(bw <= 4 * bh && bh <= 4 * bw);            // a block size
+  R1_REQUIRE(bw % tw == 0 && bh % th == 0);
+  const int ntx = (bw / tw) * (bh / th);
+  R1_REQUIRE(ntx >= 1 && ntx <= 16);
+  R1_REQUIRE(order == 0 || order == 1);
+  ChainArgs c = {};
+  const int rc = rate_args(ctx, qcoeffs, coeff_bytes, eobs, n, tx_type_mask, tx_size, 0, is_inter, use_reduced_tx_set, cdfs,
+                           n_cdfs, rate_out, cul_level_out, ntx, c.r);
+  if (rc != R1_OK) return rc;
+  R1_REQUIRE(chains);
+  if (n <= 0) return R1_OK;
+  c.chains = chains, c.txb_rate = txb_rate_out, c.ctx_out = ctx_out;
+  c.ntx = ntx, c.gw = bw / tw, c.tw4 = tw >> 2, c.th4 = th >> 2, c.order = order;
+  R1DeviceGuard guard(ctx);
+  const unsigned grid = (unsigned)((c.r.n_slots + 3) / 4);
+  if (coeff_bytes == 2) hipLaunchKernelGGL(k_coeff_rate_chain<int16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c);
+  else hipLaunchKernelGGL(k_coeff_rate_chain<int32_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c);
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }

@@ -17,6 +17,9 @@ the kernels by executing the reference's own text (tests/golden/gen_rdo_glue_ref
                                                       (which slot of r1_rdo_txsearch_batch holds which TxType)
   txb_ctx                    src/context/block_unit.rs:442-526   (BlockContext::get_txb_ctx: the two neighbour
                                                        contexts r1_coeff_rate_batch takes per candidate)
+  txb_chain_ctx              src/encoder.rs:2282, 2446, 1561-1566  (a block's contexts and edges in front of its transform
+                                                       blocks: the descriptor of r1_coeff_rate_chain_batch; pinned by
+                                                       tests/golden/coeff_rate_chain_ref.npz)
   sub_tx_size                src/context/transform_unit.rs:85-105  (sub_tx_size_map: the next transform depth)
   intra_split_cands          src/encoder.rs:2276-2311  (write_tx_blocks' transform-block grid -> the descriptors of
                                                        r1_rdo_intra_split_batch)
@@ -418,6 +421,22 @@ def txb_ctx(above_ctxs, left_ctxs, plane, plane_bsize, tx_size):
         return _SKIP_CONTEXTS[min(min(top, left_), 4)][min(top | left_, 4)], dc_sign_ctx
     # num_pels_log2_lookup[plane_bsize] > num_pels_log2_lookup[tx_size.block_size()]
     return (top != 0) + (left_ != 0) + (10 if bw * bh > tw * th else 7), dc_sign_ctx
+
+
+def txb_chain_ctx(above_row, left_col, bo_x, bo_y, bw, bh, mi_width, mi_height, w_in_b, h_in_b, y_mode, cdf_sel):
+    """The R1TxbChainCtx of r1_coeff_rate_chain_batch for a bw x bh luma block at tile block offset (bo_x, bo_y), as a
+    tuple in the field order of types.TXB_CHAIN_CTX.  above_row / left_col: above_coeff_context[0] (indexed by bo.x)
+    and left_coeff_context[0] (indexed by bo.y_in_sb() = bo_y % 16) as they stand in front of the block; mi_width /
+    mi_height: the tile's (the skip test of encoder.rs:2282, 2446); w_in_b / h_in_b: fi.w_in_b / fi.h_in_b less the
+    tile's own block offset in the frame, so that w_in_b - bo_x is fi.w_in_b - frame_bo.x (encoder.rs:1561-1566)."""
+    assert 4 <= bw <= 64 and 4 <= bh <= 64
+    y_sb = bo_y % 16
+    # the block covers the first bw / 4 and bh / 4 entries; the rest (as far as the arrays go) passes through to ctx_out
+    above = [int(v) for v in above_row[bo_x:bo_x + 16]]
+    left = [int(v) for v in left_col[y_sb:y_sb + 16]]
+    pad = lambda v: tuple(v + [0] * (16 - len(v)))
+    return (pad(above), pad(left), min(255, mi_width - bo_x), min(255, mi_height - bo_y), min(255, w_in_b - bo_x),
+            min(255, h_in_b - bo_y), int(y_mode), int(cdf_sel), (0, 0))
 
 
 def pick_tx_type(rates, dists, lam, cur_best_rd):

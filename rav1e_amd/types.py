@@ -4,7 +4,8 @@ BlockSize   src/partition.rs:130-153      TxSize  src/transform/mod.rs:101-123
 TxType      src/transform/mod.rs:56-74    FilterMode  src/mc.rs:100-106
 
 COEFF_CDFS / TXB_CTX: the NumPy mirrors of R1CoeffCdfs / R1TxbCtx (include/rav1e_amd.h, r1_coeff_rate_batch); the
-dimensions are the reference's (src/context/transform_unit.rs:27, 200-219).
+dimensions are the reference's (src/context/transform_unit.rs:27, 200-219).  TXB_CHAIN_CTX: R1TxbChainCtx
+(r1_coeff_rate_chain_batch).
 """
 import enum
 
@@ -130,3 +131,7 @@ COEFF_CDFS = np.dtype([("txb_skip", "<u2", (TXB_SKIP_CONTEXTS, 2)), ("eob_flag",
                        ("dc_sign", "<u2", (DC_SIGN_CONTEXTS, 2)), ("tx_type", "<u2", (INTRA_MODES, 16))])
 TXB_CTX = np.dtype([("txb_skip_ctx", "u1"), ("dc_sign_ctx", "u1"), ("y_mode", "u1"), ("cdf_sel", "u1")])
 COEFF_RATE_INVALID = 0xFFFFFFFF      # the rate of a slot whose device-resident inputs are out of range
+# R1TxbChainCtx (r1_coeff_rate_chain_batch): a block's neighbour contexts and edges in front of its transform blocks
+TXB_CHAIN_CTX = np.dtype([("above", "u1", (16,)), ("left", "u1", (16,)), ("mi_w", "u1"), ("mi_h", "u1"),
+                          ("clip_w4", "u1"), ("clip_h4", "u1"), ("y_mode", "u1"), ("cdf_sel", "u1"),
+                          ("reserved", "u1", (2,))])

@@ -1,8 +1,20 @@
-// cand_helpers.inc -- what the fused candidate kernel (rdo_cand_kernel.hpp), the RDO-time sub-pel search
-// (me_blocks.hip, k_me_blocks_small) and the put / prep of transform-sized blocks (mc.hip, k_mc_fast) share: the DPP Hadamard (SATD with lane = column) and its LDS-tile form for the fused kernel, v_sad, the packed
-// i16 helpers, and the put_8tap / prep_8tap column filters on v_dot4 / v_dot2 with their tap loads.
-// Included INSIDE the including file's anonymous namespace, after mc_taps_packed.inc (kTapI8 /
-// kTapI16) and with `T` (= r1tx::T, int32_t) in scope.
+// cand_common.hpp -- what the fused candidate kernel (rdo_cand_kernel.hpp), the RDO-time sub-pel search
+// (me_blocks.hip), the put / prep of transform-sized blocks (mc.hip, k_mc_fast; mc_mfma.hip) and the compound
+// candidate (mc_compound.hip) share: the DPP Hadamard (SATD with lane = column) and its LDS-tile form for the fused
+// kernel, v_sad, the packed i16 helpers, and the put_8tap / prep_8tap column filters on v_dot4 / v_dot2 with their
+// packed tap tables and tap loads.
+#pragma once
+#include <type_traits>
+
+#include "common.hpp"
+#include "dist_common.hpp"
+#include "mc_common.hpp"
+
+namespace r1cand {
+
+// kTapI8 / kTapI16 / kTapB, static: a unit carries the tables it reads and no others
+#include "mc_taps_packed.inc"
+
 // ---- cross-lane Hadamard with DPP --------------------------------------
 // DPP controls: quad_perm [1,0,3,2] = 0xB1 (lane ^ 1), [2,3,0,1] = 0x4E
 // (lane ^ 2), row_half_mirror = 0x141 (lane -> 7 - lane inside each 8).
@@ -78,9 +90,30 @@ __device__ __forceinline__ uint32_t pk_max(uint32_t a, uint32_t b) {
   asm("v_pk_max_i16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
   return r;
 }
+__device__ __forceinline__ uint32_t pk_min(uint32_t a, uint32_t b) {
+  uint32_t r;
+  asm("v_pk_min_i16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
 // both halves of (lo, hi) from the low halves of two i32
 __device__ __forceinline__ uint32_t pk_pair(int32_t lo, int32_t hi) {
   return __builtin_amdgcn_perm((uint32_t)hi, (uint32_t)lo, 0x05040100u);
+}
+// The first two stages of the 8-point butterfly on packed registers, in the order of dist.rs:95-117.  The third
+// (the sum and the difference of d[k] and d[k + 4], k = 0 .. 3) stays with each caller, formed where it is consumed:
+// satd_tile_rows folds it into an abs, and with the eight outputs formed ahead of their uses (one function,
+// uint32_t[8] out) the kernels came out in another instruction order (profiles/HISTORY.md).
+__device__ __forceinline__ void pk_bfly8_s2(const uint32_t (&a)[8], uint32_t (&d)[8]) {
+  uint32_t b[8];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    b[2 * k] = pk_add(a[2 * k], a[2 * k + 1]);
+    b[2 * k + 1] = pk_sub(a[2 * k], a[2 * k + 1]);
+  }
+  d[0] = pk_add(b[0], b[2]); d[2] = pk_sub(b[0], b[2]);
+  d[1] = pk_add(b[1], b[3]); d[3] = pk_sub(b[1], b[3]);
+  d[4] = pk_add(b[4], b[6]); d[6] = pk_sub(b[4], b[6]);
+  d[5] = pk_add(b[5], b[7]); d[7] = pk_sub(b[5], b[7]);
 }
 // this lane's share of sum |Hadamard across the 8 lanes| for both halves of x,
 // added to acc; m1 / m2: packed +-1 of the two lane stages
@@ -93,15 +126,11 @@ __device__ __forceinline__ uint32_t habs_lanes_pk(uint32_t x, uint32_t m1, uint3
                                 acc, false);
 }
 
-// (lo >> SH) in the low half, (hi >> SH) in the high half.  (Tried in round 3: the second shift as
+// (lo >> sh) in the low half, (hi >> sh) in the high half.  (Tried in round 3: the second shift as
 // an SDWA write into the upper word of the first one's register -- two instructions instead of
 // three.  +0.5 % and NOT bit-exact in the 8-bit kernels, with or without the dst_sel wait state;
 // profiles/r03_ab_notes.md.  v_perm it stays.)
-template <int SH>
-__device__ __forceinline__ uint32_t ashr_pair(int32_t lo, int32_t hi) {
-  return __builtin_amdgcn_perm((uint32_t)(hi >> SH), (uint32_t)(lo >> SH), 0x05040100u);
-}
-__device__ __forceinline__ uint32_t ashr_pair_rt(int32_t lo, int32_t hi, int sh) {
+__device__ __forceinline__ uint32_t ashr_pair(int32_t lo, int32_t hi, int sh) {
   return __builtin_amdgcn_perm((uint32_t)(hi >> sh), (uint32_t)(lo >> sh), 0x05040100u);
 }
 
@@ -130,6 +159,50 @@ __device__ __forceinline__ int32_t dot4_seed(uint32_t a, uint32_t b, int32_t c_u
   return r;
 }
 
+// ---- the taps of one candidate ----------------------------------------------
+// Loaded ahead of their use (the fused kernel fetches them with the window).  8-bit pixels: the x-taps halved, as
+// i8 for v_dot4 (see mc8_column_t); 16-bit pixels: i16 pairs on both axes.
+template <int BPP> struct Taps;
+template <> struct Taps<1> { uint32_t fx0, fx1, ty[4]; };
+template <> struct Taps<2> { uint32_t tx[4], ty[4]; };
+template <int BPP, int W, int H>
+__device__ __forceinline__ Taps<BPP> load_taps(int cf, int rf, int mx, int my) {
+  const int fxi = r1mc::filter_index(mx, W), fyi = r1mc::filter_index(my, H);
+  Taps<BPP> t;
+  if constexpr (BPP == 1) {
+    t.fx0 = kTapI8[fxi][cf][0];
+    t.fx1 = kTapI8[fxi][cf][1];
+  }
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    if constexpr (BPP == 2) t.tx[j] = kTapI16[fxi][cf][j];
+    t.ty[j] = kTapI16[fyi][rf][j];
+  }
+  return t;
+}
+// wave-uniform: do all (active) lanes' filters have zero outer taps?  (8-bit: the vertical one; 16-bit: both)
+__device__ __forceinline__ bool taps_six(const Taps<1> &t) {
+  return __all(((t.ty[0] & 0xffffu) | (t.ty[3] >> 16)) == 0);
+}
+__device__ __forceinline__ bool taps_six(const Taps<2> &t) {
+  return __all(((t.ty[0] & 0xffffu) | (t.ty[3] >> 16) | (t.tx[0] & 0xffffu) | (t.tx[3] >> 16)) == 0);
+}
+
+// ---- the vertical 8-tap pass on packed row pairs ------------------------------
+// The y-taps as i16 pairs serve the even output rows; the odd rows take the same taps moved up by one i16, five pairs
+// (0, u0) (u1, u2) .. (u7, 0): R1_ODD_ROW_TAPS, for the three places that run the pass -- mc8_column_t, mc16_column_t
+// and k_mc_mfma (mc_mfma.hip).  The pass itself (a rolling window of five packed row pairs, four v_dot2 for the even
+// row, five or -- outer taps zero -- three for the odd one) stays written out in each of them: as one function over a
+// "next pair" callable the same instructions reached the optimizer in another order, and that alone cost fused
+// kernels registers, scratch and a wave per SIMD (profiles/HISTORY.md).  The tap derivation is a macro for the same
+// reason: as a function over the two arrays it reordered the 16-bit kernels.
+#define R1_ODD_ROW_TAPS(ty, tz)                                                                   \
+  do {                                                                                            \
+    tz[0] = ty[0] << 16;                                                                          \
+    _Pragma("unroll") for (int j = 1; j < 4; j++) tz[j] = __builtin_amdgcn_alignbit(ty[j], ty[j - 1], 16); \
+    tz[4] = ty[3] >> 16;                                                                          \
+  } while (0)
+
 // ---- 8-bit fast path of put_8tap for one column ---------------------------
 // Unified 2-D evaluation.  With x-taps t (sum 128) and y-taps u (sum 128),
 // ib = 4 (8-bit): mid = (sum t*p + 4) >> 3, out = clamp((sum u*mid + 1024) >> 11).
@@ -144,66 +217,17 @@ __device__ __forceinline__ int32_t dot4_seed(uint32_t a, uint32_t b, int32_t c_u
 // (sum u*mid + 64) >> 7 without clamp; the same algebra makes the one path
 // exact for its four cases too (mid = 16 p when col_frac == 0, u = 128 picks
 // mid when row_frac == 0).
-// the taps of one candidate, loaded ahead of their use (the pipelined kernel fetches the
-// next group's taps while the current group computes)
-struct Taps8 { uint32_t fx0, fx1, ty[4]; };
-template <int W, int H>
-__device__ __forceinline__ Taps8 load_taps8(int cf, int rf, int mx, int my) {
-  const int fxi = (mx == R1_FILTER_BILINEAR || W > 4) ? mx : (mx < 1 ? mx : 1) + 4;
-  const int fyi = (my == R1_FILTER_BILINEAR || H > 4) ? my : (my < 1 ? my : 1) + 4;
-  Taps8 t;
-  t.fx0 = kTapI8[fxi][cf][0];
-  t.fx1 = kTapI8[fxi][cf][1];
-#pragma unroll
-  for (int j = 0; j < 4; j++) t.ty[j] = kTapI16[fyi][rf][j];
-  return t;
-}
-struct Taps16 { uint32_t tx[4], ty[4]; };
-// wave-uniform: do all (active) lanes' filters have zero outer taps?  (mc8: the vertical one; mc16: both)
-__device__ __forceinline__ bool taps_six(const Taps8 &t) {
-  return __all(((t.ty[0] & 0xffffu) | (t.ty[3] >> 16)) == 0);
-}
-__device__ __forceinline__ bool taps_six(const Taps16 &t) {
-  return __all(((t.ty[0] & 0xffffu) | (t.ty[3] >> 16) | (t.tx[0] & 0xffffu) | (t.tx[3] >> 16)) == 0);
-}
-template <int W, int H>
-__device__ __forceinline__ Taps16 load_taps16(int cf, int rf, int mx, int my) {
-  const int fxi = (mx == R1_FILTER_BILINEAR || W > 4) ? mx : (mx < 1 ? mx : 1) + 4;
-  const int fyi = (my == R1_FILTER_BILINEAR || H > 4) ? my : (my < 1 ? my : 1) + 4;
-  Taps16 t;
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    t.tx[j] = kTapI16[fxi][cf][j];
-    t.ty[j] = kTapI16[fyi][rf][j];
-  }
-  return t;
-}
-
-template <int W, int H, int WS, bool PREP = false>
-__device__ __forceinline__ void mc8_column_t(const uint8_t *win, int c, const Taps8 &tp, int32_t *pred, bool six = false);
-
-template <int W, int H, int WS, bool PREP = false>
-__device__ __forceinline__ void mc8_column(const uint8_t *win, int c, int cf, int rf, int mx,
-                                           int my, bool any_cf0, int32_t *pred) {
-  (void)any_cf0;
-  const Taps8 tp = load_taps8<W, H>(cf, rf, mx, my);
-  mc8_column_t<W, H, WS, PREP>(win, c, tp, pred, taps_six(tp));
-}
-
 // `six` (wave-uniform): every lane's vertical filter has zero outer taps (REGULAR, SMOOTH, bilinear:
 // 6 live taps; only SHARP has 8, mc.rs:110-219).  Then the first and the last window row never meet
 // a non-zero tap and the odd output rows' five tap pairs are three: 2 fewer horizontal rows per
 // column and one v_dot2 less per pixel pair, the same bits.
 template <int W, int H, int WS, bool PREP>
-__device__ __forceinline__ void mc8_column_t(const uint8_t *win, int c, const Taps8 &tp, int32_t *pred, bool six) {
+__device__ __forceinline__ void mc8_column_t(const uint8_t *win, int c, const Taps<1> &tp, int32_t *pred, bool six) {
   const uint32_t fx0 = tp.fx0, fx1 = tp.fx1;
   uint32_t ty[4], tz[5];
 #pragma unroll
   for (int j = 0; j < 4; j++) ty[j] = tp.ty[j];
-  tz[0] = ty[0] << 16;
-#pragma unroll
-  for (int j = 1; j < 4; j++) tz[j] = __builtin_amdgcn_alignbit(ty[j], ty[j - 1], 16);
-  tz[4] = ty[3] >> 16;
+  R1_ODD_ROW_TAPS(ty, tz);
   // The i8 table holds h = t / 2 (all AV1 taps are even; sum h = 64).  With the
   // staged q = p - 128:  sum t*p = 2 (sum h*q + 128 * 64), so
   //   mid = (sum t*p + 4) >> 3 = (sum h*q + 8192 + 2) >> 2.
@@ -212,7 +236,6 @@ __device__ __forceinline__ void mc8_column_t(const uint8_t *win, int c, const Ta
   constexpr int32_t bias = 8192 + 2 + (PREP ? 0 : 32);
   constexpr int WSD = WS / 4;
   const uint32_t *wrow = (const uint32_t *)win + (c >> 2);
-  typedef short v2s __attribute__((ext_vector_type(2)));
   // The lane's 8 window bytes start at byte c & 3 of three aligned dwords.  Instead of moving the
   // PIXELS to the taps (two v_alignbyte per row), the TAPS are moved to the pixels once per lane:
   // the 8 tap bytes shifted up by c & 3 bytes into 12, zero elsewhere -- three v_dot4 per row on
@@ -231,7 +254,7 @@ __device__ __forceinline__ void mc8_column_t(const uint8_t *win, int c, const Ta
   };
   auto hpair = [&](int r) -> uint32_t {   // rows r, r+1 packed as i16 x 2
     // the last pair has no second row: its upper half only ever meets a zero tap (tz[4]'s high half)
-    if (r + 1 < H + 7) return ashr_pair<2>(hacc(r), hacc(r + 1));
+    if (r + 1 < H + 7) return ashr_pair(hacc(r), hacc(r + 1), 2);
     return (uint32_t)(hacc(r) >> 2);
   };
   // rolling window of 5 packed pairs: output rows 2j and 2j+1 need the
@@ -251,21 +274,21 @@ __device__ __forceinline__ void mc8_column_t(const uint8_t *win, int c, const Ta
       int32_t a0 = PREP ? dot2_seed64(pk[0], ty[0]) : dot2_seed0(pk[0], ty[0]);
 #pragma unroll
       for (int k = 1; k < 4; k++)
-        a0 = __builtin_amdgcn_sdot2(__builtin_bit_cast(v2s, pk[k]),
-                                    __builtin_bit_cast(v2s, ty[k]), a0, false);
+        a0 = __builtin_amdgcn_sdot2(__builtin_bit_cast(v2s_t, pk[k]),
+                                    __builtin_bit_cast(v2s_t, ty[k]), a0, false);
       int32_t a1;
       if constexpr (SIX) {   // tz[0] = (0, u0) and tz[4] = (u7, 0) are zero
         a1 = PREP ? dot2_seed64(pk[1], tz[1]) : dot2_seed0(pk[1], tz[1]);
 #pragma unroll
         for (int k = 2; k < 4; k++)
-          a1 = __builtin_amdgcn_sdot2(__builtin_bit_cast(v2s, pk[k]),
-                                      __builtin_bit_cast(v2s, tz[k]), a1, false);
+          a1 = __builtin_amdgcn_sdot2(__builtin_bit_cast(v2s_t, pk[k]),
+                                      __builtin_bit_cast(v2s_t, tz[k]), a1, false);
       } else {
         a1 = PREP ? dot2_seed64(pk[0], tz[0]) : dot2_seed0(pk[0], tz[0]);
 #pragma unroll
         for (int k = 1; k < 5; k++)
-          a1 = __builtin_amdgcn_sdot2(__builtin_bit_cast(v2s, pk[k]),
-                                      __builtin_bit_cast(v2s, tz[k]), a1, false);
+          a1 = __builtin_amdgcn_sdot2(__builtin_bit_cast(v2s_t, pk[k]),
+                                      __builtin_bit_cast(v2s_t, tz[k]), a1, false);
       }
       if constexpr (PREP) {
         pred[2 * j] = a0 >> 7;
@@ -285,7 +308,7 @@ __device__ __forceinline__ void mc8_column_t(const uint8_t *win, int c, const Ta
 }
 
 // ---- 10/12-bit fast path of put_8tap for one column -------------------------
-// Same unified evaluation as mc8_column, on u16 pixels: intermediate_bits
+// Same unified evaluation as mc8_column_t, on u16 pixels: intermediate_bits
 // ib = 4 (10-bit) or 2 (12-bit);  mid = (sum t*p + 2^(6-ib)) >> (7-ib) fits
 // i16 (mc.rs:314,326), out = clamp((sum u*mid + 2^(6+ib)) >> (7+ib)).
 //  * col_frac == 0 (t = 128 at tap 3): mid = p << ib exactly, out =
@@ -299,34 +322,19 @@ __device__ __forceinline__ void mc8_column_t(const uint8_t *win, int c, const Ta
 // The rounding of the vertical pass is pre-added to the intermediates:
 // 2^(6+ib) = 128 * 2^(ib-1) and every tap row sums to 128.
 // PREP: (sum u*mid + 64) >> 7 - PREP_BIAS (8192), no clamp (mc.rs:355-451).
-template <int W, int H, int WS, bool PREP = false>
-__device__ __forceinline__ void mc16_column_t(const uint8_t *win, int c, const Taps16 &tp, int bit_depth,
-                                              int32_t *pred, bool six = false);
-
-template <int W, int H, int WS, bool PREP = false>
-__device__ __forceinline__ void mc16_column(const uint8_t *win, int c, int cf, int rf, int mx,
-                                            int my, int bit_depth, int32_t *pred) {
-  const Taps16 tp = load_taps16<W, H>(cf, rf, mx, my);
-  mc16_column_t<W, H, WS, PREP>(win, c, tp, bit_depth, pred, taps_six(tp));
-}
-
 template <int W, int H, int WS, bool PREP>
-__device__ __forceinline__ void mc16_column_t(const uint8_t *win, int c, const Taps16 &tp, int bit_depth,
+__device__ __forceinline__ void mc16_column_t(const uint8_t *win, int c, const Taps<2> &tp, int bit_depth,
                                               int32_t *pred, bool six) {
   // `six` (wave-uniform): BOTH filters of every lane have zero outer taps (see mc8_column_t); the
   // fifth horizontal tap pair is then zero for odd columns as it always is for even ones
-  typedef short v2s __attribute__((ext_vector_type(2)));
   uint32_t tx[4], ty[4], tz[5];
 #pragma unroll
   for (int j = 0; j < 4; j++) {
     tx[j] = tp.tx[j];
     ty[j] = tp.ty[j];
   }
-  tz[0] = ty[0] << 16;
-#pragma unroll
-  for (int j = 1; j < 4; j++) tz[j] = __builtin_amdgcn_alignbit(ty[j], ty[j - 1], 16);
-  tz[4] = ty[3] >> 16;
-  const int ib = bit_depth == 12 ? 2 : 4;
+  R1_ODD_ROW_TAPS(ty, tz);
+  const int ib = r1mc::intermediate_bits(bit_depth);
   const int hsh = 7 - ib, vsh = 7 + ib;
   // H rounding, plus (put only) the V rounding 2^(ib-1) << hsh = 64 folded into mid
   const int32_t hbias = (1 << (6 - ib)) + (PREP ? 0 : 64);
@@ -348,11 +356,11 @@ __device__ __forceinline__ void mc16_column_t(const uint8_t *win, int c, const T
       int32_t acc = dot2_seed(p[0], u[0], hbias);
 #pragma unroll
       for (int j = 1; j < (SIX ? 4 : 5); j++)
-        acc = __builtin_amdgcn_sdot2(__builtin_bit_cast(v2s, p[j]), __builtin_bit_cast(v2s, u[j]), acc, false);
+        acc = __builtin_amdgcn_sdot2(__builtin_bit_cast(v2s_t, p[j]), __builtin_bit_cast(v2s_t, u[j]), acc, false);
       return acc;
     };
     auto hpair = [&](int r) -> uint32_t {   // rows r, r+1 packed as i16 x 2
-      if (r + 1 < H + 7) return ashr_pair_rt(hacc(r), hacc(r + 1), hsh);
+      if (r + 1 < H + 7) return ashr_pair(hacc(r), hacc(r + 1), hsh);
       return (uint32_t)(hacc(r) >> hsh);
     };
     uint32_t pk[5];
@@ -365,18 +373,18 @@ __device__ __forceinline__ void mc16_column_t(const uint8_t *win, int c, const T
       int32_t a0 = PREP ? dot2_seed64(pk[0], ty[0]) : dot2_seed0(pk[0], ty[0]);
 #pragma unroll
       for (int k = 1; k < 4; k++)
-        a0 = __builtin_amdgcn_sdot2(__builtin_bit_cast(v2s, pk[k]), __builtin_bit_cast(v2s, ty[k]), a0, false);
+        a0 = __builtin_amdgcn_sdot2(__builtin_bit_cast(v2s_t, pk[k]), __builtin_bit_cast(v2s_t, ty[k]), a0, false);
       int32_t a1;
       if constexpr (SIX) {
         a1 = PREP ? dot2_seed64(pk[1], tz[1]) : dot2_seed0(pk[1], tz[1]);
 #pragma unroll
         for (int k = 2; k < 4; k++)
-          a1 = __builtin_amdgcn_sdot2(__builtin_bit_cast(v2s, pk[k]), __builtin_bit_cast(v2s, tz[k]), a1, false);
+          a1 = __builtin_amdgcn_sdot2(__builtin_bit_cast(v2s_t, pk[k]), __builtin_bit_cast(v2s_t, tz[k]), a1, false);
       } else {
         a1 = PREP ? dot2_seed64(pk[0], tz[0]) : dot2_seed0(pk[0], tz[0]);
 #pragma unroll
         for (int k = 1; k < 5; k++)
-          a1 = __builtin_amdgcn_sdot2(__builtin_bit_cast(v2s, pk[k]), __builtin_bit_cast(v2s, tz[k]), a1, false);
+          a1 = __builtin_amdgcn_sdot2(__builtin_bit_cast(v2s_t, pk[k]), __builtin_bit_cast(v2s_t, tz[k]), a1, false);
       }
       if constexpr (PREP) {
         pred[2 * j] = (a0 >> 7) - 8192;
@@ -395,6 +403,15 @@ __device__ __forceinline__ void mc16_column_t(const uint8_t *win, int c, const T
   else body(std::false_type{});
 }
 
+// One column of put_8tap (PREP: prep_8tap) of a W x H block at either pixel width, from a window staged with row
+// stride WS (8-bit: pixels biased by -128); `six` is taps_six(tp), voted by every lane that makes the call.
+template <int BPP, int W, int H, int WS, bool PREP>
+__device__ __forceinline__ void mc_column_fast(const uint8_t *win, int c, const Taps<BPP> &tp, int bit_depth,
+                                               int32_t *pred, bool six) {
+  if constexpr (BPP == 1) mc8_column_t<W, H, WS, PREP>(win, c, tp, pred, six);
+  else mc16_column_t<W, H, WS, PREP>(win, c, tp, bit_depth, pred, six);
+}
+
 // ---- SATD with the horizontal pass in registers (blocks with both sides >= 16, up to 10 bits) ----
 // The lane stages of habs_lanes_pk cost 4.5 instructions per coefficient (DPP moves, +-1 multiplies) against 2 for
 // the vertical half, only because the data sits lane = column.  Here the packed outputs of the vertical half go
@@ -402,29 +419,21 @@ __device__ __forceinline__ void mc16_column_t(const uint8_t *win, int c, const T
 // two butterfly stages and the folded last one (max(|a|, |b|) = max(max(a, b), -min(a, b))) are 36 packed
 // instructions per 16 coefficients instead of 72.  Same i16 range argument: three vertical and two horizontal
 // stages reach 32 * 1023 before the fold.
-__device__ __forceinline__ uint32_t pk_min(uint32_t a, uint32_t b) {
-  uint32_t r;
-  asm("v_pk_min_i16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
+// The first two vertical stages of 16 rows of the lane's column: 8-row groups 2g and 2g + 1 side by side
+__device__ __forceinline__ void satd_rows16_s2(const int32_t *v, uint32_t (&d)[8]) {
+  uint32_t a[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) a[k] = pk_pair(v[k], v[8 + k]);
+  pk_bfly8_s2(a, d);
 }
-// Vertical half: the lane's column, 16 rows at a time (8-row groups 2g and 2g+1 side by side), to column c of the
-// candidate's tile: W dwords per row, row g * 8 + i = coefficient row i of that group pair.
+// The vertical half, to column c of the candidate's tile: W dwords per row, row g * 8 + i = coefficient row i of
+// that group pair.
 template <int W, int H>
-__device__ __forceinline__ void satd_tile_store(const T *v, uint32_t *tcol) {
+__device__ __forceinline__ void satd_tile_store(const int32_t *v, uint32_t *tcol) {
 #pragma unroll
   for (int g = 0; g < H / 16; g++) {
-    uint32_t a[8], b[8], d[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) a[k] = pk_pair(v[g * 16 + k], v[g * 16 + 8 + k]);
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      b[2 * k] = pk_add(a[2 * k], a[2 * k + 1]);
-      b[2 * k + 1] = pk_sub(a[2 * k], a[2 * k + 1]);
-    }
-    d[0] = pk_add(b[0], b[2]); d[2] = pk_sub(b[0], b[2]);
-    d[1] = pk_add(b[1], b[3]); d[3] = pk_sub(b[1], b[3]);
-    d[4] = pk_add(b[4], b[6]); d[6] = pk_sub(b[4], b[6]);
-    d[5] = pk_add(b[5], b[7]); d[7] = pk_sub(b[5], b[7]);
+    uint32_t d[8];
+    satd_rows16_s2(v + g * 16, d);
 #pragma unroll
     for (int k = 0; k < 4; k++) {
       tcol[(g * 8 + 2 * k) * W] = pk_add(d[k], d[k + 4]);
@@ -443,16 +452,8 @@ __device__ __forceinline__ uint32_t satd_tile_rows(const uint32_t *tile, int c) 
     const uint4 *p = (const uint4 *)(tile + (c + m * P) * 8);
     const uint4 lo = p[0], hi = p[1];
     const uint32_t x[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    uint32_t y[8], z[8];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      y[2 * k] = pk_add(x[2 * k], x[2 * k + 1]);
-      y[2 * k + 1] = pk_sub(x[2 * k], x[2 * k + 1]);
-    }
-    z[0] = pk_add(y[0], y[2]); z[2] = pk_sub(y[0], y[2]);
-    z[1] = pk_add(y[1], y[3]); z[3] = pk_sub(y[1], y[3]);
-    z[4] = pk_add(y[4], y[6]); z[6] = pk_sub(y[4], y[6]);
-    z[5] = pk_add(y[5], y[7]); z[7] = pk_sub(y[5], y[7]);
+    uint32_t z[8];
+    pk_bfly8_s2(x, z);
 #pragma unroll
     for (int k = 0; k < 4; k++) {
       const uint32_t mx = pk_max(pk_max(z[k], z[k + 4]), pk_sub(0u, pk_min(z[k], z[k + 4])));
@@ -464,7 +465,7 @@ __device__ __forceinline__ uint32_t satd_tile_rows(const uint32_t *tile, int c) 
 
 // SATD contribution of one residual column (TS rows at a time).
 template <int TS, int H, int BD>
-__device__ __forceinline__ uint32_t satd_column(const T *v, int lane) {
+__device__ __forceinline__ uint32_t satd_column(const int32_t *v, int lane) {
   const LaneSigns sg = lane_signs<TS>(lane);
   uint32_t acc = 0;
   if constexpr (TS == 8 && BD <= 10) {
@@ -482,19 +483,9 @@ __device__ __forceinline__ uint32_t satd_column(const T *v, int lane) {
       acc = habs_lanes_pk(pk_sub(a1, a3), m1, m2, acc);
     } else {
 #pragma unroll
-      for (int g = 0; g < H / 16; g++) {   // 8-row groups 2g and 2g+1 side by side
-        uint32_t a[8], b[8], d[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) a[k] = pk_pair(v[g * 16 + k], v[g * 16 + 8 + k]);
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-          b[2 * k] = pk_add(a[2 * k], a[2 * k + 1]);
-          b[2 * k + 1] = pk_sub(a[2 * k], a[2 * k + 1]);
-        }
-        d[0] = pk_add(b[0], b[2]); d[2] = pk_sub(b[0], b[2]);
-        d[1] = pk_add(b[1], b[3]); d[3] = pk_sub(b[1], b[3]);
-        d[4] = pk_add(b[4], b[6]); d[6] = pk_sub(b[4], b[6]);
-        d[5] = pk_add(b[5], b[7]); d[7] = pk_sub(b[5], b[7]);
+      for (int g = 0; g < H / 16; g++) {
+        uint32_t d[8];
+        satd_rows16_s2(v + g * 16, d);
 #pragma unroll
         for (int k = 0; k < 4; k++) {
           acc = habs_lanes_pk(pk_add(d[k], d[k + 4]), m1, m2, acc);
@@ -509,7 +500,9 @@ __device__ __forceinline__ uint32_t satd_column(const T *v, int lane) {
     int32_t a[TS];
 #pragma unroll
     for (int k = 0; k < TS; k++) a[k] = v[g * TS + k];
-    // vertical pass on the lane's own TS rows (dist.rs:126-131)
+    // vertical pass on the lane's own TS rows (dist.rs:126-131).  The operations of r1dist::hadamard_1d<TS>(a, 1),
+    // written out: through that call the adds reach the back end with their operands commuted, and the 12-bit and
+    // TS = 4 kernels come out in another instruction order (profiles/HISTORY.md)
     if constexpr (TS == 4) {
       const int32_t a0 = a[0] + a[1], a1 = a[0] - a[1];
       const int32_t a2 = a[2] + a[3], a3 = a[2] - a[3];
@@ -537,3 +530,5 @@ __device__ __forceinline__ uint32_t satd_column(const T *v, int lane) {
   }
   return acc;
 }
+
+}  // namespace r1cand

@@ -25,9 +25,8 @@ __global__ __launch_bounds__(256) void k_dist(R1Plane org, R1Plane ref,
                                               int n, uint32_t *__restrict__ out) {
   __shared__ uint32_t wave_part[4];
   const int tid = threadIdx.x;
-  // XCD-aware: workgroup i runs on XCD i % 8; XCD x takes the x-th contiguous eighth of the tile list, so the
-  // K candidates of a block (same source tile, overlapping reference tiles) meet in ONE L2 (grid = multiple of 8)
-  const unsigned wg = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+  // the K candidates of a block (same source tile, overlapping reference tiles) meet in ONE L2
+  const unsigned wg = xcd_contiguous_wg();
   const long long gt = (long long)wg * 256 + tid;  // global tile id
   const int cand = (int)(gt >> tpc_log2);
   const int t = (int)(gt & ((1 << tpc_log2) - 1));
@@ -80,7 +79,7 @@ extern "C" int r1_dist_batch(r1_ctx *ctx, int kind, const R1Plane *org,
   const int ts = (w < h ? w : h) == 4 ? 4 : 8;
   const int wt_log2 = r1_ilog2(w / ts), tpc_log2 = wt_log2 + r1_ilog2(h / ts);
   const long long tiles = (long long)n << tpc_log2;
-  const unsigned grid = ((unsigned)((tiles + 255) / 256) + 7u) & ~7u;   // whole rounds over the 8 XCDs
+  const unsigned grid = xcd_grid((unsigned)((tiles + 255) / 256));
   r1_by_bpp(org->bytes_per_px, [&](auto B) {
     r1_by_value<8, 4>(ts, [&](auto TS) {
       r1_by_value<R1_DIST_SATD, R1_DIST_SAD>(kind, [&](auto KIND) {

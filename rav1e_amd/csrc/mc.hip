@@ -8,14 +8,10 @@
 // 8-deep register window (one new LDS row per output row for the vertical
 // taps).  Output blocks are dense (stride = w), so a row's P lanes store P
 // consecutive samples.
-#include "dist_common.hpp"
-#include "mc_common.hpp"
+#include "cand_common.hpp"
 #include "tx_common.hpp"
 
 namespace {
-using r1tx::T;
-#include "mc_taps_packed.inc"
-#include "cand_helpers.inc"
 
 template <int BPP, bool PREP>
 __global__ __launch_bounds__(64) void k_mc(R1Plane ref, int w, int h,
@@ -25,7 +21,7 @@ __global__ __launch_bounds__(64) void k_mc(R1Plane ref, int w, int h,
   const int P = w < 64 ? w : 64;
   const int spc = w / P;      // slabs per candidate
   const int NS = 64 / P;      // slabs per wave
-  const int ws = (((P + 7) * BPP + 3) >> 2) << 2;
+  const int ws = r1mc::window_stride(P, BPP);
   const int lane = threadIdx.x;
   const int sl = lane / P, c = lane - sl * P;
   const long long slab = (long long)blockIdx.x * NS + sl;
@@ -79,12 +75,11 @@ __global__ __launch_bounds__(64) void k_mc_fast(R1Plane ref, const R1McCand *__r
                                                 int n, void *__restrict__ dst) {
   constexpr int W = 1 << WL, H = 1 << HL;
   constexpr int P = W > H ? W : H, NC = 64 / P;
-  constexpr int WS = (((W + 7) * BPP + 3) >> 2) << 2;
+  constexpr int WS = r1mc::window_stride(W, BPP);
   __shared__ __attribute__((aligned(16))) uint8_t smem[NC * (H + 7) * WS];
   const int lane = threadIdx.x;
   const int cl = lane / P, c = lane % P;
-  // XCD-aware like k_rdo_cand: XCD x takes the x-th contiguous eighth of the list (grid = multiple of 8)
-  const unsigned wg = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+  const unsigned wg = xcd_contiguous_wg();
   const long long cand = (long long)wg * NC + cl;
   const bool live = cand < n;
   R1McCand cd = {};
@@ -93,14 +88,10 @@ __global__ __launch_bounds__(64) void k_mc_fast(R1Plane ref, const R1McCand *__r
   if (live)
     r1mc::stage_window_fast<BPP, BPP == 1 ? 0x80808080u : 0u, W, H, P>(win, WS, ref, cd.rx, cd.ry, c);
   __syncthreads();
-  const bool any_cf0 = __any(live && cd.col_frac == 0);
   if (!(live && c < W)) return;
   int32_t pred[H];
-  if constexpr (BPP == 1)
-    mc8_column<W, H, WS, PREP>(win, c, cd.col_frac, cd.row_frac, cd.mode_x, cd.mode_y, any_cf0, pred);
-  else
-    mc16_column<W, H, WS, PREP>(win, c, cd.col_frac, cd.row_frac, cd.mode_x, cd.mode_y,
-                                ref.bit_depth, pred);
+  const r1cand::Taps<BPP> tp = r1cand::load_taps<BPP, W, H>(cd.col_frac, cd.row_frac, cd.mode_x, cd.mode_y);
+  r1cand::mc_column_fast<BPP, W, H, WS, PREP>(win, c, tp, ref.bit_depth, pred, r1cand::taps_six(tp));
   // the predictions stream out (non-temporal: they would only push the reference rows out of the L2)
   if constexpr (PREP || BPP == 2) {
     uint16_t *pp = (uint16_t *)dst + (size_t)cand * W * H + c;
@@ -117,7 +108,7 @@ template <int BPP, int WL, int HL>
 int launch_mc_fast(bool prep, const R1Plane &ref, const R1McCand *cands, int n, void *dst,
                    hipStream_t st) {
   constexpr int W = 1 << WL, H = 1 << HL, P = W > H ? W : H, NC = 64 / P;
-  const unsigned grid = ((unsigned)((n + NC - 1) / NC) + 7u) & ~7u;
+  const unsigned grid = xcd_grid((unsigned)((n + NC - 1) / NC));
   r1_by_bool(prep, [&](auto PREP) {
     hipLaunchKernelGGL((k_mc_fast<BPP, WL, HL, PREP.value>), dim3(grid), dim3(64), 0, st, ref, cands, n, dst);
   });
@@ -158,7 +149,7 @@ int mc_launch(bool prep, const R1Plane *ref, int w, int h, const R1McCand *cands
   }
   const int bpp = ref->bytes_per_px;
   const int P = w < 64 ? w : 64, NS = 64 / P, spc = w / P;
-  const int ws = (((P + 7) * bpp + 3) >> 2) << 2;
+  const int ws = r1mc::window_stride(P, bpp);
   const size_t lds = (size_t)NS * (h + 7) * ws;
   const long long slabs = (long long)n * spc;
   const unsigned grid = (unsigned)((slabs + NS - 1) / NS);

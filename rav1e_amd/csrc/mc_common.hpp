@@ -9,6 +9,7 @@
 //   mc_avg             src/mc.rs:454-479     PREP_BIAS  src/mc.rs:355-357
 #pragma once
 #include "common.hpp"
+#include "mc_window.hpp"
 
 namespace r1mc {
 
@@ -64,13 +65,14 @@ __constant__ int16_t kSubpel[6][16][8] = {
      {0, 0, 6, 42, 60, 20, 0, 0}, {0, 0, 4, 40, 62, 22, 0, 0},
      {0, 0, 4, 36, 62, 26, 0, 0}, {0, 0, 2, 34, 62, 30, 0, 0}}};
 
-// mc.rs:238-247: blocks whose filtered dimension is <= 4 use the 4-tap sets.
+// mc.rs:238-247: blocks whose filtered dimension is <= 4 use the 4-tap sets.  The set of filter mode mx along a
+// side of `side` pixels, for kSubpel and for the packed tables made from it (cand_common.hpp).
+__device__ __forceinline__ int filter_index(int mx, int side) {
+  return (mx == R1_FILTER_BILINEAR || side > 4) ? mx : (mx < 1 ? mx : 1) + 4;
+}
 __device__ __forceinline__ const int16_t *get_filter(int mode, int frac,
                                                      int length) {
-  const int idx = (mode == R1_FILTER_BILINEAR || length > 4)
-                      ? mode
-                      : (mode < 1 ? mode : 1) + 4;
-  return kSubpel[idx][frac];
+  return kSubpel[filter_index(mode, length)][frac];
 }
 
 __device__ __forceinline__ int32_t round_shift(int32_t v, int b) {
@@ -254,7 +256,7 @@ __device__ __forceinline__ void stage_window_rows8(uint8_t *win, int ws, const R
 template <int BPP, uint32_t XORM, int P, int H, int NL>
 __device__ __forceinline__ void stage_window_fast(uint8_t *win, int ws, const R1Plane &ref,
                                                   int rx, int ry, int l) {
-  constexpr int ND = ((P + 7) * BPP + 3) >> 2;
+  constexpr int ND = window_stride(P, BPP) / 4;
   constexpr int NDV = ((P + 7) * BPP + 7) >> 3;
   // 8-byte chunks pay for the few-lanes-per-candidate shapes (measured: 8x8 -4.6 %,
   // larger sizes neutral to slightly worse)

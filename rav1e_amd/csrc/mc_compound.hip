@@ -14,7 +14,7 @@
 //    compile-time W x H, P = max(W, H) lanes per candidate, 64 / P candidates per wave, one wave per workgroup.
 //    Both (H + 7) x (W + 7) windows of a candidate sit side by side in LDS, staged with ONE global round trip
 //    (all loads of both windows go out before the first LDS write).  Lane = column: the two prep columns
-//    (mc8_column / mc16_column, PREP) are 2 * H registers, averaged in place; the residual column goes through
+//    (mc_column_fast of cand_common.hpp, PREP) are 2 * H registers, averaged in place; the residual column goes through
 //    satd_column's DPP Hadamard and group_sum.
 //    LDS bytes per wave = 2 * (H + 7) * row stride * candidates per wave: 64x64 at 16 bits is 2 * 71 * 144 =
 //    20448 B -> 8 workgroups in a CU's 160 KiB = 2 waves per SIMD; 64x64 at 8 bits 10224 B -> 4 per SIMD; 32x32
@@ -33,14 +33,10 @@
 //    the Hadamard.  LDS per wave = (64 / P) * (2 * (hc + 7) * row stride + hc * P * 2): 28640 B for a 128x128
 //    16-bit block -> 5 waves per CU, at most 62720 B (4-wide, 16 bits, 64 rows).  This path trades occupancy
 //    for having no per-size code; the sizes the encoder sends most are on the fast path.
-#include "dist_common.hpp"
-#include "mc_common.hpp"
+#include "cand_common.hpp"
 #include "tx_common.hpp"
 
 namespace {
-using r1tx::T;
-#include "mc_taps_packed.inc"
-#include "cand_helpers.inc"
 
 static_assert(sizeof(R1CompoundCand) == 20, "R1CompoundCand is 20 bytes");
 
@@ -65,12 +61,11 @@ __global__ __launch_bounds__(64) void k_compound_fast(R1Plane org, R1Plane ref0,
   constexpr int W = 1 << WL, H = 1 << HL;
   constexpr int P = W > H ? W : H, NC = 64 / P;
   constexpr int TS = (W < H ? W : H) == 4 ? 4 : 8;   // the reference's Hadamard size rule (dist.rs:166)
-  constexpr int WS = (((W + 7) * BPP + 3) >> 2) << 2;
+  constexpr int WS = r1mc::window_stride(W, BPP);
   constexpr int WIN = (H + 7) * WS;
-  constexpr uint32_t XORM = BPP == 1 ? 0x80808080u : 0u;   // mc8_column wants pixels biased to i8
+  constexpr uint32_t XORM = BPP == 1 ? 0x80808080u : 0u;   // mc8_column_t wants pixels biased to i8
   __shared__ __attribute__((aligned(16))) uint8_t smem[NC * 2 * WIN];
-  // XCD-aware like k_mc_fast: XCD x takes the x-th contiguous eighth of the list (grid = multiple of 8)
-  const unsigned wg = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+  const unsigned wg = xcd_contiguous_wg();
   if ((long long)wg * NC >= (long long)n) return;   // the whole wave: no lane of it has a candidate
   const int lane = threadIdx.x;
   const int cl = lane / P, c = lane % P;
@@ -91,18 +86,15 @@ __global__ __launch_bounds__(64) void k_compound_fast(R1Plane org, R1Plane ref0,
   // column (c >= W of a tall block, candidates past the list end) carry a zero residual.
   const bool col_live = live && c < W;
   const bool dist = sad_out || satd_out;   // wave-uniform: kernel arguments
-  T v[H];
+  int32_t v[H];
 #pragma unroll
   for (int r = 0; r < H; r++) v[r] = 0;
   if (col_live) {
     int32_t t0[H], t1[H];
-    if constexpr (BPP == 1) {
-      mc8_column<W, H, WS, true>(win0, c, cd.col_frac0, cd.row_frac0, cd.mode_x, cd.mode_y, false, t0);
-      mc8_column<W, H, WS, true>(win1, c, cd.col_frac1, cd.row_frac1, cd.mode_x, cd.mode_y, false, t1);
-    } else {
-      mc16_column<W, H, WS, true>(win0, c, cd.col_frac0, cd.row_frac0, cd.mode_x, cd.mode_y, BD, t0);
-      mc16_column<W, H, WS, true>(win1, c, cd.col_frac1, cd.row_frac1, cd.mode_x, cd.mode_y, BD, t1);
-    }
+    const r1cand::Taps<BPP> tp0 = r1cand::load_taps<BPP, W, H>(cd.col_frac0, cd.row_frac0, cd.mode_x, cd.mode_y);
+    r1cand::mc_column_fast<BPP, W, H, WS, true>(win0, c, tp0, BD, t0, r1cand::taps_six(tp0));
+    const r1cand::Taps<BPP> tp1 = r1cand::load_taps<BPP, W, H>(cd.col_frac1, cd.row_frac1, cd.mode_x, cd.mode_y);
+    r1cand::mc_column_fast<BPP, W, H, WS, true>(win1, c, tp1, BD, t1, r1cand::taps_six(tp1));
 #pragma unroll
     for (int r = 0; r < H; r++) t0[r] = r1mc::avg_px(t0[r], t1[r], BD);
     if (pred_out) {
@@ -131,7 +123,7 @@ __global__ __launch_bounds__(64) void k_compound_fast(R1Plane org, R1Plane ref0,
     if (live && c == 0) sad_out[cand] = s;
   }
   if (satd_out) {
-    const uint32_t s = group_sum<P>(satd_column<TS, H, BD>(v, lane));
+    const uint32_t s = group_sum<P>(r1cand::satd_column<TS, H, BD>(v, lane));
     if (live && c == 0) satd_out[cand] = satd_norm(s, TS == 4 ? 2 : 3);
   }
 }
@@ -147,7 +139,7 @@ __global__ __launch_bounds__(64) void k_compound(R1Plane org, R1Plane ref0, R1Pl
   const int spc = w / P;                // column slabs per candidate: 1 or 2
   const int hc = h <= 64 ? h : h >> 1;  // rows per slab; h > 64 splits in two halves (both > 4 rows: same filters)
   const int nrc = h / hc;               // 1 or 2
-  const int ws = (((P + 7) * BPP + 3) >> 2) << 2;
+  const int ws = r1mc::window_stride(P, BPP);
   const int winb = (hc + 7) * ws;
   const int per = 2 * winb + hc * P * 2;   // LDS bytes of one candidate's slab: two windows + the int16 tile
   const int lane = threadIdx.x;
@@ -194,10 +186,10 @@ __global__ __launch_bounds__(64) void k_compound(R1Plane org, R1Plane ref0, R1Pl
     if (satd_out) {
       // every lane takes part (DPP across the lanes of a tile); a lane without a candidate adds zeros
       for (int g = 0; g < hc / ts; g++) {
-        T v[8];
+        int32_t v[8];
 #pragma unroll
-        for (int k = 0; k < 8; k++) v[k] = live && k < ts ? (T)tile[(g * ts + k) * P] : 0;
-        satd += ts == 4 ? satd_column<4, 4, 12>(v, lane) : satd_column<8, 8, 12>(v, lane);
+        for (int k = 0; k < 8; k++) v[k] = live && k < ts ? (int32_t)tile[(g * ts + k) * P] : 0;
+        satd += ts == 4 ? r1cand::satd_column<4, 4, 12>(v, lane) : r1cand::satd_column<8, 8, 12>(v, lane);
       }
     }
   }
@@ -215,7 +207,7 @@ template <int BD, int WL, int HL>
 int launch_fast(const R1Plane &org, const R1Plane &ref0, const R1Plane &ref1, const R1CompoundCand *cands, int n,
                 uint32_t *sad_out, uint32_t *satd_out, void *pred_out, hipStream_t st) {
   constexpr int W = 1 << WL, H = 1 << HL, P = W > H ? W : H, NC = 64 / P;
-  const unsigned grid = ((unsigned)((n + NC - 1) / NC) + 7u) & ~7u;   // whole rounds over the 8 XCDs
+  const unsigned grid = xcd_grid((unsigned)((n + NC - 1) / NC));
   hipLaunchKernelGGL((k_compound_fast<BD, WL, HL>), dim3(grid), dim3(64), 0, st, org, ref0, ref1, cands, n,
                      sad_out, satd_out, pred_out);
   R1_HIP_CHECK(hipGetLastError());
@@ -260,7 +252,7 @@ extern "C" int r1_rdo_compound_cand_batch(r1_ctx *ctx, const R1Plane *org, const
 #undef R1_CF_CASE
   // the slab kernel for the rest
   const int P = w < 64 ? w : 64, NS = 64 / P, hc = h <= 64 ? h : h >> 1;
-  const int ws = (((P + 7) * bpp + 3) >> 2) << 2;
+  const int ws = r1mc::window_stride(P, bpp);
   const size_t lds = (size_t)NS * (2 * (size_t)(hc + 7) * ws + (size_t)hc * P * 2);   // <= 62720
   const unsigned grid = (unsigned)((n + NS - 1) / NS);
   r1_by_bpp(bpp, [&](auto B) {

@@ -1,7 +1,7 @@
 // mc_mfma.hip -- put_8tap / prep_8tap (8-bit) with the HORIZONTAL 8-tap pass on the
 // matrix cores (reference: src/mc.rs:250-451).  BASELINE.json's north_star asks for "MFMA
 // only for the batched put/prep 8-tap separable convolution in mc.rs"; this is that
-// variant, kept beside the dot4 path (cand_helpers.inc mc8_column) so that both can be timed
+// variant, kept beside the dot4 path (cand_common.hpp mc8_column_t) so that both can be timed
 // on the same box (tools/bench_mc_mfma.py, profiles/r02_mc_mfma_*).
 //
 // Horizontal pass as a banded-Toeplitz product on v_mfma_i32_16x16x32_i8:
@@ -12,33 +12,25 @@
 //                     byte 8 g + k            (g = column group of 8, k = 0..15)
 //   B[16 s + k][8 s + m] = half-tap h[k - m] (0 <= k - m < 8), 0 elsewhere
 //   C = 8192 + 2 (+32 for put): the -128 bias of the pixels and the rounding of
-//       mid = (sum t*p + 4) >> 3 = (sum h*(p-128) + 8192 + 2) >> 2   (mc8_column's algebra)
+//       mid = (sum t*p + 4) >> 3 = (sum h*(p-128) + 8192 + 2) >> 2   (mc8_column_t's algebra)
 // so D >> 2 IS the i16 intermediate of mc.rs:314-326 for 16 rows x 8 columns of two
 // different windows -- two 8x8 candidates per instruction, or two column groups of a wider
 // block.  8 of the 32 K entries of a column are non-zero (25 % of the MACs are useful).
 // D's layout (col = lane & 15, rows 4 (lane >> 4) + reg) is column-major in groups of four
 // rows, so the intermediates go to LDS as packed i16 pairs and the vertical pass -- lane =
-// column, v_dot2_i32_i16 on row pairs, exactly mc8_column's -- reads its column back.
+// column, v_dot2_i32_i16 on row pairs, exactly mc8_column_t's -- reads its column back.
 //
 // VALU work per intermediate: shift + half a pack (was: 2 v_alignbyte + 2 v_dot4 + shift).
-#include "mc_common.hpp"
+#include "cand_common.hpp"
 
 namespace {
-#include "mc_taps_packed.inc"
+using r1cand::dot2_seed0;
+using r1cand::dot2_seed64;
+using r1cand::kTapB;
+using r1cand::kTapI16;
+using r1cand::v2s_t;
 
 typedef int v4i __attribute__((ext_vector_type(4)));
-typedef short v2s __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ int32_t dot2_seed0(uint32_t a, uint32_t b) {
-  int32_t r;
-  asm("v_dot2_i32_i16 %0, %1, %2, 0" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-__device__ __forceinline__ int32_t dot2_seed64(uint32_t a, uint32_t b) {
-  int32_t r;
-  asm("v_dot2_i32_i16 %0, %1, %2, 64" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
 
 template <int WL, int HL, bool PREP>
 __global__ __launch_bounds__(64) void k_mc_mfma(R1Plane ref, const R1McCand *__restrict__ cands,
@@ -115,15 +107,12 @@ __global__ __launch_bounds__(64) void k_mc_mfma(R1Plane ref, const R1McCand *__r
   __syncthreads();
   if (!(live && c < W)) return;
 
-  // ---- vertical pass: lane = column, packed row pairs from LDS (mc8_column's second half) ----
+  // ---- vertical pass: lane = column, packed row pairs from LDS (mc8_column_t's second half) ----
   const int fyi = cd.mode_y;     // H >= 8
   uint32_t ty[4], tz[5];
 #pragma unroll
   for (int j = 0; j < 4; j++) ty[j] = kTapI16[fyi][cd.row_frac][j];
-  tz[0] = ty[0] << 16;
-#pragma unroll
-  for (int j = 1; j < 4; j++) tz[j] = __builtin_amdgcn_alignbit(ty[j], ty[j - 1], 16);
-  tz[4] = ty[3] >> 16;
+  R1_ODD_ROW_TAPS(ty, tz);
   const uint32_t *mp = (const uint32_t *)(mid_s + (cl * W + c) * HM);
   int32_t pred[H];
   uint32_t pk[5];
@@ -136,10 +125,10 @@ __global__ __launch_bounds__(64) void k_mc_mfma(R1Plane ref, const R1McCand *__r
     int32_t a1 = PREP ? dot2_seed64(pk[0], tz[0]) : dot2_seed0(pk[0], tz[0]);
 #pragma unroll
     for (int k = 1; k < 4; k++)
-      a0 = __builtin_amdgcn_sdot2(__builtin_bit_cast(v2s, pk[k]), __builtin_bit_cast(v2s, ty[k]), a0, false);
+      a0 = __builtin_amdgcn_sdot2(__builtin_bit_cast(v2s_t, pk[k]), __builtin_bit_cast(v2s_t, ty[k]), a0, false);
 #pragma unroll
     for (int k = 1; k < 5; k++)
-      a1 = __builtin_amdgcn_sdot2(__builtin_bit_cast(v2s, pk[k]), __builtin_bit_cast(v2s, tz[k]), a1, false);
+      a1 = __builtin_amdgcn_sdot2(__builtin_bit_cast(v2s_t, pk[k]), __builtin_bit_cast(v2s_t, tz[k]), a1, false);
     if constexpr (PREP) {
       pred[2 * j] = a0 >> 7;
       pred[2 * j + 1] = a1 >> 7;

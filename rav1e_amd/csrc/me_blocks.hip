@@ -1,15 +1,10 @@
 // me_blocks.hip -- the RDO-time block search (r1_estimate_motion_batch): independent blocks of any BlockSize up to
 // 64x64 at full resolution, full-pel on the search engine of me_search.hpp, sub-pel on the fused candidate
-// kernel's machinery (cand_helpers.inc) or the generic put_8tap (mc_common.hpp).
+// kernel's machinery (cand_common.hpp) or the generic put_8tap (mc_common.hpp).
 #include "me_search.hpp"
-#include "dist_common.hpp"
-#include "mc_common.hpp"
-#include "tx_common.hpp"
+#include "cand_common.hpp"
 
 namespace {
-using r1tx::T;
-#include "mc_taps_packed.inc"
-#include "cand_helpers.inc"
 
 // One sub-pel candidate of a W x H block (W, H in {8, 16}) inside a 16-lane group, on the fused
 // candidate kernel's machinery (rdo_cand.hip): window staged by the group with one round trip,
@@ -21,26 +16,21 @@ template <int BPP, int W, int H, int BD, int NL = 16>
 __device__ __forceinline__ uint32_t subpel_group_dist(uint8_t *win, const R1Plane &ref, int x, int y, int cf,
                                                       int rf, int fm, int gl, int lane, const uint8_t *src /* LDS: the W x H source block, dense */,
                                                       bool satd, int bit_depth) {
-  constexpr int WS = (((W + 7) * BPP + 3) >> 2) << 2;
+  constexpr int WS = r1mc::window_stride(W, BPP);
   r1mc::stage_window_fast<BPP, BPP == 1 ? 0x80808080u : 0u, W, H, NL>(win, WS, ref, x, y, gl);
   __builtin_amdgcn_wave_barrier();
-  T v[H];
+  int32_t v[H];
 #pragma unroll
   for (int r = 0; r < H; r++) v[r] = 0;
   if (gl < W) {
     int32_t pred[H];
-    if constexpr (BPP == 1) {
-      const Taps8 tp = load_taps8<W, H>(cf, rf, fm, fm);
-      mc8_column_t<W, H, WS, false>(win, gl, tp, pred, taps_six(tp));
-    } else {
-      const Taps16 tp = load_taps16<W, H>(cf, rf, fm, fm);
-      mc16_column_t<W, H, WS, false>(win, gl, tp, bit_depth, pred, taps_six(tp));
-    }
+    const r1cand::Taps<BPP> tp = r1cand::load_taps<BPP, W, H>(cf, rf, fm, fm);
+    r1cand::mc_column_fast<BPP, W, H, WS, false>(win, gl, tp, bit_depth, pred, r1cand::taps_six(tp));
 #pragma unroll
     for (int r = 0; r < H; r++) v[r] = ld_px<BPP>(src + (r * W + gl) * BPP) - pred[r];
   }
   __builtin_amdgcn_wave_barrier();   // the window is rewritten by the next candidate of this group
-  if (satd) return satd_column<8, H, BD>(v, lane);
+  if (satd) return r1cand::satd_column<8, H, BD>(v, lane);
   uint32_t s = 0;
 #pragma unroll
   for (int r = 0; r < H; r++) s += (uint32_t)iabs32(v[r]);
@@ -160,7 +150,7 @@ struct WgBlock {
         return use_satd ? (s + 4u) >> 3 : s;
       }
     }
-    const int ws = (((w + 7) * BPP + 3) >> 2) << 2;
+    const int ws = r1mc::window_stride(w, BPP);
     r1mc::stage_window<BPP>(win, ws, ref, sx, sy, w, h, lane, 64);
     __builtin_amdgcn_wave_barrier();
     if (lane < w) {
@@ -214,7 +204,7 @@ __global__ __launch_bounds__(256) void k_me_blocks(R1MeJob job, R1MeParams p,
   TileView t{job.stats, job.prev, p.stats_cols, p.stats_rows, job.tile_x / MI, job.tile_y / MI,
              job.tile_w / MI, job.tile_h / MI};
   // LDS: source block | 4 x (window | prediction)
-  const int ws = (((w + 7) * BPP + 3) >> 2) << 2;
+  const int ws = r1mc::window_stride(w, BPP);
   const int org_bytes = (w * h * BPP + 15) & ~15, win_bytes = ((h + 7) * ws + 15) & ~15;
   uint8_t *org_l = smem;
   uint8_t *win = smem + org_bytes + wave * (win_bytes + org_bytes);
@@ -323,7 +313,7 @@ __global__ __launch_bounds__(256, 3) void k_me_blocks_small(R1MeJob job, R1MePar
                                                             int n, int max_w, int max_h, int use_satd,
                                                             int filter_mode,
                                                             R1MeResult *__restrict__ out) {
-  constexpr int WS_MAX = (((16 + 7) * BPP + 3) >> 2) << 2;
+  constexpr int WS_MAX = r1mc::window_stride(16, BPP);
   constexpr int GROUP_BYTES = ((23 * WS_MAX + 15) & ~15) + 16 * 16 * BPP;   // window + prediction
   __shared__ __attribute__((aligned(16))) uint8_t sh_grp[4][4][GROUP_BYTES];
   __shared__ int16_t sh_subsets[4][kSubsetWords];
@@ -393,7 +383,7 @@ __global__ __launch_bounds__(256, 3) void k_me_blocks_small(R1MeJob job, R1MePar
   const int g = lane >> 4, gl = lane & 15;
   uint8_t *win = sh_grp[wave][g];
   uint8_t *pred = win + ((23 * WS_MAX + 15) & ~15);
-  const int ws = (((w + 7) * BPP + 3) >> 2) << 2;
+  const int ws = r1mc::window_stride(w, BPP);
   int radius_log2 = 2;
   const int end_log2 = p.allow_hp ? 0 : 1;
   // blocks whose sides are 8 or 16: the source block waits in LDS for the whole search
@@ -525,7 +515,7 @@ extern "C" int r1_estimate_motion_batch(r1_ctx *ctx, const R1MeJob *tile, const 
     return R1_OK;
   }
   // LDS for the largest block of the batch: source + 4 x (window + prediction)
-  const int ws = (((max_w + 7) * bpp + 3) >> 2) << 2;
+  const int ws = r1mc::window_stride(max_w, bpp);
   const size_t blk = ((size_t)max_w * max_h * bpp + 15) & ~(size_t)15;
   const size_t lds = blk + 4 * ((((size_t)(max_h + 7) * ws + 15) & ~(size_t)15) + blk);
   R1_REQUIRE(lds <= kMeBlocksMaxLds);

@@ -22,7 +22,7 @@
 //     vertical 8 taps are 4 (even rows) or 5 (odd rows) v_dot2_i32_i16.
 //     All four (col_frac==0?, row_frac==0?) cases of mc.rs:264-352 go through
 //     this one code path: a 128-valued tap at phase 0 reproduces the copy and
-//     1-D paths bit for bit (see the derivation at mc8_column).
+//     1-D paths bit for bit (see the derivation at mc8_column_t, cand_common.hpp).
 //     The residual COLUMN stays in registers.  SAD is a lane sum.  SATD: the
 //     vertical Hadamard on 8 registers, the horizontal one across the 8
 //     neighbouring lanes with DPP (quad_perm / row_half_mirror) -- no LDS; blocks
@@ -40,6 +40,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "cand_common.hpp"
 #include "dist_common.hpp"
 #include "intra_pred_common.hpp"
 #include "itx_common.hpp"
@@ -86,10 +87,7 @@ static __device__ unsigned long long g_phase[4096][8];   // one per profiled sli
 // Experiment builds swap slice objects of the shipped library (tools/build_variant.sh, make prof).
 namespace {
 using r1tx::T;
-
-#include "mc_taps_packed.inc"
-
-#include "cand_helpers.inc"
+using r1cand::sad_u32;
 
 // QM: 0 = coefficients to HBM (headline), 1 = + quantizer, tx-domain distortion,
 // rate (N4), 2 = + quantizer, inverse transform, pixel-domain distortion.
@@ -123,14 +121,7 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
   TB *tkeep = COLSHARE ? (TB *)(smem + TKEEP_OFF) : tbuf;
 
   R1_PROF_INIT;
-  // Workgroup -> candidate group, XCD-aware.  The dispatcher deals workgroups round-robin over the 8 XCDs
-  // (workgroup i runs on XCD i % 8), each with its own L2.  Consecutive candidate groups belong to the same
-  // block (the K candidates of a block sit next to each other in the list and share the source block and
-  // most of their reference windows): in dispatch order they would land on 8 different L2s and each would
-  // fetch the window rows again.  So XCD x takes the x-th contiguous eighth of the list: workgroup i works on
-  // group (i % 8) * (grid / 8) + i / 8 (the host rounds the grid up to a multiple of 8; groups past the
-  // list end return).  Same-box A/B: profiles/r04_ab_notes.md, ab5.
-  const unsigned wg = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+  const unsigned wg = xcd_contiguous_wg();   // workgroup -> candidate group, XCD-aware (common.hpp)
   if ((long long)wg * NC >= (long long)n) return;
   const int lane = threadIdx.x;
   const int cl = lane / P, c = lane % P;
@@ -216,13 +207,10 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
   const bool from_ref = !INTRA && live && !qa.pred_in;   // !pred_in is wave-uniform: kernel argument
   r1mc::WindowStage<BPP, BPP == 1 ? 0x80808080u : 0u, W, H, P> wst;
   if (from_ref) wst.load(ref, cd.rx, cd.ry, c);
-  typename std::conditional<BPP == 1, Taps8, Taps16>::type tp = {};
-  if (from_ref) {
-    if constexpr (BPP == 1) tp = load_taps8<W, H>(cd.col_frac, cd.row_frac, cd.mode_x, cd.mode_y);
-    else tp = load_taps16<W, H>(cd.col_frac, cd.row_frac, cd.mode_x, cd.mode_y);
-  }
+  r1cand::Taps<BPP> tp = {};
+  if (from_ref) tp = r1cand::load_taps<BPP, W, H>(cd.col_frac, cd.row_frac, cd.mode_x, cd.mode_y);
   // every filter of the wave with zero outer taps (anything but SHARP): the short column filter
-  const bool six = taps_six(tp);
+  const bool six = r1cand::taps_six(tp);
   // A.2: into LDS
   auto stage_source = [&]() {
     if (live) {
@@ -325,7 +313,7 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
 #pragma unroll
         for (int r = 0; r < H; r++) pred[r] = pi[(size_t)r * W];
       } else {
-        mc8_column_t<W, H, WS, false>(win, c, tp, pred, six);
+        r1cand::mc_column_fast<BPP, W, H, WS, false>(win, c, tp, BD, pred, six);
       }
       if (pred_out && live_st) {
         uint8_t *pp = (uint8_t *)pred_out + (size_t)cand * W * H + c;
@@ -356,7 +344,7 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
 #pragma unroll
         for (int r = 0; r < H; r++) pred[r] = pi[(size_t)r * W];
       } else {
-        mc16_column_t<W, H, WS, false>(win, c, tp, BD, pred, six);
+        r1cand::mc_column_fast<BPP, W, H, WS, false>(win, c, tp, BD, pred, six);
       }
       if (pred_out && live_st) {
         uint16_t *pp = (uint16_t *)pred_out + (size_t)cand * W * H + c;
@@ -403,11 +391,11 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
     if constexpr (SATD_T) {
       uint32_t *tile = (uint32_t *)smem + cl * SATD_STRIDE;
       __syncthreads();   // every lane has read its window and source column
-      if (c < W) satd_tile_store<W, H>(v, tile + c);
+      if (c < W) r1cand::satd_tile_store<W, H>(v, tile + c);
       __syncthreads();
-      part = satd_tile_rows<(W < H ? W : H) / 16, P>(tile, c);   // the reads end before phase C's first barrier
+      part = r1cand::satd_tile_rows<(W < H ? W : H) / 16, P>(tile, c);   // the reads end before phase C's first barrier
     } else {
-      part = satd_column<TS, H, BD>(v, lane);
+      part = r1cand::satd_column<TS, H, BD>(v, lane);
     }
     const uint32_t s = group_sum<P>(part);
     constexpr int LN = TS == 4 ? 2 : 3;
@@ -873,8 +861,7 @@ int launch(const R1Plane &org, const R1Plane &ref, const R1RdoCand *cands, int n
            hipStream_t st, const RdoIntraArgs *ia = nullptr) {
   constexpr int NC = RdoCandPlan<BD, WL, HL, QM, MT, PS>::NC;
   typedef typename std::conditional<BD == 8, int16_t, int32_t>::type CT;
-  const unsigned groups = (unsigned)((n + NC - 1) / NC);
-  const unsigned grid = (groups + 7u) & ~7u;     // whole rounds over the 8 XCDs (see the kernel's `wg`)
+  const unsigned grid = xcd_grid((unsigned)((n + NC - 1) / NC));
   if constexpr (PS == 1)
     hipLaunchKernelGGL((k_rdo_cand<BD, WL, HL, CT, QM, MT, 1>), dim3(grid), dim3(64), 0, st,
                        org, ref, cands, n, sad, satd, (CT *)coeffs, pred, *qa, *ia);

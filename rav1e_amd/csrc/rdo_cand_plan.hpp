@@ -7,6 +7,8 @@
 #include <cstdint>
 #include <type_traits>
 
+#include "mc_window.hpp"
+
 // QM: 0 = coefficients to HBM (headline), 1 = + quantizer, tx-domain distortion,
 // rate (N4), 2 = + quantizer, inverse transform, pixel-domain distortion.
 // Waves per SIMD the register allocator is asked to make room for (0 = no request).  Only
@@ -88,7 +90,7 @@ struct RdoCandPlan {
   static constexpr int W = 1 << WL, H = 1 << HL;
   static constexpr int P = W > H ? W : H, NC = 64 / P;
   static constexpr int TS = (W < H ? W : H) == 4 ? 4 : 8;
-  static constexpr int WS = (((W + 7) * BPP + 3) >> 2) << 2;   // window row stride
+  static constexpr int WS = r1mc::window_stride(W, BPP);
   // INTRA: no reference window.  The candidate's edge arrays (raw edge + the four filter / upsample arrays, FL
   // entries each) take its place and may lie over the WHOLE allocation: the source block waits in registers until
   // the prediction is made (see SRC_LATE) and nothing else of the chain is alive yet.
@@ -163,7 +165,7 @@ struct RdoCandPlan {
       SRC_KEEP ? WIN_PAD : (SRC_LATE ? (WIN_PAD > SRC_BYTES ? WIN_PAD : SRC_BYTES) : WIN_PAD + SRC_BYTES);
   static constexpr int LDS_A0 = WS_BYTES > TXB_BYTES ? WS_BYTES : TXB_BYTES;
   static constexpr int LDS_A = LDS_A0 > IRB_BYTES ? LDS_A0 : IRB_BYTES;
-  // SATD_T: the horizontal half of the SATD in registers, through a tile in LDS (cand_helpers.inc, satd_tile_store /
+  // SATD_T: the horizontal half of the SATD in registers, through a tile in LDS (cand_common.hpp, satd_tile_store /
   // satd_tile_rows): H / 2 rows of W packed dwords per candidate, P dwords between candidates (the bare strides are
   // multiples of the bank count, as with QT_PAD).  The tile lies at the start of the work area, over the window and
   // the source block -- dead once the residual and the SAD are formed; a kept source block (SRC_KEEP) sits behind

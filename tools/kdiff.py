@@ -33,7 +33,7 @@ def kernels(lib):
             if name and t and not t.startswith("s_nop") and not t.startswith("s_code_end"):
                 t = re.sub(r"\s+", " ", t)
                 if t.startswith(("s_add_u32", "s_addc_u32")):    # pc-relative offsets of constant tables move with the object
-                    t = re.sub(r"0x[0-9a-f]{8}$", "PCREL", t)
+                    t = re.sub(r"0x[0-9a-f]+$", "PCREL", t)
                 out[name].append(t)
     return out
 

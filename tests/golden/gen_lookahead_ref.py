@@ -50,7 +50,14 @@ def inter_cost_tail_source():
             "  fi: &FrameInvariants<T>,\n) -> f64 {\n" + body + "}\n")
 
 
-def main():
+CASES = [(8, 72, 40, "noise"), (8, 76, 44, "smooth"), (10, 64, 48, "noise"), (10, 52, 36, "smooth"),
+         (12, 40, 40, "noise"), (8, 40, 24, "flat")]
+ADV_CASES = [(8, 48, 40, "noise"), (8, 56, 32, "smooth"), (10, 48, 40, "noise"),
+             (10, 40, 48, "smooth"), (12, 48, 32, "noise"), (8, 64, 64, "smooth")]
+
+
+def main(cases=CASES, adv_cases=ADV_CASES, seed=20260925, name="lookahead_ref.npz"):
+    """gen_lookahead_ref_12.py calls this with its own cases, seed and file name"""
     c = L.crate("api/lookahead.rs", "api/internal.rs", "dist.rs", "predict.rs", "partition.rs", "me.rs")
     c.load_text("<estimate_inter_costs, lines after compute_motion_vectors>", inter_cost_tail_source())
     intra = c.get("estimate_intra_costs")
@@ -60,7 +67,7 @@ def main():
     MEStats, MV = L.struct(c, "MEStats"), L.struct(c, "MotionVector")
     FrameME = L.struct(c, "FrameMEStats")
     bsize8 = L.enum(c, "BlockSize", "BLOCK_8X8")
-    rng = np.random.default_rng(20260925)
+    rng = np.random.default_rng(seed)
     out, keys = {}, []
 
     def frame_stats(mv, cols, rows):
@@ -73,8 +80,6 @@ def main():
                                                        normalized_sad=0)
         return FrameME(stats=R.RSlice(flat), cols=cols, rows=rows)
 
-    cases = [(8, 72, 40, "noise"), (8, 76, 44, "smooth"), (10, 64, 48, "noise"), (10, 52, 36, "smooth"),
-             (12, 40, 40, "noise"), (8, 40, 24, "flat")]
     for (bd, w, h, kind) in cases:
         g = L.pixel_type(bd)
         dt = L.np_dtype(bd)
@@ -143,8 +148,7 @@ def main():
     # wholly off-frame on each side), len in {1, 2, 7}.  The intra costs are GIVEN (large) so that
     # every block propagates; the inter costs come from get_satd inside the executed function.
     adv_keys = []
-    for ci, (bd, w, h, kind) in enumerate([(8, 48, 40, "noise"), (8, 56, 32, "smooth"), (10, 48, 40, "noise"),
-                                           (10, 40, 48, "smooth"), (12, 48, 32, "noise"), (8, 64, 64, "smooth")]):
+    for ci, (bd, w, h, kind) in enumerate(adv_cases):
         g = L.pixel_type(bd)
         dt = L.np_dtype(bd)
         mx = (1 << bd) - 1
@@ -202,7 +206,7 @@ def main():
             assert all(type(v) is R.F32 for v in acc), "an f32 operation escaped the F32 model"
             out["refimp_out_%d_%s" % (ln, k)] = np.array([float(v) for v in acc], np.float32).reshape(hb, wb)
     out["adv_keys"] = np.array(adv_keys)
-    L.save("lookahead_ref.npz", out)
+    L.save(name, out)
 
 
 if __name__ == "__main__":

@@ -31,6 +31,7 @@ def _case(ctx, oracle, bd, ts):
     src = O.HostPlane(96, 64, bd, rng=rng)
     drec = Plane.from_numpy(rec.data, rec.width, rec.height, bd, rec.xpad, rec.ypad)
     dsrc = Plane.from_numpy(src.data, src.width, src.height, bd, src.xpad, src.ypad)
+    assert bd != 12 or min(int(rec.view().max()), int(src.view().max())) > 1023   # 12-bit data, not 10
     hbd = int(bd > 8)
     dt = np.uint16 if hbd else np.uint8
     bxs, bys = np.array([0, w, 0]), np.array([0, 0, h])      # the origin, the top row, the left column
@@ -67,7 +68,7 @@ def _case(ctx, oracle, bd, ts):
 
 
 @pytest.mark.parametrize("ts", sorted(SIZES))
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 def test_predict_intra_ragged_last_wave(ctx, oracle, bd, ts):
     cs = _case(ctx, oracle, bd, ts)
     assert len(cs["ic"]) % (64 // SIZES[ts][0]) != 0
@@ -79,7 +80,7 @@ def test_predict_intra_ragged_last_wave(ctx, oracle, bd, ts):
 
 
 @pytest.mark.parametrize("ts", sorted(SIZES))
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 def test_intra_satd_three_blocks_per_wave(ctx, oracle, bd, ts):
     cs = _case(ctx, oracle, bd, ts)
     got = ctx.intra_satd_batch(cs["dsrc"], ts, cs["ic"], 13, cs["pos"], cs["edges"], cs["lens"])

@@ -780,15 +780,16 @@ def test_cfl_ac_and_alpha_search(ctx, oracle, bd, kinds):
 
 # ------------------------------------------------------------------ motion estimation
 @pytest.mark.parametrize("kinds", SWAP)
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 def test_motion_estimation(ctx, oracle, bd, kinds):
     """one 128 x 64 tile: the three pyramid levels of the source and of the reference in alternating kinds (the
     two planes of a level never share one), with the reference's padding (88 / 44 / 22); r1_estimate_tile_motion_batch
     at launch boundaries (launch_mode 1) and as the persistent launch (2), then r1_estimate_motion_batch"""
     from rav1e_amd.api import ME_RESULT, me_lambdas
-    from test_gpu_parity import _me_images, _me_stats_numpy, _me_stats_tensor
+    from test_gpu_parity import _me_images, _me_stats_numpy, _me_stats_tensor, uses_the_depth
     w, h = 128, 64
     org, ref = _me_images("smooth", w, h, bd, 7 * bd + w)
+    assert uses_the_depth(bd, org, ref)
     pads = (88, 44, 22)
     po = [LU.lay(p, kinds[l & 1], pads[l], pads[l]) for l, p in enumerate(O.me_pyramid(org, bd))]
     pr = [LU.lay(p, kinds[~l & 1], pads[l], pads[l]) for l, p in enumerate(O.me_pyramid(ref, bd))]
@@ -801,6 +802,7 @@ def test_motion_estimation(ctx, oracle, bd, kinds):
     lam = me_lambdas(30.0)
     want = init.copy()
     O.me_oracle(oracle, po, pr, w // 4, h // 4, (0, 0, w, h), bd, lam, want, prev)
+    assert (want != init).any()
     for mode in (1, 2):
         st = _me_stats_tensor(init)
         job = dict(org=dpo, ref=dpr, stats=st, prev=_me_stats_tensor(prev), tile=(0, 0, w, h))
@@ -824,4 +826,5 @@ def test_motion_estimation(ctx, oracle, bd, kinds):
                                         allow_hp=bool(hp)).cpu().numpy().view(ME_RESULT)
         bad = np.nonzero(got != wres)[0]
         assert len(bad) == 0, (bd, kinds, use_satd, fmode, c[bad[0]], got[bad[0]], wres[bad[0]])
+        assert not hp or (((wres["row"] | wres["col"]) & 7) != 0).any()      # the sub-pel diamond moved a block
     assert LU.guards_intact(*dpo, *dpr)

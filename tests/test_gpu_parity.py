@@ -31,6 +31,11 @@ def planes(bd, w=320, h=192, seed=0, pads=(88, 88)):
     return a, b
 
 
+def uses_the_depth(bd, *imgs):
+    """a 12-bit case says nothing on data that 10 bits hold: every image has a value above 1023"""
+    return bd != 12 or all(int(np.max(a)) > 1023 for a in imgs)
+
+
 def rand_dist_cands(rng, n, pw, ph, w, h, slack):
     c = np.zeros(n, O.DIST_CAND)
     c["ox"] = rng.integers(0, pw - w + 1, n)
@@ -635,11 +640,12 @@ def test_intra_edges_and_predict_vs_oracle(ctx, oracle, bd):
                 assert np.array_equal(got[i], out), (ts, i, int(pm[i]), int(angle[i]), int(ief[i]))
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 def test_cfl_ac_vs_oracle(ctx, oracle, bd):
     from rav1e_amd.api import CFL_AC_CAND
     rng = np.random.default_rng(77 + bd)
     hp = O.HostPlane(256, 128, bd, rng=rng)
+    assert uses_the_depth(bd, hp.view())
     dp = dev_plane(hp)
     hbd = int(bd > 8)
     for (bw, bh) in ((4, 4), (8, 8), (16, 16), (32, 32), (8, 16), (16, 8), (4, 16), (32, 8)):
@@ -749,7 +755,7 @@ def test_cdef_frame_plane_scratch_ring_reuse_and_regrowth():
         own.close()
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 def test_cdef_filter_block_vs_oracle(ctx, oracle, bd):
     """cdef_filter_block with every edge-flag combination, direction and tap parity."""
     from rav1e_amd.api import CDEF_BLOCK_CAND
@@ -758,6 +764,7 @@ def test_cdef_filter_block_vs_oracle(ctx, oracle, bd):
     img = np.clip(np.cumsum(rng.integers(-9, 10, (96, 128)), axis=1) + (1 << (bd - 1)), 0,
                   (1 << bd) - 1).astype(dt)
     hp, dp = _plane_from(img, bd)
+    assert uses_the_depth(bd, img)
     for (xdec, ydec) in ((0, 0), (1, 1), (1, 0)):
         xs, ys = 8 >> xdec, 8 >> ydec
         n = min(256, (128 // xs - 2) * (96 // ys - 2))
@@ -774,6 +781,7 @@ def test_cdef_filter_block_vs_oracle(ctx, oracle, bd):
         out_h, out_d = _plane_from(np.zeros_like(img), bd)
         ctx.cdef_filter_block_batch(dp, out_d, xdec, ydec, c)
         got = out_d.data.cpu().numpy().view(dt)[16:16 + 96, out_d.xorigin:out_d.xorigin + 128]
+        filtered = 0
         for i in range(n):
             want = np.zeros((ys, xs), dt)
             x, y = int(c["x"][i]), int(c["y"][i])
@@ -782,6 +790,8 @@ def test_cdef_filter_block_vs_oracle(ctx, oracle, bd):
                                          int(c["dir"][i]), int(c["damping"][i]), bd, xdec, ydec,
                                          int(c["edges"][i]), int(bd > 8))
             assert np.array_equal(got[y:y + ys, x:x + xs], want), (bd, xdec, ydec, i)
+            filtered += int(not np.array_equal(want, img[y:y + ys, x:x + xs]))
+        assert filtered, (bd, xdec, ydec)      # some block came out changed, not copied
 
 
 # ------------------------------------------- compat shims of the widened rows
@@ -852,7 +862,7 @@ def test_compat_shims_inverse_cdef_ipred(ctx, oracle):
 
 
 # --------------------------------------------------- lookahead cost maps (N1)
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 def test_lookahead_cost_maps(ctx, oracle, bd):
     """estimate_intra_costs / estimate_inter_costs / importance block difference
     for a whole frame vs the oracle's composition of get_intra_edges ->
@@ -866,6 +876,7 @@ def test_lookahead_cost_maps(ctx, oracle, bd):
     a.view()[:] = np.clip((np.sin(xx / 9.0) + np.cos(yy / 5.0)) * 60 * (1 << (bd - 8)) +
                           (1 << (bd - 1)) + rng.integers(-8, 9, (184, 328)), 0, (1 << bd) - 1)
     da, db = dev_plane(a), dev_plane(b)
+    assert uses_the_depth(bd, a.view(), b.view())
     hb, wb = 184 // 8, 328 // 8
     pa, pb = a.cstruct(), b.cstruct()
     want = np.zeros(hb * wb, np.uint32)
@@ -887,7 +898,7 @@ def test_lookahead_cost_maps(ctx, oracle, bd):
 
 
 # ------------------------ N4 (first step): quantize + tx-domain distortion + rate
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 def test_quantize_rdo_vs_oracle(ctx, oracle, bd):
     """r1_quantize_rdo_batch: eob / qcoeffs / rcoeffs as r1_quantize_batch, plus
     the transform-domain distortion of encode_tx_block and estimate_rate."""
@@ -903,6 +914,7 @@ def test_quantize_rdo_vs_oracle(ctx, oracle, bd):
                          (rng.random((n, full)) < 0.3), np.iinfo(ct).min, np.iinfo(ct).max).astype(ct)
             if ct == np.int16:
                 co[0, :8] = [32767, -32768, 30000, -30000, 1, -1, 0, 5]   # i32 wrap in c*c
+            co[1] = 0                                                     # a block that quantizes to nothing
             q = np.zeros((n, area), ct)
             r = np.zeros((n, area), ct)
             eobs = np.zeros(n, np.uint16)
@@ -913,6 +925,7 @@ def test_quantize_rdo_vs_oracle(ctx, oracle, bd):
                                                  O.ptr(rate)) == 0
             o = ctx.quantize_rdo_batch(_t(co), ts, 0, qi, bd, 0)
             assert np.array_equal(o["eobs"].cpu().numpy().view(np.uint16), eobs), (bd, ts, qi)
+            assert eobs[1] == 0 and (eobs != 0).any(), (bd, ts, qi)
             assert np.array_equal(o["qcoeffs"].cpu().numpy(), q), (bd, ts, qi)
             assert np.array_equal(o["rcoeffs"].cpu().numpy(), r), (bd, ts, qi)
             assert np.array_equal(o["tx_dist"].cpu().numpy().view(np.uint64), dist), (bd, ts, qi)
@@ -1020,15 +1033,16 @@ def _me_images(kind, w, h, bd, seed):
     return org, np.clip(ref, 0, (1 << bd) - 1)
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 @pytest.mark.parametrize("kind", ["noise", "smooth", "flat"])
 def test_estimate_tile_motion_vs_oracle(ctx, oracle, bd, kind):
     """r1_estimate_tile_motion_batch against oracle/me.c: frame sizes that are not
     multiples of 64 (cropped superblocks and blocks), previous-frame predictors,
-    8- and 10-bit, with and without the full-search stage."""
+    8-, 10- and 12-bit, with and without the full-search stage."""
     from rav1e_amd.api import me_lambdas
     for (w, h, full) in ((200, 136, 0), (320, 192, 0), (136, 72, 1)):
         org, ref = _me_images(kind, w, h, bd, 7 * bd + w)
+        assert uses_the_depth(bd, org, ref)
         po, pr = O.me_pyramid(org, bd), O.me_pyramid(ref, bd)
         rng = np.random.default_rng(w)
         prev = np.zeros((h // 4, w // 4), O.ME_STATS)
@@ -1043,6 +1057,7 @@ def test_estimate_tile_motion_vs_oracle(ctx, oracle, bd, kind):
         want = init.copy()
         O.me_oracle(oracle, po, pr, w // 4, h // 4, (0, 0, w, h), bd, lam, want, prev,
                     allow_full_search=full)
+        assert (want != init).any()
         st = _me_stats_tensor(init)
         ctx.estimate_tile_motion([dict(org=_me_dev_pyr(po), ref=_me_dev_pyr(pr), stats=st,
                                        prev=_me_stats_tensor(prev), tile=(0, 0, w, h))],
@@ -1116,7 +1131,7 @@ def test_estimate_tile_motion_from_concurrent_threads(ctx, oracle):
     assert not errors, errors
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 def test_estimate_motion_blocks_subpel_vs_oracle(ctx, oracle, bd):
     """r1_estimate_motion_batch (the RDO-time estimate_motion with pmv: full-pel from the
     tile's MEStats, SATD re-cost, sub-pel diamond through put_8tap) for every BlockSize up to
@@ -1125,6 +1140,7 @@ def test_estimate_motion_blocks_subpel_vs_oracle(ctx, oracle, bd):
     w, h = 320, 192
     org, ref = _me_images("smooth", w, h, bd, 21 + bd)
     ref = np.clip(ref + np.random.default_rng(5).integers(-6, 7, ref.shape), 0, (1 << bd) - 1)
+    assert uses_the_depth(bd, org, ref)
     po, pr = O.me_pyramid(org, bd), O.me_pyramid(ref, bd)
     lam = me_lambdas(25.0)
     stats = np.zeros((h // 4, w // 4), O.ME_STATS)
@@ -1146,13 +1162,16 @@ def test_estimate_motion_blocks_subpel_vs_oracle(ctx, oracle, bd):
         c["pmv"][i] = rng.integers(-40, 41, (2, 2))
     job = dict(org=_me_dev_pyr(po), ref=_me_dev_pyr(pr), stats=_me_stats_tensor(stats),
                prev=_me_stats_tensor(prev), tile=(0, 0, w, h))
+    fractional = 0          # results the sub-pel diamond moved off the full-pel grid
     for use_satd, mode, hp in ((1, 0, 1), (0, 0, 1), (1, 2, 0), (1, 1, 1), (0, 3, 0)):
         want = O.me_block_oracle(oracle, po, pr, w // 4, h // 4, (0, 0, w, h), bd, lam, stats, prev, c,
                                  use_satd=use_satd, filter_mode=mode, allow_hp=hp)
+        fractional += int((((want["row"] | want["col"]) & 7) != 0).sum()) if hp else 0
         got = ctx.estimate_motion_batch(job, c, w // 4, h // 4, bd, lam, use_satd=bool(use_satd),
                                         filter_mode=mode, allow_hp=bool(hp)).cpu().numpy().view(ME_RESULT)
         bad = np.nonzero(got != want)[0]
         assert len(bad) == 0, (bd, use_satd, mode, hp, c[bad[0]], got[bad[0]], want[bad[0]])
+    assert fractional > 0
     # a launch sized for 16x16 refuses the larger blocks (empty result), serves the rest
     got = ctx.estimate_motion_batch(job, c, w // 4, h // 4, bd, lam, max_w=16, max_h=16).cpu().numpy().view(ME_RESULT)
     big = (c["w"] > 16) | (c["h"] > 16)
@@ -1257,7 +1276,7 @@ def test_deblock_frame_vs_oracle(ctx, oracle, cfg):
 
 
 # ------------------------ N1: intra mode pre-screen in one launch
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 def test_intra_prescreen_vs_oracle(ctx, oracle, bd):
     """r1_intra_satd_batch: 13 luma modes per block from one edge set (get_intra_edges with
     IntraParam::None, as src/rdo.rs:1442-1458), SATD against the source; oracle = the reference's
@@ -1268,6 +1287,7 @@ def test_intra_prescreen_vs_oracle(ctx, oracle, bd):
     rec = O.HostPlane(192, 128, bd, rng=rng)
     srcp = O.HostPlane(192, 128, bd, rng=rng)
     drec, dsrc = dev_plane(rec), dev_plane(srcp)
+    assert uses_the_depth(bd, rec.view(), srcp.view())
     hbd = int(bd > 8)
     dt = np.uint16 if hbd else np.uint8
     MODES = list(range(13))                      # RAV1E_INTRA_MODES: DC .. PAETH
@@ -1410,13 +1430,15 @@ def test_quantizer_at_the_coefficient_range_limits(ctx, oracle, bd):
                 assert int(np.abs(wq).max()) > 0
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 def test_rdo_pred_cand_vs_oracle(ctx, oracle, bd):
     """r1_rdo_pred_cand_batch: the chains with the prediction taken from a dense buffer (intra
     predictions / compound averages): transform-domain and both pixel-domain distortions."""
     import ctypes as C
     a, _ = planes(bd, seed=90 + bd)
     da = dev_plane(a)
+    assert uses_the_depth(bd, a.view())
+    eob_zero = eob_some = 0
     rng = np.random.default_rng(970 + bd)
     ct = np.int16 if bd == 8 else np.int32
     dt = np.uint8 if bd == 8 else np.uint16
@@ -1450,6 +1472,8 @@ def test_rdo_pred_cand_vs_oracle(ctx, oracle, bd):
             assert np.array_equal(o["dist"].cpu().numpy().view(np.uint64), wdist), key
             if kind:
                 assert np.array_equal(o["rec"].cpu().numpy().view(dt), wrec), key
+            eob_zero, eob_some = eob_zero + int((weob == 0).sum()), eob_some + int((weob != 0).sum())
+    assert eob_zero and eob_some, (bd, eob_zero, eob_some)
 
 
 @pytest.mark.parametrize("bd", [8, 10, 12])
@@ -1826,7 +1850,7 @@ def test_activity_scales_vs_oracle(ctx, oracle, bd):
     assert np.array_equal(sc.cpu().numpy().view(np.uint32), wsc)
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 def test_cfl_alpha_search_vs_oracle(ctx, oracle, bd):
     """r1_cfl_alpha_search_batch (rdo_cfl_alpha): the oracle predicts UV_CFL_PRED for all 33
     alphas, takes the plain SSE over the visible area and replays the reference's selection."""
@@ -1839,6 +1863,7 @@ def test_cfl_alpha_search_vs_oracle(ctx, oracle, bd):
     rec = O.plane_from_image(np.clip(sub // 2 + rng.integers(0, 1 << (bd - 1), sub.shape), 0, (1 << bd) - 1), bd, 44, 44)
     src = O.plane_from_image(np.clip(sub * 3 // 4 + rng.integers(0, 1 << (bd - 2), sub.shape), 0, (1 << bd) - 1), bd, 44, 44)
     dl, dr, dsrc = dev_plane(luma), dev_plane(rec), dev_plane(src)
+    assert uses_the_depth(bd, luma.view(), rec.view(), src.view())
     hbd = int(bd > 8)
     dt = np.uint16 if hbd else np.uint8
     for ts in (0, 1, 2, 3, 7, 8):

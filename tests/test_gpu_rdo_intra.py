@@ -101,7 +101,7 @@ def make_case(rng, ctx, rec, drec, ts, n, group, chroma=False):
 
 
 def check_call(ctx, oracle, org, dorg, ts, bd, cs, group, mask, qi, kind, scales, dscales, xdec, ydec, full, key):
-    """one fused call against the two-launch device route and the oracle composition"""
+    """one fused call against the two-launch device route and the oracle composition; -> the oracle's eob"""
     import torch
     w, h = TX_DIMS[ts]
     n, nt = len(cs["ic"]), bin(mask).count("1")
@@ -166,6 +166,7 @@ def check_call(ctx, oracle, org, dorg, ts, bd, cs, group, mask, qi, kind, scales
             assert np.array_equal(o["rec"].cpu().numpy().view(dt), wrec), (key, "rec", "oracle")
         else:
             assert np.array_equal(o["est_rate"].cpu().numpy().view(np.uint64), wrate), (key, "est_rate", "oracle")
+    return weob
 
 
 def _planes(bd, seed, width=204, height=140):
@@ -218,22 +219,24 @@ def test_intra_cand_equals_two_launch_route_and_oracle(ctx, oracle, ts, bd):
             step += 1
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 def test_intra_cand_cfl_on_a_420_chroma_plane(ctx, oracle, bd):
     """UV_CFL_PRED with its AC blocks (candidate i uses block i) and DC_PRED on a 4:2:0 chroma plane, 8x8: kind 0 and
     the weighted SSE with the luma scale grid at xdec = ydec = 1"""
     ts = 1
     rec, org = _planes(bd, 5100 + bd, 100, 68)
     drec, dorg = _dev_plane(rec), _dev_plane(org)
-    rng = np.random.default_rng(61 + bd)
+    assert bd != 12 or min(int(rec.view().max()), int(org.view().max())) > 1023   # 12-bit data, not 10
+    rng = np.random.default_rng(61 + bd + (bd == 12))     # (73 draws no UV_CFL_PRED for the last call)
     scales = rng.integers(1 << 12, 1 << 16, ((2 * org.height + 23) // 8, (2 * org.width + 23) // 8)).astype(np.uint32)
     dscales = _t(scales.view(np.int32))
     for step, (n, group) in enumerate(((9, 1), (25, 5), (7, 1))):
         kind = (2, 0, 2)[step]
         cs = make_case(rng, ctx, rec, drec, ts, n, group, chroma=True)
         assert (cs["ic"]["mode"] == 13).any()
-        check_call(ctx, oracle, org, dorg, ts, bd, cs, group, ctx.tx_type_mask(ts, False), 90, kind, scales, dscales,
-                   1, 1, step != 2, ("cfl", bd, n, group, kind))
+        eob = check_call(ctx, oracle, org, dorg, ts, bd, cs, group, ctx.tx_type_mask(ts, False), 90, kind, scales,
+                         dscales, 1, 1, step != 2, ("cfl", bd, n, group, kind))
+        assert (eob != 0).any()
 
 
 def test_two_launch_route_scratch_ring_reuse_and_regrowth():

@@ -199,13 +199,14 @@ def test_reference_fixture_through_the_one_launch(ctx):
 
 
 @pytest.mark.parametrize("kind_of_layout", LU.KINDS)
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 def test_odd_and_tight_plane_layouts(ctx, oracle, kind_of_layout, bd):
     """planes whose rows start at odd element offsets / planes without a spare byte, `org` and `rec` in different
     layouts, 8 pixels of padding, blocks whole inside the frame (a tight plane has nothing behind its last row):
     outputs inside guard bytes, guard bytes around both planes intact, `rec` unchanged"""
     bw, bh, ts = 16, 16, 1
     rec0, org0 = _planes(bd, 7300 + bd, 76, 52)
+    assert bd != 12 or min(int(rec0.view().max()), int(org0.view().max())) > 1023   # 12-bit data, not 10
     other = LU.KINDS[1 - LU.KINDS.index(kind_of_layout)]
     rec, drec = LU.relayout(rec0, kind_of_layout, 8, 8)
     org, dorg = LU.relayout(org0, other, 8, 8)
@@ -213,11 +214,14 @@ def test_odd_and_tight_plane_layouts(ctx, oracle, kind_of_layout, bd):
     scales = rng.integers(1 << 12, 1 << 16, (8, 11)).astype(np.uint32)
     dscales = _t(scales.view(np.int32))
     before = drec.host().copy()
+    eobs = []
     for kind, tile in ((3, (0, 0, 76, 52)), (0, (4, 8, 72, 44))):
         cands = make_cands(rng, 9, bw, bh, 8, tile[2], tile[3], inside_only=True)
         got = one_launch(ctx, dorg, drec, tile, bw, bh, ts, cands, True, 0x203, 90, kind, dscales)
         want = SU.oracle_split(oracle, org, rec, tile, bw, bh, ts, cands, True, 0x203, 90, kind, scales)
         _same(got, want, list(got), (kind_of_layout, bd, kind), "oracle composition")
+        eobs.append(got["eob"].ravel())
+    assert (np.concatenate(eobs) != 0).any()
     assert LU.guards_intact(drec, dorg)
     assert np.array_equal(drec.host(), before), "rec was written"
 

@@ -1,6 +1,7 @@
 """The lookahead cost maps and the block-importance propagation of the oracle against
-tests/golden/lookahead_ref.npz -- vectors produced by executing the reference's own text
-(src/api/lookahead.rs:30-267, src/api/internal.rs:912-1068; tests/golden/gen_lookahead_ref.py)."""
+tests/golden/lookahead_ref.npz and lookahead_ref_12.npz (two more 12-bit frames) -- vectors
+produced by executing the reference's own text (src/api/lookahead.rs:30-267,
+src/api/internal.rs:912-1068; tests/golden/gen_lookahead_ref.py, gen_lookahead_ref_12.py)."""
 import ctypes as C
 import os
 
@@ -8,14 +9,15 @@ import numpy as np
 
 import oracle_lib as O
 
-GOLD = os.path.join(os.path.dirname(__file__), "golden", "lookahead_ref.npz")
+GOLDS = [os.path.join(os.path.dirname(__file__), "golden", f) for f in ("lookahead_ref.npz", "lookahead_ref_12.npz")]
 
 
-def cases():
-    G = np.load(GOLD)
-    for k in G["keys"]:
-        bd, w, h, _ = k.split("_")
-        yield G, str(k), int(bd), int(w), int(h)
+def cases(which="keys"):
+    for f in GOLDS:
+        G = np.load(f)
+        for k in G[which]:
+            bd, w, h, _ = k.split("_")
+            yield G, str(k), int(bd), int(w), int(h)
 
 
 def planes(G, k, bd):
@@ -50,18 +52,16 @@ def test_lookahead_maps_reproduce_the_executed_reference(oracle):
             want = G["refimp_out_%d_%s" % (ln, k)]
             assert np.array_equal(acc.view(np.uint32), want.view(np.uint32).ravel().reshape(acc.shape)), (k, ln)
             n += 1
-    assert n == 12
+    assert n == 16
+    assert sum(bd == 12 for _, _, bd, _, _ in cases()) == 3
 
 
 def test_update_block_importances_adversarial_positions(oracle):
     """the adversarial set (gen_lookahead_ref.py): reference positions on / either side of
     importance-block boundaries, negative positions (-1, -63, -64, -65, -127, -128), positions at and
     beyond the right / bottom edge, len in {1, 2, 7}; intra costs given, inter costs = get_satd"""
-    G = np.load(GOLD)
     n = 0
-    for k in G["adv_keys"]:
-        k = str(k)
-        bd, w, h = [int(v) for v in k.split("_")[:3]]
+    for G, k, bd, w, h in cases("adv_keys"):
         org, ref = planes(G, k, bd)
         po, pr = org.cstruct(), ref.cstruct()
         hb, wb = h // 8, w // 8
@@ -81,7 +81,7 @@ def test_update_block_importances_adversarial_positions(oracle):
             want = G["refimp_out_%d_%s" % (ln, k)]
             assert np.array_equal(acc.view(np.uint32), want.view(np.uint32).ravel().reshape(acc.shape)), (k, ln)
             n += 1
-    assert n == 18
+    assert n == 24
 
 
 def test_search_to_cost_to_importance_chain_reproduces_the_reference(oracle):

@@ -103,6 +103,10 @@ def test_full_search_never_worsens_the_first_pass(oracle):
     (136, 72, 8, "noise", None, True, 1, 1),          # cropped superblocks, full search stage
     (200, 136, 10, "smooth", None, True, 0, 0),       # 10-bit, quarter-pel rates
     (192, 128, 8, "flat", (64, 0, 128, 128), True, 1, 0),   # a tile inside the frame, many ties
+    # 12-bit: the two restatements agree before the device is compared with oracle/me.c there
+    (136, 72, 12, "noise", None, True, 1, 1),
+    (200, 136, 12, "smooth", None, True, 0, 0),
+    (192, 128, 12, "flat", (64, 0, 128, 128), True, 1, 0),
 ])
 def test_tile_motion_equals_the_independent_model(oracle, case):
     """oracle/me.c against tests/me_model.py: every MEStats entry (mv and normalised SAD) of the
@@ -181,7 +185,7 @@ def test_tile_motion_pattern_entries_against_the_model(oracle, shift):
     assert len(bad) == 0, (shift, len(bad), bad[:4], got[tuple(bad[0])], want[tuple(bad[0])])
 
 
-@pytest.mark.parametrize("cfg", [(8, 1, 1), (8, 0, 1), (10, 1, 0), (8, 1, 0)])
+@pytest.mark.parametrize("cfg", [(8, 1, 1), (8, 0, 1), (10, 1, 0), (8, 1, 0), (12, 1, 1), (12, 0, 1), (12, 1, 0)])
 def test_rdo_time_estimate_motion_equals_the_independent_model(oracle, cfg):
     """the RDO-time estimate_motion (predicted MVs in the rate, SATD re-cost, sub-pel diamond
     through put_8tap) of oracle/me.c against tests/me_model.py: mv, sad and cost of every block"""

@@ -1,6 +1,7 @@
-"""oracle/me.c against tests/golden/me_ref.npz: MEStats maps and RDO-time block searches
-produced by EXECUTING the reference's own src/me.rs text (tests/golden/gen_me_ref.py,
-tools/rustlite) -- the pin of the motion-estimation oracle to the reference."""
+"""oracle/me.c against tests/golden/me_ref.npz and me_ref_12.npz (the 12-bit case): MEStats maps
+and RDO-time block searches produced by EXECUTING the reference's own src/me.rs text
+(tests/golden/gen_me_ref.py, gen_me_ref_12.py, tools/rustlite) -- the pin of the
+motion-estimation oracle to the reference."""
 import os
 
 import numpy as np
@@ -9,8 +10,10 @@ import pytest
 import oracle_lib as O
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF = np.load(os.path.join(HERE, "golden", "me_ref.npz"))
-CASES = sorted(k[:-5] for k in REF.files if k.endswith("_meta"))
+# case names are unique across the two files: one table
+REF = {k: v for f in ("me_ref.npz", "me_ref_12.npz") for k, v in np.load(os.path.join(HERE, "golden", f)).items()}
+CASES = sorted(k[:-5] for k in REF if k.endswith("_meta"))
+assert "d0" in CASES and int(REF["d0_meta"][2]) == 12
 
 
 def load_case(name):
@@ -44,7 +47,7 @@ def test_tile_motion_equals_the_executed_reference(oracle, name):
         assert len(bad) == 0, (name, k, len(bad), bad[:4], got[tuple(bad[0])], want[tuple(bad[0])])
 
 
-@pytest.mark.parametrize("name", [n for n in CASES if n + "_blk" in REF.files])
+@pytest.mark.parametrize("name", [n for n in CASES if n + "_blk" in REF])
 def test_rdo_time_estimate_motion_equals_the_executed_reference(oracle, name):
     c = load_case(name)
     pyr, prev, stats = c["refs"][0]

@@ -464,7 +464,30 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
   // ---- C: column transform on the residual registers ----
   __syncthreads();  // every lane is done reading the window (MT: the previous type's last phase); LDS becomes buf
   const int tx_col = MT ? t0 : (QM != 0 && qa.tx_mask != 0 ? (int)__builtin_ctz(qa.tx_mask) : (int)cd.tx_type);
-  const bool any_ud = __any(live && r1tx::ud_flip(tx_col));
+  // TX_VOTE (rdo_tx_vote, rdo_cand_plan.hpp): the type comes from the descriptors, a per-lane value -- the 1-D kernel
+  // switches of phases C and D are lane-divergent branches then, paid by every wave in class decodes, exec
+  // bookkeeping and the copies that merge the arms with the identity's pass-through.  A mode-decision pass evaluates
+  // ONE type over many predictions, so the wave votes once: when all its candidates agree (every lane holds a
+  // descriptor: the dead slots of the last wave repeat a live candidate and agree by construction) the type goes
+  // through readfirstlane and the switch between the kernels is a scalar branch.  A wave of mixed types keeps the
+  // per-lane switch, and so does a wave of one type whose class in this pass is the identity (col_uni / row_uni): with
+  // no pass-through arm every arm of the scalar switch writes all its outputs and nothing is copied to merge them.
+  // Only the switch forks: the flip, the shifts and the tile stores around it are one code for both, or the values
+  // the fork's second arm reads stay live across its first (the scalar branch sits inside structurized control flow)
+  // and the 16x16 kernel loses a wave per SIMD (profiles/r16_txuniform_notes.md).
+  constexpr bool TX_VOTE = rdo_tx_vote(WL, HL, QM, MT, PS);
+  static_assert(!TX_VOTE || UNMASK, "the vote reads every lane's descriptor");
+  int tx_s = 0;
+  bool tx_uni = false, col_uni = false, row_uni = false;
+  if constexpr (TX_VOTE) {
+    tx_s = __builtin_amdgcn_readfirstlane(tx_col);
+    tx_uni = __all(tx_col == tx_s);
+    col_uni = tx_uni && r1tx::vtx_1d(tx_s) != 3;
+    row_uni = tx_uni && r1tx::htx_1d(tx_s) != 3;
+  }
+  bool any_ud;
+  if (TX_VOTE && tx_uni) any_ud = r1tx::ud_flip(tx_s);   // scalar
+  else any_ud = __any(live && r1tx::ud_flip(tx_col));
   if (col_live) {
     if (any_ud) {   // wave-uniform: skipped when no candidate of the wave flips
       const bool ud = r1tx::ud_flip(tx_col);
@@ -477,7 +500,8 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
     }
 #pragma unroll
     for (int r = 0; r < H; r++) v[r] = r1tx::shift_fwd_ct<SH0>(v[r]);
-    r1tx::fwd_1d_m24<H>(v, r1tx::vtx_1d(tx_col));
+    if (TX_VOTE && col_uni) r1tx::fwd_1d_m24_kernel<H>(v, r1tx::vtx_1d(tx_s));
+    else r1tx::fwd_1d_m24<H>(v, r1tx::vtx_1d(tx_col));
     if constexpr (!SPLIT_T) {
       const int cc = cl * W + (r1tx::lr_flip(tx_col) ? W - 1 - c : c);
 #pragma unroll
@@ -526,7 +550,9 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
 #pragma unroll
       for (int k = 0; k < W; k++) u[k] = tkeep[r * LSTRIDE + cl2 * W + k];
     }
-    r1tx::fwd_1d_m24<W>(u, r1tx::htx_1d(tt));
+    // the switch on the scalar or per lane, as in phase C (the left-right flip is the tile store's column)
+    if (TX_VOTE && row_uni) r1tx::fwd_1d_m24_kernel<W>(u, r1tx::htx_1d(tx_s));
+    else r1tx::fwd_1d_m24<W>(u, r1tx::htx_1d(tt));
 #pragma unroll
     for (int k = 0; k < W; k++) {
       u[k] = r1tx::shift_fwd_ct<SH2>(u[k]);

@@ -80,6 +80,18 @@ constexpr bool rdo_cand_instantiated(int bd, int wl, int hl, int qm, bool mt, in
   return !mt || (qm != 0 && rdo_type_fanout(wl, hl));
 }
 
+// Whether an instantiation votes on its wave's transform types before phase C and takes the switch between the 1-D
+// kernels as a scalar branch when they agree (TX_VOTE, rdo_cand_kernel.hpp).  Only where the type is a per-lane
+// value from the descriptors: the coefficient kernels (QM 0).  The quantizer chains take the type from a kernel
+// argument whenever the caller gives a mask, the type search (MT) and the intra prediction source always do; a
+// 64-point side admits only DCT_DCT.  Those instantiations keep their code.  So do the sizes with a 32-point side,
+// which has one kernel and the identity, nothing to switch between: with the vote the 8-bit 32x32 launch was not
+// faster (+0.2 %, inside the spread), the 16-bit 32x32 kernel, held at 80 VGPRs by rdo_waves_hint, spilled 20 B per
+// lane, and 8x32 / 32x8 / 16x32 / 32x16 lost one to three waves per SIMD (profiles/r16_txuniform_notes.md).
+constexpr bool rdo_tx_vote(int wl, int hl, int qm, bool mt, int ps) {
+  return qm == 0 && !mt && ps == 0 && wl <= 4 && hl <= 4;
+}
+
 // ---- one instantiation: geometry, choices, LDS layout ----
 // PS: where the prediction comes from -- 0 = put_8tap of the reference window (or the dense qa.pred_in buffer),
 // 1 = intra prediction from the candidate's edge set.  One wave per workgroup; a wave owns NC candidates.

@@ -166,6 +166,26 @@ __device__ __forceinline__ void fwd_1d_m24(T *c, int k) {
     m24::r1_fdct64(c);
   }
 }
+// ... for a class the caller knows to have a kernel (anything but the identity): every arm writes all of c, so a
+// switch on a wave-uniform `k` merges its arms without a copy (k_rdo_cand, TX_VOTE).  The switch is written out a
+// second time: the compiler does not carry a `k != 3` assumption through to the test above, and fwd_1d_m24 expressed
+// through this function changes the code of every kernel that calls it.
+template <int N>
+__device__ __forceinline__ void fwd_1d_m24_kernel(T *c, int k) {
+  if constexpr (N == 4) {
+    if (k == 0) m24::r1_fdct4(c);
+    else if (k == 4) m24::r1_fwht4(c);
+    else m24::r1_fdst_vii_4(c);
+  } else if constexpr (N == 8) {
+    if (k == 0) m24::r1_fdct8(c); else m24::r1_fdst8(c);
+  } else if constexpr (N == 16) {
+    if (k == 0) m24::r1_fdct16(c); else m24::r1_fdst16(c);
+  } else if constexpr (N == 32) {
+    m24::r1_fdct32(c);
+  } else {
+    m24::r1_fdct64(c);
+  }
+}
 
 // One 1-D forward transform of length N on a register array, class `k`
 // (0 DCT, 1/2 ADST (flip handled by the caller), 3 identity, 4 WHT).

@@ -122,8 +122,9 @@ const char *r1_last_error(void);
  * (r1_rdo_compound_cand_batch, R1CompoundCand) under version 7, as were the frame's scale maps and segmentation
  * inputs (r1_frame_scales, r1_scale_kmeans, r1_segmentation_from_centroids, r1_spatiotemporal_scale_batch) and the
  * intra candidate (r1_rdo_intra_cand_batch), the coefficient rate (r1_coeff_rate_batch, R1CoeffCdfs, R1TxbCtx), the
- * intra transform-split candidate (r1_rdo_intra_split_batch, R1IntraSplitCand) and the coefficient rate across a
- * block's transform blocks (r1_coeff_rate_chain_batch, R1TxbChainCtx). */
+ * intra transform-split candidate (r1_rdo_intra_split_batch, R1IntraSplitCand), the coefficient rate across a
+ * block's transform blocks (r1_coeff_rate_chain_batch, R1TxbChainCtx) and across its three planes on one writer
+ * (r1_coeff_rate_block_batch, R1BlockChainCtx, R1BlockRateTrial). */
 int r1_abi_version(void);
 
 /* ---- dist:: (reference: src/dist.rs get_sad 31, get_satd 156; dispatch
@@ -1238,8 +1239,9 @@ int r1_coeff_rate_batch(r1_ctx *ctx, const void *qcoeffs, int coeff_bytes, const
  * mi_h > clip_h4 -- gives the trial rate 0xFFFFFFFF and zero side outputs; nothing is read or written out of bounds.
  * `above` / `left` bytes hold what set_coeff_context stores (below 192); a sign field of 3 counts as no sign.
  * Every loop is bounded by ntx, the coded area, the four base-range rounds or the Golomb length.
- * OUT OF SCOPE: the chroma half of write_tx_blocks / write_tx_tree (other R1CoeffCdfs slices, U then V behind luma);
- * every non-coefficient symbol; exporting the adapted CDFs; making the serial range-coder chain itself faster. */
+ * The chroma half of write_tx_blocks / write_tx_tree (other R1CoeffCdfs slices, U then V behind luma on the same
+ * writer): r1_coeff_rate_block_batch below.
+ * OUT OF SCOPE: every non-coefficient symbol; exporting the adapted CDFs; making the serial range-coder chain itself faster. */
 typedef struct R1TxbChainCtx {          /* 40 bytes */
   uint8_t above[16];   /* above_coeff_context[0][bo.x + c], c < bw / 4: the state in front of the block */
   uint8_t left[16];    /* left_coeff_context[0][bo.y_in_sb() + r], r < bh / 4 */
@@ -1254,6 +1256,81 @@ int r1_coeff_rate_chain_batch(r1_ctx *ctx, const void *qcoeffs, int coeff_bytes,
                               int use_reduced_tx_set, const R1TxbChainCtx *chains, const R1CoeffCdfs *cdfs, int n_cdfs,
                               uint32_t *rate_out, uint32_t *txb_rate_out, uint8_t *cul_level_out, uint8_t *ctx_out,
                               void *stream);
+
+/* ---- the real coefficient rate of a whole block: luma, U, V on one writer (added under ABI 7): the mode decision
+ * (luma_chroma_mode_rdo, src/rdo.rs:855-945) makes a fresh WriterCounter per candidate, writes a handful of head symbols
+ * (partition, skip, segment, modes, angle deltas, CFL alphas, tx size) and ends in ONE write_tx_blocks (intra) or
+ * write_tx_tree (inter, skip = false) call with luma_only = false (src/encoder.rs:2202-2240): write_coeffs_lv_map over
+ * the block's luma transform blocks, then U's, then V's, on that same writer.  This call computes the rate of that
+ * coefficient part for every trial, behind the launches that made the coefficients, with no copy.
+ * The hand-over: the head symbols use CDFs the coefficients never touch, and for a counting writer tell_frac behind any
+ * continuation depends on the state in front through `rng` alone (total bits = a sum of per-symbol shifts plus a
+ * constant).  The host writes the head on its own counter and hands over the writer's rng; then
+ *     rate_out + (host tell_frac at the hand-over - tell_frac of the fresh counter)
+ * is the reference's number.  rng = 0x8000 is the fresh writer.
+ * Two snapshots per trial: luma and chroma rows of CDFContext are disjoint (indexed by plane_type; txb_skip is shared by
+ * txs_ctx, but luma reads rows 0-6 and chroma 7-12), so cdfs[cdf_sel] is the luma slice as r1_coeff_rate_chain_batch
+ * takes it and cdfs[cdf_sel_uv] the (txs_ctx(uv_tx_size), plane_type 1) slice; each is copied and adapts symbol by
+ * symbol, U adapts the second and V continues on it.  `cdfs` is never written.
+ *   grid:        luma ntx = (bw / tw) * (bh / th) in raster order, 1..16, as r1_coeff_rate_chain_batch.  Chroma:
+ *                uv_tx_size = largest_chroma_tx_size(bsize, xdec, ydec) and the grid of src/encoder.rs:2327-2338 /
+ *                2492-2505, integer divisions and the `== 0 -> 1` rule included (4x16 and 16x4 in 4:2:0 code NO chroma
+ *                transform block); ntx_uv <= 4.  (xdec, ydec): (1, 1), (1, 0) or (0, 0).
+ *   arrays:      transform block k of a trial's plane lies at first + k * step (dense coded-area blocks in qcoeffs_*, one
+ *                entry in eobs_*): step_y 1 reads what r1_rdo_intra_split_batch left, step_y nt what
+ *                r1_rdo_txsearch_batch left; several trials may name the same luma blocks.  n_txb_y / n_txb_uv: how
+ *                many transform blocks the luma arrays and EACH chroma array hold.  The four chroma arrays may all be
+ *                NULL when no trial has do_chroma.
+ *   trials[t]:   R1BlockRateTrial, device resident.  uv_tx_type is an input: whatever the launch that made the chroma
+ *                coefficients used (uv_intra_mode_to_tx_type_context or DCT_DCT for intra; tx_type.uv_inter(..), or
+ *                DCT_DCT when luma had no coefficient, for inter).  do_chroma: has_chroma(..) and not Cs400.
+ *   blocks[b]:   R1BlockChainCtx, device resident: R1TxbChainCtx widened to three planes.
+ * Per plane, per coded transform block what r1_coeff_rate_chain_batch does; for chroma: a transform block is coded iff
+ * its LUMA-unit origin lies inside mi_w / mi_h (encoder.rs:1441), get_txb_ctx takes the chroma arm (txb_skip_ctx =
+ * (top != 0) + (left != 0) + 10 when the plane's block has more pixels than the transform, else + 7), write_tx_type is
+ * not written, set_coeff_context covers the chroma transform's full span.
+ *   rate_out[t]:        tell_frac behind the last block minus tell_frac of the start state, 1/8 bit.
+ *   plane_rate_out (optional) [t * 3 + p]: the same per plane; the three sum to rate_out[t].
+ *   rng_out (optional) [t]: the writer's rng behind the last block.
+ *   cul_level_out (optional) [(t * 3 + p) * 16 + k]: per plane and transform block; 0 for a block that is not coded.
+ *   ctx_out (optional): 96 bytes per trial, R1BlockChainCtx.ctx behind the last block.
+ * A trial with do_chroma = 0 and rng = 0x8000 returns r1_coeff_rate_chain_batch's numbers.
+ * R1_EINVAL (what the host can see): a NULL required pointer (chroma arrays: all four or none), coeff_bytes not 2 / 4, a
+ * bad tx_size, bw / bh that is no block size up to 64x64 or that the subsampling does not admit, a transform that does
+ * not divide the block, ntx outside 1..16, (xdec, ydec) outside the three pairs, a step < 1, n_blocks < 1, n_cdfs
+ * outside 1..256, n_txb_* < 0.  Device-resident faults give that trial rate 0xFFFFFFFF and zero side outputs, with
+ * nothing read or written out of bounds: block >= n_blocks, tx_type outside the set of (tx_size, is_inter, reduced),
+ * do_chroma with a uv_tx_type the chroma size has no scan for (32-point sides: DCT_DCT and IDTX only) or, where the
+ * chroma grid is not empty, with NULL chroma arrays, a `first` whose last transform block lies beyond n_txb_*, an eob
+ * above the coded area in a coded transform block, y_mode >= 13, cdf_sel / cdf_sel_uv >= n_cdfs, rng < 0x8000, mi_w > clip_w4 or mi_h > clip_h4, a coded chroma
+ * transform block at or beyond clip_uv_w4 / clip_uv_h4.
+ * Every loop is bounded by ntx, the coded area, the four base-range rounds or the Golomb length; no spin-waits, no atomics.
+ * OUT OF SCOPE: the head symbols themselves (the host's dozen); exporting the adapted CDFs; skip = true (no coefficient
+ * is written); making the serial range-coder chain itself faster. */
+typedef struct R1BlockChainCtx {        /* 108 bytes */
+  uint8_t ctx[3][2][16];  /* [plane][0: above, 1: left][16]: above_coeff_context[p][(tx_bo.x >> xdec) + c] and
+                             left_coeff_context[p][(tx_bo.y_in_sb() >> ydec) + r] in front of the block, tx_bo = the
+                             plane's FIRST transform block: the block's offset, for chroma less the one-unit shift of a
+                             4-wide / 4-high block (encoder.rs:2365-2368) */
+  uint8_t mi_w, mi_h, clip_w4, clip_h4;   /* as R1TxbChainCtx */
+  uint8_t clip_uv_w4, clip_uv_h4;  /* min(255, (((fi.w_in_b - frame_bo.x) << 2) >> xdec) >> 2) for the first chroma
+                             transform block's frame_bo, same for h: frame_clipped_txw >> 2 of chroma transform block
+                             (bx, by) = min(uv_tw / 4, clip_uv_w4 - bx * uv_tw / 4) (encoder.rs:1561-1566) */
+  uint8_t y_mode, cdf_sel, cdf_sel_uv, reserved[3];
+} R1BlockChainCtx;
+typedef struct R1BlockRateTrial {       /* 24 bytes */
+  uint32_t first_y, first_u, first_v;   /* the trial's first transform block in qcoeffs_y / _u / _v and eobs_* */
+  uint32_t block;                       /* index into blocks */
+  uint16_t rng;                         /* the writer's rng in front: 0x8000..0xFFFF */
+  uint8_t tx_type, uv_tx_type, do_chroma, reserved[3];
+} R1BlockRateTrial;
+int r1_coeff_rate_block_batch(r1_ctx *ctx, const void *qcoeffs_y, const uint16_t *eobs_y, int n_txb_y, int step_y,
+                              const void *qcoeffs_u, const uint16_t *eobs_u, const void *qcoeffs_v,
+                              const uint16_t *eobs_v, int n_txb_uv, int step_uv, int coeff_bytes,
+                              const R1BlockRateTrial *trials, int n, int bw, int bh, int tx_size, int xdec, int ydec,
+                              int is_inter, int use_reduced_tx_set, const R1BlockChainCtx *blocks, int n_blocks,
+                              const R1CoeffCdfs *cdfs, int n_cdfs, uint32_t *rate_out, uint32_t *plane_rate_out,
+                              uint16_t *rng_out, uint8_t *cul_level_out, uint8_t *ctx_out, void *stream);
 
 /* ---- multi-GPU: the tile-boundary exchange and the reference-frame all-gather (RCCL over
  * xGMI), SURVEY.md 8(e).  One process (or host thread) per GPU, tile r on rank r.  Rendezvous:

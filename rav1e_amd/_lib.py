@@ -172,6 +172,8 @@ SYMBOLS = {
     "r1_coeff_rate_batch": (_i, [_vp, _vp, _i, _vp, _i, C.c_uint32, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "r1_coeff_rate_chain_batch": (_i, [_vp, _vp, _i, _vp, _i, C.c_uint32, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp,
                                        _vp, _vp, _vp]),
+    "r1_coeff_rate_block_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _i,
+                                       _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "r1_lrf_sgrproj_plane": (_i, [_vp, _PP, _PP, _PP, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "r1_sgrproj_solve_batch": (_i, [_vp, _PP, _PP, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "r1_lrf_search_batch": (_i, [_vp, _PP, _PP, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, C.c_uint32, _vp, _vp, _vp, _vp]),

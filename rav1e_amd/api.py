@@ -13,7 +13,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .types import COEFF_CDFS, COEFF_RATE_INVALID, TX_DIMS, TXB_CHAIN_CTX, TXB_CTX, TxSize, valid_av1_transform  # noqa: F401
+from .types import (BLOCK_CHAIN_CTX, BLOCK_RATE_TRIAL, COEFF_CDFS, COEFF_RATE_INVALID, TX_DIMS, TXB_CHAIN_CTX, TXB_CTX,  # noqa: F401
+                    TxSize, valid_av1_transform)
 
 DIST_CAND = np.dtype([("ox", "<i2"), ("oy", "<i2"), ("rx", "<i2"), ("ry", "<i2")])
 MC_CAND = np.dtype([("rx", "<i2"), ("ry", "<i2"), ("col_frac", "u1"), ("row_frac", "u1"),
@@ -1126,6 +1127,58 @@ class Context:
             int(tx_size), int(order), int(bool(is_inter)), int(bool(use_reduced_tx_set)), dch.data_ptr(),
             dcdf.data_ptr(), n_cdfs, ptr["rate"], ptr["txb_rate"], ptr["cul_level"], ptr["ctx"], _stream_ptr()),
             "r1_coeff_rate_chain_batch")
+        return o
+
+    def coeff_rate_block_batch(self, qcoeffs_y, eobs_y, step_y, chroma, step_uv, trials, bw, bh, tx_size, xdec, ydec,
+                               is_inter, blocks, cdfs, use_reduced_tx_set=False, want_plane_rate=True, want_rng=True,
+                               want_cul_level=True, want_ctx=True, outs=None):
+        """r1_coeff_rate_block_batch: the real coefficient rate of a whole block per trial -- write_coeffs_lv_map over
+        the luma transform blocks, then U's, then V's, on ONE counter that starts at the trial's handed-over rng, as
+        write_tx_blocks / write_tx_tree with luma_only = false code them behind the head symbols of
+        luma_chroma_mode_rdo (src/rdo.rs:855-945, src/encoder.rs:2202-2240).
+        qcoeffs_y / eobs_y: the int16 / int32 and 2-byte device tensors of luma transform blocks a candidate call
+        wrote; transform block k of a trial lies at first_y + k * step_y.  chroma: None (no trial has do_chroma) or
+        (qcoeffs_u, eobs_u, qcoeffs_v, eobs_v), all of the chroma transform size and as many blocks each, at
+        first_u / first_v + k * step_uv.  trials: n BLOCK_RATE_TRIAL (rdo_glue.block_rate_trial); blocks:
+        BLOCK_CHAIN_CTX (rdo_glue.block_chain_ctx); cdfs: COEFF_CDFS, the luma and chroma slices -- each a NumPy array
+        or a uint8 device tensor of the struct's bytes.
+        -> {"rate": (n,) int32 holding uint32 1/8 bits (COEFF_RATE_INVALID for a trial with out-of-range device
+        inputs), "plane_rate": (n, 3) int32, "rng": (n,) int16 holding uint16, "cul_level": (n, 3, 16) uint8,
+        "ctx": (n, 3, 2, 16) uint8}; the four side outputs are optional."""
+        from . import rdo_glue
+        tw, th = TxSize(tx_size).dims
+        assert qcoeffs_y.is_cuda and qcoeffs_y.is_contiguous() and qcoeffs_y.dtype in (torch.int16, torch.int32)
+        assert eobs_y.is_cuda and eobs_y.is_contiguous() and eobs_y.element_size() == 2
+        area = min(tw, 32) * min(th, 32)
+        assert qcoeffs_y.numel() == eobs_y.numel() * area, (qcoeffs_y.numel(), eobs_y.numel(), area)
+        uv_ptrs, n_uv = [None] * 4, 0
+        if chroma is not None:
+            qu, eu, qv, ev = chroma
+            uw, uh = TxSize(rdo_glue.largest_chroma_tx_size(rdo_glue.block_size(bw, bh), xdec, ydec)).dims
+            for q, e in ((qu, eu), (qv, ev)):
+                assert q.is_cuda and q.is_contiguous() and q.dtype == qcoeffs_y.dtype
+                assert e.is_cuda and e.is_contiguous() and e.element_size() == 2
+                assert q.numel() == e.numel() * uw * uh and e.numel() == eu.numel(), (q.numel(), e.numel(), uw, uh)
+            uv_ptrs, n_uv = [t.data_ptr() for t in (qu, eu, qv, ev)], eu.numel()
+        dtr, n = _dev_cands(trials, BLOCK_RATE_TRIAL)
+        dbl, n_blocks = _dev_cands(blocks, BLOCK_CHAIN_CTX)
+        dcdf, n_cdfs = _dev_cands(cdfs, COEFF_CDFS)
+        dev = qcoeffs_y.device
+        o = dict(outs) if outs else {}
+        spec = {"rate": (True, (n,), torch.int32), "plane_rate": (want_plane_rate, (n, 3), torch.int32),
+                "rng": (want_rng, (n,), torch.int16), "cul_level": (want_cul_level, (n, 3, 16), torch.uint8),
+                "ctx": (want_ctx, (n, 3, 2, 16), torch.uint8)}
+        ptr = {}
+        for k, (want, shape, dtype) in spec.items():
+            if want and k not in o:
+                o[k] = torch.empty(shape, dtype=dtype, device=dev)
+            ptr[k] = o[k].data_ptr() if want else None
+        self._check(self.lib.r1_coeff_rate_block_batch(
+            self.h, qcoeffs_y.data_ptr(), eobs_y.data_ptr(), eobs_y.numel(), int(step_y), *uv_ptrs, n_uv, int(step_uv),
+            qcoeffs_y.element_size(), dtr.data_ptr(), n, int(bw), int(bh), int(tx_size), int(xdec), int(ydec),
+            int(bool(is_inter)), int(bool(use_reduced_tx_set)), dbl.data_ptr(), n_blocks, dcdf.data_ptr(), n_cdfs,
+            ptr["rate"], ptr["plane_rate"], ptr["rng"], ptr["cul_level"], ptr["ctx"], _stream_ptr()),
+            "r1_coeff_rate_block_batch")
         return o
 
     # ---- lrf:: ----

@@ -5,6 +5,10 @@
 // r1_coeff_rate_chain_batch: the same over the luma transform blocks of a block in raster order, as rdo_tx_size_type
 // measures a transform depth (src/rdo.rs:725-802): one counter, one adapting CDF copy and the block's 32 neighbour
 // context bytes carried from transform block to transform block (k_coeff_rate_chain, below the block body).
+// r1_coeff_rate_block_batch: the same over the luma, U and V transform blocks of a block, as write_tx_blocks /
+// write_tx_tree code them with luma_only = false behind the head symbols of the mode decision (src/rdo.rs:855-945,
+// src/encoder.rs:2202-2240): one counter that starts at a handed-over rng, the luma snapshot and then the chroma one in
+// the adapting copy, 96 context bytes (k_coeff_rate_block, behind the chain).
 //
 // One wave per slot, four slots per workgroup.  Inside a slot, per transform block (txb_rate, stated once):
 //  A  (parallel over the coded area) txb_init_levels: min(|c|, 127), transposed, stride H + TX_PAD_HOR, in LDS.
@@ -509,11 +513,210 @@ __global__ __launch_bounds__(256) void k_coeff_rate_chain(const ChainArgs c) {
   if (lane == 0) a.rate[trial] = w.tell_frac() - tell0;
   if (c.ctx_out && lane < 32) c.ctx_out[(size_t)trial * 32 + lane] = nb[lane];
 }
+
+// ---- the whole block: luma, then U, then V on one counter that starts at a handed-over rng (r1_coeff_rate_block_batch)
+struct PlaneArgs {             // one plane's arrays and transform-block grid
+  const void *qc;
+  const uint16_t *eobs;
+  int n_txb, step;             // transform blocks in the arrays; block k of a trial lies at first + k * step
+  int ntx, gw, tw4, th4;       // the grid in the plane's 4x4 units, as ChainArgs (chroma: encoder.rs:2327-2338, 2492-2505;
+                               // ntx 0..4, gw >= 1)
+  int xdec, ydec, adj_x, adj_y;   // luma-unit origin of block (bx, by) = ((bx * tw4) << xdec) - adj_x: the subsampling and
+                               // the one-unit shift of a 4-wide / 4-high block (encoder.rs:2365-2368); luma: all 0
+};
+struct BlockArgs {
+  RateArgs r[2];               // by plane type; .cul = 48 bytes per trial, type[] = identity, r[0].n_slots = trials;
+                               // .qc, .eobs, .ctxs, .nt are unused
+  PlaneArgs pl[3];
+  const R1BlockRateTrial *trials;
+  const R1BlockChainCtx *blocks;
+  uint32_t *plane_rate;        // optional
+  uint16_t *rng_out;           // optional
+  uint8_t *ctx_out;            // optional
+  uint32_t mask[2];            // the types the luma set / the chroma size's scans admit
+  int n_blocks;
+  int uv_skip_off;             // 10 when the plane's block has more pixels than the chroma transform, else 7
+};
+static_assert(sizeof(R1BlockChainCtx) == 108 && sizeof(R1BlockRateTrial) == 24, "ABI layout");
+
+// One wave per trial, four trials per workgroup, as k_coeff_rate_chain and on the same per-block body.  The wave's LDS
+// CDF copy and the lanes' coeff_base / coeff_br rows hold the luma snapshot for the luma chain and are overwritten with
+// the chroma snapshot in front of U; V continues on what U left.  The 96 context bytes live in LDS, 32 per plane.
+// The loops are bounded by three planes and ntx <= 16.
+template <typename CT>
+__global__ __launch_bounds__(256) void k_coeff_rate_block(const BlockArgs c) {
+  R1_RATE_LDS;
+  __shared__ __attribute__((aligned(16))) R1CoeffCdfs s_cdf[4];
+  __shared__ uint8_t s_nb[4][96];      // [plane]: above[16], left[16]
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int trial = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + wave);
+  if (trial >= c.r[0].n_slots) return;
+  const R1BlockRateTrial *tr = c.trials + trial;
+  const uint32_t *first = &tr->first_y;      // first_y, first_u, first_v
+  const uint32_t bi = (uint32_t)__builtin_amdgcn_readfirstlane((int)tr->block);
+  const uint32_t rng0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)tr->rng);
+  const int np = __builtin_amdgcn_readfirstlane((int)tr->do_chroma) != 0 ? 3 : 1;
+  const uint8_t *chb = (const uint8_t *)(c.blocks + (bi < (uint32_t)c.n_blocks ? bi : 0));   // n_blocks >= 1
+  const int mi_w = __builtin_amdgcn_readfirstlane((int)chb[96]), mi_h = __builtin_amdgcn_readfirstlane((int)chb[97]);
+  const int y_mode = __builtin_amdgcn_readfirstlane((int)chb[102]), sel = __builtin_amdgcn_readfirstlane((int)chb[103]);
+  const int sel_uv = __builtin_amdgcn_readfirstlane((int)chb[104]);
+  // whether the loop codes transform block k of a plane (encoder.rs:1441, 2282, 2446: the LUMA-unit origin against the
+  // tile grid), and its origin in the plane's 4x4 units
+  auto coded = [mi_w, mi_h](const PlaneArgs &g, int k, int &x4, int &y4) -> bool {
+    const int by = k / g.gw, bx = k - by * g.gw;
+    x4 = bx * g.tw4, y4 = by * g.th4;
+    return (x4 << g.xdec) - g.adj_x < mi_w && (y4 << g.ydec) - g.adj_y < mi_h;
+  };
+  {
+    // device-resident data the host cannot see: lane k looks at transform block k of every plane
+    bool bad = bi >= (uint32_t)c.n_blocks || rng0 < 0x8000u || y_mode >= R1_INTRA_MODES || sel >= c.r[0].n_cdfs ||
+               mi_w > (int)chb[98] || mi_h > (int)chb[99] || (np == 3 && sel_uv >= c.r[0].n_cdfs);
+    for (int p = 0; p < np; p++) {
+      const PlaneArgs &g = c.pl[p];
+      const int tt = p ? tr->uv_tx_type : tr->tx_type;
+      if (tt >= 16 || !((c.mask[p != 0] >> (tt & 15)) & 1)) bad = true;
+      if (g.ntx == 0 || bad) continue;
+      if (g.qc == nullptr) {     // chroma arrays the call left out
+        bad = true;
+        continue;
+      }
+      const uint32_t f = first[p];
+      if ((uint64_t)f + (uint64_t)(g.ntx - 1) * (uint32_t)g.step >= (uint64_t)g.n_txb) {
+        bad = true;
+        continue;
+      }
+      int x4, y4;      // the read is inside n_txb by the test above
+      if (lane < g.ntx && coded(g, lane, x4, y4)) {
+        if ((int)g.eobs[(size_t)f + (size_t)lane * g.step] > c.r[p != 0].area) bad = true;
+        if (p && ((int)chb[100] - x4 < 1 || (int)chb[101] - y4 < 1)) bad = true;
+      }
+    }
+    if (__ballot(bad) != 0) {
+      if (lane == 0) {
+        c.r[0].rate[trial] = 0xFFFFFFFFu;
+        if (c.rng_out) c.rng_out[trial] = 0;
+      }
+      if (c.plane_rate && lane < 3) c.plane_rate[(size_t)trial * 3 + lane] = 0;
+      if (c.r[0].cul && lane < 48) c.r[0].cul[(size_t)trial * 48 + lane] = 0;
+      if (c.ctx_out)
+        for (int e = lane; e < 96; e += 64) c.ctx_out[(size_t)trial * 96 + e] = 0;
+      return;
+    }
+  }
+  R1CoeffCdfs *cdf = &s_cdf[wave];
+  for (int e = lane; e < 96; e += 64) s_nb[wave][e] = chb[e];
+  LaneRow row;
+  Counter w;
+  w.rng = rng0;
+  const uint32_t tell0 = w.tell_frac();
+  uint32_t tell_p = tell0;
+  const WaveLds lds{s_lv[wave], s_tok[wave], s_off[wave], s_sym[wave]};
+  for (int p = 0; p < np; p++) {
+    const RateArgs &a = c.r[p != 0];
+    const PlaneArgs &g = c.pl[p];
+    if (p < 2) {    // the plane type's snapshot into the LDS copy and the lanes' rows; in front of U every lane is behind
+                    // its last read of the luma copy (the barriers of txb_rate)
+      const R1CoeffCdfs *snap = a.cdfs + (p ? sel_uv : sel);
+      for (int e = lane; e < (int)(sizeof(R1CoeffCdfs) / 4); e += 64) ((uint32_t *)cdf)[e] = ((const uint32_t *)snap)[e];
+      row.load(snap, lane);
+      wave_sync();
+    }
+    const int ntx = g.ntx, tw4 = g.tw4, th4 = g.th4;
+    const int cw4 = __builtin_amdgcn_readfirstlane((int)chb[p ? 100 : 98]), ch4 = __builtin_amdgcn_readfirstlane((int)chb[p ? 101 : 99]);
+    const uint32_t f = (uint32_t)__builtin_amdgcn_readfirstlane((int)first[p]);
+    const int j = __builtin_amdgcn_readfirstlane((int)(p ? tr->uv_tx_type : tr->tx_type));
+    uint8_t *nb = s_nb[wave] + p * 32;
+    uint8_t *cul_out = a.cul ? a.cul + (size_t)trial * 48 + p * 16 : nullptr;
+    for (int k = 0; k < ntx; k++) {
+      int x4, y4;
+      if (!coded(g, k, x4, y4)) {
+        if (lane == 0 && cul_out) cul_out[k] = 0;
+        continue;
+      }
+      const size_t idx = (size_t)f + (size_t)k * g.step;
+      const int eob = __builtin_amdgcn_readfirstlane((int)g.eobs[idx]);
+      const CT *qc = (const CT *)g.qc + idx * (size_t)a.area;
+      // get_txb_ctx (block_unit.rs:442-526) over the frame-clipped span (encoder.rs:1561-1566), >= 1 by the tests above
+      const int sw = tw4 < cw4 - x4 ? tw4 : cw4 - x4, sh = th4 < ch4 - y4 ? th4 : ch4 - y4;
+      int dc_sign = 0;
+      uint32_t top = 0, left = 0;
+      for (int i = 0; i < sw; i++) {
+        const uint32_t v = nb[x4 + i];
+        top |= v;
+        dc_sign += (v >> 6) == 1 ? -1 : ((v >> 6) == 2 ? 1 : 0);
+      }
+      for (int i = 0; i < sh; i++) {
+        const uint32_t v = nb[16 + y4 + i];
+        left |= v;
+        dc_sign += (v >> 6) == 1 ? -1 : ((v >> 6) == 2 ? 1 : 0);
+      }
+      const int sign_ctx = dc_sign == 0 ? 0 : (dc_sign < 0 ? 1 : 2);
+      int skip_ctx = 0;
+      if (p) {               // the chroma arm: the whole bytes, sign bits included
+        skip_ctx = (int)(top != 0) + (int)(left != 0) + c.uv_skip_off;
+      } else if (ntx > 1) {  // plane_bsize != tx_size.block_size(): skip_contexts[min][max]
+        top &= 63, left &= 63;
+        const uint32_t mx = (top | left) < 4 ? (top | left) : 4, lo = top < left ? top : left, mn = lo < 4 ? lo : 4;
+        skip_ctx = mx == 0 ? 1 : (mn == 0 ? 2 + (mx > 3) : (mx <= 3 ? 4 : (mn <= 3 ? 5 : 6)));
+      }
+      uint32_t sum, cul = 0;
+      if (txb_rate<CT, true>(a, w, cdf, row, qc, eob, skip_ctx, sign_ctx, y_mode, j, lane, lds, sum))
+        cul = cul_level(sum, (int32_t)qc[0]);
+      // set_coeff_context over the transform's full span (block_unit.rs:333-347)
+      if (lane < 16 ? (lane >= x4 && lane < x4 + tw4) : (lane < 32 && lane - 16 >= y4 && lane - 16 < y4 + th4))
+        nb[lane] = (uint8_t)cul;
+      wave_sync();
+      if (lane == 0 && cul_out) cul_out[k] = (uint8_t)cul;
+    }
+    if (cul_out && lane >= ntx && lane < 16) cul_out[lane] = 0;    // the entries no transform block stands for
+    const uint32_t t = w.tell_frac();
+    if (lane == 0 && c.plane_rate) c.plane_rate[(size_t)trial * 3 + p] = t - tell_p;
+    tell_p = t;
+  }
+  if (lane == 0) {
+    c.r[0].rate[trial] = tell_p - tell0;
+    if (c.rng_out) c.rng_out[trial] = (uint16_t)w.rng;
+  }
+  if (np == 1) {
+    if (c.plane_rate && lane >= 1 && lane < 3) c.plane_rate[(size_t)trial * 3 + lane] = 0;
+    if (c.r[0].cul && lane >= 16 && lane < 48) c.r[0].cul[(size_t)trial * 48 + lane] = 0;
+  }
+  if (c.ctx_out)
+    for (int e = lane; e < 96; e += 64) c.ctx_out[(size_t)trial * 96 + e] = s_nb[wave][e];
+}
 #undef R1_RATE_LDS
 }  // namespace
 
-// The checks and the launch arguments both entry points share: what the transform size, the type mask and the set
-// decide.  `per_block`: slots per candidate beyond the types (1, or the chain's ntx) for the 2^31 bound.
+// num_tx_set / av1_tx_ind (transform_unit.rs:36, 51-58), rows in TxSet order; the set from the mask of its types
+static const uint8_t kNumTxSet[6] = {1, 2, 5, 7, 12, 16};
+static const uint32_t kSetMask[6] = {0x0001, 0x0201, 0x020F, 0x0E0F, 0x0FFF, 0xFFFF};
+static const uint8_t kTxInd[6][16] = {{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0},
+                                      {1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0},
+                                      {1, 3, 4, 2, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0},
+                                      {1, 5, 6, 4, 0, 0, 0, 0, 0, 0, 2, 3, 0, 0, 0, 0},
+                                      {3, 4, 5, 8, 6, 7, 9, 10, 11, 0, 1, 2, 0, 0, 0, 0},
+                                      {7, 8, 9, 12, 10, 11, 13, 14, 15, 0, 1, 2, 3, 4, 5, 6}};
+
+// What the transform size and the set decide of the launch arguments (tx_size is valid, the flags are 0 / 1) -> the set
+static int rate_shape(r1_ctx *ctx, int tx_size, int plane, int is_inter, int use_reduced_tx_set, RateArgs &a) {
+  const uint32_t allowed = r1_tx_type_mask(tx_size, is_inter, use_reduced_tx_set, 0);
+  int set = 0;
+  while (kSetMask[set] != allowed) set++;
+  const int wl = r1tx::kTxWLog2[tx_size], hl = r1tx::kTxHLog2[tx_size];
+  for (int k = 0; k < 3; k++) a.scan[k] = ctx->scan_dev + ctx->scan_off[tx_size][k];
+  a.plane = plane;
+  a.w_coded = r1q::coded_dim(wl);
+  a.hl = r1_ilog2(r1q::coded_dim(hl));
+  a.area = a.w_coded << a.hl;
+  a.shape = wl < hl ? 1 : (wl > hl ? 2 : 0);
+  a.eob_flag_n = 5 + (wl + hl - 4 < 6 ? wl + hl - 4 : 6);   // eob_multi_size = area_log2 - 4; `_ =>`: eob_flag_cdf1024
+  a.tx_n = kNumTxSet[set] > 1 ? kNumTxSet[set] : 0;
+  a.is_inter = is_inter;
+  return set;
+}
+
+// The checks and the launch arguments the slot and chain entry points share: what the transform size, the type mask and
+// the set decide.  `per_block`: slots per candidate beyond the types (1, or the chain's ntx) for the 2^31 bound.
 static int rate_args(r1_ctx *ctx, const void *qcoeffs, int coeff_bytes, const uint16_t *eobs, int n, uint32_t tx_type_mask,
                      int tx_size, int plane, int is_inter, int use_reduced_tx_set, const R1CoeffCdfs *cdfs, int n_cdfs,
                      uint32_t *rate_out, uint8_t *cul_level_out, int per_block, RateArgs &a) {
@@ -527,31 +730,12 @@ static int rate_args(r1_ctx *ctx, const void *qcoeffs, int coeff_bytes, const ui
   const uint32_t allowed = r1_tx_type_mask(tx_size, is_inter, use_reduced_tx_set, 0);
   R1_REQUIRE(tx_type_mask != 0 && (tx_type_mask & ~allowed) == 0);
   R1_REQUIRE(qcoeffs && eobs && cdfs && rate_out);
-  // num_tx_set / av1_tx_ind (transform_unit.rs:36, 51-58), rows in TxSet order; the set from the mask of its types
-  static const uint8_t kNumTxSet[6] = {1, 2, 5, 7, 12, 16};
-  static const uint32_t kSetMask[6] = {0x0001, 0x0201, 0x020F, 0x0E0F, 0x0FFF, 0xFFFF};
-  static const uint8_t kTxInd[6][16] = {{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0},
-                                        {1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0},
-                                        {1, 3, 4, 2, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0},
-                                        {1, 5, 6, 4, 0, 0, 0, 0, 0, 0, 2, 3, 0, 0, 0, 0},
-                                        {3, 4, 5, 8, 6, 7, 9, 10, 11, 0, 1, 2, 0, 0, 0, 0},
-                                        {7, 8, 9, 12, 10, 11, 13, 14, 15, 0, 1, 2, 3, 4, 5, 6}};
-  int set = 0;
-  while (kSetMask[set] != allowed) set++;
-  const int wl = r1tx::kTxWLog2[tx_size], hl = r1tx::kTxHLog2[tx_size];
   a = {};
   a.qc = qcoeffs, a.eobs = eobs, a.cdfs = cdfs, a.rate = rate_out, a.cul = cul_level_out;
-  for (int k = 0; k < 3; k++) a.scan[k] = ctx->scan_dev + ctx->scan_off[tx_size][k];
   a.nt = __builtin_popcount(tx_type_mask);
   R1_REQUIRE((long long)(n > 0 ? n : 0) * a.nt * per_block <= 0x7fffffffLL);
-  a.n_slots = (n > 0 ? n : 0) * a.nt, a.n_cdfs = n_cdfs, a.plane = plane;
-  a.w_coded = r1q::coded_dim(wl);
-  a.hl = r1_ilog2(r1q::coded_dim(hl));
-  a.area = a.w_coded << a.hl;
-  a.shape = wl < hl ? 1 : (wl > hl ? 2 : 0);
-  a.eob_flag_n = 5 + (wl + hl - 4 < 6 ? wl + hl - 4 : 6);   // eob_multi_size = area_log2 - 4; `_ =>`: eob_flag_cdf1024
-  a.tx_n = kNumTxSet[set] > 1 ? kNumTxSet[set] : 0;
-  a.is_inter = is_inter;
+  a.n_slots = (n > 0 ? n : 0) * a.nt, a.n_cdfs = n_cdfs;
+  const int set = rate_shape(ctx, tx_size, plane, is_inter, use_reduced_tx_set, a);
   for (int t = 0, j = 0; t < 16; t++)
     if ((tx_type_mask >> t) & 1) a.type[j] = (uint8_t)t, a.tx_sym[j] = kTxInd[set][t], j++;
   return R1_OK;
@@ -601,6 +785,74 @@ extern "C" int r1_coeff_rate_chain_batch(r1_ctx *ctx, const void *qcoeffs, int c
   const unsigned grid = (unsigned)((c.r.n_slots + 3) / 4);
   if (coeff_bytes == 2) hipLaunchKernelGGL(k_coeff_rate_chain<int16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c);
   else hipLaunchKernelGGL(k_coeff_rate_chain<int32_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c);
+  R1_HIP_CHECK(hipGetLastError());
+  return R1_OK;
+}
+
+extern "C" int r1_coeff_rate_block_batch(r1_ctx *ctx, const void *qcoeffs_y, const uint16_t *eobs_y, int n_txb_y, int step_y,
+                                         const void *qcoeffs_u, const uint16_t *eobs_u, const void *qcoeffs_v,
+                                         const uint16_t *eobs_v, int n_txb_uv, int step_uv, int coeff_bytes,
+                                         const R1BlockRateTrial *trials, int n, int bw, int bh, int tx_size, int xdec,
+                                         int ydec, int is_inter, int use_reduced_tx_set, const R1BlockChainCtx *blocks,
+                                         int n_blocks, const R1CoeffCdfs *cdfs, int n_cdfs, uint32_t *rate_out,
+                                         uint32_t *plane_rate_out, uint16_t *rng_out, uint8_t *cul_level_out,
+                                         uint8_t *ctx_out, void *stream) {
+  R1_REQUIRE(ctx);
+  R1_REQUIRE(coeff_bytes == 2 || coeff_bytes == 4);
+  R1_REQUIRE(r1_tx_size_ok(tx_size));
+  const int tw = 1 << r1tx::kTxWLog2[tx_size], th = 1 << r1tx::kTxHLog2[tx_size];
+  R1_REQUIRE(r1_is_pow2(bw) && r1_is_pow2(bh) && bw >= 4 && bh >= 4 && bw <= 64 && bh <= 64);
+  R1_REQUIRE(bw <= 4 * bh && bh <= 4 * bw);            // a block size
+  R1_REQUIRE(bw % tw == 0 && bh % th == 0);
+  const int ntx = (bw / tw) * (bh / th);
+  R1_REQUIRE(ntx >= 1 && ntx <= 16);
+  R1_REQUIRE((xdec == 1 && ydec == 1) || (xdec == 1 && ydec == 0) || (xdec == 0 && ydec == 0));
+  R1_REQUIRE(!(xdec == 1 && ydec == 0) || bw >= bh);   // subsampled_size (partition.rs:337-379): what 4:2:2 admits
+  R1_REQUIRE(step_y >= 1 && step_uv >= 1 && n_txb_y >= 0 && n_txb_uv >= 0);
+  R1_REQUIRE(n_blocks >= 1 && n_cdfs >= 1 && n_cdfs <= 256);
+  R1_REQUIRE(qcoeffs_y && eobs_y && trials && blocks && cdfs && rate_out);
+  const int n_uv_ptrs = (qcoeffs_u != nullptr) + (eobs_u != nullptr) + (qcoeffs_v != nullptr) + (eobs_v != nullptr);
+  R1_REQUIRE(n_uv_ptrs == 0 || n_uv_ptrs == 4);
+  is_inter = is_inter != 0;
+  use_reduced_tx_set = use_reduced_tx_set != 0;
+  // largest_chroma_tx_size (partition.rs:385-393): the subsampled block, its largest transform, 64-point sides coded as 32
+  const int pw = (bw >> xdec) > 4 ? bw >> xdec : 4, ph = (bh >> ydec) > 4 ? bh >> ydec : 4;
+  const int uw = pw < 32 ? pw : 32, uh = ph < 32 ? ph : 32;
+  int uv_tx_size = 0;
+  while (uv_tx_size < 19 && ((1 << r1tx::kTxWLog2[uv_tx_size]) != uw || (1 << r1tx::kTxHLog2[uv_tx_size]) != uh)) uv_tx_size++;
+  R1_REQUIRE(uv_tx_size < 19);
+  // the chroma grid, literally (encoder.rs:2327-2338; 2492-2505 has max_txsize_rect_lookup[bsize] in place of the block,
+  // the same dimensions up to 64x64)
+  int bw_uv = (bw >> 2) >> xdec, bh_uv = (bh >> 2) >> ydec;
+  if (bw_uv == 0 || bh_uv == 0) bw_uv = 1, bh_uv = 1;
+  bw_uv /= uw >> 2, bh_uv /= uh >> 2;
+
+  BlockArgs c = {};
+  c.r[0].cdfs = cdfs, c.r[0].rate = rate_out, c.r[0].cul = cul_level_out;
+  c.r[0].n_slots = n > 0 ? n : 0, c.r[0].n_cdfs = n_cdfs;
+  c.r[1] = c.r[0];
+  const int set = rate_shape(ctx, tx_size, 0, is_inter, use_reduced_tx_set, c.r[0]);
+  rate_shape(ctx, uv_tx_size, 1, is_inter, use_reduced_tx_set, c.r[1]);
+  for (int t = 0; t < 16; t++) {
+    c.r[0].type[t] = c.r[1].type[t] = (uint8_t)t;
+    c.r[0].tx_sym[t] = kTxInd[set][t];
+  }
+  c.mask[0] = kSetMask[set];
+  c.mask[1] = (uw == 32 || uh == 32) ? 0x0201u : 0xFFFFu;   // the scans av1_scan_orders holds for the size
+  if (n <= 0) return R1_OK;
+  c.pl[0] = {qcoeffs_y, eobs_y, n_txb_y, step_y, ntx, bw / tw, tw >> 2, th >> 2, 0, 0, 0, 0};
+  c.pl[1] = {qcoeffs_u, eobs_u, n_txb_uv, step_uv, bw_uv * bh_uv, bw_uv > 0 ? bw_uv : 1, uw >> 2, uh >> 2, xdec, ydec,
+             (bw == 4) * xdec, (bh == 4) * ydec};
+  c.pl[2] = c.pl[1];
+  c.pl[2].qc = qcoeffs_v, c.pl[2].eobs = eobs_v;
+  c.trials = trials, c.blocks = blocks;
+  c.plane_rate = plane_rate_out, c.rng_out = rng_out, c.ctx_out = ctx_out;
+  c.n_blocks = n_blocks;
+  c.uv_skip_off = pw * ph > uw * uh ? 10 : 7;
+  R1DeviceGuard guard(ctx);
+  const unsigned grid = (unsigned)((c.r[0].n_slots + 3) / 4);
+  if (coeff_bytes == 2) hipLaunchKernelGGL(k_coeff_rate_block<int16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c);
+  else hipLaunchKernelGGL(k_coeff_rate_block<int32_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, c);
   R1_HIP_CHECK(hipGetLastError());
   return R1_OK;
 }

@@ -21,6 +21,15 @@ the kernels by executing the reference's own text (tests/golden/gen_rdo_glue_ref
                                                        blocks: the descriptor of r1_coeff_rate_chain_batch; pinned by
                                                        tests/golden/coeff_rate_chain_ref.npz)
   sub_tx_size                src/context/transform_unit.rs:85-105  (sub_tx_size_map: the next transform depth)
+  has_chroma                 src/context/transform_unit.rs:108-121
+  chroma_tx_grid             src/encoder.rs:2327-2338, 2492-2505  (uv_tx_size and the chroma transform-block grid of
+                                                       write_tx_blocks / write_tx_tree, the integer arithmetic literally)
+  uv_tx_type_intra / uv_tx_type_inter   src/encoder.rs:2346-2350, 2507-2511; src/context/transform_unit.rs:162-197;
+                                                       src/transform/mod.rs:81-97
+  block_chain_ctx / block_rate_trial    src/encoder.rs:2364-2369, 2525-2530, 1441, 1561-1566  (a block's three planes'
+                                                       contexts and edges, and one trial: the descriptors of
+                                                       r1_coeff_rate_block_batch; all pinned by
+                                                       tests/golden/coeff_rate_block_ref.npz)
   intra_split_cands          src/encoder.rs:2276-2311  (write_tx_blocks' transform-block grid -> the descriptors of
                                                        r1_rdo_intra_split_batch)
   has_top_right / has_bottom_left   src/recon_intra.rs:174-243, 374-450   (luma, blocks up to 64x64; the reference's
@@ -437,6 +446,92 @@ def txb_chain_ctx(above_row, left_col, bo_x, bo_y, bw, bh, mi_width, mi_height, 
     pad = lambda v: tuple(v + [0] * (16 - len(v)))
     return (pad(above), pad(left), min(255, mi_width - bo_x), min(255, mi_height - bo_y), min(255, w_in_b - bo_x),
             min(255, h_in_b - bo_y), int(y_mode), int(cdf_sel), (0, 0))
+
+
+def block_size(bw, bh):
+    """the BlockSize of bw x bh luma pixels"""
+    return BlockSize["BLOCK_%dX%d" % (bw, bh)]
+
+
+def has_chroma(bo_x, bo_y, bsize, xdec, ydec, monochrome=False):
+    """has_chroma (src/context/transform_unit.rs:108-121): whether the block at tile block offset (bo_x, bo_y) carries
+    the chroma of its 8x8 -- with subsampling, a 4-wide / 4-high block does at odd offsets only.  monochrome: Cs400."""
+    if monochrome:
+        return False
+    w, h = BlockSize(bsize).dims
+    bw, bh = w >> MI_SIZE_LOG2, h >> MI_SIZE_LOG2
+    return ((bo_x & 1) == 1 or (bw & 1) == 0 or xdec == 0) and ((bo_y & 1) == 1 or (bh & 1) == 0 or ydec == 0)
+
+
+def chroma_tx_grid(bsize, xdec, ydec, is_inter=False):
+    """-> (uv_tx_size, bw_uv, bh_uv): the chroma transform size and the grid write_tx_blocks (src/encoder.rs:2327-2338)
+    or write_tx_tree (2492-2505) loops over per chroma plane, the integer arithmetic as it stands -- either side 0
+    makes both 1 BEFORE the division by the transform's width_mi / height_mi, so BLOCK_4X16 and BLOCK_16X4 in 4:2:0
+    come out with an empty grid."""
+    w, h = BlockSize(bsize).dims
+    uv_tx_size = largest_chroma_tx_size(bsize, xdec, ydec)
+    if is_inter:      # max_txsize_rect_lookup[bsize].width_mi(), height_mi(): 64 at most
+        w_mi, h_mi = min(w, 64) >> MI_SIZE_LOG2, min(h, 64) >> MI_SIZE_LOG2
+    else:             # bw * tx_size.width_mi() with bw = bsize.width_mi() / tx_size.width_mi()
+        w_mi, h_mi = w >> MI_SIZE_LOG2, h >> MI_SIZE_LOG2
+    bw_uv, bh_uv = w_mi >> xdec, h_mi >> ydec
+    if bw_uv == 0 or bh_uv == 0:
+        bw_uv = bh_uv = 1
+    uw, uh = TxSize(uv_tx_size).dims
+    return uv_tx_size, bw_uv // (uw >> MI_SIZE_LOG2), bh_uv // (uh >> MI_SIZE_LOG2)
+
+
+# intra_mode_to_tx_type_context over uv2y (src/context/transform_unit.rs:162-193): DC .. PAETH, then UV_CFL -> DC
+_INTRA_MODE_TX_TYPE = (0, 1, 2, 0, 3, 1, 2, 2, 1, 3, 1, 2, 3, 0)
+
+
+def uv_tx_type_intra(chroma_mode, uv_tx_size):
+    """the uv_tx_type of write_tx_blocks (src/encoder.rs:2346-2350); chroma_mode: DC_PRED 0 .. PAETH_PRED 12, UV_CFL_PRED 13"""
+    uw, uh = TxSize(uv_tx_size).dims
+    return 0 if uw >= 32 or uh >= 32 else _INTRA_MODE_TX_TYPE[int(chroma_mode)]
+
+
+def uv_tx_type_inter(tx_type, uv_tx_size, partition_has_coeff):
+    """the uv_tx_type of write_tx_tree (src/encoder.rs:2507-2511): TxType::uv_inter (src/transform/mod.rs:81-97) of the
+    luma type, DCT_DCT when no luma transform block had a coefficient"""
+    if not partition_has_coeff:
+        return 0
+    uw, uh = TxSize(uv_tx_size).dims
+    tx_type = int(tx_type)
+    if max(uw, uh) == 32:                  # sqr_up() == TX_32X32
+        return 9 if tx_type == 9 else 0
+    if min(uw, uh) == 16:                  # sqr() == TX_16X16
+        return 0 if tx_type in (12, 13, 14, 15) else tx_type
+    return tx_type
+
+
+def block_chain_ctx(above_rows, left_cols, bo_x, bo_y, bsize, xdec, ydec, mi_width, mi_height, w_in_b, h_in_b, y_mode,
+                    cdf_sel, cdf_sel_uv):
+    """The R1BlockChainCtx of r1_coeff_rate_block_batch for the block at tile block offset (bo_x, bo_y), as a tuple in the
+    field order of types.BLOCK_CHAIN_CTX.  above_rows[p] / left_cols[p]: above_coeff_context[p] (indexed by x >> xdec
+    for chroma) and left_coeff_context[p] (by y_in_sb() >> ydec) in front of the block; the rest as txb_chain_ctx.
+    The chroma arrays and the chroma clip start at the first chroma transform block's tx_bo: the block's offset less
+    one unit where the block is 4 wide / high and the plane is subsampled (src/encoder.rs:2364-2369, 2525-2530)."""
+    bw, bh = BlockSize(bsize).dims
+    assert 4 <= bw <= 64 and 4 <= bh <= 64
+    ux, uy = bo_x - (bw == 4) * xdec, bo_y - (bh == 4) * ydec
+    pad = lambda v: [int(e) for e in v] + [0] * (16 - len(v))
+    ctx = []
+    for p in range(3):
+        x0, y0 = (bo_x, bo_y % 16) if p == 0 else (ux >> xdec, (uy % 16) >> ydec)
+        ctx.append((pad(above_rows[p][x0:x0 + 16]), pad(left_cols[p][y0:y0 + 16])))
+    clip_uv = lambda edge, o, dec: min(255, max(0, (((edge - o) << MI_SIZE_LOG2) >> dec) >> 2))
+    return (ctx, min(255, mi_width - bo_x), min(255, mi_height - bo_y), min(255, w_in_b - bo_x), min(255, h_in_b - bo_y),
+            clip_uv(w_in_b, ux, xdec), clip_uv(h_in_b, uy, ydec), int(y_mode), int(cdf_sel), int(cdf_sel_uv), (0, 0, 0))
+
+
+def block_rate_trial(first_y, first_u, first_v, block, tx_type, uv_tx_type, do_chroma, rng=0x8000):
+    """One R1BlockRateTrial, in the field order of types.BLOCK_RATE_TRIAL.  rng: the host counter's `rng` behind the
+    last head symbol (0x8000: a fresh WriterCounter); the reference's rate is then the call's rate_out plus the host's
+    tell_frac at that point less the fresh counter's."""
+    assert 0x8000 <= int(rng) <= 0xFFFF
+    return (int(first_y), int(first_u), int(first_v), int(block), int(rng), int(tx_type), int(uv_tx_type),
+            int(bool(do_chroma)), (0, 0, 0))
 
 
 def pick_tx_type(rates, dists, lam, cur_best_rd):

@@ -5,7 +5,8 @@ TxType      src/transform/mod.rs:56-74    FilterMode  src/mc.rs:100-106
 
 COEFF_CDFS / TXB_CTX: the NumPy mirrors of R1CoeffCdfs / R1TxbCtx (include/rav1e_amd.h, r1_coeff_rate_batch); the
 dimensions are the reference's (src/context/transform_unit.rs:27, 200-219).  TXB_CHAIN_CTX: R1TxbChainCtx
-(r1_coeff_rate_chain_batch).
+(r1_coeff_rate_chain_batch).  BLOCK_CHAIN_CTX / BLOCK_RATE_TRIAL: R1BlockChainCtx / R1BlockRateTrial
+(r1_coeff_rate_block_batch).
 """
 import enum
 
@@ -135,3 +136,10 @@ COEFF_RATE_INVALID = 0xFFFFFFFF      # the rate of a slot whose device-resident 
 TXB_CHAIN_CTX = np.dtype([("above", "u1", (16,)), ("left", "u1", (16,)), ("mi_w", "u1"), ("mi_h", "u1"),
                           ("clip_w4", "u1"), ("clip_h4", "u1"), ("y_mode", "u1"), ("cdf_sel", "u1"),
                           ("reserved", "u1", (2,))])
+# R1BlockChainCtx / R1BlockRateTrial (r1_coeff_rate_block_batch): the same for luma, U and V -- ctx[plane][0: above,
+# 1: left][16] -- and one trial's place in the coefficient arrays, its transform types and the writer's rng in front
+BLOCK_CHAIN_CTX = np.dtype([("ctx", "u1", (3, 2, 16)), ("mi_w", "u1"), ("mi_h", "u1"), ("clip_w4", "u1"),
+                            ("clip_h4", "u1"), ("clip_uv_w4", "u1"), ("clip_uv_h4", "u1"), ("y_mode", "u1"),
+                            ("cdf_sel", "u1"), ("cdf_sel_uv", "u1"), ("reserved", "u1", (3,))])
+BLOCK_RATE_TRIAL = np.dtype([("first_y", "<u4"), ("first_u", "<u4"), ("first_v", "<u4"), ("block", "<u4"), ("rng", "<u2"),
+                             ("tx_type", "u1"), ("uv_tx_type", "u1"), ("do_chroma", "u1"), ("reserved", "u1", (3,))])

@@ -30,7 +30,7 @@ def kernels(lib):
                 out[name] = []
                 continue
             t = line.split("//")[0].strip()
-            if name and t and not t.startswith("s_nop") and not t.startswith("s_code_end"):
+            if name and t and t != "..." and not t.startswith("s_nop") and not t.startswith("s_code_end"):    # "...": elided padding
                 t = re.sub(r"\s+", " ", t)
                 if t.startswith(("s_add_u32", "s_addc_u32")):    # pc-relative offsets of constant tables move with the object
                     t = re.sub(r"0x[0-9a-f]+$", "PCREL", t)

@@ -6,13 +6,15 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import cand_size_cases as K
 import oracle_lib as O
 
 pytestmark = pytest.mark.gpu
 
 PW, PH, PAD = 160, 128, 88
-# the 4-tap set, both mappings (128-wide / -high: the slab kernel), every slab count (1, 2, 4)
-SIZES = [(4, 4), (4, 16), (8, 8), (16, 8), (8, 32), (32, 32), (64, 16), (64, 64), (128, 64), (128, 128)]
+# every transform size (one k_compound_fast per size and depth; the 4-tap set among them) and the slab kernel with two
+# and four slabs (128-wide / -high); test_cand_size_cases.py holds the table against the 19 x 3 without a device
+SIZES = K.COMPOUND_SIZES
 NS = (1, 5, 67)
 
 
@@ -139,7 +141,7 @@ def test_compound_reference_vectors(ctx):
 
 
 # ---- 2. parity with the oracle composition ----
-@pytest.fixture(scope="module", params=[8, 10, 12])
+@pytest.fixture(scope="module", params=list(K.COMPOUND_DEPTHS))
 def random_planes(request):
     bd = request.param
     rng = np.random.default_rng(1000 + bd)
@@ -159,7 +161,7 @@ def test_compound_parity_random(ctx, oracle, random_planes):
             check_all(ctx, oracle, planes, dplanes, w, h, c, EACH if n == 5 else ALL3)
 
 
-@pytest.mark.parametrize("bd", [8, 10, 12])
+@pytest.mark.parametrize("bd", list(K.COMPOUND_DEPTHS))
 def test_compound_parity_saturated(ctx, oracle, bd):
     """PREP_BIAS and the final clamp: references that are all `max`, and a 0 / max checkerboard (the sharpest
     overshoot both filter passes can produce), in the three pairings"""

@@ -14,6 +14,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import cand_size_cases as K
 import oracle_lib as O
 import test_gpu_rdo_intra as RI
 import test_gpu_rdo_intra_split as SP
@@ -225,8 +226,8 @@ def test_lookahead_ref_12_cost_maps(ctx):
 # ------------------------------------------------ the fused intra candidate, every 12-bit instantiation
 # TxSize ids: 4x4, 32x32, 64x64, 4x16, 16x4, 16x64 and the pair 8x16 / 16x8 (8x8 and 16x16 are cases of
 # test_gpu_rdo_intra.py at 12 bits)
-INTRA_SIZES = [0, 3, 4, 13, 14, 17, 7, 8]
-KINDS = (3, 0, 2)                    # the three distortion kinds; dist_kind 0 is QM 1 of the plan, the others QM 2
+INTRA_SIZES = K.DEPTH12_INTRA_SIZES
+KINDS = K.INTRA_KINDS                # the three distortion kinds; dist_kind 0 is QM 1 of the plan, the others QM 2
 TWO_LAUNCH = 2
 
 

@@ -7,13 +7,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import cand_size_cases as K
 import oracle_lib as O
 
 pytestmark = pytest.mark.gpu
 
-TX_DIMS = [(4, 4), (8, 8), (16, 16), (32, 32), (64, 64), (4, 8), (8, 4), (8, 16), (16, 8),
-           (16, 32), (32, 16), (32, 64), (64, 32), (4, 16), (16, 4), (8, 32), (32, 8),
-           (16, 64), (64, 16)]
+TX_DIMS = K.TX_DIMS
 GUARD = 0x5A
 
 
@@ -180,10 +179,9 @@ def _planes(bd, seed, width=204, height=140):
     return rec, org
 
 
-# 4x4: 16 candidates per wave; 8x8 / 16x16: the fan-out with the full intra mask; 4x16 / 16x4: lanes per candidate
-# != width; 32x32: the plain kernel (int16 transpose tile at 10-bit); 64x64: split transpose (masked at 8-bit); 16x64
-CASES = [(0, 8), (0, 10), (1, 8), (1, 10), (1, 12), (2, 8), (2, 10), (2, 12), (13, 8), (13, 10), (14, 8), (14, 10),
-         (3, 8), (3, 10), (4, 8), (4, 10), (17, 8), (17, 10)]
+# every (TxSize id, bit depth) with a fused point that test_gpu_depth12.py does not launch (cand_size_cases.py says
+# which is which; test_cand_size_cases.py holds the table against the plan's 105 instantiations without a device)
+CASES = K.INTRA_CASES
 
 
 @pytest.mark.parametrize("ts,bd", CASES)
@@ -191,10 +189,15 @@ def test_intra_cand_equals_two_launch_route_and_oracle(ctx, oracle, ts, bd):
     """all 13 luma modes, angle deltas -3 .. 3, ief 0 / 1 / 2, every edge-set shape, blocks cut by the frame edge;
     n = 1, NC - 1, NC + 1, 3 NC + 1 (ragged last wave, replicated dead slots); edge_group 1 (shuffled, one set per
     candidate) and 5 (the modes of a block share a set); the three distortion kinds with a random scale grid; every
-    optional output and the minimal set; guard words around every output"""
+    optional output and the minimal set; guard words around every output.  The rows of K.INTRA_CASES_EOB hold a flat
+    block at the origin (in every call, DC_PRED without neighbours: nothing to code) and must see zero and non-zero
+    eob both"""
     w, h = TX_DIMS[ts]
     nc = 64 // max(w, h)
     rec, org = _planes(bd, 4200 + 10 * ts + bd)
+    want_eob = (ts, bd) in K.INTRA_CASES_EOB
+    if want_eob:
+        rec.view()[:h, :w] = org.view()[:h, :w] = 128 << (bd - 8)
     drec, dorg = _dev_plane(rec), _dev_plane(org)
     rng = np.random.default_rng(977 + 31 * ts + bd)
     # (a block cut by the frame edge is evaluated whole, as the two-launch route does: the grid covers it)
@@ -204,19 +207,24 @@ def test_intra_cand_equals_two_launch_route_and_oracle(ctx, oracle, ts, bd):
     masks = [ctx.tx_type_mask(ts, False)] if side <= 16 else ([1, 0x201] if side == 32 else [1])
     if side <= 16:
         masks.append(1 << 9)          # a single type through the fan-out form
-    step = 0
+    step, eobs = 0, []
     for n0 in sorted({1, max(1, nc - 1), nc + 1, 3 * nc + 1}):
         for group in (1, 5):
             n = n0 if group == 1 else (n0 + 4) // 5 * 5
-            kind = (3, 0, 2)[step % 3]
+            kind = K.INTRA_KINDS[step % 3]
             full = step % 4 != 3
             mask = masks[step % len(masks)]
             qi = (40, 110, 200)[step % 3]
             cs = make_case(rng, ctx, rec, drec, ts, n, group)
             use_sc = step % 2 == 0
-            check_call(ctx, oracle, org, dorg, ts, bd, cs, group, mask, qi, kind, scales if use_sc else None,
-                       dscales if use_sc else None, 0, 0, full, (ts, bd, n, group, kind, hex(mask), full))
+            eobs.append(check_call(ctx, oracle, org, dorg, ts, bd, cs, group, mask, qi, kind,
+                                   scales if use_sc else None, dscales if use_sc else None, 0, 0, full,
+                                   (ts, bd, n, group, kind, hex(mask), full)).ravel())
             step += 1
+    assert step >= 3          # every kind of K.INTRA_KINDS was launched
+    if want_eob:
+        eobs = np.concatenate(eobs)
+        assert (eobs == 0).any() and (eobs != 0).any(), (ts, bd, int((eobs == 0).sum()), len(eobs))
 
 
 @pytest.mark.parametrize("bd", [8, 10, 12])

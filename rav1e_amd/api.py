@@ -192,6 +192,25 @@ def _ptrs(o, *keys):
     return [o[k].data_ptr() if k in o else None for k in keys]
 
 
+def _check_coeffs(qcoeffs, eobs, dtype=None):
+    """a (qcoeffs, eobs) pair of the coefficient-rate calls: contiguous device tensors, int16 / int32 (or `dtype`) and
+    two bytes per entry"""
+    assert qcoeffs.is_cuda and qcoeffs.is_contiguous() and qcoeffs.dtype in ((dtype,) if dtype else (torch.int16, torch.int32))
+    assert eobs.is_cuda and eobs.is_contiguous() and eobs.element_size() == 2
+
+
+def _bind_wanted(outs, spec, dev):
+    """(a copy of outs with every wanted output of spec = {key: (want, shape, dtype)} allocated on dev that is not in
+    it yet, the data pointers by key: None for an output that is not wanted, handed in or not)"""
+    o = dict(outs) if outs else {}
+    ptr = {}
+    for k, (want, shape, dtype) in spec.items():
+        if want and k not in o:
+            o[k] = torch.empty(shape, dtype=dtype, device=dev)
+        ptr[k] = o[k].data_ptr() if want else None
+    return o, ptr
+
+
 def segmentation_from_centroids(centroids, base_q_idx, bit_depth, lib=None):
     """r1_segmentation_from_centroids: a host function of the library (no context, no GPU); see
     Context.segmentation_from_centroids"""
@@ -1071,23 +1090,16 @@ class Context:
         (n_cdfs, 1088)) of 1..256 snapshots.  -> {"rate": (n, nt) int32 holding uint32 1/8 bits (COEFF_RATE_INVALID
         for a slot with out-of-range device inputs), "cul_level": (n, nt) uint8}"""
         nt = bin(int(tx_type_mask)).count("1")
-        assert qcoeffs.is_cuda and qcoeffs.is_contiguous() and qcoeffs.dtype in (torch.int16, torch.int32)
-        assert eobs.is_cuda and eobs.is_contiguous() and eobs.element_size() == 2
+        _check_coeffs(qcoeffs, eobs)
         dctx, n = _dev_cands(ctxs, TXB_CTX)
         dcdf, n_cdfs = _dev_cands(cdfs, COEFF_CDFS)
         assert eobs.numel() == n * nt or nt == 0, (eobs.numel(), n, nt)      # (an empty mask: the library refuses it)
-        dev = qcoeffs.device
-        o = dict(outs) if outs else {}
-        if "rate" not in o:
-            o["rate"] = torch.empty((n, nt), dtype=torch.int32, device=dev)
-        if want_cul_level and "cul_level" not in o:
-            o["cul_level"] = torch.empty((n, nt), dtype=torch.uint8, device=dev)
-        cul = o.get("cul_level") if want_cul_level else None
+        o, ptr = _bind_wanted(outs, {"rate": (True, (n, nt), torch.int32),
+                                     "cul_level": (want_cul_level, (n, nt), torch.uint8)}, qcoeffs.device)
         self._check(self.lib.r1_coeff_rate_batch(
             self.h, qcoeffs.data_ptr(), qcoeffs.element_size(), eobs.data_ptr(), n, int(tx_type_mask), int(tx_size),
             int(plane), int(bool(is_inter)), int(bool(use_reduced_tx_set)), dctx.data_ptr(), dcdf.data_ptr(),
-            n_cdfs, o["rate"].data_ptr(), cul.data_ptr() if cul is not None else None, _stream_ptr()),
-            "r1_coeff_rate_batch")
+            n_cdfs, ptr["rate"], ptr["cul_level"], _stream_ptr()), "r1_coeff_rate_batch")
         return o
 
     def coeff_rate_chain_batch(self, qcoeffs, eobs, tx_type_mask, bw, bh, tx_size, order, is_inter, chains, cdfs,
@@ -1108,20 +1120,14 @@ class Context:
         nt = bin(int(tx_type_mask)).count("1")
         tw, th = TxSize(tx_size).dims
         ntx = max(1, bw // tw) * max(1, bh // th)
-        assert qcoeffs.is_cuda and qcoeffs.is_contiguous() and qcoeffs.dtype in (torch.int16, torch.int32)
-        assert eobs.is_cuda and eobs.is_contiguous() and eobs.element_size() == 2
+        _check_coeffs(qcoeffs, eobs)
         dch, n = _dev_cands(chains, TXB_CHAIN_CTX)
         dcdf, n_cdfs = _dev_cands(cdfs, COEFF_CDFS)
         assert eobs.numel() == n * nt * ntx or nt == 0, (eobs.numel(), n, nt, ntx)
-        dev = qcoeffs.device
-        o = dict(outs) if outs else {}
-        spec = {"rate": (True, (n, nt), torch.int32), "txb_rate": (want_txb_rate, (n, nt, ntx), torch.int32),
-                "cul_level": (want_cul_level, (n, nt, ntx), torch.uint8), "ctx": (want_ctx, (n, nt, 32), torch.uint8)}
-        ptr = {}
-        for k, (want, shape, dtype) in spec.items():
-            if want and k not in o:
-                o[k] = torch.empty(shape, dtype=dtype, device=dev)
-            ptr[k] = o[k].data_ptr() if want else None
+        o, ptr = _bind_wanted(outs, {
+            "rate": (True, (n, nt), torch.int32), "txb_rate": (want_txb_rate, (n, nt, ntx), torch.int32),
+            "cul_level": (want_cul_level, (n, nt, ntx), torch.uint8), "ctx": (want_ctx, (n, nt, 32), torch.uint8)},
+            qcoeffs.device)
         self._check(self.lib.r1_coeff_rate_chain_batch(
             self.h, qcoeffs.data_ptr(), qcoeffs.element_size(), eobs.data_ptr(), n, int(tx_type_mask), int(bw), int(bh),
             int(tx_size), int(order), int(bool(is_inter)), int(bool(use_reduced_tx_set)), dch.data_ptr(),
@@ -1147,8 +1153,7 @@ class Context:
         "ctx": (n, 3, 2, 16) uint8}; the four side outputs are optional."""
         from . import rdo_glue
         tw, th = TxSize(tx_size).dims
-        assert qcoeffs_y.is_cuda and qcoeffs_y.is_contiguous() and qcoeffs_y.dtype in (torch.int16, torch.int32)
-        assert eobs_y.is_cuda and eobs_y.is_contiguous() and eobs_y.element_size() == 2
+        _check_coeffs(qcoeffs_y, eobs_y)
         area = min(tw, 32) * min(th, 32)
         assert qcoeffs_y.numel() == eobs_y.numel() * area, (qcoeffs_y.numel(), eobs_y.numel(), area)
         uv_ptrs, n_uv = [None] * 4, 0
@@ -1156,23 +1161,16 @@ class Context:
             qu, eu, qv, ev = chroma
             uw, uh = TxSize(rdo_glue.largest_chroma_tx_size(rdo_glue.block_size(bw, bh), xdec, ydec)).dims
             for q, e in ((qu, eu), (qv, ev)):
-                assert q.is_cuda and q.is_contiguous() and q.dtype == qcoeffs_y.dtype
-                assert e.is_cuda and e.is_contiguous() and e.element_size() == 2
+                _check_coeffs(q, e, qcoeffs_y.dtype)
                 assert q.numel() == e.numel() * uw * uh and e.numel() == eu.numel(), (q.numel(), e.numel(), uw, uh)
             uv_ptrs, n_uv = [t.data_ptr() for t in (qu, eu, qv, ev)], eu.numel()
         dtr, n = _dev_cands(trials, BLOCK_RATE_TRIAL)
         dbl, n_blocks = _dev_cands(blocks, BLOCK_CHAIN_CTX)
         dcdf, n_cdfs = _dev_cands(cdfs, COEFF_CDFS)
-        dev = qcoeffs_y.device
-        o = dict(outs) if outs else {}
-        spec = {"rate": (True, (n,), torch.int32), "plane_rate": (want_plane_rate, (n, 3), torch.int32),
-                "rng": (want_rng, (n,), torch.int16), "cul_level": (want_cul_level, (n, 3, 16), torch.uint8),
-                "ctx": (want_ctx, (n, 3, 2, 16), torch.uint8)}
-        ptr = {}
-        for k, (want, shape, dtype) in spec.items():
-            if want and k not in o:
-                o[k] = torch.empty(shape, dtype=dtype, device=dev)
-            ptr[k] = o[k].data_ptr() if want else None
+        o, ptr = _bind_wanted(outs, {
+            "rate": (True, (n,), torch.int32), "plane_rate": (want_plane_rate, (n, 3), torch.int32),
+            "rng": (want_rng, (n,), torch.int16), "cul_level": (want_cul_level, (n, 3, 16), torch.uint8),
+            "ctx": (want_ctx, (n, 3, 2, 16), torch.uint8)}, qcoeffs_y.device)
         self._check(self.lib.r1_coeff_rate_block_batch(
             self.h, qcoeffs_y.data_ptr(), eobs_y.data_ptr(), eobs_y.numel(), int(step_y), *uv_ptrs, n_uv, int(step_uv),
             qcoeffs_y.element_size(), dtr.data_ptr(), n, int(bw), int(bh), int(tx_size), int(xdec), int(ydec),

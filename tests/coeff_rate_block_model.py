@@ -13,7 +13,6 @@ replay) and rdo_glue.txb_ctx / chroma_tx_grid.  What this file states itself:
 It is pinned by tests/golden/coeff_rate_block_ref.npz (tests/test_coeff_rate_block_ref.py).  Nothing here is imported
 by the product."""
 import os
-from unittest import mock
 
 import numpy as np
 
@@ -32,9 +31,8 @@ TRIAL_DTYPE = np.dtype([("first_y", "<u4"), ("first_u", "<u4"), ("first_v", "<u4
 def plane_grids(bw, bh, tx_size, xdec, ydec, is_inter):
     """per plane (tx_size, ntx, gw, tw4, th4, xdec, ydec, adj_x, adj_y, plane_bsize): the luma grid and the chroma grid of
     encoder.rs:2327-2338 / 2492-2505 with the one-unit shift of a 4-wide / 4-high block (2365-2368)"""
-    gw, gh = CM.grid(bw, bh, tx_size)
     bsize = CM.BLOCK_DIMS[(bw, bh)]
-    luma = (tx_size, gw * gh, gw, M.TX_W[tx_size] >> 2, M.TX_H[tx_size] >> 2, 0, 0, 0, 0, bsize)
+    luma = (tx_size,) + CM.luma_grid(bw, bh, tx_size) + (bsize,)
     uv_ts, bw_uv, bh_uv = RG.chroma_tx_grid(bsize, xdec, ydec, is_inter)
     uv_ts = int(uv_ts)
     pb = CM.BLOCK_DIMS[(max(4, bw >> xdec), max(4, bh >> ydec))]          # subsampled_size
@@ -67,9 +65,7 @@ def coeff_rate_block(qcs, eobs, bw, bh, tx_size, xdec, ydec, is_inter, reduced, 
     bad = {"rate": INVALID, "plane_rate": [0] * 3, "rng": 0, "cul": [[0] * 16 for _ in range(3)], "ctx": [0] * 96,
            "tell": [[0] * 16 for _ in range(3)]}
 
-    def coded(p):
-        ts, ntx, gw, tw4, th4, xd, yd, ax, ay, _pb = grids[p]
-        return [k for k in range(ntx) if (((k % gw) * tw4) << xd) - ax < mi_w and (((k // gw) * th4) << yd) - ay < mi_h]
+    coded = [CM.coded_txbs(g[1:9], mi_w, mi_h) for g in grids]
 
     if rng0 < 0x8000 or y_mode >= M.INTRA_MODES or sels[0] >= len(cdfs) or mi_w > clips[0][0] or mi_h > clips[0][1]:
         return bad
@@ -80,7 +76,7 @@ def coeff_rate_block(qcs, eobs, bw, bh, tx_size, xdec, ydec, is_inter, reduced, 
     for p in range(n_planes):
         ts, ntx, gw, tw4, th4 = grids[p][:5]
         W, H = M.coded_dims(ts)
-        for k in coded(p):
+        for k in coded[p]:
             if int(eobs[p][k]) > W * H:
                 return bad
             if p and (clips[p][0] - (k % gw) * tw4 < 1 or clips[p][1] - (k // gw) * th4 < 1):
@@ -98,26 +94,15 @@ def coeff_rate_block(qcs, eobs, bw, bh, tx_size, xdec, ydec, is_inter, reduced, 
             rec = np.array(cdfs[sels[p]], M.CDFS_DTYPE)         # the plane type's snapshot; V continues on U's record
         above, left = ctx[p][:16], ctx[p][16:]
         t_p = w.tell_frac()
-        todo = coded(p)
-        for k in range(ntx):
-            if k not in todo:
-                continue
+        for k in coded[p]:
             x4, y4 = (k % gw) * tw4, (k // gw) * th4
             sw, sh = min(tw4, clips[p][0] - x4), min(th4, clips[p][1] - y4)      # frame_clipped_txw >> 2 (encoder.rs:1561-1566)
             if p and not chroma_clip:
                 sw, sh = tw4, th4
             skip_ctx, sign_ctx = RG.txb_ctx(above[x4:x4 + max(sw, 0)], left[y4:y4 + max(sh, 0)], p, plane_bsize, ts)
-            with mock.patch.object(M, "Counter", lambda: w):
-                r = M.coeff_rate(qcs[p][k], int(eobs[p][k]), ts, types[p], p, is_inter, reduced, skip_ctx, sign_ctx, y_mode, rec)
-            assert r[0] != INVALID and (r[2], r[3]) == (w.bits, w.rng)
-            cul[p][k] = r[1]
+            _rate, cul[p][k] = CM.carried_txb(w, rec, qcs[p][k], eobs[p][k], ts, types[p], p, is_inter, reduced, skip_ctx,
+                                              sign_ctx, y_mode)
             tell[p][k] = w.tell_frac() - tell0
-            for (cid, s) in r[4]:
-                f, row = cid >> 6, cid & 63
-                n = CM.row_len(f, ts, is_inter, reduced)
-                head = [int(v) for v in rec[M.FIELDS[f]][row][:n]]
-                M.update_cdf(head, s)
-                rec[M.FIELDS[f]][row][:n] = head
             above[x4:x4 + tw4] = [cul[p][k]] * tw4
             left[y4:y4 + th4] = [cul[p][k]] * th4
         ctx[p] = above + left
@@ -125,7 +110,7 @@ def coeff_rate_block(qcs, eobs, bw, bh, tx_size, xdec, ydec, is_inter, reduced, 
     # tell: carried across blocks that are not coded and across planes, as the fixture stores it
     last = 0
     for p in range(3):
-        done = set(coded(p)) if p < n_planes else set()
+        done = set(coded[p]) if p < n_planes else set()
         for k in range(16):
             if k in done:
                 last = tell[p][k]
@@ -198,11 +183,10 @@ class BlockCase:
 
     def coded(self, p):
         """raster indices of plane p's transform blocks the loop codes"""
-        g = plane_grids(self.bw, self.bh, self.ts, self.xdec, self.ydec, self.inter)[p]
-        _ts, ntx, gw, tw4, th4, xd, yd, ax, ay, _pb = g
         if p and not self.do_chroma:
             return []
-        return [k for k in range(ntx) if (((k % gw) * tw4) << xd) - ax < self.mi_w and (((k // gw) * th4) << yd) - ay < self.mi_h]
+        g = plane_grids(self.bw, self.bh, self.ts, self.xdec, self.ydec, self.inter)[p]
+        return CM.coded_txbs(g[1:9], self.mi_w, self.mi_h)
 
     def model(self, **kw):
         return coeff_rate_block(self.qc, self.eobs, self.bw, self.bh, self.ts, self.xdec, self.ydec, self.inter, self.red,

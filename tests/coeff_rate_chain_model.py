@@ -42,12 +42,33 @@ def row_len(field, tx_size, is_inter, reduced):
     return (2, 0, 2, 3, 4, 4, 2)[field]
 
 
-def coded_blocks(bw, bh, tx_size, mi_w, mi_h, skip_test=True):
-    """raster indices of the transform blocks the loop codes (encoder.rs:2282, 2446)"""
+def luma_grid(bw, bh, tx_size):
+    """the grid tuple (ntx, gw, tw4, th4, xdec, ydec, adj_x, adj_y) of a block's luma transform blocks"""
     gw, gh = grid(bw, bh, tx_size)
-    tw4, th4 = M.TX_W[tx_size] >> 2, M.TX_H[tx_size] >> 2
-    return [by * gw + bx for by in range(gh) for bx in range(gw)
-            if not skip_test or (bx * tw4 < mi_w and by * th4 < mi_h)]
+    return (gw * gh, gw, M.TX_W[tx_size] >> 2, M.TX_H[tx_size] >> 2, 0, 0, 0, 0)
+
+
+def coded_txbs(g, mi_w, mi_h):
+    """raster indices of the transform blocks of grid g = (ntx, gw, tw4, th4, xdec, ydec, adj_x, adj_y) the loop codes:
+    those whose LUMA-unit origin lies inside the tile (encoder.rs:1441, 2282, 2446)"""
+    ntx, gw, tw4, th4, xd, yd, ax, ay = g
+    return [k for k in range(ntx) if (((k % gw) * tw4) << xd) - ax < mi_w and (((k // gw) * th4) << yd) - ay < mi_h]
+
+
+def carried_txb(w, rec, qc, eob, tx_size, tx_type, plane, is_inter, reduced, skip_ctx, sign_ctx, y_mode, carry_cdfs=True):
+    """write_coeffs_lv_map for one transform block on the carried writer w and the carried CDF record rec (both
+    updated in place; rec stays as it is without carry_cdfs) -> (the block's rate, cul_level)"""
+    with mock.patch.object(M, "Counter", lambda: w):
+        r = M.coeff_rate(qc, int(eob), tx_size, tx_type, plane, is_inter, reduced, skip_ctx, sign_ctx, y_mode, rec)
+    assert r[0] != INVALID and (r[2], r[3]) == (w.bits, w.rng)
+    if carry_cdfs:
+        for (cid, s) in r[4]:
+            f, row = cid >> 6, cid & 63
+            n = row_len(f, tx_size, is_inter, reduced)
+            head = [int(v) for v in rec[M.FIELDS[f]][row][:n]]
+            M.update_cdf(head, s)
+            rec[M.FIELDS[f]][row][:n] = head
+    return r[0], r[1]
 
 
 def coeff_rate_chain(qcs, eobs, bw, bh, tx_size, tx_type, is_inter, reduced, chain, cdfs, carry_cdfs=True,
@@ -63,8 +84,8 @@ def coeff_rate_chain(qcs, eobs, bw, bh, tx_size, tx_type, is_inter, reduced, cha
     area = min(tw, 32) * min(th, 32)
     mi_w, mi_h, clip_w4, clip_h4 = (int(chain[f]) for f in ("mi_w", "mi_h", "clip_w4", "clip_h4"))
     y_mode, sel = int(chain["y_mode"]), int(chain["cdf_sel"])
-    coded = coded_blocks(bw, bh, tx_size, mi_w, mi_h)
-    bad = {"rate": INVALID, "txb_rate": [0] * ntx, "cul": [0] * ntx, "ctx": [0] * 32, "tell": [0] * ntx}
+    coded = coded_txbs(luma_grid(bw, bh, tx_size), mi_w, mi_h)
+    bad ={"rate": INVALID, "txb_rate": [0] * ntx, "cul": [0] * ntx, "ctx": [0] * 32, "tell": [0] * ntx}
     if y_mode >= M.INTRA_MODES or sel >= len(cdfs) or mi_w > clip_w4 or mi_h > clip_h4:
         return bad
     if any(int(eobs[k]) > area for k in coded):
@@ -84,18 +105,9 @@ def coeff_rate_chain(qcs, eobs, bw, bh, tx_size, tx_type, is_inter, reduced, cha
         sw = min(tw4, clip_w4 - x4) if clipped_span else tw4          # frame_clipped_txw >> 2 (encoder.rs:1561-1566)
         sh = min(th4, clip_h4 - y4) if clipped_span else th4
         skip_ctx, sign_ctx = RG.txb_ctx(above[x4:x4 + max(sw, 0)], left[y4:y4 + max(sh, 0)], 0, BLOCK_DIMS[(bw, bh)], tx_size)
-        with mock.patch.object(M, "Counter", lambda: w):
-            r = M.coeff_rate(qcs[k], int(eobs[k]), tx_size, tx_type, 0, is_inter, reduced, skip_ctx, sign_ctx, y_mode, rec)
-        assert r[0] != INVALID and (r[2], r[3]) == (w.bits, w.rng)
-        txb_rate[k], cul[k] = r[0], r[1]
+        txb_rate[k], cul[k] = carried_txb(w, rec, qcs[k], eobs[k], tx_size, tx_type, 0, is_inter, reduced, skip_ctx, sign_ctx,
+                                          y_mode, carry_cdfs)
         tell[k] = w.tell_frac() - tell0
-        if carry_cdfs:
-            for (cid, s) in r[4]:
-                f, row = cid >> 6, cid & 63
-                n = row_len(f, tx_size, is_inter, reduced)
-                head = [int(v) for v in rec[M.FIELDS[f]][row][:n]]
-                M.update_cdf(head, s)
-                rec[M.FIELDS[f]][row][:n] = head
         if set_context:
             above[x4:x4 + tw4] = [cul[k]] * tw4
             left[y4:y4 + th4] = [cul[k]] * th4
@@ -174,6 +186,10 @@ class ChainCase:
         self.chain["above"], self.chain["left"] = self.ctx_in[:16], self.ctx_in[16:]
         for f in ("mi_w", "mi_h", "clip_w4", "clip_h4", "y_mode"):
             self.chain[f] = getattr(self, f)
+
+    def coded(self):
+        """raster indices of the transform blocks the loop codes"""
+        return coded_txbs(luma_grid(self.bw, self.bh, self.ts), self.mi_w, self.mi_h)
 
     def model(self, **kw):
         return coeff_rate_chain(self.qc, self.eobs, self.bw, self.bh, self.ts, self.tt, self.inter, self.red, self.chain,

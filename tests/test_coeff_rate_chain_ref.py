@@ -53,8 +53,7 @@ def test_fixture_covers_what_the_issue_lists(fixture):
     # eob == 0 first, in the middle, last, everywhere
     where = set()
     for c in synth:
-        coded = CM.coded_blocks(c.bw, c.bh, c.ts, c.mi_w, c.mi_h)
-        z = [int(c.eobs[k]) == 0 for k in coded]
+        z = [int(c.eobs[k]) == 0 for k in c.coded()]
         if len(z) > 2 and any(z):
             where |= {"first"} if z[0] and not all(z) else set()
             where |= {"last"} if z[-1] and not all(z) else set()
@@ -108,7 +107,7 @@ def test_every_carried_mechanism_moves_named_cases(fixture):
     # the CDF carry: needs two coded blocks
     moved = _moved(cases, carry_cdfs=False)
     assert "8x8/4x4 r0 e0 p0 c0" in moved and len(moved) >= 40
-    assert all(len(CM.coded_blocks(by_name[n].bw, by_name[n].bh, by_name[n].ts, by_name[n].mi_w, by_name[n].mi_h)) > 1 for n in moved)
+    assert all(len(by_name[n].coded()) > 1 for n in moved)
     # set_coeff_context: needs a later block inside the block and a stored value that differs from the one in front
     # (a non-zero cul_level, or the 0 of an eob == 0 block over a non-zero starting context)
     moved = _moved(cases, set_context=False)

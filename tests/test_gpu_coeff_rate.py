@@ -6,29 +6,11 @@ import numpy as np
 import pytest
 
 import coeff_rate_model as M
+from coeff_rate_gpu_util import GUARD, _guarded, _guards_intact, _t
 
 pytestmark = pytest.mark.gpu
 
-GUARD, GUARD_BYTES = 0xA5, 256
 RAV1E_MASK = 0x0E0F
-
-
-def _t(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _guarded(shape, dtype):
-    """a device tensor of `shape` inside a buffer with 256 guard bytes before and behind it"""
-    import torch
-    n = int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
-    raw = torch.full((n + 2 * GUARD_BYTES,), GUARD, dtype=torch.uint8, device="cuda")
-    return raw, raw[GUARD_BYTES:GUARD_BYTES + n].view(dtype).view(*shape)
-
-
-def _guards_intact(raw):
-    g = raw.cpu().numpy()
-    return bool((g[:GUARD_BYTES] == GUARD).all() and (g[-GUARD_BYTES:] == GUARD).all())
 
 
 def _call(ctx, qc, eobs, mask, ts, plane, inter, red, ctxs, cdfs, cb, want_cul=True):

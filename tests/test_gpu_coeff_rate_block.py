@@ -10,29 +10,11 @@ import pytest
 import coeff_rate_model as M
 import coeff_rate_chain_model as CM
 import coeff_rate_block_model as BM
+from coeff_rate_gpu_util import GUARD, _guarded, _guards_intact, _t
 
 pytestmark = pytest.mark.gpu
 
-GUARD, GUARD_BYTES = 0xA5, 256
 OUTS = ("rate", "plane_rate", "rng", "cul_level", "ctx")
-
-
-def _t(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _guarded(shape, dtype):
-    """a device tensor of `shape` inside a buffer with 256 guard bytes before and behind it"""
-    import torch
-    n = int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
-    raw = torch.full((n + 2 * GUARD_BYTES,), GUARD, dtype=torch.uint8, device="cuda")
-    return raw, raw[GUARD_BYTES:GUARD_BYTES + n].view(dtype).view(*shape)
-
-
-def _guards_intact(raw):
-    g = raw.cpu().numpy()
-    return bool((g[:GUARD_BYTES] == GUARD).all() and (g[-GUARD_BYTES:] == GUARD).all())
 
 
 def _shifted(host, lead):

@@ -124,7 +124,8 @@ const char *r1_last_error(void);
  * intra candidate (r1_rdo_intra_cand_batch), the coefficient rate (r1_coeff_rate_batch, R1CoeffCdfs, R1TxbCtx), the
  * intra transform-split candidate (r1_rdo_intra_split_batch, R1IntraSplitCand), the coefficient rate across a
  * block's transform blocks (r1_coeff_rate_chain_batch, R1TxbChainCtx) and across its three planes on one writer
- * (r1_coeff_rate_block_batch, R1BlockChainCtx, R1BlockRateTrial). */
+ * (r1_coeff_rate_block_batch, R1BlockChainCtx, R1BlockRateTrial), and the decision on the device (r1_rd_pick_batch,
+ * r1_rd_commit_batch, R1RdPick). */
 int r1_abi_version(void);
 
 /* ---- dist:: (reference: src/dist.rs get_sad 31, get_satd 156; dispatch
@@ -1010,9 +1011,11 @@ int r1_rdo_compound_cand_batch(r1_ctx *ctx, const R1Plane *org, const R1Plane *r
  *   R1_DIST_WSSE / R1_DIST_CDEF: the pixel-domain leg of r1_rdo_pixel_cand_batch; est_rate_out must be NULL
  * Outputs: sad_out / satd_out (optional): n words; eob_out, dist_out (, est_rate_out): n * nt entries,
  * entry [i * nt + j] = candidate i, slot j; qcoeffs_out (optional): n * nt dense coded-area blocks;
- * rec_out (optional): n * nt dense w*h reconstructions.  The host adds the rate of each slot's qcoeffs
- * and keeps the cheapest (compute_rd_cost, rdo.rs:718-723), applying the reference's early exit after the
- * first type itself (rdo.rs:1793-1802: a pure saving there, it changes no result).
+ * rec_out (optional): n * nt dense w*h reconstructions.  The rate of each slot's qcoeffs comes from
+ * r1_coeff_rate_batch and the cheapest is kept by r1_rd_pick_batch (compute_rd_cost, rdo.rs:718-723), which applies
+ * the reference's early exit after the first type (rdo.rs:1793-1802).  That exit is a pure saving only at the first
+ * transform depth, where cur_best_rd is f64::MAX; at a later depth it DECIDES: a first type above the carried
+ * cur_best_rd drops the whole depth, a later type below it included, so whoever picks must replay it.
  * Sizes up to 16x16 (up to 7 types here, 16 in AV1) run the fan-out kernel.  Sizes with a 32-point side
  * (DCT_DCT, + IDTX for inter blocks) and with a 64-point side (TX_SET_DCTONLY: tx_type_mask must be 1) run one
  * plain launch per type with the type forced -- two waves per SIMD of the fan-out kernel lose against two
@@ -1331,6 +1334,82 @@ int r1_coeff_rate_block_batch(r1_ctx *ctx, const void *qcoeffs_y, const uint16_t
                               int is_inter, int use_reduced_tx_set, const R1BlockChainCtx *blocks, int n_blocks,
                               const R1CoeffCdfs *cdfs, int n_cdfs, uint32_t *rate_out, uint32_t *plane_rate_out,
                               uint16_t *rng_out, uint8_t *cul_level_out, uint8_t *ctx_out, void *stream);
+
+/* ---- the decision on the device (added under ABI 7): what the reference does with the rate and the distortion of
+ * every trial -- compute_rd_cost (src/rdo.rs:718-723), the tail of rdo_tx_type_decision's loop (1801-1818), the carry
+ * across the transform depths in rdo_tx_size_type (780-784) and `rd < best.rd_cost` in luma_chroma_mode_rdo (923-938) --
+ * behind the candidate and rate launches on the same stream, with no copy and no synchronisation.  A block's decision
+ * is an R1RdPick that is carried from call to call; r1_rd_commit_batch then moves the winner's results to where the
+ * next step reads them.  All pointers are DEVICE pointers.
+ *   state s owns rows s * group .. s * group + group - 1; trial (row r, slot j) is entry [(s * group + r) * nt + j] of
+ *   rate, dist and the optional rate_add: the slot layout every candidate call and every rate call writes.
+ * Trials are visited rows ascending, slots ascending, and each costs
+ *   rd = fma(lambda, (double)(rate + rate_add) / 8.0, (double)dist)
+ * in ONE rounding, as f64::mul_add: rate / 8 is exact and the u64 -> f64 conversion rounds to nearest even, as Rust's
+ * `as f64`.  A slot whose rate is 0xFFFFFFFF (the rate calls' refusal value), or whose 64-bit sum with rate_add reaches
+ * it, is invalid: it costs +infinity and sets invalid_out[s] = 1 (optional; otherwise written 0), whether or not the
+ * rule below looks at the slot.
+ *   R1_PICK_FIRST_MIN: a trial is kept when rd < state.best_rd, strictly: a tie keeps the earlier trial, one kept by an
+ *                      earlier call included.  The mode loop (rate_add = the head's tell_frac difference that
+ *                      r1_coeff_rate_block_batch tells the host to add) and the depth carry of rdo_tx_size_type.
+ *   R1_PICK_TX_TYPE:   (group == 1) rdo_tx_type_decision's loop: cur_best_rd = state.best_rd on entry; when the FIRST
+ *                      slot's rd > cur_best_rd nothing of this call is kept -- later slots are not considered, even one
+ *                      below cur_best_rd; otherwise the call's own first minimum (strict < from f64::MAX) is taken and
+ *                      kept when it is < state.best_rd (rdo.rs:780).  rdo_glue.pick_tx_type is the statement.
+ * A kept trial writes all six fields with best_call = call_id; a state of which nothing is kept is not written.  The
+ * three depths of a block are three calls with call_id 0, 1, 2 on the same state array, each behind its search and
+ * rate launches.
+ * A pick over picks (the mode loop over the states the depth calls left: rate = their best_rate, dist = their best_dist,
+ * gathered) is the CALLER's to guard: a state that kept nothing holds rate 0 and distortion 0 and would cost its
+ * rate_add alone.  Hand such a trial the rate 0xFFFFFFFF (best_call < 0 tells), and it costs +infinity.
+ * R1_EINVAL: a NULL rate, dist or state; n_states < 0; group outside 1..4096; nt outside 1..16; group * nt > 4096; rule
+ * outside 0..1; R1_PICK_TX_TYPE with group != 1; call_id outside 0..127; a lambda that is negative, infinite or NaN.
+ * n_states == 0 returns 0 and touches nothing. */
+typedef struct R1RdPick {      /* 24 bytes; the decision state of one block, carried from call to call */
+  double   best_rd;            /* f64::MAX (DBL_MAX) = nothing kept yet */
+  uint64_t best_dist;          /* the kept trial's distortion (is_zero_dist, rdo.rs:922) */
+  uint32_t best_rate;          /* its rate, rate_add included, 1/8 bit */
+  int16_t  best_row;           /* row inside the state's group in the winning call, -1 = none */
+  int8_t   best_slot;          /* slot j of the winning call, -1 = none */
+  int8_t   best_call;          /* call_id of the winning call, -1 = none */
+} R1RdPick;
+#define R1_PICK_FIRST_MIN 0    /* luma_chroma_mode_rdo / rdo_tx_size_type: keep on rd < best_rd */
+#define R1_PICK_TX_TYPE   1    /* rdo_tx_type_decision's loop, early exit included; needs group == 1 */
+int r1_rd_pick_batch(r1_ctx *ctx, const uint32_t *rate, const uint32_t *rate_add, const uint64_t *dist,
+                     int n_states, int group, int nt, double lambda, int rule, int call_id,
+                     R1RdPick *state, uint8_t *invalid_out, void *stream);
+/* The winner's results where the next step reads them.  The call acts for every state s with
+ * state[s].best_call == call_id; a state won by another call, or by none, has NOTHING of its outputs written, so the
+ * commits of the three depths fill disjoint blocks of the same outputs.  Let t = (s * group + best_row) * nt + best_slot.
+ * Three parts, each present whole (its inputs and outputs non-NULL) or absent (all NULL):
+ *   eobs / qcoeffs -> eob_win / qcoeffs_win: transform block k < ntx of trial t lies at t * ntx + k for order 0 (the
+ *       layout of r1_rdo_intra_split_batch, and of one block per trial) and, with group == 1 and order 1, at
+ *       (s * ntx + k) * nt + best_slot -- the two orders of r1_coeff_rate_chain_batch.  Its eob goes to
+ *       eob_win[s * 16 + k], its coded_area coefficients of coeff_bytes (2 or 4) each to element
+ *       s * win_stride + k * coded_area of qcoeffs_win; win_stride >= ntx * coded_area.  Both coefficient arrays are
+ *       aligned to coeff_bytes, as arrays of that type are; where both are 16-byte aligned and win_stride * coeff_bytes
+ *       is a multiple of 16 the blocks move in 16-byte pieces.
+ *   side -> side_win: side_bytes (1..128) bytes per trial at t * side_bytes go to side_win + s * side_bytes: ctx_out of
+ *       the chain or block rate call, or cul_level.
+ *   rec_trials -> rec: the dense bw x bh block of trial t in the plane's pixel type (rec_out of the candidate calls;
+ *       the array 16-byte aligned) goes to `rec` at (pos_xy[2s], pos_xy[2s + 1]), clipped to [0, store_w) x
+ *       [0, store_h): nothing outside that rectangle and nothing outside the plane's allocation is written.  The blocks
+ *       of one call MUST NOT overlap: overlapping pixels would be stored in no defined order.
+ * R1_EINVAL: a part with only some of its pointers; n_states < 0; group / nt / call_id as for the pick; ntx outside
+ * 1..16; order outside 0..1, or 1 with group != 1; coeff_bytes not 2 or 4; coded_area outside 16..1024; win_stride
+ * below ntx * coded_area; side_bytes outside 1..128; bw / bh that are no block size up to 64x64; a plane whose
+ * bytes_per_px / bit_depth are not 1 / 8 or 2 / 10, 12; store_w above stride - xorigin or store_h above alloc_height -
+ * yorigin (the visible plane plus its right and bottom padding as the allocation holds it), or negative; and two
+ * alignments the kernel's loads rest on: rec_trials not 16-byte aligned (the dense blocks are read in 16-byte pieces;
+ * rec_out of the candidate calls is), qcoeffs or qcoeffs_win not aligned to coeff_bytes.  n_states == 0 returns 0.
+ * Device-resident faults: a best_row >= group or best_slot >= nt found in the state writes nothing for that state;
+ * every loop is bounded by the arguments, never by data.  No atomics, no spin-waits. */
+int r1_rd_commit_batch(r1_ctx *ctx, const R1RdPick *state, int n_states, int call_id, int group, int nt,
+                       int ntx, int order, int coded_area, int coeff_bytes,
+                       const uint16_t *eobs, const void *qcoeffs, const void *side, int side_bytes,
+                       const void *rec_trials, int bw, int bh, const R1Plane *rec, const int16_t *pos_xy,
+                       int store_w, int store_h,
+                       uint16_t *eob_win, void *qcoeffs_win, int win_stride, void *side_win, void *stream);
 
 /* ---- multi-GPU: the tile-boundary exchange and the reference-frame all-gather (RCCL over
  * xGMI), SURVEY.md 8(e).  One process (or host thread) per GPU, tile r on rank r.  Rendezvous:

@@ -13,8 +13,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .types import (BLOCK_CHAIN_CTX, BLOCK_RATE_TRIAL, COEFF_CDFS, COEFF_RATE_INVALID, TX_DIMS, TXB_CHAIN_CTX, TXB_CTX,  # noqa: F401
-                    TxSize, valid_av1_transform)
+from .types import (BLOCK_CHAIN_CTX, BLOCK_RATE_TRIAL, COEFF_CDFS, COEFF_RATE_INVALID, PICK_FIRST_MIN, PICK_TX_TYPE,  # noqa: F401
+                    RD_PICK, TX_DIMS, TXB_CHAIN_CTX, TXB_CTX, TxSize, valid_av1_transform)
 
 DIST_CAND = np.dtype([("ox", "<i2"), ("oy", "<i2"), ("rx", "<i2"), ("ry", "<i2")])
 MC_CAND = np.dtype([("rx", "<i2"), ("ry", "<i2"), ("col_frac", "u1"), ("row_frac", "u1"),
@@ -1177,6 +1177,93 @@ class Context:
             int(bool(is_inter)), int(bool(use_reduced_tx_set)), dbl.data_ptr(), n_blocks, dcdf.data_ptr(), n_cdfs,
             ptr["rate"], ptr["plane_rate"], ptr["rng"], ptr["cul_level"], ptr["ctx"], _stream_ptr()),
             "r1_coeff_rate_block_batch")
+        return o
+
+    @staticmethod
+    def rd_pick_state(n):
+        """n initial R1RdPick states -- (f64::MAX, 0, 0, -1, -1, -1): nothing kept yet -- as an (n, 24) uint8 device
+        tensor (RD_PICK records; .cpu().numpy().view(RD_PICK) reads them)"""
+        import sys
+        st = np.zeros(n, RD_PICK)
+        st["best_rd"], st["best_row"], st["best_slot"], st["best_call"] = sys.float_info.max, -1, -1, -1
+        return torch.from_numpy(st.view(np.uint8).reshape(n, RD_PICK.itemsize)).cuda()
+
+    def rd_pick_batch(self, rate, dist, state, group, nt, lam, rule=PICK_FIRST_MIN, call_id=0, rate_add=None,
+                      want_invalid=False, outs=None):
+        """r1_rd_pick_batch: compute_rd_cost (src/rdo.rs:718-723) of every trial and the reference's comparison, on
+        the current stream behind the launches that made `rate` and `dist`, no copy.
+        rate / rate_add: 4-byte device tensors of n_states * group * nt entries (uint32 1/8 bits; the rate calls'
+        outputs as they lie), dist: 8-byte (uint64).  state: (n_states, 24) uint8 device tensor (rd_pick_state),
+        updated in place.  rule: PICK_FIRST_MIN, or PICK_TX_TYPE (group == 1: rdo_tx_type_decision's loop with its
+        early exit).  -> {"state": state, "invalid": (n_states,) uint8 when wanted}"""
+        n = state.numel() // RD_PICK.itemsize
+        assert state.is_cuda and state.is_contiguous() and state.element_size() == 1
+        for t, size in ((rate, 4), (dist, 8)) + (((rate_add, 4),) if rate_add is not None else ()):
+            assert t.is_cuda and t.is_contiguous() and t.element_size() == size and t.numel() == n * group * nt, \
+                (t.shape, t.dtype, n, group, nt)
+        o, ptr = _bind_wanted(outs, {"invalid": (want_invalid, (n,), torch.uint8)}, state.device)
+        o["state"] = state
+        self._check(self.lib.r1_rd_pick_batch(
+            self.h, rate.data_ptr(), rate_add.data_ptr() if rate_add is not None else None, dist.data_ptr(), n,
+            int(group), int(nt), float(lam), int(rule), int(call_id), state.data_ptr(), ptr["invalid"], _stream_ptr()),
+            "r1_rd_pick_batch")
+        return o
+
+    def rd_commit_batch(self, state, call_id, group, nt, coeffs=None, ntx=1, order=0, side=None, rec_trials=None,
+                        rec=None, pos_xy=None, store_w=None, store_h=None, outs=None):
+        """r1_rd_commit_batch: for every state the call `call_id` won, the winner's results where the next step
+        reads them; states won by another call or by none keep what `outs` holds.
+        coeffs: (eobs, qcoeffs) as the candidate calls wrote them -- transform block k of trial t at t * ntx + k
+        (order 0) or, group == 1, at (s * ntx + k) * nt + slot (order 1) -> outs["eob_win"] (n, 16) int16,
+        outs["qcoeffs_win"] (n, win_stride) in the coefficients' type (allocated (n, ntx * coded area) when not handed
+        in; the commits of several depths share one of the largest depth's stride).
+        side: (trials, side_bytes) uint8 -> outs["side_win"] (n, side_bytes).
+        rec_trials: (trials, bh, bw) dense blocks in the plane's pixel type -> `rec` (a Plane) at pos_xy ((n, 2) int16
+        device tensor), clipped to store_w x store_h (the plane's visible size by default); blocks must not overlap."""
+        n = state.numel() // RD_PICK.itemsize
+        assert state.is_cuda and state.is_contiguous() and state.element_size() == 1
+        o = dict(outs) if outs else {}
+        eobs = qc = None
+        area = cbytes = stride = 0
+        if coeffs is not None:
+            eobs, qc = coeffs
+            _check_coeffs(qc, eobs)
+            assert qc.numel() % eobs.numel() == 0 and eobs.numel() == n * group * nt * ntx, (eobs.shape, n, group, nt, ntx)
+            area, cbytes = qc.numel() // eobs.numel(), qc.element_size()
+            if "eob_win" not in o:
+                o["eob_win"] = torch.zeros((n, 16), dtype=torch.int16, device=state.device)
+            if "qcoeffs_win" not in o:
+                o["qcoeffs_win"] = torch.zeros((n, ntx * area), dtype=qc.dtype, device=state.device)
+            qw = o["qcoeffs_win"]
+            assert qw.dtype == qc.dtype and qw.dim() == 2 and qw.shape[0] == n and qw.stride(1) == 1, qw.shape
+            assert o["eob_win"].is_contiguous() and o["eob_win"].numel() == n * 16 and o["eob_win"].element_size() == 2
+            stride = qw.stride(0)
+        side_bytes = 0
+        if side is not None:
+            assert side.is_cuda and side.is_contiguous() and side.element_size() == 1 and side.numel() % (n * group * nt) == 0
+            side_bytes = side.numel() // (n * group * nt)
+            if "side_win" not in o:
+                o["side_win"] = torch.zeros((n, side_bytes), dtype=torch.uint8, device=state.device)
+            assert o["side_win"].is_contiguous() and o["side_win"].numel() == n * side_bytes
+        bw = bh = 0
+        pr = None
+        if rec_trials is not None:
+            assert rec_trials.is_cuda and rec_trials.is_contiguous() and rec_trials.element_size() == rec.bpp
+            bh, bw = rec_trials.shape[-2:]
+            assert rec_trials.numel() == n * group * nt * bw * bh, (rec_trials.shape, n, group, nt)
+            assert pos_xy.is_cuda and pos_xy.is_contiguous() and pos_xy.element_size() == 2 and pos_xy.numel() == 2 * n
+            pr = rec.cstruct()
+            store_w = rec.width if store_w is None else store_w
+            store_h = rec.height if store_h is None else store_h
+        self._check(self.lib.r1_rd_commit_batch(
+            self.h, state.data_ptr(), n, int(call_id), int(group), int(nt), int(ntx), int(order), int(area), int(cbytes),
+            eobs.data_ptr() if eobs is not None else None, qc.data_ptr() if qc is not None else None,
+            side.data_ptr() if side is not None else None, int(side_bytes),
+            rec_trials.data_ptr() if rec_trials is not None else None, int(bw), int(bh),
+            C.byref(pr) if pr is not None else None, pos_xy.data_ptr() if rec_trials is not None else None,
+            int(store_w or 0), int(store_h or 0), o["eob_win"].data_ptr() if eobs is not None else None,
+            o["qcoeffs_win"].data_ptr() if eobs is not None else None, int(stride),
+            o["side_win"].data_ptr() if side is not None else None, _stream_ptr()), "r1_rd_commit_batch")
         return o
 
     # ---- lrf:: ----

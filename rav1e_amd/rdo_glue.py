@@ -39,6 +39,11 @@ the kernels by executing the reference's own text (tests/golden/gen_rdo_glue_ref
                              pinned by tests/golden/rdo_intra_split_ref.npz / tests/test_rdo_intra_split_ref.py
   pick_tx_type               src/rdo.rs:1801-1818     (the tail of rdo_tx_type_decision's loop on the device's rates)
                              both pinned by tests/golden/coeff_rate_ref.npz / tests/test_coeff_rate_ref.py
+  pick_first_min             src/rdo.rs:923-938, 780-784   (`rd < best.rd_cost`: the mode loop and the depth carry)
+  tx_size_type_decision      src/rdo.rs:748-799       (rdo_tx_size_type's loop over the depths, over pick_tx_type)
+  dist_as_f64                src/rdo.rs:722           (`distortion.0 as f64`, applied by the two above before they cost)
+                             the host statements of r1_rd_pick_batch; pinned by tests/golden/rd_pick_ref.npz /
+                             tests/test_rd_pick_ref.py
 """
 from .types import BlockSize, TxSize
 
@@ -388,6 +393,15 @@ def compute_rd_cost(lam, rate, distortion):
     return float(Fraction(float(lam)) * Fraction(int(rate), 8) + Fraction(int(distortion)))
 
 
+def dist_as_f64(distortion):
+    """`distortion.0 as f64` (src/rdo.rs:722): the u64 distortion rounded to the nearest f64, ties to even, returned
+    as the integer that f64 holds.  The reference converts BEFORE its fused multiply-add, so from 2^53 on its cost
+    has two roundings; compute_rd_cost above adds the integer it is given exactly.  The statements r1_rd_pick_batch
+    is held to (pick_first_min, tx_size_type_decision) therefore hand compute_rd_cost / pick_tx_type
+    dist_as_f64(dist): below 2^53 that is dist itself"""
+    return int(float(int(distortion)))
+
+
 def pick_restoration_filter(options, lam, best_cost=-1.0):
     """The choice of one restoration unit (src/rdo.rs:2617-2745).  options: [(rate, err)] in the order the leg tries
     them -- the no-filter option first, then one per parameter set, err = what r1_lrf_search_batch returned, rate =
@@ -549,3 +563,36 @@ def pick_tx_type(rates, dists, lam, cur_best_rd):
         if rd < best_rd:
             best, best_rd = j, rd
     return best, best_rd
+
+
+RATE_INVALID = 0xFFFFFFFF   # the rate calls' refusal value; r1_rd_pick_batch costs such a slot +infinity
+
+
+def pick_first_min(rates, dists, lam, best=None, rate_adds=None):
+    """`rd < best.rd_cost` over trials in order (luma_chroma_mode_rdo, src/rdo.rs:923-938; the carry across depths of
+    rdo_tx_size_type, 780-784): a trial is kept on strict `<`, so a tie keeps the earlier one -- one kept before
+    included.  best: (index, rd, rate, dist) carried in, None = (None, f64::MAX, 0, 0).  rate_adds: what the host adds
+    per trial (the head's tell_frac difference).  A rate of RATE_INVALID, or a sum that reaches it, costs +infinity.
+    -> (index kept or the one carried in, its rd, its rate with the addition, its dist)"""
+    import sys
+    idx, best_rd, best_rate, best_dist = best if best is not None else (None, sys.float_info.max, 0, 0)
+    for i, (rate, dist) in enumerate(zip(rates, dists)):
+        rate = int(rate) + (int(rate_adds[i]) if rate_adds is not None else 0)
+        rd = float("inf") if rate >= RATE_INVALID else compute_rd_cost(lam, rate, dist_as_f64(dist))
+        if rd < best_rd:
+            idx, best_rd, best_rate, best_dist = i, rd, rate, int(dist)
+    return idx, best_rd, best_rate, best_dist
+
+
+def tx_size_type_decision(per_depth_rates, per_depth_dists, lam):
+    """rdo_tx_size_type's loop over the transform depths (src/rdo.rs:748-799): depth d runs rdo_tx_type_decision with
+    cur_best_rd = the rd kept so far -- pick_tx_type, early exit included -- and its result replaces what is kept when
+    its rd is strictly below (780).  per_depth_rates[d] / per_depth_dists[d]: the slots of depth d in slot order.
+    -> (depth kept, slot kept, rd); (None, None, f64::MAX) when no depth kept anything"""
+    import sys
+    best_depth, best_slot, best_rd = None, None, sys.float_info.max
+    for depth, (rates, dists) in enumerate(zip(per_depth_rates, per_depth_dists)):
+        slot, rd = pick_tx_type(rates, [dist_as_f64(d) for d in dists], lam, best_rd)
+        if slot is not None and rd < best_rd:
+            best_depth, best_slot, best_rd = depth, slot, rd
+    return best_depth, best_slot, best_rd

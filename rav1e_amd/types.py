@@ -143,3 +143,8 @@ BLOCK_CHAIN_CTX = np.dtype([("ctx", "u1", (3, 2, 16)), ("mi_w", "u1"), ("mi_h", 
                             ("cdf_sel", "u1"), ("cdf_sel_uv", "u1"), ("reserved", "u1", (3,))])
 BLOCK_RATE_TRIAL = np.dtype([("first_y", "<u4"), ("first_u", "<u4"), ("first_v", "<u4"), ("block", "<u4"), ("rng", "<u2"),
                              ("tx_type", "u1"), ("uv_tx_type", "u1"), ("do_chroma", "u1"), ("reserved", "u1", (3,))])
+# R1RdPick (r1_rd_pick_batch / r1_rd_commit_batch): the decision state of one block, carried from call to call
+RD_PICK = np.dtype([("best_rd", "<f8"), ("best_dist", "<u8"), ("best_rate", "<u4"), ("best_row", "<i2"),
+                    ("best_slot", "i1"), ("best_call", "i1")])
+assert RD_PICK.itemsize == 24
+PICK_FIRST_MIN, PICK_TX_TYPE = 0, 1   # R1_PICK_*

@@ -115,6 +115,11 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
   // forward-transform shifts of this (size, bit depth): immediates
   constexpr int SH0 = r1tx::fwd_shift_ct(WL, HL, BD, 0), SH1 = r1tx::fwd_shift_ct(WL, HL, BD, 1),
                 SH2 = r1tx::fwd_shift_ct(WL, HL, BD, 2);
+  // COL_FOLD (rdo_cand_plan.hpp): phase C runs the column family, whose outputs already carry shift[1] -- the tile
+  // stores then shift by SH1C = 0
+  constexpr bool COL_FOLD = PL::COL_FOLD;
+  static_assert(!COL_FOLD || SH0 > 0, "the column family starts from a pending shift[0]");
+  constexpr int SH1C = COL_FOLD ? 0 : SH1;
   __shared__ __attribute__((aligned(16))) uint8_t smem[LDS_BYTES];
   T *buf = (T *)smem;
   TB *tbuf = (TB *)smem;
@@ -498,15 +503,20 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
         v[H - 1 - r] = ud ? t0 : t1;
       }
     }
+    if constexpr (COL_FOLD) {   // shift[0], the network and shift[1] as one: the column family on the unshifted residuals
+      if (TX_VOTE && col_uni) r1tx::fwd_col_m24_kernel<H, SH0, SH1>(v, r1tx::vtx_1d(tx_s));
+      else r1tx::fwd_col_m24<H, SH0, SH1>(v, r1tx::vtx_1d(tx_col));
+    } else {
 #pragma unroll
-    for (int r = 0; r < H; r++) v[r] = r1tx::shift_fwd_ct<SH0>(v[r]);
-    if (TX_VOTE && col_uni) r1tx::fwd_1d_m24_kernel<H>(v, r1tx::vtx_1d(tx_s));
-    else r1tx::fwd_1d_m24<H>(v, r1tx::vtx_1d(tx_col));
+      for (int r = 0; r < H; r++) v[r] = r1tx::shift_fwd_ct<SH0>(v[r]);
+      if (TX_VOTE && col_uni) r1tx::fwd_1d_m24_kernel<H>(v, r1tx::vtx_1d(tx_s));
+      else r1tx::fwd_1d_m24<H>(v, r1tx::vtx_1d(tx_col));
+    }
     if constexpr (!SPLIT_T) {
       const int cc = cl * W + (r1tx::lr_flip(tx_col) ? W - 1 - c : c);
 #pragma unroll
       for (int r = 0; r < HU; r++)
-        tkeep[r * LSTRIDE + cc] = (TB)r1tx::shift_fwd_ct<SH1>(v[r]);
+        tkeep[r * LSTRIDE + cc] = (TB)r1tx::shift_fwd_ct<SH1C>(v[r]);
     }
   }
   if constexpr (!SPLIT_T) __syncthreads();
@@ -535,7 +545,7 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
       if (col_live) {
 #pragma unroll
         for (int rr = 0; rr < 32; rr++)
-          tbuf[rr * LSTRIDE + cc] = (TB)r1tx::shift_fwd_ct<SH1>(v[half * 32 + rr]);
+          tbuf[rr * LSTRIDE + cc] = (TB)r1tx::shift_fwd_ct<SH1C>(v[half * 32 + rr]);
       }
       __syncthreads();
       if (row_live && (r >> 5) == half) {

@@ -92,6 +92,24 @@ constexpr bool rdo_tx_vote(int wl, int hl, int qm, bool mt, int ps) {
   return qm == 0 && !mt && ps == 0 && wl <= 4 && hl <= 4;
 }
 
+// Whether an instantiation's column pass (phase C) runs the column family of the 1-D networks (fwd_col_m24,
+// tx_common.hpp: unshifted residuals in, shift[1] already applied on the way out) instead of shift[0], the plain
+// network and shift[1].  At 12 bits shift[0] is 0 and there is nothing pending.  Elsewhere the family is taken only
+// where its launch was measured faster, every folded pass against every plain pass of a same-box A/B, in two
+// sessions (profiles/r19_colfold_notes.md): the coefficient kernels at 8x8 / 16x16 / 32x32 (8 bits -1.6 / -2.0 /
+// -1.0 %) and 16x16 / 32x32 (10 bits -1.1 / -1.6 %), and the 8-bit transform-domain chain at 8x8 / 16x16 (-1.4 %
+// each).  Measured and not faster, so on the plain column with the code they had: 64x64 at both depths (8 bits: 95
+// VALU instructions fewer per wave, 2.3 %, and the launch within +-0.4 % -- what identical kernels differ by between
+// two builds), 10-bit 8x8, the 8-bit QM 1 chain at 32x32 / 64x64 (+0.3 / +1.3 %), the 8-bit pixel-domain chain at
+// every size (+0.7 % at 64x64).  Not measured, so on the plain column too: the rectangular sizes, 4x4, the type
+// search (MT), the intra prediction source and the 10-bit quantizer chains; of those, 20 would also have lost a
+// waves-per-SIMD step or gained scratch (tools/kres.py).
+constexpr bool rdo_col_fold(int bd, int wl, int hl, int qm, bool mt, int ps) {
+  if (mt || ps != 0 || wl != hl) return false;
+  if (bd == 8) return qm == 0 ? (wl >= 3 && wl <= 5) : (qm == 1 && (wl == 3 || wl == 4));
+  return bd == 10 && qm == 0 && (wl == 4 || wl == 5);
+}
+
 // ---- one instantiation: geometry, choices, LDS layout ----
 // PS: where the prediction comes from -- 0 = put_8tap of the reference window (or the dense qa.pred_in buffer),
 // 1 = intra prediction from the candidate's edge set.  One wave per workgroup; a wave owns NC candidates.
@@ -102,6 +120,7 @@ struct RdoCandPlan {
   static constexpr int W = 1 << WL, H = 1 << HL;
   static constexpr int P = W > H ? W : H, NC = 64 / P;
   static constexpr int TS = (W < H ? W : H) == 4 ? 4 : 8;
+  static constexpr bool COL_FOLD = rdo_col_fold(BD, WL, HL, QM, MT, PS);
   static constexpr int WS = r1mc::window_stride(W, BPP);
   // INTRA: no reference window.  The candidate's edge arrays (raw edge + the four filter / upsample arrays, FL
   // entries each) take its place and may lie over the WHOLE allocation: the source block waits in registers until

@@ -55,6 +55,37 @@ __device__ __forceinline__ T mul_rs(T a) {
 }
 #define TX_MUL(a, m, s) (mul_rs<(m), (s)>(a))
 #include "fwd_tx_1d.inc"
+// The column family (fwd_tx_1d_col.inc, tools/gen_tx1d.py fold()): r1_<net>_col<K0, S> takes the residuals unshifted
+// and returns round_shift(r1_<net>(c << K0), S); a value is carried as (reg, k), value = reg * 2^k, so shift[0] and
+// the halvings of the first levels are never executed.  The factor of every mad is the plain network's divided by
+// 2^k: the 24-bit range proof above carries over (the generator asserts it per network).
+// mul_rs on a value with pending scale K: floor((X 2^K M + 2^(S-1)) / 2^S) = floor((X M + 2^(S-1-K)) / 2^(S-K))
+template <int M, int S, int K>
+__device__ __forceinline__ T mul_rk(T a) {
+  static_assert(K >= 1 && K <= S - 1, "the rounding term stays an integer");
+  T r;
+  asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(M), "v"(1 << (S - 1 - K)));
+  return r >> (S - K);
+}
+// a - (b << D) as one mad by -2^D (an inline constant)
+template <int D>
+__device__ __forceinline__ T shl_subr(T b, T a) {
+  static_assert(D >= 1 && D <= 4, "-2^D is an inline constant");
+  T r;
+  asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r) : "v"(b), "n"(-(1 << D)), "v"(a));
+  return r;
+}
+#define TX_MULK(a, m, s, k) (mul_rk<(m), (s), (k)>(a))
+#define TX_SHL(a, d) ((T)((uint32_t)(a) << (d)))
+#define TX_SHL_ADD(a, d, b) ((T)(((uint32_t)(a) << (d)) + (uint32_t)(b)))
+#define TX_SHL_SUBR(b, d, a) (shl_subr<(d)>((b), (a)))
+#define TX_RND(a, s) (((a) + (1 << ((s) - 1))) >> (s))
+#include "fwd_tx_1d_col.inc"
+#undef TX_MULK
+#undef TX_SHL
+#undef TX_SHL_ADD
+#undef TX_SHL_SUBR
+#undef TX_RND
 #undef TX_MUL
 }  // namespace m24
 #undef TX1D_FN
@@ -186,6 +217,51 @@ __device__ __forceinline__ void fwd_1d_m24_kernel(T *c, int k) {
     m24::r1_fdct64(c);
   }
 }
+
+// The column pass of the fused kernels in one piece: c[r] = shift_fwd_ct<SH1>(fwd_1d_m24<N>(shift_fwd_ct<SH0>(c))[r]),
+// bit for bit, on the column family -- the inputs are the unshifted residuals, the outputs go to the transpose tile
+// as they are.  SH0 > 0 (8 and 10 bits); the WHT (4-point, k == 4) keeps the plain network between its shifts, the
+// identity is one exact shift when shift[0] covers the rounding (it does at every size).  IDENT: the per-lane form
+// with the identity's arm; without it the switch is fwd_1d_m24_kernel's (wave-uniform class, every arm writes all of c).
+template <int SH0, int SH1>
+__device__ __forceinline__ T shift_col_ident(T v) {
+  if constexpr (SH0 + SH1 >= 0) return shift_fwd_ct<SH0 + SH1>(v);
+  else return shift_fwd_ct<SH1>(shift_fwd_ct<SH0>(v));
+}
+template <int N, int SH0, int SH1, bool IDENT>
+__device__ __forceinline__ void fwd_col_m24_sw(T *c, int k) {
+  static_assert(SH0 > 0 && SH1 <= 0, "shift[0] = 0 and a left shift[1] have no member in the column family");
+  constexpr int S = -SH1;
+  if constexpr (IDENT) {
+    if (k == 3) {
+#pragma unroll
+      for (int r = 0; r < N; r++) c[r] = shift_col_ident<SH0, SH1>(c[r]);
+      return;
+    }
+  }
+  if constexpr (N == 4) {
+    if (k == 0) m24::r1_fdct4_col<SH0, S>(c);
+    else if (k == 4) {
+#pragma unroll
+      for (int r = 0; r < N; r++) c[r] = shift_fwd_ct<SH0>(c[r]);
+      m24::r1_fwht4(c);
+#pragma unroll
+      for (int r = 0; r < N; r++) c[r] = shift_fwd_ct<SH1>(c[r]);
+    } else m24::r1_fdst_vii_4_col<SH0, S>(c);
+  } else if constexpr (N == 8) {
+    if (k == 0) m24::r1_fdct8_col<SH0, S>(c); else m24::r1_fdst8_col<SH0, S>(c);
+  } else if constexpr (N == 16) {
+    if (k == 0) m24::r1_fdct16_col<SH0, S>(c); else m24::r1_fdst16_col<SH0, S>(c);
+  } else if constexpr (N == 32) {
+    m24::r1_fdct32_col<SH0, S>(c);
+  } else {
+    m24::r1_fdct64_col<SH0, S>(c);
+  }
+}
+template <int N, int SH0, int SH1>
+__device__ __forceinline__ void fwd_col_m24(T *c, int k) { fwd_col_m24_sw<N, SH0, SH1, true>(c, k); }
+template <int N, int SH0, int SH1>
+__device__ __forceinline__ void fwd_col_m24_kernel(T *c, int k) { fwd_col_m24_sw<N, SH0, SH1, false>(c, k); }
 
 // One 1-D forward transform of length N on a register array, class `k`
 // (0 DCT, 1/2 ADST (flip handled by the caller), 3 identity, 4 WHT).

@@ -125,7 +125,8 @@ const char *r1_last_error(void);
  * intra transform-split candidate (r1_rdo_intra_split_batch, R1IntraSplitCand), the coefficient rate across a
  * block's transform blocks (r1_coeff_rate_chain_batch, R1TxbChainCtx) and across its three planes on one writer
  * (r1_coeff_rate_block_batch, R1BlockChainCtx, R1BlockRateTrial), and the decision on the device (r1_rd_pick_batch,
- * r1_rd_commit_batch, R1RdPick). */
+ * r1_rd_commit_batch, R1RdPick), and the device-resident coefficient CDF context (r1_coeff_cdf_slice_batch,
+ * r1_coeff_cdf_adapt_batch, R1CoeffCdfContext). */
 int r1_abi_version(void);
 
 /* ---- dist:: (reference: src/dist.rs get_sad 31, get_satd 156; dispatch
@@ -1203,6 +1204,7 @@ typedef struct R1TxbCtx { uint8_t txb_skip_ctx, dc_sign_ctx, y_mode, cdf_sel; } 
  * txb_skip_ctx / dc_sign_ctx / y_mode is out of range or whose cdf_sel >= n_cdfs gets rate 0xFFFFFFFF and cul_level 0,
  * and nothing is read out of bounds.  Every loop of the kernel is bounded independently of the data's values.
  * Blocks that write_tx_tree / write_tx_blocks code as several transform blocks: r1_coeff_rate_chain_batch below.
+ * Snapshots cut on the device from a context that carries the winners' adaptation: r1_coeff_cdf_slice_batch below.
  * OUT OF SCOPE: every non-coefficient symbol (modes, motion vectors, partition, count_lrf_switchable). */
 int r1_coeff_rate_batch(r1_ctx *ctx, const void *qcoeffs, int coeff_bytes, const uint16_t *eobs, int n,
                         uint32_t tx_type_mask, int tx_size, int plane, int is_inter, int use_reduced_tx_set,
@@ -1244,7 +1246,8 @@ int r1_coeff_rate_batch(r1_ctx *ctx, const void *qcoeffs, int coeff_bytes, const
  * Every loop is bounded by ntx, the coded area, the four base-range rounds or the Golomb length.
  * The chroma half of write_tx_blocks / write_tx_tree (other R1CoeffCdfs slices, U then V behind luma on the same
  * writer): r1_coeff_rate_block_batch below.
- * OUT OF SCOPE: every non-coefficient symbol; exporting the adapted CDFs; making the serial range-coder chain itself faster. */
+ * The adapted CDFs are dropped here; r1_coeff_cdf_adapt_batch below keeps a block's winner's on a device-resident context.
+ * OUT OF SCOPE: every non-coefficient symbol; making the serial range-coder chain itself faster. */
 typedef struct R1TxbChainCtx {          /* 40 bytes */
   uint8_t above[16];   /* above_coeff_context[0][bo.x + c], c < bw / 4: the state in front of the block */
   uint8_t left[16];    /* left_coeff_context[0][bo.y_in_sb() + r], r < bh / 4 */
@@ -1308,7 +1311,9 @@ int r1_coeff_rate_chain_batch(r1_ctx *ctx, const void *qcoeffs, int coeff_bytes,
  * above the coded area in a coded transform block, y_mode >= 13, cdf_sel / cdf_sel_uv >= n_cdfs, rng < 0x8000, mi_w > clip_w4 or mi_h > clip_h4, a coded chroma
  * transform block at or beyond clip_uv_w4 / clip_uv_h4.
  * Every loop is bounded by ntx, the coded area, the four base-range rounds or the Golomb length; no spin-waits, no atomics.
- * OUT OF SCOPE: the head symbols themselves (the host's dozen); exporting the adapted CDFs; skip = true (no coefficient
+ * The adapted CDFs are dropped here: r1_coeff_cdf_adapt_batch below replays the winner on a device-resident
+ * R1CoeffCdfContext and leaves it adapted; r1_coeff_cdf_slice_batch cuts this call's `cdfs` out of one.
+ * OUT OF SCOPE: the head symbols themselves (the host's dozen); skip = true (no coefficient
  * is written); making the serial range-coder chain itself faster. */
 typedef struct R1BlockChainCtx {        /* 108 bytes */
   uint8_t ctx[3][2][16];  /* [plane][0: above, 1: left][16]: above_coeff_context[p][(tx_bo.x >> xdec) + c] and
@@ -1410,6 +1415,77 @@ int r1_rd_commit_batch(r1_ctx *ctx, const R1RdPick *state, int n_states, int cal
                        const void *rec_trials, int bw, int bh, const R1Plane *rec, const int16_t *pos_xy,
                        int store_w, int store_h,
                        uint16_t *eob_win, void *qcoeffs_win, int win_stride, void *side_win, void *stream);
+
+/* ---- the adapted coefficient CDFs carried from block to block on the device (added under ABI 7): the rate calls
+ * above start from R1CoeffCdfs snapshots and never write them, so a host that wants block k + 1 measured against what
+ * block k's winner left would have to download the winner, adapt its own CDFContext and upload fresh slices.  These two
+ * calls keep the state on the device instead: a context holds the coefficient side of the reference's CDFContext,
+ * r1_coeff_cdf_slice_batch cuts the slices the rate calls take out of it, and r1_coeff_cdf_adapt_batch replays a
+ * block's winner on it and leaves it adapted.  Per block, on one stream with nothing read back:
+ *     slice -> rates (cdf_sel = the context's index) -> pick -> commit -> adapt (gated by the pick's state).
+ * A rollback (rdo_partition_decision codes sub-block after sub-block and rolls everything back) is the caller's
+ * device copy of the struct.  Head symbols use CDFs the coefficients never touch; they stay the host's.
+ * R1CoeffCdfContext: every field write_coeffs_lv_map and write_tx_type can touch, in the reference's shapes
+ * (src/context/cdf_context.rs:23-96; [TxSize::TX_SIZES = 5][PLANE_TYPES = 2], TX_SIZE_SQR_CONTEXTS = 4), so a host
+ * fills it field by field.  The padding is never read and never written. */
+typedef struct R1CoeffCdfContext {      /* 7872 bytes */
+  uint16_t txb_skip[5][R1_TXB_SKIP_CONTEXTS][2];
+  uint16_t eob_extra[5][2][R1_EOB_COEF_CONTEXTS][2];
+  uint16_t coeff_base_eob[5][2][R1_SIG_COEF_CONTEXTS_EOB][3];
+  uint16_t coeff_base[5][2][R1_SIG_COEF_CONTEXTS][4];
+  uint16_t coeff_br[5][2][R1_LEVEL_CONTEXTS][R1_BR_CDF_SIZE];
+  uint16_t dc_sign[2][R1_DC_SIGN_CONTEXTS][2];
+  uint16_t eob_flag16[2][2][5];
+  uint16_t eob_flag32[2][2][6];
+  uint16_t eob_flag64[2][2][7];
+  uint16_t eob_flag128[2][2][8];
+  uint16_t eob_flag256[2][2][9];
+  uint16_t eob_flag512[2][2][10];
+  uint16_t eob_flag1024[2][2][11];
+  uint16_t intra_tx_1[4][R1_INTRA_MODES][7];
+  uint16_t intra_tx_2[4][R1_INTRA_MODES][5];
+  uint16_t inter_tx_1[4][16];
+  uint16_t inter_tx_2[4][12];
+  uint16_t inter_tx_3[4][2];
+  uint16_t pad[6];                      /* to a multiple of 16 bytes */
+} R1CoeffCdfContext;
+/* slices_out[i] = the R1CoeffCdfs slice of contexts[i] that the three rate calls take for (tx_size, plane_type,
+ * is_inter, use_reduced_tx_set), i < n: txs_ctx = get_txsize_entropy_ctx(tx_size); txb_skip[txs_ctx];
+ * eob_flag{16 << min(area_log2 - 4, 6)}[plane_type]; eob_extra, coeff_base_eob, coeff_base[txs_ctx][plane_type];
+ * coeff_br[min(txs_ctx, 3)][plane_type]; dc_sign[plane_type]; for plane_type 0 and a set of more than one type, the
+ * table of get_tx_set_index at tx_size.sqr(): all 13 rows of intra_tx_1 / intra_tx_2, or row 0 from inter_tx_1 / 2 / 3.
+ * Every slice entry the rule does not fill -- the tail of a row past its CDF's length, tx_type for chroma or a one-type
+ * set -- is written 0.  `contexts` is never written.
+ * R1_EINVAL: a NULL pointer, n < 0, an invalid tx_size, plane_type outside 0..1.  n == 0 returns 0. */
+int r1_coeff_cdf_slice_batch(r1_ctx *ctx, const R1CoeffCdfContext *contexts, int n, int tx_size, int plane_type,
+                             int is_inter, int use_reduced_tx_set, R1CoeffCdfs *slices_out, void *stream);
+/* The winner's replay.  The coefficient, trial and block arguments are r1_coeff_rate_block_batch's, with the same
+ * addressing (first + k * step), so the call reads trial arrays or r1_rd_commit_batch's winner arrays: with
+ * win_stride = 16 * coded_area, transform block k of state s lies at s * 16 + k of both eob_win and qcoeffs_win
+ * (first_y = s * 16, step_y = 1).  In place of cdfs / n_cdfs -- and of blocks[].cdf_sel / cdf_sel_uv, which are ignored
+ * -- trial t reads and adapts contexts[t], in place: one context per trial, no two trials share one.
+ *   state / call_id (optional gate): with state non-NULL, trial t acts only when state[t].best_call == call_id;
+ *                otherwise NOTHING of trial t is written, neither its context nor any output -- the pattern of
+ *                r1_rd_commit_batch, so the calls of the three depths fill disjoint contexts.
+ * Per acting trial what r1_coeff_rate_block_batch does, on the luma slice of contexts[t] (the rule above), then the
+ * chroma one; what the slice holds behind the luma plane is written back to the context, and again behind V.  A plane
+ * writes only the rows it owns: luma txb_skip[txs_ctx] rows 0-6, everything indexed by plane type 0 and the tx-type
+ * table; chroma txb_skip[txs_ctx(uv)] rows 7-12 and everything indexed by plane type 1.  Every other entry of the
+ * context stays bit-identical.
+ *   rate_out (optional) [t]: what r1_coeff_rate_block_batch returns for the trial on the slices cut from contexts[t].
+ *   rng_out (optional) [t], ctx_out (optional, 96 bytes per trial): as there.
+ * R1_EINVAL: what r1_coeff_rate_block_batch refuses on the host (less cdfs, n_cdfs and rate_out), a NULL contexts, a
+ * call_id outside 0..127 with state given.  A trial with one of that call's device-resident faults (less the cdf_sel
+ * ones) leaves contexts[t] untouched and gets rate 0xFFFFFFFF and zero side outputs.
+ * Every loop is bounded as there; no atomics, no spin-waits, one wave per trial.
+ * OUT OF SCOPE: head-symbol CDFs; skip = true; several winners per context in one launch. */
+int r1_coeff_cdf_adapt_batch(r1_ctx *ctx, const void *qcoeffs_y, const uint16_t *eobs_y, int n_txb_y, int step_y,
+                             const void *qcoeffs_u, const uint16_t *eobs_u, const void *qcoeffs_v,
+                             const uint16_t *eobs_v, int n_txb_uv, int step_uv, int coeff_bytes,
+                             const R1BlockRateTrial *trials, int n, int bw, int bh, int tx_size, int xdec, int ydec,
+                             int is_inter, int use_reduced_tx_set, const R1BlockChainCtx *blocks, int n_blocks,
+                             R1CoeffCdfContext *contexts, const R1RdPick *state, int call_id, uint32_t *rate_out,
+                             uint16_t *rng_out, uint8_t *ctx_out, void *stream);
 
 /* ---- multi-GPU: the tile-boundary exchange and the reference-frame all-gather (RCCL over
  * xGMI), SURVEY.md 8(e).  One process (or host thread) per GPU, tile r on rank r.  Rendezvous:

@@ -177,6 +177,9 @@ SYMBOLS = {
     "r1_rd_pick_batch": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, C.c_double, _i, _i, _vp, _vp, _vp]),
     "r1_rd_commit_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _PP, _vp, _i, _i,
                                 _vp, _vp, _i, _vp, _vp]),
+    "r1_coeff_cdf_slice_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "r1_coeff_cdf_adapt_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _i,
+                                      _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "r1_lrf_sgrproj_plane": (_i, [_vp, _PP, _PP, _PP, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "r1_sgrproj_solve_batch": (_i, [_vp, _PP, _PP, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "r1_lrf_search_batch": (_i, [_vp, _PP, _PP, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, C.c_uint32, _vp, _vp, _vp, _vp]),

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .types import (BLOCK_CHAIN_CTX, BLOCK_RATE_TRIAL, COEFF_CDFS, COEFF_RATE_INVALID, PICK_FIRST_MIN, PICK_TX_TYPE,  # noqa: F401
+from .types import (BLOCK_CHAIN_CTX, BLOCK_RATE_TRIAL, COEFF_CDF_CONTEXT, COEFF_CDFS, COEFF_RATE_INVALID, PICK_FIRST_MIN, PICK_TX_TYPE,  # noqa: F401
                     RD_PICK, TX_DIMS, TXB_CHAIN_CTX, TXB_CTX, TxSize, valid_av1_transform)
 
 DIST_CAND = np.dtype([("ox", "<i2"), ("oy", "<i2"), ("rx", "<i2"), ("ry", "<i2")])
@@ -1177,6 +1177,62 @@ class Context:
             int(bool(is_inter)), int(bool(use_reduced_tx_set)), dbl.data_ptr(), n_blocks, dcdf.data_ptr(), n_cdfs,
             ptr["rate"], ptr["plane_rate"], ptr["rng"], ptr["cul_level"], ptr["ctx"], _stream_ptr()),
             "r1_coeff_rate_block_batch")
+        return o
+
+    def coeff_cdf_slice_batch(self, contexts, tx_size, plane_type, is_inter, use_reduced_tx_set=False, out=None):
+        """r1_coeff_cdf_slice_batch: the COEFF_CDFS slice of every context that the rate calls take for (tx_size,
+        plane_type, is_inter, reduced set), cut on the device.  contexts: (n, 7872) uint8 device tensor of
+        COEFF_CDF_CONTEXT records (rdo_glue.coeff_cdf_context), or a NumPy array of them.
+        -> (n, 1088) uint8 device tensor: hand it to a rate call as `cdfs`, cdf_sel = the context's index"""
+        dctx, n = _dev_cands(contexts, COEFF_CDF_CONTEXT)
+        if out is None:
+            out = torch.empty((n, COEFF_CDFS.itemsize), dtype=torch.uint8, device=dctx.device)
+        assert out.is_cuda and out.is_contiguous() and out.element_size() == 1 and out.numel() == n * COEFF_CDFS.itemsize
+        self._check(self.lib.r1_coeff_cdf_slice_batch(
+            self.h, dctx.data_ptr(), n, int(tx_size), int(plane_type), int(bool(is_inter)), int(bool(use_reduced_tx_set)),
+            out.data_ptr(), _stream_ptr()), "r1_coeff_cdf_slice_batch")
+        return out
+
+    def coeff_cdf_adapt_batch(self, qcoeffs_y, eobs_y, step_y, chroma, step_uv, trials, bw, bh, tx_size, xdec, ydec,
+                              is_inter, blocks, contexts, use_reduced_tx_set=False, state=None, call_id=0,
+                              want_rate=True, want_rng=True, want_ctx=True, outs=None):
+        """r1_coeff_cdf_adapt_batch: the winner's replay -- what coeff_rate_block_batch does for every trial, on the
+        slices of contexts[t], which is left adapted in place.  The coefficient, trial and block arguments are
+        coeff_rate_block_batch's (trial arrays, or rd_commit_batch's winner arrays: first_y = s * 16, step 1 with
+        win_stride = 16 * coded area).  contexts: (n, 7872) uint8 device tensor, one COEFF_CDF_CONTEXT per trial.
+        state / call_id: the optional gate -- (n, 24) uint8 device tensor of RD_PICK; trial t acts only when
+        state[t].best_call == call_id, else nothing of it is written.
+        -> {"rate": (n,) int32 holding uint32, "rng": (n,) int16 holding uint16, "ctx": (n, 3, 2, 16) uint8}, all
+        optional"""
+        from . import rdo_glue
+        tw, th = TxSize(tx_size).dims
+        _check_coeffs(qcoeffs_y, eobs_y)
+        area = min(tw, 32) * min(th, 32)
+        assert qcoeffs_y.numel() == eobs_y.numel() * area, (qcoeffs_y.numel(), eobs_y.numel(), area)
+        uv_ptrs, n_uv = [None] * 4, 0
+        if chroma is not None:
+            qu, eu, qv, ev = chroma
+            uw, uh = TxSize(rdo_glue.largest_chroma_tx_size(rdo_glue.block_size(bw, bh), xdec, ydec)).dims
+            for q, e in ((qu, eu), (qv, ev)):
+                _check_coeffs(q, e, qcoeffs_y.dtype)
+                assert q.numel() == e.numel() * uw * uh and e.numel() == eu.numel(), (q.numel(), e.numel(), uw, uh)
+            uv_ptrs, n_uv = [t.data_ptr() for t in (qu, eu, qv, ev)], eu.numel()
+        dtr, n = _dev_cands(trials, BLOCK_RATE_TRIAL)
+        dbl, n_blocks = _dev_cands(blocks, BLOCK_CHAIN_CTX)
+        assert isinstance(contexts, torch.Tensor) and contexts.is_cuda and contexts.is_contiguous() and \
+            contexts.element_size() == 1 and contexts.numel() == n * COEFF_CDF_CONTEXT.itemsize, "one context per trial"
+        if state is not None:
+            assert state.is_cuda and state.is_contiguous() and state.element_size() == 1 and \
+                state.numel() == n * RD_PICK.itemsize
+        o, ptr = _bind_wanted(outs, {"rate": (want_rate, (n,), torch.int32), "rng": (want_rng, (n,), torch.int16),
+                                     "ctx": (want_ctx, (n, 3, 2, 16), torch.uint8)}, qcoeffs_y.device)
+        self._check(self.lib.r1_coeff_cdf_adapt_batch(
+            self.h, qcoeffs_y.data_ptr(), eobs_y.data_ptr(), eobs_y.numel(), int(step_y), *uv_ptrs, n_uv, int(step_uv),
+            qcoeffs_y.element_size(), dtr.data_ptr(), n, int(bw), int(bh), int(tx_size), int(xdec), int(ydec),
+            int(bool(is_inter)), int(bool(use_reduced_tx_set)), dbl.data_ptr(), n_blocks, contexts.data_ptr(),
+            state.data_ptr() if state is not None else None, int(call_id), ptr["rate"], ptr["rng"], ptr["ctx"],
+            _stream_ptr()), "r1_coeff_cdf_adapt_batch")
+        o["contexts"] = contexts
         return o
 
     @staticmethod

@@ -9,6 +9,9 @@
 // write_tx_tree code them with luma_only = false behind the head symbols of the mode decision (src/rdo.rs:855-945,
 // src/encoder.rs:2202-2240): one counter that starts at a handed-over rng, the luma snapshot and then the chroma one in
 // the adapting copy, 96 context bytes (k_coeff_rate_block).
+// r1_coeff_cdf_slice_batch / r1_coeff_cdf_adapt_batch: the CDF state carried from block to block on the device -- the
+// snapshot the calls above take, cut out of an R1CoeffCdfContext, and the whole-block walk once more on the winner, with
+// the adapted rows written back to the context (k_coeff_cdf_slice, k_coeff_cdf_adapt).
 // This is the host half: tables, checks, launch arguments, entry points; the kernels are coeff_rate_kernel.hpp.
 // Restated from the reference (pinned by tests/golden/coeff_rate_ref.npz through every fixture case):
 //  av1_tx_ind / num_tx_set (transform_unit.rs:36-58) as the host tables below.
@@ -43,13 +46,19 @@ static int rate_shape(r1_ctx *ctx, int tx_size, int plane, int is_inter, int use
   return set;
 }
 
-// The checks the three entry points share -- the context, the coefficient width, the transform size, the snapshots, the
-// output every call writes -- and the launch arguments they decide
-static int rate_base(r1_ctx *ctx, int coeff_bytes, int tx_size, const R1CoeffCdfs *cdfs, int n_cdfs, uint32_t *rate_out,
-                     uint8_t *cul_level_out, RateArgs &a) {
+// The checks every rate entry point shares -- the context, the coefficient width, the transform size (rate_common) --
+// and those of the three that read snapshots: the snapshots, the output every call writes, the launch arguments they
+// decide (rate_base)
+static int rate_common(r1_ctx *ctx, int coeff_bytes, int tx_size) {
   R1_REQUIRE(ctx);
   R1_REQUIRE(coeff_bytes == 2 || coeff_bytes == 4);
   R1_REQUIRE(r1_tx_size_ok(tx_size));
+  return R1_OK;
+}
+static int rate_base(r1_ctx *ctx, int coeff_bytes, int tx_size, const R1CoeffCdfs *cdfs, int n_cdfs, uint32_t *rate_out,
+                     uint8_t *cul_level_out, RateArgs &a) {
+  const int rc = rate_common(ctx, coeff_bytes, tx_size);
+  if (rc != R1_OK) return rc;
   R1_REQUIRE(n_cdfs >= 1 && n_cdfs <= 256);
   R1_REQUIRE(cdfs && rate_out);
   a = {};
@@ -136,19 +145,16 @@ extern "C" int r1_coeff_rate_chain_batch(r1_ctx *ctx, const void *qcoeffs, int c
   return rate_launch(ctx, coeff_bytes, c.r.n_slots, stream, c, [](auto ct) { return k_coeff_rate_chain<decltype(ct)>; });
 }
 
-extern "C" int r1_coeff_rate_block_batch(r1_ctx *ctx, const void *qcoeffs_y, const uint16_t *eobs_y, int n_txb_y, int step_y,
-                                         const void *qcoeffs_u, const uint16_t *eobs_u, const void *qcoeffs_v,
-                                         const uint16_t *eobs_v, int n_txb_uv, int step_uv, int coeff_bytes,
-                                         const R1BlockRateTrial *trials, int n, int bw, int bh, int tx_size, int xdec,
-                                         int ydec, int is_inter, int use_reduced_tx_set, const R1BlockChainCtx *blocks,
-                                         int n_blocks, const R1CoeffCdfs *cdfs, int n_cdfs, uint32_t *rate_out,
-                                         uint32_t *plane_rate_out, uint16_t *rng_out, uint8_t *cul_level_out,
-                                         uint8_t *ctx_out, void *stream) {
-  BlockArgs c = {};
-  int rc = rate_base(ctx, coeff_bytes, tx_size, cdfs, n_cdfs, rate_out, cul_level_out, c.r[0]);
-  if (rc != R1_OK) return rc;
+// What r1_coeff_rate_block_batch and r1_coeff_cdf_adapt_batch share: the checks of the coefficient, trial and block
+// arguments and everything of the launch arguments they decide.  c.r[0] holds the caller's part (the snapshots and the
+// outputs) on entry.  -> the chroma transform size in uv_tx_size
+static int block_args(r1_ctx *ctx, const void *qcoeffs_y, const uint16_t *eobs_y, int n_txb_y, int step_y,
+                      const void *qcoeffs_u, const uint16_t *eobs_u, const void *qcoeffs_v, const uint16_t *eobs_v,
+                      int n_txb_uv, int step_uv, const R1BlockRateTrial *trials, int n, int bw, int bh, int tx_size,
+                      int xdec, int ydec, int is_inter, int use_reduced_tx_set, const R1BlockChainCtx *blocks,
+                      int n_blocks, BlockArgs &c, int &uv_tx_size) {
   TxbGrid g;
-  rc = luma_grid(bw, bh, tx_size, g);
+  const int rc = luma_grid(bw, bh, tx_size, g);
   if (rc != R1_OK) return rc;
   R1_REQUIRE((xdec == 1 && ydec == 1) || (xdec == 1 && ydec == 0) || (xdec == 0 && ydec == 0));
   R1_REQUIRE(!(xdec == 1 && ydec == 0) || bw >= bh);   // subsampled_size (partition.rs:337-379): what 4:2:2 admits
@@ -157,12 +163,10 @@ extern "C" int r1_coeff_rate_block_batch(r1_ctx *ctx, const void *qcoeffs_y, con
   R1_REQUIRE(qcoeffs_y && eobs_y && trials && blocks);
   const int n_uv_ptrs = (qcoeffs_u != nullptr) + (eobs_u != nullptr) + (qcoeffs_v != nullptr) + (eobs_v != nullptr);
   R1_REQUIRE(n_uv_ptrs == 0 || n_uv_ptrs == 4);
-  is_inter = is_inter != 0;
-  use_reduced_tx_set = use_reduced_tx_set != 0;
   // largest_chroma_tx_size (partition.rs:385-393): the subsampled block, its largest transform, 64-point sides coded as 32
   const int pw = (bw >> xdec) > 4 ? bw >> xdec : 4, ph = (bh >> ydec) > 4 ? bh >> ydec : 4;
   const int uw = pw < 32 ? pw : 32, uh = ph < 32 ? ph : 32;
-  int uv_tx_size = 0;
+  uv_tx_size = 0;
   while (uv_tx_size < 19 && ((1 << r1tx::kTxWLog2[uv_tx_size]) != uw || (1 << r1tx::kTxHLog2[uv_tx_size]) != uh)) uv_tx_size++;
   R1_REQUIRE(uv_tx_size < 19);
   // the chroma grid, literally (encoder.rs:2327-2338; 2492-2505 has max_txsize_rect_lookup[bsize] in place of the block,
@@ -181,15 +185,124 @@ extern "C" int r1_coeff_rate_block_batch(r1_ctx *ctx, const void *qcoeffs_y, con
   }
   c.mask[0] = kSetMask[set];
   c.mask[1] = (uw == 32 || uh == 32) ? 0x0201u : 0xFFFFu;   // the scans av1_scan_orders holds for the size
-  if (n <= 0) return R1_OK;
   c.pl[0] = {qcoeffs_y, eobs_y, n_txb_y, step_y, g};
   c.pl[1] = {qcoeffs_u, eobs_u, n_txb_uv, step_uv,
              {bw_uv * bh_uv, bw_uv > 0 ? bw_uv : 1, uw >> 2, uh >> 2, xdec, ydec, (bw == 4) * xdec, (bh == 4) * ydec}};
   c.pl[2] = c.pl[1];
   c.pl[2].qc = qcoeffs_v, c.pl[2].eobs = eobs_v;
   c.trials = trials, c.blocks = blocks;
-  c.plane_rate = plane_rate_out, c.rng_out = rng_out, c.ctx_out = ctx_out;
   c.n_blocks = n_blocks;
   c.uv_skip_off = pw * ph > uw * uh ? 10 : 7;
+  return R1_OK;
+}
+
+extern "C" int r1_coeff_rate_block_batch(r1_ctx *ctx, const void *qcoeffs_y, const uint16_t *eobs_y, int n_txb_y, int step_y,
+                                         const void *qcoeffs_u, const uint16_t *eobs_u, const void *qcoeffs_v,
+                                         const uint16_t *eobs_v, int n_txb_uv, int step_uv, int coeff_bytes,
+                                         const R1BlockRateTrial *trials, int n, int bw, int bh, int tx_size, int xdec,
+                                         int ydec, int is_inter, int use_reduced_tx_set, const R1BlockChainCtx *blocks,
+                                         int n_blocks, const R1CoeffCdfs *cdfs, int n_cdfs, uint32_t *rate_out,
+                                         uint32_t *plane_rate_out, uint16_t *rng_out, uint8_t *cul_level_out,
+                                         uint8_t *ctx_out, void *stream) {
+  BlockArgs c = {};
+  int rc = rate_base(ctx, coeff_bytes, tx_size, cdfs, n_cdfs, rate_out, cul_level_out, c.r[0]);
+  if (rc != R1_OK) return rc;
+  int uv_tx_size;
+  rc = block_args(ctx, qcoeffs_y, eobs_y, n_txb_y, step_y, qcoeffs_u, eobs_u, qcoeffs_v, eobs_v, n_txb_uv, step_uv, trials, n,
+                  bw, bh, tx_size, xdec, ydec, is_inter != 0, use_reduced_tx_set != 0, blocks, n_blocks, c, uv_tx_size);
+  if (rc != R1_OK) return rc;
+  if (n <= 0) return R1_OK;
+  c.plane_rate = plane_rate_out, c.rng_out = rng_out, c.ctx_out = ctx_out;
   return rate_launch(ctx, coeff_bytes, c.r[0].n_slots, stream, c, [](auto ct) { return k_coeff_rate_block<decltype(ct)>; });
+}
+
+// ---- the device-resident coefficient CDF context: r1_coeff_cdf_slice_batch, r1_coeff_cdf_adapt_batch
+// Where the R1CoeffCdfs slice of (tx_size, plane_type, is_inter, reduced) lies in an R1CoeffCdfContext: the gather rule
+// of the header (tx_size is valid, the other three are 0 / 1)
+static void cdf_map(int tx_size, int plane_type, int is_inter, int use_reduced_tx_set, CdfMap &m) {
+  auto off = [](size_t bytes) { return (uint16_t)(bytes / 2); };
+  const int wl = r1tx::kTxWLog2[tx_size], hl = r1tx::kTxHLog2[tx_size];
+  const int sqr = (wl < hl ? wl : hl) - 2, sqr_up = (wl > hl ? wl : hl) - 2;   // TX_4X4 = 0 .. TX_64X64 = 4
+  const int txs_ctx = (sqr + sqr_up + 1) >> 1;                                 // get_txsize_entropy_ctx
+  const int ems = wl + hl - 4 < 6 ? wl + hl - 4 : 6;                           // eob_multi_size; `_ =>`: eob_flag_cdf1024
+  const int tp = txs_ctx * 2 + plane_type, br = (txs_ctx < 3 ? txs_ctx : 3) * 2 + plane_type;
+  static const size_t kEobFlag[7] = {offsetof(R1CoeffCdfContext, eob_flag16),  offsetof(R1CoeffCdfContext, eob_flag32),
+                                     offsetof(R1CoeffCdfContext, eob_flag64),  offsetof(R1CoeffCdfContext, eob_flag128),
+                                     offsetof(R1CoeffCdfContext, eob_flag256), offsetof(R1CoeffCdfContext, eob_flag512),
+                                     offsetof(R1CoeffCdfContext, eob_flag1024)};
+  const uint16_t nf = (uint16_t)(5 + ems);
+  m = {};
+  // txb_skip is shared by txs_ctx: luma adapts rows 0-6, chroma 7-12 (get_txb_ctx)
+  m.seg[0] = {off(offsetof(R1CoeffCdfContext, txb_skip) + txs_ctx * sizeof(uint16_t[R1_TXB_SKIP_CONTEXTS][2])), 2, R1_TXB_SKIP_CONTEXTS, (uint16_t)(plane_type ? 7 : 0),
+              (uint16_t)(plane_type ? R1_TXB_SKIP_CONTEXTS : 7)};
+  m.seg[1] = {(uint16_t)(off(kEobFlag[ems]) + plane_type * 2 * nf), nf, 2, 0, 2};
+  m.seg[2] = {off(offsetof(R1CoeffCdfContext, eob_extra) + tp * sizeof(uint16_t[R1_EOB_COEF_CONTEXTS][2])), 2, R1_EOB_COEF_CONTEXTS,
+              0, R1_EOB_COEF_CONTEXTS};
+  m.seg[3] = {off(offsetof(R1CoeffCdfContext, coeff_base_eob) + tp * sizeof(uint16_t[R1_SIG_COEF_CONTEXTS_EOB][3])), 3,
+              R1_SIG_COEF_CONTEXTS_EOB, 0, R1_SIG_COEF_CONTEXTS_EOB};
+  m.seg[4] = {off(offsetof(R1CoeffCdfContext, coeff_base) + tp * sizeof(uint16_t[R1_SIG_COEF_CONTEXTS][4])), 4, R1_SIG_COEF_CONTEXTS,
+              0, R1_SIG_COEF_CONTEXTS};
+  m.seg[5] = {off(offsetof(R1CoeffCdfContext, coeff_br) + br * sizeof(uint16_t[R1_LEVEL_CONTEXTS][R1_BR_CDF_SIZE])), R1_BR_CDF_SIZE,
+              R1_LEVEL_CONTEXTS, 0, R1_LEVEL_CONTEXTS};
+  m.seg[6] = {off(offsetof(R1CoeffCdfContext, dc_sign) + plane_type * sizeof(uint16_t[R1_DC_SIGN_CONTEXTS][2])), 2,
+              R1_DC_SIGN_CONTEXTS, 0, R1_DC_SIGN_CONTEXTS};
+  // write_tx_type (transform_unit.rs:530-574): the table of get_tx_set_index at tx_size.sqr(); sets in TxSet order
+  const uint32_t allowed = r1_tx_type_mask(tx_size, is_inter, use_reduced_tx_set, 0);
+  int set = 0;
+  while (kSetMask[set] != allowed) set++;
+  if (plane_type == 0 && kNumTxSet[set] > 1) {
+    const uint16_t n = kNumTxSet[set];
+    size_t at = 0;
+    switch (set) {
+      case 1: at = offsetof(R1CoeffCdfContext, inter_tx_3); break;   // TX_SET_INTER_3: index 3
+      case 2: at = offsetof(R1CoeffCdfContext, intra_tx_2); break;   // TX_SET_INTRA_2: index 2
+      case 3: at = offsetof(R1CoeffCdfContext, intra_tx_1); break;   // TX_SET_INTRA_1: index 1
+      case 4: at = offsetof(R1CoeffCdfContext, inter_tx_2); break;   // TX_SET_INTER_2: index 2
+      default: at = offsetof(R1CoeffCdfContext, inter_tx_1); break;  // TX_SET_INTER_1: index 1
+    }
+    const uint16_t rows = is_inter ? 1 : R1_INTRA_MODES;             // row 0 for inter, row y_mode for intra
+    m.seg[7] = {(uint16_t)(off(at) + sqr * rows * n), n, rows, 0, rows};
+  }
+}
+
+extern "C" int r1_coeff_cdf_slice_batch(r1_ctx *ctx, const R1CoeffCdfContext *contexts, int n, int tx_size, int plane_type,
+                                        int is_inter, int use_reduced_tx_set, R1CoeffCdfs *slices_out, void *stream) {
+  R1_REQUIRE(ctx);
+  R1_REQUIRE(r1_tx_size_ok(tx_size));
+  R1_REQUIRE(plane_type == 0 || plane_type == 1);
+  R1_REQUIRE(n >= 0);
+  R1_REQUIRE(contexts && slices_out);
+  if (n == 0) return R1_OK;
+  SliceArgs a = {contexts, slices_out, n, {}};
+  cdf_map(tx_size, plane_type, is_inter != 0, use_reduced_tx_set != 0, a.map);
+  R1DeviceGuard guard(ctx);
+  hipLaunchKernelGGL(k_coeff_cdf_slice, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
+  R1_HIP_CHECK(hipGetLastError());
+  return R1_OK;
+}
+
+extern "C" int r1_coeff_cdf_adapt_batch(r1_ctx *ctx, const void *qcoeffs_y, const uint16_t *eobs_y, int n_txb_y, int step_y,
+                                        const void *qcoeffs_u, const uint16_t *eobs_u, const void *qcoeffs_v,
+                                        const uint16_t *eobs_v, int n_txb_uv, int step_uv, int coeff_bytes,
+                                        const R1BlockRateTrial *trials, int n, int bw, int bh, int tx_size, int xdec,
+                                        int ydec, int is_inter, int use_reduced_tx_set, const R1BlockChainCtx *blocks,
+                                        int n_blocks, R1CoeffCdfContext *contexts, const R1RdPick *state, int call_id,
+                                        uint32_t *rate_out, uint16_t *rng_out, uint8_t *ctx_out, void *stream) {
+  AdaptArgs c = {};
+  int rc = rate_common(ctx, coeff_bytes, tx_size);
+  if (rc != R1_OK) return rc;
+  R1_REQUIRE(contexts);
+  R1_REQUIRE(!state || (call_id >= 0 && call_id <= 127));
+  c.b.r[0].rate = rate_out;
+  is_inter = is_inter != 0, use_reduced_tx_set = use_reduced_tx_set != 0;
+  int uv_tx_size;
+  rc = block_args(ctx, qcoeffs_y, eobs_y, n_txb_y, step_y, qcoeffs_u, eobs_u, qcoeffs_v, eobs_v, n_txb_uv, step_uv, trials, n,
+                  bw, bh, tx_size, xdec, ydec, is_inter, use_reduced_tx_set, blocks, n_blocks, c.b, uv_tx_size);
+  if (rc != R1_OK) return rc;
+  if (n <= 0) return R1_OK;
+  c.b.rng_out = rng_out, c.b.ctx_out = ctx_out;
+  c.io.contexts = contexts, c.io.state = state, c.io.call_id = call_id;
+  cdf_map(tx_size, 0, is_inter, use_reduced_tx_set, c.io.map[0]);
+  cdf_map(uv_tx_size, 1, is_inter, use_reduced_tx_set, c.io.map[1]);
+  return rate_launch(ctx, coeff_bytes, c.b.r[0].n_slots, stream, c, [](auto ct) { return k_coeff_cdf_adapt<decltype(ct)>; });
 }

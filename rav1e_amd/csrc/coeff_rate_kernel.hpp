@@ -1,5 +1,7 @@
 // coeff_rate_kernel.hpp -- the device half of the coefficient-rate unit (its entry points: coeff_rate.hip): the three
-// kernels on one per-transform-block body (txb_rate), one update_cdf, one snapshot load and one plane walk.
+// rate kernels on one per-transform-block body (txb_rate), one update_cdf, one snapshot load and one plane walk; the
+// whole-block body (block_trial) once more on a device-resident R1CoeffCdfContext that it leaves adapted
+// (k_coeff_cdf_adapt), and the copy that cuts a snapshot out of such a context (k_coeff_cdf_slice).
 //
 // One wave per slot, four slots per workgroup.  Inside a slot, per transform block (txb_rate, stated once):
 //  A  (parallel over the coded area) txb_init_levels: min(|c|, 127), transposed, stride H + TX_PAD_HOR, in LDS.
@@ -17,7 +19,8 @@
 //  then encode_coeff_signs, in chunks from scan position 0 up: the values gathered in parallel, the sign bits,
 //  the DC sign symbol and the Golomb tails chained serially (they depend on rng only).
 // Every loop bound is eob <= area, the four base-range rounds or the Golomb length <= 32; no spin-waits, no
-// atomics, no dependence between workgroups.  `cdfs` is never written.
+// atomics, no dependence between workgroups.  `cdfs` is never written; k_coeff_cdf_adapt writes its trial's own context,
+// which no other wave touches.
 //
 // Restated from the reference (pinned by tests/golden/coeff_rate_ref.npz through every fixture case):
 //  tx_type_to_class, eob_to_pos_small / eob_to_pos_large, k_eob_group_start, k_eob_offset_bits, nz_map_ctx_offset_1d
@@ -101,6 +104,12 @@ struct LaneRow {
   __device__ __forceinline__ void load(const R1CoeffCdfs *cdf, int lane) {
     const uint16_t *r = lane < kBaseRows ? cdf->coeff_base[lane] : cdf->coeff_br[lane < 63 ? lane - kBaseRows : 0];
     c0 = r[0], c1 = r[1], c2 = r[2], cnt = r[3];
+  }
+  // the row back into a copy the lanes were loaded from (lane 63 keeps none)
+  __device__ __forceinline__ void store(R1CoeffCdfs *cdf, int lane) const {
+    if (lane >= 63) return;
+    uint16_t *r = lane < kBaseRows ? cdf->coeff_base[lane] : cdf->coeff_br[lane - kBaseRows];
+    r[0] = (uint16_t)c0, r[1] = (uint16_t)c1, r[2] = (uint16_t)c2, r[3] = (uint16_t)cnt;
   }
 };
 
@@ -557,19 +566,111 @@ struct BlockArgs {
 };
 static_assert(sizeof(R1BlockChainCtx) == 108 && sizeof(R1BlockRateTrial) == 24, "ABI layout");
 
+// ---- where a trial's CDFs come from and where they go: the two places in which r1_coeff_rate_block_batch and
+// r1_coeff_cdf_adapt_batch differ, as the `Io` parameter of one body (block_trial)
+// Snapshots the host hands over, picked by the block's cdf_sel / cdf_sel_uv; what has adapted is dropped.
+struct FromSnapshots {
+  static constexpr bool kRateOptional = false;
+  __device__ __forceinline__ bool acts(int) const { return true; }
+  __device__ __forceinline__ bool bad_sel(const BlockArgs &c, int sel) const { return sel >= c.r[0].n_cdfs; }
+  __device__ __forceinline__ void load(const RateArgs &a, R1CoeffCdfs *cdf, LaneRow &row, int, int, int sel, int lane) const {
+    load_snapshot(cdf, row, a.cdfs + sel, lane);
+  }
+  __device__ __forceinline__ void store(R1CoeffCdfs *, const LaneRow &, int, int, int) const {}
+};
+
+// One field of an R1CoeffCdfs slice inside an R1CoeffCdfContext, in uint16_t units: `rows` rows of `n` entries from
+// `src` on, row after row.  The slice's own row has sizeof(field[0]) / 2 entries, `n` or more; what lies beyond `n` and
+// beyond `rows` is no part of the context and reads 0.  The plane that adapts the slice owns rows own_lo .. own_hi - 1.
+struct CdfSeg {
+  uint16_t src, n, rows, own_lo, own_hi;
+};
+struct CdfMap {
+  CdfSeg seg[8];   // in R1CoeffCdfs field order
+};
+static_assert(sizeof(R1CoeffCdfContext) == 7872 && sizeof(R1CoeffCdfContext) % 16 == 0, "ABI layout");
+
+// f(field index, the field's first entry, row length and entry count in the slice, all compile-time once inlined)
+#define R1_SLICE_FIELD(i, name)                                                                        \
+  f(i, (int)(offsetof(R1CoeffCdfs, name) / 2), (int)(sizeof(((R1CoeffCdfs *)nullptr)->name[0]) / 2), \
+    (int)(sizeof(((R1CoeffCdfs *)nullptr)->name) / 2))
+template <typename F>
+__device__ __forceinline__ void slice_fields(F f) {
+  R1_SLICE_FIELD(0, txb_skip);
+  R1_SLICE_FIELD(1, eob_flag);
+  R1_SLICE_FIELD(2, eob_extra);
+  R1_SLICE_FIELD(3, coeff_base_eob);
+  R1_SLICE_FIELD(4, coeff_base);
+  R1_SLICE_FIELD(5, coeff_br);
+  R1_SLICE_FIELD(6, dc_sign);
+  R1_SLICE_FIELD(7, tx_type);
+}
+#undef R1_SLICE_FIELD
+
+// The slice of context `ctx` that `map` describes into `slice` (LDS or global), every entry of it written; by one wave.
+// The loops are bounded by the slice's size.
+__device__ __forceinline__ void cdf_gather(const CdfMap &map, const uint16_t *ctx, uint16_t *slice, int lane) {
+  slice_fields([&](int i, int dst, int stride, int len) __attribute__((always_inline)) {
+    const int src = map.seg[i].src, n = map.seg[i].n, rows = map.seg[i].rows;
+    for (int e = lane; e < len; e += 64) {
+      const int r = e / stride, col = e - r * stride;
+      slice[dst + e] = r < rows && col < n ? ctx[src + r * n + col] : (uint16_t)0;
+    }
+  });
+}
+// ... and back: the rows the plane owns, nothing else of the context
+__device__ __forceinline__ void cdf_scatter(const CdfMap &map, uint16_t *ctx, const uint16_t *slice, int lane) {
+  slice_fields([&](int i, int dst, int stride, int len) __attribute__((always_inline)) {
+    const int src = map.seg[i].src, n = map.seg[i].n, lo = map.seg[i].own_lo, hi = map.seg[i].own_hi;
+    for (int e = lane; e < len; e += 64) {
+      const int r = e / stride, col = e - r * stride;
+      if (r >= lo && r < hi && col < n) ctx[src + r * n + col] = slice[dst + e];
+    }
+  });
+}
+
+// A device-resident context per trial, read and adapted in place; an optional gate on the pick's state.
+struct InContext {
+  static constexpr bool kRateOptional = true;
+  R1CoeffCdfContext *contexts;
+  const R1RdPick *state;     // optional
+  int call_id;
+  CdfMap map[2];             // by plane type
+  __device__ __forceinline__ bool acts(int trial) const {
+    return state == nullptr || __builtin_amdgcn_readfirstlane((int)state[trial].best_call) == call_id;
+  }
+  __device__ __forceinline__ bool bad_sel(const BlockArgs &, int) const { return false; }
+  // the plane type's slice into the wave's LDS copy and the lanes' rows; the first barrier covers the caller's LDS
+  // writes and the copy, as load_snapshot's
+  __device__ __forceinline__ void load(const RateArgs &, R1CoeffCdfs *cdf, LaneRow &row, int pt, int trial, int, int lane) const {
+    cdf_gather(map[pt], (const uint16_t *)(contexts + trial), (uint16_t *)cdf, lane);
+    wave_sync();
+    row.load(cdf, lane);
+    wave_sync();
+  }
+  // what stands in the lanes' rows and in LDS, back to the context; the copy may be overwritten behind the last barrier
+  __device__ __forceinline__ void store(R1CoeffCdfs *cdf, const LaneRow &row, int pt, int trial, int lane) const {
+    row.store(cdf, lane);
+    wave_sync();
+    cdf_scatter(map[pt], (uint16_t *)(contexts + trial), (const uint16_t *)cdf, lane);
+    wave_sync();
+  }
+};
+struct AdaptArgs {
+  BlockArgs b;               // b.r[].cdfs / n_cdfs are unused; b.r[0].rate is optional
+  InContext io;
+};
+
 // One wave per trial, four trials per workgroup, as k_coeff_rate_chain and on the same walk.  The wave's LDS CDF copy
-// and the lanes' coeff_base / coeff_br rows hold the luma snapshot for the luma plane and are overwritten with the
-// chroma snapshot in front of U; V continues on what U left.  The 96 context bytes live in LDS, 32 per plane.
+// and the lanes' coeff_base / coeff_br rows hold the luma slice for the luma plane and are overwritten with the
+// chroma slice in front of U; V continues on what U left.  io.store stands behind the luma plane and behind V.
+// The 96 context bytes live in LDS (s_nb), 32 per plane.
 // A plane's record is read from the arguments by the plane index and handed on by reference: selects on the index
 // would keep all three planes' values live in SGPRs.  The loop is bounded by three planes.
-template <typename CT>
-__global__ __launch_bounds__(256) void k_coeff_rate_block(const BlockArgs c) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  R1_RATE_LDS(wave);
-  __shared__ __attribute__((aligned(16))) R1CoeffCdfs s_cdf[4];
-  __shared__ uint8_t s_nb[4][96];      // [plane]: above[16], left[16]
-  const int trial = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + wave);
-  if (trial >= c.r[0].n_slots) return;
+template <typename CT, typename Io>
+__device__ __forceinline__ void block_trial(const BlockArgs &c, const Io &io, const int trial, const int wave,
+                                            const int lane, const WaveLds lds, R1CoeffCdfs *s_cdf, uint8_t (*s_nb)[96]) {
+  if (!io.acts(trial)) return;
   const R1BlockRateTrial *tr = c.trials + trial;
   const uint32_t *first = &tr->first_y;      // first_y, first_u, first_v
   const uint32_t bi = (uint32_t)__builtin_amdgcn_readfirstlane((int)tr->block);
@@ -581,8 +682,8 @@ __global__ __launch_bounds__(256) void k_coeff_rate_block(const BlockArgs c) {
   const int sel_uv = __builtin_amdgcn_readfirstlane((int)chb[104]);
   {
     // device-resident data the host cannot see: lane k looks at transform block k of every plane
-    bool bad = bi >= (uint32_t)c.n_blocks || rng0 < 0x8000u || y_mode >= R1_INTRA_MODES || sel >= c.r[0].n_cdfs ||
-               mi_w > (int)chb[98] || mi_h > (int)chb[99] || (np == 3 && sel_uv >= c.r[0].n_cdfs);
+    bool bad = bi >= (uint32_t)c.n_blocks || rng0 < 0x8000u || y_mode >= R1_INTRA_MODES || io.bad_sel(c, sel) ||
+               mi_w > (int)chb[98] || mi_h > (int)chb[99] || (np == 3 && io.bad_sel(c, sel_uv));
     for (int p = 0; p < np; p++) {
       const PlaneArgs &pl = c.pl[p];
       const int tt = p ? tr->uv_tx_type : tr->tx_type;
@@ -605,7 +706,7 @@ __global__ __launch_bounds__(256) void k_coeff_rate_block(const BlockArgs c) {
     }
     if (__ballot(bad) != 0) {
       if (lane == 0) {
-        c.r[0].rate[trial] = 0xFFFFFFFFu;
+        if (!Io::kRateOptional || c.r[0].rate) c.r[0].rate[trial] = 0xFFFFFFFFu;
         if (c.rng_out) c.rng_out[trial] = 0;
       }
       if (c.plane_rate && lane < 3) c.plane_rate[(size_t)trial * 3 + lane] = 0;
@@ -625,9 +726,9 @@ __global__ __launch_bounds__(256) void k_coeff_rate_block(const BlockArgs c) {
   for (int p = 0; p < np; p++) {
     const RateArgs &a = c.r[p != 0];
     const PlaneArgs &pl = c.pl[p];
-    // the plane type's snapshot; in front of U every lane is behind its last read of the luma copy (the barriers of
-    // txb_rate)
-    if (p < 2) load_snapshot(cdf, row, a.cdfs + (p ? sel_uv : sel), lane);
+    // the plane type's slice; in front of U every lane is behind its last read of the luma copy (the barriers of
+    // txb_rate and of io.store)
+    if (p < 2) io.load(a, cdf, row, p, trial, p ? sel_uv : sel, lane);
     const int cw4 = __builtin_amdgcn_readfirstlane((int)chb[p ? 100 : 98]), ch4 = __builtin_amdgcn_readfirstlane((int)chb[p ? 101 : 99]);
     const uint32_t f = (uint32_t)__builtin_amdgcn_readfirstlane((int)first[p]);
     const int j = __builtin_amdgcn_readfirstlane((int)(p ? tr->uv_tx_type : tr->tx_type));
@@ -638,13 +739,14 @@ __global__ __launch_bounds__(256) void k_coeff_rate_block(const BlockArgs c) {
         [&](int k, uint32_t cul, uint32_t) {
           if (lane == 0 && cul_out) cul_out[k] = (uint8_t)cul;
         });
+    if (p != 1) io.store(cdf, row, p != 0, trial, lane);
     if (cul_out && lane >= pl.g.ntx && lane < 16) cul_out[lane] = 0;    // the entries no transform block stands for
     const uint32_t t = w.tell_frac();
     if (lane == 0 && c.plane_rate) c.plane_rate[(size_t)trial * 3 + p] = t - tell_p;
     tell_p = t;
   }
   if (lane == 0) {
-    c.r[0].rate[trial] = tell_p - tell0;
+    if (!Io::kRateOptional || c.r[0].rate) c.r[0].rate[trial] = tell_p - tell0;
     if (c.rng_out) c.rng_out[trial] = (uint16_t)w.rng;
   }
   if (np == 1) {
@@ -653,6 +755,47 @@ __global__ __launch_bounds__(256) void k_coeff_rate_block(const BlockArgs c) {
   }
   if (c.ctx_out)
     for (int e = lane; e < 96; e += 64) c.ctx_out[(size_t)trial * 96 + e] = s_nb[wave][e];
+}
+
+// the wave's adapting CDF copy and the trial's 96 context bytes ([plane]: above[16], left[16])
+#define R1_BLOCK_LDS                                                      \
+  __shared__ __attribute__((aligned(16))) R1CoeffCdfs s_cdf[4];           \
+  __shared__ uint8_t s_nb[4][96]
+
+template <typename CT>
+__global__ __launch_bounds__(256) void k_coeff_rate_block(const BlockArgs c) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  R1_RATE_LDS(wave);
+  R1_BLOCK_LDS;
+  const int trial = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + wave);
+  if (trial >= c.r[0].n_slots) return;
+  block_trial<CT>(c, FromSnapshots{}, trial, wave, lane, lds, s_cdf, s_nb);
+}
+
+// r1_coeff_cdf_adapt_batch: the same trial on contexts[trial], which it leaves adapted
+template <typename CT>
+__global__ __launch_bounds__(256) void k_coeff_cdf_adapt(const AdaptArgs c) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  R1_RATE_LDS(wave);
+  R1_BLOCK_LDS;
+  const int trial = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + wave);
+  if (trial >= c.b.r[0].n_slots) return;
+  block_trial<CT>(c.b, c.io, trial, wave, lane, lds, s_cdf, s_nb);
+}
+#undef R1_BLOCK_LDS
+
+// r1_coeff_cdf_slice_batch: one wave per context, four per workgroup; one small copy
+struct SliceArgs {
+  const R1CoeffCdfContext *contexts;
+  R1CoeffCdfs *out;
+  int n;
+  CdfMap map;
+};
+__global__ __launch_bounds__(256) void k_coeff_cdf_slice(const SliceArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int i = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + (int)(threadIdx.x >> 6));
+  if (i >= a.n) return;
+  cdf_gather(a.map, (const uint16_t *)(a.contexts + i), (uint16_t *)(a.out + i), lane);
 }
 #undef R1_RATE_LDS
 }  // namespace

@@ -548,6 +548,29 @@ def block_rate_trial(first_y, first_u, first_v, block, tx_type, uv_tx_type, do_c
             int(bool(do_chroma)), (0, 0, 0))
 
 
+def coeff_cdf_context(fields):
+    """One R1CoeffCdfContext (a types.COEFF_CDF_CONTEXT record) from a dict of the reference's CDFContext field arrays
+    (src/context/cdf_context.rs:23-96), keyed by the reference's names with or without the `_cdf` in them
+    (`txb_skip_cdf`, `eob_flag_cdf16`, `intra_tx_1_cdf`, ... or the struct's `txb_skip`, `eob_flag16`, `intra_tx_1`):
+    every coefficient field must be there, in the reference's shape; the padding is zero."""
+    import numpy as np
+    from .types import COEFF_CDF_CONTEXT
+    rec = np.zeros(1, COEFF_CDF_CONTEXT)[0]
+    for name in COEFF_CDF_CONTEXT.names:
+        if name == "pad":
+            continue
+        if name.startswith("eob_flag"):
+            ref = "eob_flag_cdf" + name[len("eob_flag"):]
+        else:
+            ref = name + "_cdf"
+        v = fields[ref] if ref in fields else fields[name]
+        a = np.asarray(v)
+        assert a.shape == rec[name].shape, (name, a.shape, rec[name].shape)
+        assert a.min() >= 0 and a.max() <= 0xFFFF, name
+        rec[name] = a
+    return rec
+
+
 def pick_tx_type(rates, dists, lam, cur_best_rd):
     """The tail of rdo_tx_type_decision's loop (src/rdo.rs:1801-1818) over the slots of one candidate, in slot order
     (tx_type_slots): rd = compute_rd_cost(rate, distortion); after the FIRST type the loop ends when rd > cur_best_rd;

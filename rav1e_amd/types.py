@@ -6,7 +6,7 @@ TxType      src/transform/mod.rs:56-74    FilterMode  src/mc.rs:100-106
 COEFF_CDFS / TXB_CTX: the NumPy mirrors of R1CoeffCdfs / R1TxbCtx (include/rav1e_amd.h, r1_coeff_rate_batch); the
 dimensions are the reference's (src/context/transform_unit.rs:27, 200-219).  TXB_CHAIN_CTX: R1TxbChainCtx
 (r1_coeff_rate_chain_batch).  BLOCK_CHAIN_CTX / BLOCK_RATE_TRIAL: R1BlockChainCtx / R1BlockRateTrial
-(r1_coeff_rate_block_batch).
+(r1_coeff_rate_block_batch).  COEFF_CDF_CONTEXT: R1CoeffCdfContext (r1_coeff_cdf_slice_batch, r1_coeff_cdf_adapt_batch).
 """
 import enum
 
@@ -147,4 +147,19 @@ BLOCK_RATE_TRIAL = np.dtype([("first_y", "<u4"), ("first_u", "<u4"), ("first_v",
 RD_PICK = np.dtype([("best_rd", "<f8"), ("best_dist", "<u8"), ("best_rate", "<u4"), ("best_row", "<i2"),
                     ("best_slot", "i1"), ("best_call", "i1")])
 assert RD_PICK.itemsize == 24
+# R1CoeffCdfContext (r1_coeff_cdf_slice_batch / r1_coeff_cdf_adapt_batch): the coefficient side of the reference's
+# CDFContext in its own shapes (src/context/cdf_context.rs:23-96), padded to a multiple of 16 bytes
+TX_SIZES, PLANE_TYPES, TX_SIZE_SQR_CONTEXTS = 5, 2, 4
+COEFF_CDF_CONTEXT = np.dtype(
+    [("txb_skip", "<u2", (TX_SIZES, TXB_SKIP_CONTEXTS, 2)),
+     ("eob_extra", "<u2", (TX_SIZES, PLANE_TYPES, EOB_COEF_CONTEXTS, 2)),
+     ("coeff_base_eob", "<u2", (TX_SIZES, PLANE_TYPES, SIG_COEF_CONTEXTS_EOB, 3)),
+     ("coeff_base", "<u2", (TX_SIZES, PLANE_TYPES, SIG_COEF_CONTEXTS, 4)),
+     ("coeff_br", "<u2", (TX_SIZES, PLANE_TYPES, LEVEL_CONTEXTS, BR_CDF_SIZE)),
+     ("dc_sign", "<u2", (PLANE_TYPES, DC_SIGN_CONTEXTS, 2))]
+    + [("eob_flag%d" % (16 << k), "<u2", (PLANE_TYPES, 2, 5 + k)) for k in range(7)]
+    + [("intra_tx_1", "<u2", (TX_SIZE_SQR_CONTEXTS, INTRA_MODES, 7)), ("intra_tx_2", "<u2", (TX_SIZE_SQR_CONTEXTS, INTRA_MODES, 5)),
+       ("inter_tx_1", "<u2", (TX_SIZE_SQR_CONTEXTS, 16)), ("inter_tx_2", "<u2", (TX_SIZE_SQR_CONTEXTS, 12)),
+       ("inter_tx_3", "<u2", (TX_SIZE_SQR_CONTEXTS, 2)), ("pad", "<u2", (6,))])
+assert COEFF_CDF_CONTEXT.itemsize == 7872 and COEFF_CDF_CONTEXT.itemsize % 16 == 0
 PICK_FIRST_MIN, PICK_TX_TYPE = 0, 1   # R1_PICK_*

@@ -126,7 +126,9 @@ const char *r1_last_error(void);
  * block's transform blocks (r1_coeff_rate_chain_batch, R1TxbChainCtx) and across its three planes on one writer
  * (r1_coeff_rate_block_batch, R1BlockChainCtx, R1BlockRateTrial), and the decision on the device (r1_rd_pick_batch,
  * r1_rd_commit_batch, R1RdPick), and the device-resident coefficient CDF context (r1_coeff_cdf_slice_batch,
- * r1_coeff_cdf_adapt_batch, R1CoeffCdfContext). */
+ * r1_coeff_cdf_adapt_batch, R1CoeffCdfContext), and the device-resident coefficient neighbour contexts with the
+ * winner's transform type (r1_coeff_nbr_gather_batch, r1_coeff_nbr_store_batch, r1_coeff_nbr_reset_left_batch,
+ * r1_rd_winner_tx_type_batch, R1CoeffNbrContext, R1NbrBlock). */
 int r1_abi_version(void);
 
 /* ---- dist:: (reference: src/dist.rs get_sad 31, get_satd 156; dispatch
@@ -1486,6 +1488,94 @@ int r1_coeff_cdf_adapt_batch(r1_ctx *ctx, const void *qcoeffs_y, const uint16_t 
                              int is_inter, int use_reduced_tx_set, const R1BlockChainCtx *blocks, int n_blocks,
                              R1CoeffCdfContext *contexts, const R1RdPick *state, int call_id, uint32_t *rate_out,
                              uint16_t *rng_out, uint8_t *ctx_out, void *stream);
+
+/* ---- the coefficient neighbour contexts carried from block to block on the device (added under ABI 7):
+ * R1BlockChainCtx.ctx / R1TxbChainCtx.above, left are cuts from BlockContext::above_coeff_context / left_coeff_context
+ * (src/context/block_unit.rs:237-238) as they stand in front of a block, and what a block leaves there --
+ * set_coeff_context with the winner's cul_level -- is known on the device alone.  These calls keep the arrays on the
+ * device: a context holds them for one tile (or one speculative branch of one), r1_coeff_nbr_gather_batch cuts the
+ * records the rate calls take, r1_coeff_nbr_store_batch writes back what the winner left.  With the CDF context above, a
+ * tile's blocks are enqueued in coding order on one stream with nothing read back:
+ *     gather -> search -> slice -> rates -> pick -> commit -> winner tx type -> adapt -> store.
+ * A fresh tile is the struct zeroed (BlockContext::new); a rollback (rdo_partition_decision) is the caller's device copy
+ * of the struct, as for R1CoeffCdfContext -- the reference's 16-entry checkpoint window restores nothing a whole copy
+ * would not.  Head symbols, the above_tx_context / partition contexts and the partition decision stay the host's. */
+#define R1_COEFF_NBR_WIDTH 1024            /* COEFF_CONTEXT_MAX_WIDTH = MAX_TILE_WIDTH / MI_SIZE (block_unit.rs:36) */
+typedef struct R1CoeffNbrContext {         /* 3120 bytes: one per tile, or per speculative branch of one */
+  uint8_t above[3][R1_COEFF_NBR_WIDTH];    /* above_coeff_context[p][x >> xdec_p] */
+  uint8_t left[3][16];                     /* left_coeff_context[p][y_in_sb >> ydec_p] */
+} R1CoeffNbrContext;
+typedef struct R1NbrBlock {                /* 20 bytes, device resident: a block's place; static geometry the host knows */
+  uint32_t nbr;                            /* which context */
+  uint16_t bo_x, bo_y;                     /* tile block offset, 4x4 units */
+  uint16_t mi_width, mi_height;            /* the tile's (ts.mi_width / mi_height) */
+  uint16_t w_in_b, h_in_b;                 /* fi.w_in_b / h_in_b less the tile's own block offset in the frame */
+  uint8_t y_mode, cdf_sel, cdf_sel_uv;     /* copied into the records */
+  uint8_t flags;                           /* bit 0: do_chroma (has_chroma(..) and not Cs400); bit 1: skip.  The gather
+                                              reads neither */
+} R1NbrBlock;
+/* blocks_out[i] (optional) = the R1BlockChainCtx of the bw x bh block descs[i] on contexts[descs[i].nbr], i < n:
+ * ctx[0] = above[0][bo_x ..] / left[0][bo_y % 16 ..]; ctx[1], ctx[2] from the first chroma transform block's offset --
+ * ((bo_x - ax) >> xdec, ((bo_y - ay) % 16) >> ydec) with ax = xdec for a 4-wide block, ay = ydec for a 4-high one
+ * (encoder.rs:2364-2369); sixteen entries each, zeros where a window runs past entry 1023 or past left[15] (and
+ * throughout where a shifted chroma column would be -1).  mi_w / mi_h = min(255, mi_width - bo_x), ..; clip_w4 / clip_h4
+ * = min(255, max(0, w_in_b - bo_x)), ..; clip_uv_w4 = min(255, max(0, (((w_in_b - (bo_x - ax)) << 2) >> xdec) >> 2)),
+ * same for h; y_mode, cdf_sel, cdf_sel_uv copied; reserved 0.  rdo_glue.block_chain_ctx is the statement.
+ * chains_out[i] (optional) = the R1TxbChainCtx of the same block (rdo_glue.txb_chain_ctx): the luma rows and clamps.
+ * At least one output is given.  Many descs may name one context (the K modes of a block); `contexts` is never written.
+ * A desc the device must refuse -- nbr >= n_contexts, bo_x >= 1024, y_mode >= 13, mi_width <= bo_x, mi_height <= bo_y --
+ * gets an all-zero record with y_mode = 255, which every rate call answers with rate 0xFFFFFFFF.
+ * R1_EINVAL: a NULL ctx, contexts or descs, both outputs NULL, n < 0, n_contexts < 1, bw / bh that are no block size up
+ * to 64x64 or that the subsampling does not admit, (xdec, ydec) outside (1, 1), (1, 0), (0, 0).  n == 0 returns 0.
+ * Eight lanes per desc; aligned dwords with a byte shift where contexts and outputs are 4-byte aligned, bytes otherwise. */
+int r1_coeff_nbr_gather_batch(r1_ctx *ctx, const R1CoeffNbrContext *contexts, int n_contexts, const R1NbrBlock *descs,
+                              int n, int bw, int bh, int xdec, int ydec, R1BlockChainCtx *blocks_out,
+                              R1TxbChainCtx *chains_out, void *stream);
+/* What a coded or a skipped winner leaves on contexts[descs[i].nbr].  ctx_in + 96 * i is the R1BlockChainCtx.ctx BEHIND
+ * block i: ctx_out of r1_coeff_rate_block_batch / r1_coeff_cdf_adapt_batch, or r1_rd_commit_batch's side_win.
+ *   state / call_id (optional gate): desc i acts when state is NULL or state[i].best_call == call_id, the gate of the
+ *                commit and of the adapt call; otherwise nothing of it is written.
+ * A coded block (flags bit 1 clear) stores
+ *   luma:   ctx_in[0][0][c] to above[0][bo_x + c], c < bw / 4; ctx_in[0][1][r] to left[0][bo_y % 16 + r], r < bh / 4;
+ *   chroma (with do_chroma), per plane: the span of the chroma transform grid -- bw_uv * (uv_tw / 4) by bh_uv *
+ *           (uv_th / 4) entries, r1_coeff_rate_block_batch's grid -- from the chroma origin of the gather.  The grid of
+ *           4x16 / 16x4 in 4:2:0 is empty: nothing of chroma is stored.
+ * This is set_coeff_context (block_unit.rs:333-348) over the block's transform blocks: ctx_out passes through what no
+ * coded transform block wrote, and a transform block coded at a tile edge writes its full span past mi_width.
+ * A skipped block (bit 1 set) ignores ctx_in (NULL is allowed when every desc is skipped) and writes zeros as
+ * reset_skip_context does (src/context/partition_unit.rs:434-469): the spans of bsize.subsampled_size(xdec, ydec) from
+ * bo_x >> xdec / (bo_y % 16) >> ydec; chroma with do_chroma and, whatever the flag, for 4x16 / 16x4 -- `bsize >=
+ * BLOCK_8X8` holds for them in the enum's order, so the reference writes three planes there.  (Under Cs400 that touches
+ * chroma rows nothing reads.)
+ * Every byte outside the spans stays bit-identical.  Acting descs of one call MUST name distinct contexts: two descs on
+ * one context would store in no defined order; the call does not detect it.
+ * tx_size: the luma transform (it must divide the block; the spans do not depend on it).
+ * A desc is refused -- nothing of it is written -- on one of the gather's refusal cases, when a span leaves the arrays
+ * (bo_x + bw / 4 > 1024, a chroma span past 1023, a chroma origin of -1), when bo_y % 16 + bh / 4 > 16, or when it is
+ * coded and ctx_in is NULL.
+ * R1_EINVAL: a NULL ctx, descs or contexts, n < 0, n_contexts < 1, the gather's size and subsampling checks, an invalid
+ * tx_size or one that does not divide the block, call_id outside 0..127 with state given.  n == 0 returns 0. */
+int r1_coeff_nbr_store_batch(r1_ctx *ctx, const R1NbrBlock *descs, int n, int bw, int bh, int tx_size, int xdec, int ydec,
+                             const uint8_t *ctx_in, const R1RdPick *state, int call_id, R1CoeffNbrContext *contexts,
+                             int n_contexts, void *stream);
+/* The coefficient part of reset_left_contexts (block_unit.rs:394-401) at the start of a superblock row:
+ * contexts[sel[i]].left[p][*] = 0 for p < planes, i < n; a sel[i] >= n_contexts writes nothing.
+ * R1_EINVAL: a NULL pointer, n < 0, n_contexts < 1, planes outside 1..3.  n == 0 returns 0. */
+int r1_coeff_nbr_reset_left_batch(r1_ctx *ctx, R1CoeffNbrContext *contexts, int n_contexts, const uint32_t *sel, int n,
+                                  int planes, void *stream);
+/* The winner's transform type where r1_coeff_cdf_adapt_batch reads it.  For every state s < n_states with
+ * state[s].best_call == call_id, trials[s].tx_type becomes the best_slot-th set bit of tx_type_mask (the slot order of
+ * every candidate call).  With is_inter, trials[s].uv_tx_type becomes write_tx_tree's (src/encoder.rs:2507-2511):
+ * tx_type.uv_inter(uv_tx_size) (src/transform/mod.rs:81-97), DCT_DCT when eob_win[s * 16 + k] == 0 for all k < ntx
+ * (r1_rd_commit_batch's eob_win); rdo_glue.uv_tx_type_inter is the statement.  For intra uv_tx_type belongs to the
+ * chroma mode and is not touched; eob_win may be NULL.  No other field and no other state's trial is written; a
+ * best_slot outside the mask's popcount writes nothing.
+ * R1_EINVAL: a NULL ctx, state or trials, eob_win NULL with is_inter, n_states < 0, call_id outside 0..127, an empty
+ * mask or one with bits outside r1_tx_type_mask(TX_4X4, is_inter, 0, 0) (the largest set of the prediction kind), an
+ * invalid uv_tx_size, ntx outside 1..16.  n_states == 0 returns 0. */
+int r1_rd_winner_tx_type_batch(r1_ctx *ctx, const R1RdPick *state, int n_states, int call_id, uint32_t tx_type_mask,
+                               int is_inter, int uv_tx_size, const uint16_t *eob_win, int ntx, R1BlockRateTrial *trials,
+                               void *stream);
 
 /* ---- multi-GPU: the tile-boundary exchange and the reference-frame all-gather (RCCL over
  * xGMI), SURVEY.md 8(e).  One process (or host thread) per GPU, tile r on rank r.  Rendezvous:

@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 from .types import (BLOCK_CHAIN_CTX, BLOCK_RATE_TRIAL, COEFF_CDF_CONTEXT, COEFF_CDFS, COEFF_RATE_INVALID, PICK_FIRST_MIN, PICK_TX_TYPE,  # noqa: F401
-                    RD_PICK, TX_DIMS, TXB_CHAIN_CTX, TXB_CTX, TxSize, valid_av1_transform)
+                    COEFF_NBR_CONTEXT, NBR_BLOCK, RD_PICK, TX_DIMS, TXB_CHAIN_CTX, TXB_CTX, TxSize, valid_av1_transform)
 
 DIST_CAND = np.dtype([("ox", "<i2"), ("oy", "<i2"), ("rx", "<i2"), ("ry", "<i2")])
 MC_CAND = np.dtype([("rx", "<i2"), ("ry", "<i2"), ("col_frac", "u1"), ("row_frac", "u1"),
@@ -1321,6 +1321,80 @@ class Context:
             o["qcoeffs_win"].data_ptr() if eobs is not None else None, int(stride),
             o["side_win"].data_ptr() if side is not None else None, _stream_ptr()), "r1_rd_commit_batch")
         return o
+
+    # ---- the coefficient neighbour contexts carried on the device ----
+    @staticmethod
+    def coeff_nbr_contexts(n):
+        """n fresh R1CoeffNbrContext (BlockContext::new: all zero) as an (n, 3120) uint8 device tensor
+        (COEFF_NBR_CONTEXT records; .cpu().numpy().view(COEFF_NBR_CONTEXT) reads them)"""
+        return torch.zeros((n, COEFF_NBR_CONTEXT.itemsize), dtype=torch.uint8, device="cuda")
+
+    @staticmethod
+    def _nbr_contexts(contexts):
+        assert isinstance(contexts, torch.Tensor) and contexts.is_cuda and contexts.is_contiguous() and \
+            contexts.element_size() == 1 and contexts.numel() % COEFF_NBR_CONTEXT.itemsize == 0, "(n, 3120) uint8 on the device"
+        return contexts.numel() // COEFF_NBR_CONTEXT.itemsize
+
+    def coeff_nbr_gather_batch(self, contexts, descs, bw, bh, xdec, ydec, want_blocks=True, want_chains=False, outs=None):
+        """r1_coeff_nbr_gather_batch: the BLOCK_CHAIN_CTX (and / or TXB_CHAIN_CTX) record of every desc, cut from
+        contexts[desc.nbr] on the device -- rdo_glue.block_chain_ctx / txb_chain_ctx.  contexts: (n_contexts, 3120)
+        uint8 device tensor; descs: NBR_BLOCK records (rdo_glue.nbr_block), a NumPy array or a uint8 device tensor.
+        -> {"blocks": (n, 108) uint8, "chains": (n, 40) uint8}: hand them to the rate calls as `blocks` / `chains`"""
+        n_ctx = self._nbr_contexts(contexts)
+        dd, n = _dev_cands(descs, NBR_BLOCK)
+        o, ptr = _bind_wanted(outs, {"blocks": (want_blocks, (n, BLOCK_CHAIN_CTX.itemsize), torch.uint8),
+                                     "chains": (want_chains, (n, TXB_CHAIN_CTX.itemsize), torch.uint8)}, contexts.device)
+        self._check(self.lib.r1_coeff_nbr_gather_batch(
+            self.h, contexts.data_ptr(), n_ctx, dd.data_ptr(), n, int(bw), int(bh), int(xdec), int(ydec), ptr["blocks"],
+            ptr["chains"], _stream_ptr()), "r1_coeff_nbr_gather_batch")
+        return o
+
+    def coeff_nbr_store_batch(self, contexts, descs, bw, bh, tx_size, xdec, ydec, ctx_in=None, state=None, call_id=0):
+        """r1_coeff_nbr_store_batch: what every coded or skipped desc leaves on contexts[desc.nbr], in place --
+        rdo_glue.coeff_nbr_store.  ctx_in: (n, 96) uint8 device bytes, the `ctx` output of coeff_rate_block_batch /
+        coeff_cdf_adapt_batch or rd_commit_batch's side_win (None when every desc is skipped).  state / call_id: the
+        optional gate, as coeff_cdf_adapt_batch.  Acting descs must name distinct contexts.  -> contexts"""
+        n_ctx = self._nbr_contexts(contexts)
+        dd, n = _dev_cands(descs, NBR_BLOCK)
+        if ctx_in is not None:
+            assert ctx_in.is_cuda and ctx_in.is_contiguous() and ctx_in.element_size() == 1 and ctx_in.numel() == n * 96
+        if state is not None:
+            assert state.is_cuda and state.is_contiguous() and state.element_size() == 1 and \
+                state.numel() == n * RD_PICK.itemsize
+        self._check(self.lib.r1_coeff_nbr_store_batch(
+            self.h, dd.data_ptr(), n, int(bw), int(bh), int(tx_size), int(xdec), int(ydec),
+            ctx_in.data_ptr() if ctx_in is not None else None, state.data_ptr() if state is not None else None,
+            int(call_id), contexts.data_ptr(), n_ctx, _stream_ptr()), "r1_coeff_nbr_store_batch")
+        return contexts
+
+    def coeff_nbr_reset_left_batch(self, contexts, sel, planes=3):
+        """r1_coeff_nbr_reset_left_batch: left[p][*] = 0, p < planes, on contexts[sel[i]] (reset_left_contexts'
+        coefficient part at the start of a superblock row).  sel: indices, a sequence or an int32 device tensor."""
+        n_ctx = self._nbr_contexts(contexts)
+        if not isinstance(sel, torch.Tensor):
+            sel = torch.from_numpy(np.ascontiguousarray(sel, dtype=np.int32)).to(contexts.device)
+        assert sel.is_cuda and sel.is_contiguous() and sel.element_size() == 4
+        self._check(self.lib.r1_coeff_nbr_reset_left_batch(
+            self.h, contexts.data_ptr(), n_ctx, sel.data_ptr(), sel.numel(), int(planes), _stream_ptr()),
+            "r1_coeff_nbr_reset_left_batch")
+        return contexts
+
+    def rd_winner_tx_type_batch(self, state, call_id, tx_type_mask, is_inter, uv_tx_size, trials, eob_win=None, ntx=1):
+        """r1_rd_winner_tx_type_batch: for every state the call `call_id` won, trials[s].tx_type = the best_slot-th type
+        of tx_type_mask and, with is_inter, trials[s].uv_tx_type = rdo_glue.uv_tx_type_inter of it (DCT_DCT when the
+        winner's ntx eobs in eob_win, rd_commit_batch's (n, 16), are all zero).  trials: (n, 24) uint8 device tensor of
+        BLOCK_RATE_TRIAL, updated in place.  -> trials"""
+        n = state.numel() // RD_PICK.itemsize
+        assert state.is_cuda and state.is_contiguous() and state.element_size() == 1
+        assert isinstance(trials, torch.Tensor) and trials.is_cuda and trials.is_contiguous() and \
+            trials.element_size() == 1 and trials.numel() == n * BLOCK_RATE_TRIAL.itemsize
+        if eob_win is not None:
+            assert eob_win.is_cuda and eob_win.is_contiguous() and eob_win.element_size() == 2 and eob_win.numel() == n * 16
+        self._check(self.lib.r1_rd_winner_tx_type_batch(
+            self.h, state.data_ptr(), n, int(call_id), int(tx_type_mask), int(bool(is_inter)), int(uv_tx_size),
+            eob_win.data_ptr() if eob_win is not None else None, int(ntx), trials.data_ptr(), _stream_ptr()),
+            "r1_rd_winner_tx_type_batch")
+        return trials
 
     # ---- lrf:: ----
     def lrf_sgrproj_plane(self, cdeffed, deblocked, out, ydec, crop_w, crop_h, frame_height, unit_size,

@@ -44,6 +44,13 @@ the kernels by executing the reference's own text (tests/golden/gen_rdo_glue_ref
   dist_as_f64                src/rdo.rs:722           (`distortion.0 as f64`, applied by the two above before they cost)
                              the host statements of r1_rd_pick_batch; pinned by tests/golden/rd_pick_ref.npz /
                              tests/test_rd_pick_ref.py
+  coeff_nbr_store            src/context/block_unit.rs:333-348, src/context/partition_unit.rs:434-469  (what a coded or a
+                                                       skipped block leaves in the coefficient neighbour contexts)
+  coeff_nbr_reset_left       src/context/block_unit.rs:350-354, 394-397
+  winner_tx_type             src/encoder.rs:2507-2511  (the winner's slot as the adapt trial's tx_type / uv_tx_type)
+                             the host statements of r1_coeff_nbr_store_batch, r1_coeff_nbr_reset_left_batch and
+                             r1_rd_winner_tx_type_batch; pinned by tests/golden/coeff_nbr_ref.npz /
+                             tests/test_coeff_nbr_ref.py
 """
 from .types import BlockSize, TxSize
 
@@ -569,6 +576,79 @@ def coeff_cdf_context(fields):
         assert a.min() >= 0 and a.max() <= 0xFFFF, name
         rec[name] = a
     return rec
+
+
+def nbr_block(nbr, bo_x, bo_y, mi_width, mi_height, w_in_b, h_in_b, y_mode=0, cdf_sel=0, cdf_sel_uv=0, do_chroma=True,
+              skip=False):
+    """One R1NbrBlock, in the field order of types.NBR_BLOCK: a block's place on the device-resident neighbour context
+    `nbr`; the geometry arguments as block_chain_ctx takes them."""
+    return (int(nbr), int(bo_x), int(bo_y), int(mi_width), int(mi_height), int(w_in_b), int(h_in_b), int(y_mode),
+            int(cdf_sel), int(cdf_sel_uv), int(bool(do_chroma)) | int(bool(skip)) << 1)
+
+
+def coeff_nbr_store(above_rows, left_cols, bo_x, bo_y, bsize, xdec, ydec, do_chroma, skip, ctx_behind=None):
+    """What a block leaves in above_coeff_context / left_coeff_context, IN PLACE (the statement of
+    r1_coeff_nbr_store_batch).  above_rows[p] / left_cols[p]: the arrays as block_chain_ctx indexes them.
+    Coded (skip false): ctx_behind, the [3][2][16] R1BlockChainCtx.ctx behind the block (the rate call's ctx_out), goes
+    back over the block's spans -- luma bw / 4 and bh / 4 entries at (bo_x, bo_y % 16); with do_chroma the chroma
+    transform grid's span (chroma_tx_grid) at block_chain_ctx's chroma origin.  That is every set_coeff_context
+    (src/context/block_unit.rs:333-348) of the block's transform blocks: ctx_out passes through what none of them wrote.
+    Skipped: reset_skip_context (src/context/partition_unit.rs:434-469) -- zeros over bsize.subsampled_size(xdec, ydec) at
+    (bo_x >> xdec, (bo_y % 16) >> ydec); chroma with do_chroma and, whatever the flag, for BLOCK_4X16 / BLOCK_16X4: they
+    are not below BLOCK_8X8 in the enum's order, so the reference resets three planes there even where has_chroma says no
+    (every other size at or above BLOCK_8X8 has has_chroma true, and do_chroma false then means Cs400: one plane).
+    -> False, nothing written, where a span leaves the arrays (the device's refusal), else True"""
+    bw, bh = BlockSize(bsize).dims
+    bw4, bh4 = bw >> MI_SIZE_LOG2, bh >> MI_SIZE_LOG2
+    y_sb = bo_y % 16
+    width = len(above_rows[0])
+    if bo_x + bw4 > width or y_sb + bh4 > 16:
+        return False
+    if skip:
+        chroma = bool(do_chroma) or (bw, bh) in ((4, 16), (16, 4))
+        cx, cy = bo_x >> xdec, y_sb >> ydec
+        cw, ch = max(bw >> xdec, 4) >> MI_SIZE_LOG2, max(bh >> ydec, 4) >> MI_SIZE_LOG2
+    else:
+        uv_tx_size, bw_uv, bh_uv = chroma_tx_grid(bsize, xdec, ydec)
+        uw, uh = TxSize(uv_tx_size).dims
+        chroma = bool(do_chroma) and bw_uv * bh_uv > 0
+        ux, uy = bo_x - (bw == 4) * xdec, bo_y - (bh == 4) * ydec
+        if chroma and (ux < 0 or uy < 0):
+            return False
+        cx, cy = ux >> xdec, (uy % 16) >> ydec
+        cw, ch = bw_uv * (uw >> MI_SIZE_LOG2), bh_uv * (uh >> MI_SIZE_LOG2)
+    if chroma and (cx + cw > width or cy + ch > 16):
+        return False
+    value = (lambda p, a, k: 0) if skip else (lambda p, a, k: int(ctx_behind[p][a][k]))
+    for p in range(3 if chroma else 1):
+        x0, y0, w, h = (bo_x, y_sb, bw4, bh4) if p == 0 else (cx, cy, cw, ch)
+        for k in range(w):
+            above_rows[p][x0 + k] = value(p, 0, k)
+        for k in range(h):
+            left_cols[p][y0 + k] = value(p, 1, k)
+    return True
+
+
+def coeff_nbr_reset_left(left_cols, planes=3):
+    """reset_left_contexts' coefficient part (src/context/block_unit.rs:350-354, 394-397), IN PLACE: the statement of
+    r1_coeff_nbr_reset_left_batch"""
+    for p in range(planes):
+        for k in range(len(left_cols[p])):
+            left_cols[p][k] = 0
+
+
+def winner_tx_type(best_slot, tx_type_mask, is_inter, uv_tx_size=None, eobs=None):
+    """The statement of r1_rd_winner_tx_type_batch: -> (tx_type, uv_tx_type or None).  tx_type: the best_slot-th type of
+    the mask (tx_type_slots); None, None when best_slot lies outside it.  uv_tx_type: for inter, uv_tx_type_inter with
+    partition_has_coeff = any(eobs) over the winner's luma transform blocks (src/encoder.rs:2507-2511); for intra None --
+    it belongs to the chroma mode (uv_tx_type_intra)."""
+    slots = tx_type_slots(tx_type_mask)
+    if not 0 <= int(best_slot) < len(slots):
+        return None, None
+    tx_type = slots[int(best_slot)]
+    if not is_inter:
+        return tx_type, None
+    return tx_type, uv_tx_type_inter(tx_type, uv_tx_size, any(int(e) != 0 for e in eobs))
 
 
 def pick_tx_type(rates, dists, lam, cur_best_rd):

@@ -7,6 +7,7 @@ COEFF_CDFS / TXB_CTX: the NumPy mirrors of R1CoeffCdfs / R1TxbCtx (include/rav1e
 dimensions are the reference's (src/context/transform_unit.rs:27, 200-219).  TXB_CHAIN_CTX: R1TxbChainCtx
 (r1_coeff_rate_chain_batch).  BLOCK_CHAIN_CTX / BLOCK_RATE_TRIAL: R1BlockChainCtx / R1BlockRateTrial
 (r1_coeff_rate_block_batch).  COEFF_CDF_CONTEXT: R1CoeffCdfContext (r1_coeff_cdf_slice_batch, r1_coeff_cdf_adapt_batch).
+COEFF_NBR_CONTEXT / NBR_BLOCK: R1CoeffNbrContext / R1NbrBlock (r1_coeff_nbr_gather_batch, r1_coeff_nbr_store_batch).
 """
 import enum
 
@@ -163,3 +164,12 @@ COEFF_CDF_CONTEXT = np.dtype(
        ("inter_tx_3", "<u2", (TX_SIZE_SQR_CONTEXTS, 2)), ("pad", "<u2", (6,))])
 assert COEFF_CDF_CONTEXT.itemsize == 7872 and COEFF_CDF_CONTEXT.itemsize % 16 == 0
 PICK_FIRST_MIN, PICK_TX_TYPE = 0, 1   # R1_PICK_*
+# R1CoeffNbrContext / R1NbrBlock (r1_coeff_nbr_gather_batch, r1_coeff_nbr_store_batch, r1_coeff_nbr_reset_left_batch):
+# above_coeff_context / left_coeff_context of one tile (src/context/block_unit.rs:237-238), and a block's place in it
+COEFF_NBR_WIDTH = 1024                # COEFF_CONTEXT_MAX_WIDTH
+COEFF_NBR_CONTEXT = np.dtype([("above", "u1", (3, COEFF_NBR_WIDTH)), ("left", "u1", (3, 16))])
+NBR_BLOCK = np.dtype([("nbr", "<u4"), ("bo_x", "<u2"), ("bo_y", "<u2"), ("mi_width", "<u2"), ("mi_height", "<u2"),
+                      ("w_in_b", "<u2"), ("h_in_b", "<u2"), ("y_mode", "u1"), ("cdf_sel", "u1"), ("cdf_sel_uv", "u1"),
+                      ("flags", "u1")])
+assert COEFF_NBR_CONTEXT.itemsize == 3120 and NBR_BLOCK.itemsize == 20
+NBR_DO_CHROMA, NBR_SKIP = 1, 2        # R1NbrBlock.flags

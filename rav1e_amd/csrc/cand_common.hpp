@@ -221,7 +221,13 @@ __device__ __forceinline__ bool taps_six(const Taps<2> &t) {
 // 6 live taps; only SHARP has 8, mc.rs:110-219).  Then the first and the last window row never meet
 // a non-zero tap and the odd output rows' five tap pairs are three: 2 fewer horizontal rows per
 // column and one v_dot2 less per pixel pair, the same bits.
-template <int W, int H, int WS, bool PREP>
+// PACK4 (put only; the fused coefficient kernels, rdo_mc_pack4 of rdo_cand_plan.hpp): the packed intermediates are
+// 4 * mid, not mid.  The horizontal accumulator 4 * mid + fraction lies in [-7106, 23494] over every row of the tap
+// table with the bias below included (tests/test_mc8_pack4.py), so its low 16 bits are the value and clearing the two
+// fraction bits of each half after the v_perm leaves 4 * mid there: two instructions per row pair instead of three.
+// The vertical sums are then exactly four times what they were, below 2^23 in magnitude, and >> 13 returns the bits
+// of >> 11.  Every other caller keeps PACK4 off and its code.
+template <int W, int H, int WS, bool PREP, bool PACK4 = false>
 __device__ __forceinline__ void mc8_column_t(const uint8_t *win, int c, const Taps<1> &tp, int32_t *pred, bool six) {
   const uint32_t fx0 = tp.fx0, fx1 = tp.fx1;
   uint32_t ty[4], tz[5];
@@ -233,6 +239,7 @@ __device__ __forceinline__ void mc8_column_t(const uint8_t *win, int c, const Ta
   //   mid = (sum t*p + 4) >> 3 = (sum h*q + 8192 + 2) >> 2.
   // put only: the vertical rounding 1024 = 128 * 8 is pre-added to the
   // intermediates (every tap row sums to 128): + 8 after the shift = + 32 before.
+  static_assert(!(PREP && PACK4), "the shift-free pack is stated for put_8tap only");
   constexpr int32_t bias = 8192 + 2 + (PREP ? 0 : 32);
   constexpr int WSD = WS / 4;
   const uint32_t *wrow = (const uint32_t *)win + (c >> 2);
@@ -254,8 +261,13 @@ __device__ __forceinline__ void mc8_column_t(const uint8_t *win, int c, const Ta
   };
   auto hpair = [&](int r) -> uint32_t {   // rows r, r+1 packed as i16 x 2
     // the last pair has no second row: its upper half only ever meets a zero tap (tz[4]'s high half)
-    if (r + 1 < H + 7) return ashr_pair(hacc(r), hacc(r + 1), 2);
-    return (uint32_t)(hacc(r) >> 2);
+    if constexpr (PACK4) {
+      if (r + 1 < H + 7) return pk_pair(hacc(r), hacc(r + 1)) & 0xfffcfffcu;
+      return (uint32_t)hacc(r) & 0xfffffffcu;
+    } else {
+      if (r + 1 < H + 7) return ashr_pair(hacc(r), hacc(r + 1), 2);
+      return (uint32_t)(hacc(r) >> 2);
+    }
   };
   // rolling window of 5 packed pairs: output rows 2j and 2j+1 need the
   // intermediates 2j .. 2j+8
@@ -263,7 +275,8 @@ __device__ __forceinline__ void mc8_column_t(const uint8_t *win, int c, const Ta
     constexpr bool SIX = decltype(six_tag)::value;
     uint32_t pk[5];
     // SIX: window row 0 only meets u0 = 0 -- the pair (row 0, row 1) is (anything, row 1)
-    pk[0] = SIX ? (uint32_t)(hacc(1) >> 2) << 16 : hpair(0);
+    if constexpr (PACK4) pk[0] = SIX ? ((uint32_t)hacc(1) & 0xfffcu) << 16 : hpair(0);
+    else pk[0] = SIX ? (uint32_t)(hacc(1) >> 2) << 16 : hpair(0);
 #pragma unroll
     for (int j = 1; j < 4; j++) pk[j] = hpair(2 * j);
 #pragma unroll
@@ -294,8 +307,8 @@ __device__ __forceinline__ void mc8_column_t(const uint8_t *win, int c, const Ta
         pred[2 * j] = a0 >> 7;
         pred[2 * j + 1] = a1 >> 7;
       } else {
-        a0 >>= 11;
-        a1 >>= 11;
+        a0 >>= PACK4 ? 13 : 11;
+        a1 >>= PACK4 ? 13 : 11;
         pred[2 * j] = a0 < 0 ? 0 : (a0 > 255 ? 255 : a0);
         pred[2 * j + 1] = a1 < 0 ? 0 : (a1 > 255 ? 255 : a1);
       }
@@ -405,10 +418,11 @@ __device__ __forceinline__ void mc16_column_t(const uint8_t *win, int c, const T
 
 // One column of put_8tap (PREP: prep_8tap) of a W x H block at either pixel width, from a window staged with row
 // stride WS (8-bit: pixels biased by -128); `six` is taps_six(tp), voted by every lane that makes the call.
-template <int BPP, int W, int H, int WS, bool PREP>
+template <int BPP, int W, int H, int WS, bool PREP, bool PACK4 = false>
 __device__ __forceinline__ void mc_column_fast(const uint8_t *win, int c, const Taps<BPP> &tp, int bit_depth,
                                                int32_t *pred, bool six) {
-  if constexpr (BPP == 1) mc8_column_t<W, H, WS, PREP>(win, c, tp, pred, six);
+  static_assert(!PACK4 || BPP == 1, "8 * mid of 16-bit pixels does not fit i16");
+  if constexpr (BPP == 1) mc8_column_t<W, H, WS, PREP, PACK4>(win, c, tp, pred, six);
   else mc16_column_t<W, H, WS, PREP>(win, c, tp, bit_depth, pred, six);
 }
 

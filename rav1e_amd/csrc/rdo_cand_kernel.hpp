@@ -120,6 +120,8 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
   constexpr bool COL_FOLD = PL::COL_FOLD;
   static_assert(!COL_FOLD || SH0 > 0, "the column family starts from a pending shift[0]");
   constexpr int SH1C = COL_FOLD ? 0 : SH1;
+  // HALVE2 / MC_PACK4 (rdo_cand_plan.hpp): the networks of m24h in both passes; the shift-free pack of the 8-bit filter
+  constexpr bool HALVE2 = PL::HALVE2, MC_PACK4 = PL::MC_PACK4;
   __shared__ __attribute__((aligned(16))) uint8_t smem[LDS_BYTES];
   T *buf = (T *)smem;
   TB *tbuf = (TB *)smem;
@@ -318,7 +320,7 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
 #pragma unroll
         for (int r = 0; r < H; r++) pred[r] = pi[(size_t)r * W];
       } else {
-        r1cand::mc_column_fast<BPP, W, H, WS, false>(win, c, tp, BD, pred, six);
+        r1cand::mc_column_fast<BPP, W, H, WS, false, MC_PACK4>(win, c, tp, BD, pred, six);
       }
       if (pred_out && live_st) {
         uint8_t *pp = (uint8_t *)pred_out + (size_t)cand * W * H + c;
@@ -504,13 +506,13 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
       }
     }
     if constexpr (COL_FOLD) {   // shift[0], the network and shift[1] as one: the column family on the unshifted residuals
-      if (TX_VOTE && col_uni) r1tx::fwd_col_m24_kernel<H, SH0, SH1>(v, r1tx::vtx_1d(tx_s));
-      else r1tx::fwd_col_m24<H, SH0, SH1>(v, r1tx::vtx_1d(tx_col));
+      if (TX_VOTE && col_uni) r1tx::fwd_col_m24_kernel<H, SH0, SH1, HALVE2>(v, r1tx::vtx_1d(tx_s));
+      else r1tx::fwd_col_m24<H, SH0, SH1, HALVE2>(v, r1tx::vtx_1d(tx_col));
     } else {
 #pragma unroll
       for (int r = 0; r < H; r++) v[r] = r1tx::shift_fwd_ct<SH0>(v[r]);
-      if (TX_VOTE && col_uni) r1tx::fwd_1d_m24_kernel<H>(v, r1tx::vtx_1d(tx_s));
-      else r1tx::fwd_1d_m24<H>(v, r1tx::vtx_1d(tx_col));
+      if (TX_VOTE && col_uni) r1tx::fwd_1d_m24_kernel<H, HALVE2>(v, r1tx::vtx_1d(tx_s));
+      else r1tx::fwd_1d_m24<H, HALVE2>(v, r1tx::vtx_1d(tx_col));
     }
     if constexpr (!SPLIT_T) {
       const int cc = cl * W + (r1tx::lr_flip(tx_col) ? W - 1 - c : c);
@@ -561,8 +563,8 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
       for (int k = 0; k < W; k++) u[k] = tkeep[r * LSTRIDE + cl2 * W + k];
     }
     // the switch on the scalar or per lane, as in phase C (the left-right flip is the tile store's column)
-    if (TX_VOTE && row_uni) r1tx::fwd_1d_m24_kernel<W>(u, r1tx::htx_1d(tx_s));
-    else r1tx::fwd_1d_m24<W>(u, r1tx::htx_1d(tt));
+    if (TX_VOTE && row_uni) r1tx::fwd_1d_m24_kernel<W, HALVE2>(u, r1tx::htx_1d(tx_s));
+    else r1tx::fwd_1d_m24<W, HALVE2>(u, r1tx::htx_1d(tt));
 #pragma unroll
     for (int k = 0; k < W; k++) {
       u[k] = r1tx::shift_fwd_ct<SH2>(u[k]);

@@ -110,6 +110,29 @@ constexpr bool rdo_col_fold(int bd, int wl, int hl, int qm, bool mt, int ps) {
   return bd == 10 && qm == 0 && (wl == 4 || wl == 5);
 }
 
+// Whether an instantiation's forward networks, both passes, halve toward zero in two instructions (m24h, tx_common.hpp:
+// exact while the operand is below 2^24, and every halving operand of a chain fed from pixels is below 2^18.01), and
+// whether its 8-bit motion compensation packs the horizontal accumulators without shifting them (mc8_column_t<..,
+// PACK4>, cand_common.hpp).  Both are exact; like COL_FOLD each is on only where its launch was measured faster than
+// the parent's on one box, in four sessions of alternated passes (profiles/r20_halve_pack_notes.md).  Candidates were
+// the coefficient kernels (QM 0) of the square sizes 8x8 .. 64x64: the halving at 8 and 10 bits, the pack at 8 bits.
+//   halving, 8 bits    64x64 / 32x32 / 16x16 / 8x8 launches -3.1 / -3.7 / -2.4 / -1.3 %
+//   halving, 10 bits   64x64 / 16x16 -1.8 / -1.9 %.  32x32 measured -3.7 % but the kernel, held at 80 VGPRs by
+//                      rdo_waves_hint, gains 8 B of scratch per lane: off (tools/kres.py).  8x8: inside the spread, off.
+//   pack, on the halving   32x32 / 16x16 / 8x8 a further -0.3 .. -0.9 %; 64x64 nothing in any session: off there.
+// Nothing else was measured, so the quantizer chains, the type search, the intra prediction source, the rectangles, 4x4
+// and 12 bits keep the code they had.
+constexpr bool rdo_plain_square(int wl, int hl, int qm, bool mt, int ps) {
+  return qm == 0 && !mt && ps == 0 && wl == hl && wl >= 3 && wl <= 6;
+}
+constexpr bool rdo_halve2(int bd, int wl, int hl, int qm, bool mt, int ps) {
+  if (!rdo_plain_square(wl, hl, qm, mt, ps)) return false;
+  return bd == 8 || (bd == 10 && (wl == 4 || wl == 6));
+}
+constexpr bool rdo_mc_pack4(int bd, int wl, int hl, int qm, bool mt, int ps) {
+  return bd == 8 && rdo_plain_square(wl, hl, qm, mt, ps) && wl <= 5;
+}
+
 // ---- one instantiation: geometry, choices, LDS layout ----
 // PS: where the prediction comes from -- 0 = put_8tap of the reference window (or the dense qa.pred_in buffer),
 // 1 = intra prediction from the candidate's edge set.  One wave per workgroup; a wave owns NC candidates.
@@ -121,6 +144,8 @@ struct RdoCandPlan {
   static constexpr int P = W > H ? W : H, NC = 64 / P;
   static constexpr int TS = (W < H ? W : H) == 4 ? 4 : 8;
   static constexpr bool COL_FOLD = rdo_col_fold(BD, WL, HL, QM, MT, PS);
+  static constexpr bool HALVE2 = rdo_halve2(BD, WL, HL, QM, MT, PS);
+  static constexpr bool MC_PACK4 = rdo_mc_pack4(BD, WL, HL, QM, MT, PS);
   static constexpr int WS = r1mc::window_stride(W, BPP);
   // INTRA: no reference window.  The candidate's edge arrays (raw edge + the four filter / upsample arrays, FL
   // entries each) take its place and may lie over the WHOLE allocation: the source block waits in registers until

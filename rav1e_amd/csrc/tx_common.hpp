@@ -81,14 +81,38 @@ __device__ __forceinline__ T shl_subr(T b, T a) {
 #define TX_SHL_SUBR(b, d, a) (shl_subr<(d)>((b), (a)))
 #define TX_RND(a, s) (((a) + (1 << ((s) - 1))) >> (s))
 #include "fwd_tx_1d_col.inc"
+}  // namespace m24
+// Third instantiation, both families again: the halving toward zero as (a - (a >> 24)) >> 1.  For |a| < 2^24 the
+// byte a >> 24 is the sign, 0 or -1, so the value is TX_RSHIFT1's; the compiler folds the shift into the subtract's
+// operand (v_sub_u32_sdwa .. sext(BYTE_3)), two instructions and one link of the dependent chain instead of three.
+// Every halving operand of a column or row network of a chain fed from pixels is bounded below 2^18.01, plain and
+// column family alike (tools/tx_range.py halving_bounds(), asserted by tools/gen_tx1d.py); for the square sizes
+// 8x8 .. 64x64 at 8 and 10 bits, the only ones that take the form (rdo_halve2, rdo_cand_plan.hpp), both forms are also
+// run against each other on the host (tests/test_tx_halve2.py).
+namespace m24h {
+using m24::mul_rk;
+using m24::mul_rs;
+using m24::shl_subr;
+#undef TX_RSHIFT1
+#define TX_RSHIFT1(a) (TX_SUB((a), (a) >> 24) >> 1)
+#include "fwd_tx_1d.inc"
+#include "fwd_tx_1d_col.inc"
+#undef TX_RSHIFT1
+#define TX_RSHIFT1(a) (TX_ADD((a), (T)((a) < 0)) >> 1)
+}  // namespace m24h
 #undef TX_MULK
 #undef TX_SHL
 #undef TX_SHL_ADD
 #undef TX_SHL_SUBR
 #undef TX_RND
 #undef TX_MUL
-}  // namespace m24
 #undef TX1D_FN
+// m24:: or, H2, m24h:: in front of a network call
+#define R1_M24(H2, ...)                  \
+  do {                                   \
+    if constexpr (H2) m24h::__VA_ARGS__; \
+    else m24::__VA_ARGS__;               \
+  } while (0)
 
 // 1-D transform classes: 0 DCT, 1 ADST, 2 FLIPADST, 3 IDTX, 4 WHT (VTX_TAB / HTX_TAB,
 // src/transform/mod.rs:364-402).  Two bits per tx_type 0..15 in one immediate (WHT = 16 apart):
@@ -180,41 +204,44 @@ __device__ __forceinline__ T shift_fwd(T v, int shift) {
 }
 
 // Same dispatch on the 24-bit-multiply instantiation.
-template <int N>
+// H2: the networks of m24h (the two-instruction halving), for the sizes that have them (N >= 8).
+template <int N, bool H2 = false>
 __device__ __forceinline__ void fwd_1d_m24(T *c, int k) {
+  static_assert(!H2 || N >= 8, "the 4-point networks keep the plain halving");
   if (k == 3) return;
   if constexpr (N == 4) {
     if (k == 0) m24::r1_fdct4(c);
     else if (k == 4) m24::r1_fwht4(c);
     else m24::r1_fdst_vii_4(c);
   } else if constexpr (N == 8) {
-    if (k == 0) m24::r1_fdct8(c); else m24::r1_fdst8(c);
+    if (k == 0) R1_M24(H2, r1_fdct8(c)); else R1_M24(H2, r1_fdst8(c));
   } else if constexpr (N == 16) {
-    if (k == 0) m24::r1_fdct16(c); else m24::r1_fdst16(c);
+    if (k == 0) R1_M24(H2, r1_fdct16(c)); else R1_M24(H2, r1_fdst16(c));
   } else if constexpr (N == 32) {
-    m24::r1_fdct32(c);
+    R1_M24(H2, r1_fdct32(c));
   } else {
-    m24::r1_fdct64(c);
+    R1_M24(H2, r1_fdct64(c));
   }
 }
 // ... for a class the caller knows to have a kernel (anything but the identity): every arm writes all of c, so a
 // switch on a wave-uniform `k` merges its arms without a copy (k_rdo_cand, TX_VOTE).  The switch is written out a
 // second time: the compiler does not carry a `k != 3` assumption through to the test above, and fwd_1d_m24 expressed
 // through this function changes the code of every kernel that calls it.
-template <int N>
+template <int N, bool H2 = false>
 __device__ __forceinline__ void fwd_1d_m24_kernel(T *c, int k) {
+  static_assert(!H2 || N >= 8, "the 4-point networks keep the plain halving");
   if constexpr (N == 4) {
     if (k == 0) m24::r1_fdct4(c);
     else if (k == 4) m24::r1_fwht4(c);
     else m24::r1_fdst_vii_4(c);
   } else if constexpr (N == 8) {
-    if (k == 0) m24::r1_fdct8(c); else m24::r1_fdst8(c);
+    if (k == 0) R1_M24(H2, r1_fdct8(c)); else R1_M24(H2, r1_fdst8(c));
   } else if constexpr (N == 16) {
-    if (k == 0) m24::r1_fdct16(c); else m24::r1_fdst16(c);
+    if (k == 0) R1_M24(H2, r1_fdct16(c)); else R1_M24(H2, r1_fdst16(c));
   } else if constexpr (N == 32) {
-    m24::r1_fdct32(c);
+    R1_M24(H2, r1_fdct32(c));
   } else {
-    m24::r1_fdct64(c);
+    R1_M24(H2, r1_fdct64(c));
   }
 }
 
@@ -228,9 +255,10 @@ __device__ __forceinline__ T shift_col_ident(T v) {
   if constexpr (SH0 + SH1 >= 0) return shift_fwd_ct<SH0 + SH1>(v);
   else return shift_fwd_ct<SH1>(shift_fwd_ct<SH0>(v));
 }
-template <int N, int SH0, int SH1, bool IDENT>
+template <int N, int SH0, int SH1, bool IDENT, bool H2>
 __device__ __forceinline__ void fwd_col_m24_sw(T *c, int k) {
   static_assert(SH0 > 0 && SH1 <= 0, "shift[0] = 0 and a left shift[1] have no member in the column family");
+  static_assert(!H2 || N >= 8, "the 4-point networks keep the plain halving");
   constexpr int S = -SH1;
   if constexpr (IDENT) {
     if (k == 3) {
@@ -249,19 +277,19 @@ __device__ __forceinline__ void fwd_col_m24_sw(T *c, int k) {
       for (int r = 0; r < N; r++) c[r] = shift_fwd_ct<SH1>(c[r]);
     } else m24::r1_fdst_vii_4_col<SH0, S>(c);
   } else if constexpr (N == 8) {
-    if (k == 0) m24::r1_fdct8_col<SH0, S>(c); else m24::r1_fdst8_col<SH0, S>(c);
+    if (k == 0) R1_M24(H2, r1_fdct8_col<SH0, S>(c)); else R1_M24(H2, r1_fdst8_col<SH0, S>(c));
   } else if constexpr (N == 16) {
-    if (k == 0) m24::r1_fdct16_col<SH0, S>(c); else m24::r1_fdst16_col<SH0, S>(c);
+    if (k == 0) R1_M24(H2, r1_fdct16_col<SH0, S>(c)); else R1_M24(H2, r1_fdst16_col<SH0, S>(c));
   } else if constexpr (N == 32) {
-    m24::r1_fdct32_col<SH0, S>(c);
+    R1_M24(H2, r1_fdct32_col<SH0, S>(c));
   } else {
-    m24::r1_fdct64_col<SH0, S>(c);
+    R1_M24(H2, r1_fdct64_col<SH0, S>(c));
   }
 }
-template <int N, int SH0, int SH1>
-__device__ __forceinline__ void fwd_col_m24(T *c, int k) { fwd_col_m24_sw<N, SH0, SH1, true>(c, k); }
-template <int N, int SH0, int SH1>
-__device__ __forceinline__ void fwd_col_m24_kernel(T *c, int k) { fwd_col_m24_sw<N, SH0, SH1, false>(c, k); }
+template <int N, int SH0, int SH1, bool H2 = false>
+__device__ __forceinline__ void fwd_col_m24(T *c, int k) { fwd_col_m24_sw<N, SH0, SH1, true, H2>(c, k); }
+template <int N, int SH0, int SH1, bool H2 = false>
+__device__ __forceinline__ void fwd_col_m24_kernel(T *c, int k) { fwd_col_m24_sw<N, SH0, SH1, false, H2>(c, k); }
 
 // One 1-D forward transform of length N on a register array, class `k`
 // (0 DCT, 1/2 ADST (flip handled by the caller), 3 identity, 4 WHT).

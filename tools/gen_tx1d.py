@@ -116,6 +116,19 @@ def value_bounds(n, ops, inmax):
     return {k: int(math.ceil(inmax * sum(abs(x) for x in v) + err[k])) for k, v in vec.items()}
 
 
+def halving_bound(n, ops, outs, inmax):
+    """(largest |operand| of a TX_RSHIFT1, largest |output|) of the network fed with |input| <= inmax.  The column
+    family executes a halving only on a value with no pending scale (k = 0), whose register IS the plain network's
+    value when that is fed with inmax << K0: the bound of the plain network covers both."""
+    vb = value_bounds(n, ops, inmax)
+    hs = [vb[a[0]] for op, a in (_parse(expr) for _, expr in ops) if op == "RSHIFT1"]
+    return (max(hs) if hs else 0), max(vb[o] for o in outs)
+
+
+# (a - (a >> 24)) >> 1, the halving of m24h (csrc/tx_common.hpp), is TX_RSHIFT1 while a >> 24 is the sign
+HALVE2_LIMIT = 1 << 24
+
+
 def plain_counts(n, ops, k0, s):
     """(fast, slow) instructions of shift[0], the plain network and shift[1]"""
     fast, slow = (2 * n if s > 0 else 0), (n if k0 > 0 else 0)
@@ -289,6 +302,8 @@ def col_family():
             lines, (ff, fs), fm, pm = fold(n, ops, outs, k0, s, inmax)
             pf, ps = plain_counts(n, ops, k0, s)
             assert fm <= pm and pm < (1 << 23), (nm, k0, s, fm, pm)
+            hb, _ = halving_bound(n, ops, outs, inmax << k0)
+            assert hb < HALVE2_LIMIT, (nm, k0, s, hb)
             body.append("template <> TX1D_FN void r1_%s_col<%d, %d>(T *c) {\n" % (nm, k0, s) +
                         "  const T " + ", ".join("c%d = c[%d]" % (i, i) for i in range(n)) + ";\n" +
                         "\n".join(lines) + "\n}")
@@ -332,4 +347,7 @@ def main():
 
 
 if __name__ == "__main__":
+    import tx_range   # column and row pass in their chain: every halving operand the fused kernels meet
+    for (bd, ts, tt), hb in sorted(tx_range.halving_bounds().items()):
+        assert hb < HALVE2_LIMIT, (bd, ts, tt, hb)
     main()

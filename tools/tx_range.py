@@ -81,7 +81,46 @@ def shifted_coefficient_bound():
     return worst
 
 
+def halving_bounds():
+    """{(bit depth, tx_size, tx_type): largest |operand| of a TX_RSHIFT1 in the column pass and the row pass of a
+    fused kernel}, residuals from pixels: the plain networks fed with residual << shift[0], or the column family on
+    the unshifted residual (the same values, tools/gen_tx1d.py halving_bound), then the row network fed with the
+    column outputs after shift[1].  The two-instruction halving of m24h (csrc/tx_common.hpp) needs them below
+    2^24.  Bounds are L1 norms of the SSA values' responses plus the accumulated rounding, as for the 24-bit mads.
+    The composition is forward_transform's (oracle/fwd_tx_np.py, forward.rs:71-161) for all 19 sizes: that function
+    has no step of its own for rectangles (the daala networks carry their scaling), and its identity is a no-op
+    (forward_shared.rs:1775).  The form is enabled, and run numerically by tests/test_tx_halve2.py, only for the
+    square sizes 8x8 .. 64x64; for the other sizes this is the bound alone."""
+    import math
+    import gen_tx1d as G
+    nets = {}
+
+    def bound(t, inmax):
+        if G.NAMES[t] is None:    # the identity: no halving, outputs = inputs (tx_type < 16: the WHT is never met)
+            return 0, inmax
+        if t not in nets:
+            nets[t] = G.trace_ops(t)
+        n, ops, outs = nets[t]
+        return G.halving_bound(n, ops, outs, inmax)
+    res = {}
+    for bd in (8, 10, 12):
+        for ts, (w, h) in enumerate(F.TX_DIMS):
+            for tt in range(16):
+                if not F.valid_av1_transform(ts, tt):
+                    continue
+                sh = F.FWD_SHIFT[ts][(bd - 8) // 2]
+                tcol = F.TXFM_TYPE_LS[h.bit_length() - 3][F.VTX_TAB[tt]]
+                trow = F.TXFM_TYPE_LS[w.bit_length() - 3][F.HTX_TAB[tt]]
+                hcol, ocol = bound(tcol, ((1 << bd) - 1) << sh[0])
+                hrow, _ = bound(trow, int(math.ceil(ocol * 2.0 ** sh[1])) + 1)
+                res[bd, ts, tt] = max(hcol, hrow)
+    return res
+
+
 if __name__ == "__main__":
+    hb = halving_bounds()
+    for bd in (8, 10, 12):
+        print("bd %d: halving operands < 2^%.2f" % (bd, np.log2(max(v for k, v in hb.items() if k[0] == bd))))
     rows = analyse()
     worst = max(rows, key=lambda r: r[3])
     print("worst multiplier input: bd=%d tx_size=%d tx_type=%d |a| <= %.0f = 2^%.2f"

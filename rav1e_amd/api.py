@@ -199,6 +199,36 @@ def _check_coeffs(qcoeffs, eobs, dtype=None):
     assert eobs.is_cuda and eobs.is_contiguous() and eobs.element_size() == 2
 
 
+def _block_coeffs(qcoeffs_y, eobs_y, chroma, trials, blocks, bw, bh, tx_size, xdec, ydec):
+    """The coefficient, trial and block arguments coeff_rate_block_batch and coeff_cdf_adapt_batch share: the arrays
+    checked against the luma and the chroma transform size, the records on the device.
+    -> (the four chroma pointers -- None each without chroma --, chroma transform blocks per plane, trials, n, blocks,
+    n_blocks)"""
+    from . import rdo_glue
+    tw, th = TxSize(tx_size).dims
+    _check_coeffs(qcoeffs_y, eobs_y)
+    area = min(tw, 32) * min(th, 32)
+    assert qcoeffs_y.numel() == eobs_y.numel() * area, (qcoeffs_y.numel(), eobs_y.numel(), area)
+    uv_ptrs, n_uv = [None] * 4, 0
+    if chroma is not None:
+        qu, eu, qv, ev = chroma
+        uw, uh = TxSize(rdo_glue.largest_chroma_tx_size(rdo_glue.block_size(bw, bh), xdec, ydec)).dims
+        for q, e in ((qu, eu), (qv, ev)):
+            _check_coeffs(q, e, qcoeffs_y.dtype)
+            assert q.numel() == e.numel() * uw * uh and e.numel() == eu.numel(), (q.numel(), e.numel(), uw, uh)
+        uv_ptrs, n_uv = [t.data_ptr() for t in (qu, eu, qv, ev)], eu.numel()
+    dtr, n = _dev_cands(trials, BLOCK_RATE_TRIAL)
+    dbl, n_blocks = _dev_cands(blocks, BLOCK_CHAIN_CTX)
+    return uv_ptrs, n_uv, dtr, n, dbl, n_blocks
+
+
+def _rd_pick_states(state, n=None):
+    """state: a uint8 device tensor of RD_PICK records, n of them where the caller knows the count -> the count"""
+    assert state.is_cuda and state.is_contiguous() and state.element_size() == 1
+    assert n is None or state.numel() == n * RD_PICK.itemsize
+    return state.numel() // RD_PICK.itemsize
+
+
 def _bind_wanted(outs, spec, dev):
     """(a copy of outs with every wanted output of spec = {key: (want, shape, dtype)} allocated on dev that is not in
     it yet, the data pointers by key: None for an output that is not wanted, handed in or not)"""
@@ -1151,21 +1181,8 @@ class Context:
         -> {"rate": (n,) int32 holding uint32 1/8 bits (COEFF_RATE_INVALID for a trial with out-of-range device
         inputs), "plane_rate": (n, 3) int32, "rng": (n,) int16 holding uint16, "cul_level": (n, 3, 16) uint8,
         "ctx": (n, 3, 2, 16) uint8}; the four side outputs are optional."""
-        from . import rdo_glue
-        tw, th = TxSize(tx_size).dims
-        _check_coeffs(qcoeffs_y, eobs_y)
-        area = min(tw, 32) * min(th, 32)
-        assert qcoeffs_y.numel() == eobs_y.numel() * area, (qcoeffs_y.numel(), eobs_y.numel(), area)
-        uv_ptrs, n_uv = [None] * 4, 0
-        if chroma is not None:
-            qu, eu, qv, ev = chroma
-            uw, uh = TxSize(rdo_glue.largest_chroma_tx_size(rdo_glue.block_size(bw, bh), xdec, ydec)).dims
-            for q, e in ((qu, eu), (qv, ev)):
-                _check_coeffs(q, e, qcoeffs_y.dtype)
-                assert q.numel() == e.numel() * uw * uh and e.numel() == eu.numel(), (q.numel(), e.numel(), uw, uh)
-            uv_ptrs, n_uv = [t.data_ptr() for t in (qu, eu, qv, ev)], eu.numel()
-        dtr, n = _dev_cands(trials, BLOCK_RATE_TRIAL)
-        dbl, n_blocks = _dev_cands(blocks, BLOCK_CHAIN_CTX)
+        uv_ptrs, n_uv, dtr, n, dbl, n_blocks = _block_coeffs(qcoeffs_y, eobs_y, chroma, trials, blocks, bw, bh, tx_size,
+                                                             xdec, ydec)
         dcdf, n_cdfs = _dev_cands(cdfs, COEFF_CDFS)
         o, ptr = _bind_wanted(outs, {
             "rate": (True, (n,), torch.int32), "plane_rate": (want_plane_rate, (n, 3), torch.int32),
@@ -1204,26 +1221,12 @@ class Context:
         state[t].best_call == call_id, else nothing of it is written.
         -> {"rate": (n,) int32 holding uint32, "rng": (n,) int16 holding uint16, "ctx": (n, 3, 2, 16) uint8}, all
         optional"""
-        from . import rdo_glue
-        tw, th = TxSize(tx_size).dims
-        _check_coeffs(qcoeffs_y, eobs_y)
-        area = min(tw, 32) * min(th, 32)
-        assert qcoeffs_y.numel() == eobs_y.numel() * area, (qcoeffs_y.numel(), eobs_y.numel(), area)
-        uv_ptrs, n_uv = [None] * 4, 0
-        if chroma is not None:
-            qu, eu, qv, ev = chroma
-            uw, uh = TxSize(rdo_glue.largest_chroma_tx_size(rdo_glue.block_size(bw, bh), xdec, ydec)).dims
-            for q, e in ((qu, eu), (qv, ev)):
-                _check_coeffs(q, e, qcoeffs_y.dtype)
-                assert q.numel() == e.numel() * uw * uh and e.numel() == eu.numel(), (q.numel(), e.numel(), uw, uh)
-            uv_ptrs, n_uv = [t.data_ptr() for t in (qu, eu, qv, ev)], eu.numel()
-        dtr, n = _dev_cands(trials, BLOCK_RATE_TRIAL)
-        dbl, n_blocks = _dev_cands(blocks, BLOCK_CHAIN_CTX)
+        uv_ptrs, n_uv, dtr, n, dbl, n_blocks = _block_coeffs(qcoeffs_y, eobs_y, chroma, trials, blocks, bw, bh, tx_size,
+                                                             xdec, ydec)
         assert isinstance(contexts, torch.Tensor) and contexts.is_cuda and contexts.is_contiguous() and \
             contexts.element_size() == 1 and contexts.numel() == n * COEFF_CDF_CONTEXT.itemsize, "one context per trial"
         if state is not None:
-            assert state.is_cuda and state.is_contiguous() and state.element_size() == 1 and \
-                state.numel() == n * RD_PICK.itemsize
+            _rd_pick_states(state, n)
         o, ptr = _bind_wanted(outs, {"rate": (want_rate, (n,), torch.int32), "rng": (want_rng, (n,), torch.int16),
                                      "ctx": (want_ctx, (n, 3, 2, 16), torch.uint8)}, qcoeffs_y.device)
         self._check(self.lib.r1_coeff_cdf_adapt_batch(
@@ -1252,8 +1255,7 @@ class Context:
         outputs as they lie), dist: 8-byte (uint64).  state: (n_states, 24) uint8 device tensor (rd_pick_state),
         updated in place.  rule: PICK_FIRST_MIN, or PICK_TX_TYPE (group == 1: rdo_tx_type_decision's loop with its
         early exit).  -> {"state": state, "invalid": (n_states,) uint8 when wanted}"""
-        n = state.numel() // RD_PICK.itemsize
-        assert state.is_cuda and state.is_contiguous() and state.element_size() == 1
+        n = _rd_pick_states(state)
         for t, size in ((rate, 4), (dist, 8)) + (((rate_add, 4),) if rate_add is not None else ()):
             assert t.is_cuda and t.is_contiguous() and t.element_size() == size and t.numel() == n * group * nt, \
                 (t.shape, t.dtype, n, group, nt)
@@ -1276,8 +1278,7 @@ class Context:
         side: (trials, side_bytes) uint8 -> outs["side_win"] (n, side_bytes).
         rec_trials: (trials, bh, bw) dense blocks in the plane's pixel type -> `rec` (a Plane) at pos_xy ((n, 2) int16
         device tensor), clipped to store_w x store_h (the plane's visible size by default); blocks must not overlap."""
-        n = state.numel() // RD_PICK.itemsize
-        assert state.is_cuda and state.is_contiguous() and state.element_size() == 1
+        n = _rd_pick_states(state)
         o = dict(outs) if outs else {}
         eobs = qc = None
         area = cbytes = stride = 0
@@ -1359,8 +1360,7 @@ class Context:
         if ctx_in is not None:
             assert ctx_in.is_cuda and ctx_in.is_contiguous() and ctx_in.element_size() == 1 and ctx_in.numel() == n * 96
         if state is not None:
-            assert state.is_cuda and state.is_contiguous() and state.element_size() == 1 and \
-                state.numel() == n * RD_PICK.itemsize
+            _rd_pick_states(state, n)
         self._check(self.lib.r1_coeff_nbr_store_batch(
             self.h, dd.data_ptr(), n, int(bw), int(bh), int(tx_size), int(xdec), int(ydec),
             ctx_in.data_ptr() if ctx_in is not None else None, state.data_ptr() if state is not None else None,
@@ -1384,8 +1384,7 @@ class Context:
         of tx_type_mask and, with is_inter, trials[s].uv_tx_type = rdo_glue.uv_tx_type_inter of it (DCT_DCT when the
         winner's ntx eobs in eob_win, rd_commit_batch's (n, 16), are all zero).  trials: (n, 24) uint8 device tensor of
         BLOCK_RATE_TRIAL, updated in place.  -> trials"""
-        n = state.numel() // RD_PICK.itemsize
-        assert state.is_cuda and state.is_contiguous() and state.element_size() == 1
+        n = _rd_pick_states(state)
         assert isinstance(trials, torch.Tensor) and trials.is_cuda and trials.is_contiguous() and \
             trials.element_size() == 1 and trials.numel() == n * BLOCK_RATE_TRIAL.itemsize
         if eob_win is not None:

@@ -10,8 +10,8 @@
 // (write_tx_tree's rule for chroma, src/encoder.rs:2507-2511; TxType::uv_inter, src/transform/mod.rs:81-97).
 // Byte movers: no LDS, no scratch, no atomics, no spin-waits; every loop is bounded by 16.  All enqueue on the caller's
 // stream; nothing is read back.  Pinned by tests/golden/coeff_nbr_ref.npz.
+#include "block_geom.hpp"
 #include "common.hpp"
-#include "entry.hpp"
 
 #include <stddef.h>
 
@@ -248,24 +248,11 @@ static bool aligned4(const void *p) { return ((uintptr_t)p & 3) == 0; }
 
 // The checks of the block's size and subsampling the gather and the store share, and the geometry they decide
 static int nbr_geom(int bw, int bh, int xdec, int ydec, NbrGeom &g) {
-  R1_REQUIRE(r1_is_pow2(bw) && r1_is_pow2(bh) && bw >= 4 && bh >= 4 && bw <= 64 && bh <= 64);
-  R1_REQUIRE(bw <= 4 * bh && bh <= 4 * bw);            // a block size
-  R1_REQUIRE((xdec == 1 && ydec == 1) || (xdec == 1 && ydec == 0) || (xdec == 0 && ydec == 0));
-  R1_REQUIRE(!(xdec == 1 && ydec == 0) || bw >= bh);   // subsampled_size (partition.rs:337-379): what 4:2:2 admits
-  g = {};
-  g.bw4 = bw >> 2, g.bh4 = bh >> 2, g.xdec = xdec, g.ydec = ydec;
-  g.adj_x = (bw == 4) * xdec, g.adj_y = (bh == 4) * ydec;
-  // subsampled_size, then largest_chroma_tx_size (partition.rs:385-393): 64-point sides coded as 32
-  const int pw = (bw >> xdec) > 4 ? bw >> xdec : 4, ph = (bh >> ydec) > 4 ? bh >> ydec : 4;
-  const int uw = pw < 32 ? pw : 32, uh = ph < 32 ? ph : 32;
-  g.sub_w4 = pw >> 2, g.sub_h4 = ph >> 2;
-  // the chroma grid, literally (encoder.rs:2327-2338, 2492-2505): either side 0 makes both 1 before the division
-  int bw_uv = g.bw4 >> xdec, bh_uv = g.bh4 >> ydec;
-  if (bw_uv == 0 || bh_uv == 0) bw_uv = 1, bh_uv = 1;
-  bw_uv /= uw >> 2, bh_uv /= uh >> 2;
-  g.uv_w4 = bw_uv * bh_uv ? bw_uv * (uw >> 2) : 0;
-  g.uv_h4 = bw_uv * bh_uv ? bh_uv * (uh >> 2) : 0;
-  g.skip_all_planes = (bw == 4 && bh == 16) || (bw == 16 && bh == 4);
+  R1_REQUIRE(r1_block_size_ok(bw, bh));
+  R1_REQUIRE(r1_subsampling_ok(xdec, ydec));
+  R1_REQUIRE(r1_subsampling_admits(xdec, ydec, bw, bh));
+  const R1BlockGeom b = r1_block_geom(bw, bh, xdec, ydec);
+  g = {b.bw4, b.bh4, xdec, ydec, b.adj_x, b.adj_y, b.uv_w4, b.uv_h4, b.sub_w4, b.sub_h4, b.skip_all_planes};
   return R1_OK;
 }
 
@@ -303,7 +290,7 @@ extern "C" int r1_coeff_nbr_store_batch(r1_ctx *ctx, const R1NbrBlock *descs, in
   const int rc = nbr_geom(bw, bh, xdec, ydec, a.g);
   if (rc != R1_OK) return rc;
   R1_REQUIRE(r1_tx_size_ok(tx_size));
-  R1_REQUIRE(bw % (1 << r1tx::kTxWLog2[tx_size]) == 0 && bh % (1 << r1tx::kTxHLog2[tx_size]) == 0);
+  R1_REQUIRE(r1_luma_grid(bw, bh, tx_size).divides);
   if (n == 0) return R1_OK;
   a.descs = descs, a.ctx_in = ctx_in, a.state = state, a.contexts = contexts;
   a.n = n, a.n_contexts = n_contexts, a.call_id = call_id;
@@ -345,10 +332,7 @@ extern "C" int r1_rd_winner_tx_type_batch(r1_ctx *ctx, const R1RdPick *state, in
   R1_REQUIRE(ntx >= 1 && ntx <= 16);
   R1_REQUIRE(!is_inter || eob_win);
   if (n_states == 0) return R1_OK;
-  // TxType::uv_inter: sqr_up() == TX_32X32 keeps IDTX alone, sqr() == TX_16X16 drops the 1-D ADSTs
-  const int wl = r1tx::kTxWLog2[uv_tx_size], hl = r1tx::kTxHLog2[uv_tx_size];
-  const int up = wl > hl ? wl : hl, dn = wl < hl ? wl : hl;
-  const WinnerArgs a = {state, eob_win, (uint8_t *)trials, n_states, call_id, is_inter, ntx, up == 5 ? 1 : (dn == 4 ? 2 : 0),
+  const WinnerArgs a = {state, eob_win, (uint8_t *)trials, n_states, call_id, is_inter, ntx, r1_uv_inter_rule(uv_tx_size),
                         tx_type_mask};
   R1DeviceGuard guard(ctx);
   hipLaunchKernelGGL(k_rd_winner_tx_type, dim3(nbr_grid(n_states, 1)), dim3(256), 0, (hipStream_t)stream, a);

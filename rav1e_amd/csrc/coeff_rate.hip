@@ -12,27 +12,15 @@
 // r1_coeff_cdf_slice_batch / r1_coeff_cdf_adapt_batch: the CDF state carried from block to block on the device -- the
 // snapshot the calls above take, cut out of an R1CoeffCdfContext, and the whole-block walk once more on the winner, with
 // the adapted rows written back to the context (k_coeff_cdf_slice, k_coeff_cdf_adapt).
-// This is the host half: tables, checks, launch arguments, entry points; the kernels are coeff_rate_kernel.hpp.
-// Restated from the reference (pinned by tests/golden/coeff_rate_ref.npz through every fixture case):
-//  av1_tx_ind / num_tx_set (transform_unit.rs:36-58) as the host tables below.
+// This is the host half: checks, launch arguments, entry points; the kernels are coeff_rate_kernel.hpp, and what the
+// reference says of a block and of the transform sets (av1_tx_ind / num_tx_set / av1_tx_used) is block_geom.hpp.
+#include "block_geom.hpp"
 #include "coeff_rate_kernel.hpp"
 #include "quant_common.hpp"
 
-// num_tx_set / av1_tx_ind (transform_unit.rs:36, 51-58), rows in TxSet order; the set from the mask of its types
-static const uint8_t kNumTxSet[6] = {1, 2, 5, 7, 12, 16};
-static const uint32_t kSetMask[6] = {0x0001, 0x0201, 0x020F, 0x0E0F, 0x0FFF, 0xFFFF};
-static const uint8_t kTxInd[6][16] = {{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0},
-                                      {1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0},
-                                      {1, 3, 4, 2, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0},
-                                      {1, 5, 6, 4, 0, 0, 0, 0, 0, 0, 2, 3, 0, 0, 0, 0},
-                                      {3, 4, 5, 8, 6, 7, 9, 10, 11, 0, 1, 2, 0, 0, 0, 0},
-                                      {7, 8, 9, 12, 10, 11, 13, 14, 15, 0, 1, 2, 3, 4, 5, 6}};
-
 // What the transform size and the set decide of the launch arguments (tx_size is valid, the flags are 0 / 1) -> the set
 static int rate_shape(r1_ctx *ctx, int tx_size, int plane, int is_inter, int use_reduced_tx_set, RateArgs &a) {
-  const uint32_t allowed = r1_tx_type_mask(tx_size, is_inter, use_reduced_tx_set, 0);
-  int set = 0;
-  while (kSetMask[set] != allowed) set++;
+  const int set = r1_tx_set(tx_size, is_inter, use_reduced_tx_set);
   const int wl = r1tx::kTxWLog2[tx_size], hl = r1tx::kTxHLog2[tx_size];
   for (int k = 0; k < 3; k++) a.scan[k] = ctx->scan_dev + ctx->scan_off[tx_size][k];
   a.plane = plane;
@@ -41,7 +29,7 @@ static int rate_shape(r1_ctx *ctx, int tx_size, int plane, int is_inter, int use
   a.area = a.w_coded << a.hl;
   a.shape = wl < hl ? 1 : (wl > hl ? 2 : 0);
   a.eob_flag_n = 5 + (wl + hl - 4 < 6 ? wl + hl - 4 : 6);   // eob_multi_size = area_log2 - 4; `_ =>`: eob_flag_cdf1024
-  a.tx_n = kNumTxSet[set] > 1 ? kNumTxSet[set] : 0;
+  a.tx_n = r1tx::kNumTxSet[set] > 1 ? r1tx::kNumTxSet[set] : 0;
   a.is_inter = is_inter;
   return set;
 }
@@ -76,7 +64,7 @@ static int rate_args(r1_ctx *ctx, const void *qcoeffs, int coeff_bytes, const ui
   R1_REQUIRE(plane >= 0 && plane <= 2);
   is_inter = is_inter != 0;
   use_reduced_tx_set = use_reduced_tx_set != 0;
-  const uint32_t allowed = r1_tx_type_mask(tx_size, is_inter, use_reduced_tx_set, 0);
+  const uint32_t allowed = r1tx::kTxUsed[r1_tx_set(tx_size, is_inter, use_reduced_tx_set)];
   R1_REQUIRE(tx_type_mask != 0 && (tx_type_mask & ~allowed) == 0);
   R1_REQUIRE(qcoeffs && eobs);
   a.qc = qcoeffs, a.eobs = eobs;
@@ -85,18 +73,17 @@ static int rate_args(r1_ctx *ctx, const void *qcoeffs, int coeff_bytes, const ui
   a.n_slots = (n > 0 ? n : 0) * a.nt;
   const int set = rate_shape(ctx, tx_size, plane, is_inter, use_reduced_tx_set, a);
   for (int t = 0, j = 0; t < 16; t++)
-    if ((tx_type_mask >> t) & 1) a.type[j] = (uint8_t)t, a.tx_sym[j] = kTxInd[set][t], j++;
+    if ((tx_type_mask >> t) & 1) a.type[j] = (uint8_t)t, a.tx_sym[j] = r1tx::kTxInd[set][t], j++;
   return R1_OK;
 }
 
 // A bw x bh block under transforms of tx_size: the luma grid of the chain and of the whole block
 static int luma_grid(int bw, int bh, int tx_size, TxbGrid &g) {
   R1_REQUIRE(r1_tx_size_ok(tx_size));
-  const int tw = 1 << r1tx::kTxWLog2[tx_size], th = 1 << r1tx::kTxHLog2[tx_size];
-  R1_REQUIRE(r1_is_pow2(bw) && r1_is_pow2(bh) && bw >= 4 && bh >= 4 && bw <= 64 && bh <= 64);
-  R1_REQUIRE(bw <= 4 * bh && bh <= 4 * bw);            // a block size
-  R1_REQUIRE(bw % tw == 0 && bh % th == 0);
-  g = {(bw / tw) * (bh / th), bw / tw, tw >> 2, th >> 2, 0, 0, 0, 0};
+  R1_REQUIRE(r1_block_size_ok(bw, bh));
+  const R1LumaGrid l = r1_luma_grid(bw, bh, tx_size);
+  R1_REQUIRE(l.divides);
+  g = {l.ntx, l.gw, l.tw4, l.th4, 0, 0, 0, 0};
   R1_REQUIRE(g.ntx >= 1 && g.ntx <= 16);
   return R1_OK;
 }
@@ -156,24 +143,15 @@ static int block_args(r1_ctx *ctx, const void *qcoeffs_y, const uint16_t *eobs_y
   TxbGrid g;
   const int rc = luma_grid(bw, bh, tx_size, g);
   if (rc != R1_OK) return rc;
-  R1_REQUIRE((xdec == 1 && ydec == 1) || (xdec == 1 && ydec == 0) || (xdec == 0 && ydec == 0));
-  R1_REQUIRE(!(xdec == 1 && ydec == 0) || bw >= bh);   // subsampled_size (partition.rs:337-379): what 4:2:2 admits
+  R1_REQUIRE(r1_subsampling_ok(xdec, ydec));
+  R1_REQUIRE(r1_subsampling_admits(xdec, ydec, bw, bh));
   R1_REQUIRE(step_y >= 1 && step_uv >= 1 && n_txb_y >= 0 && n_txb_uv >= 0);
   R1_REQUIRE(n_blocks >= 1);
   R1_REQUIRE(qcoeffs_y && eobs_y && trials && blocks);
   const int n_uv_ptrs = (qcoeffs_u != nullptr) + (eobs_u != nullptr) + (qcoeffs_v != nullptr) + (eobs_v != nullptr);
   R1_REQUIRE(n_uv_ptrs == 0 || n_uv_ptrs == 4);
-  // largest_chroma_tx_size (partition.rs:385-393): the subsampled block, its largest transform, 64-point sides coded as 32
-  const int pw = (bw >> xdec) > 4 ? bw >> xdec : 4, ph = (bh >> ydec) > 4 ? bh >> ydec : 4;
-  const int uw = pw < 32 ? pw : 32, uh = ph < 32 ? ph : 32;
-  uv_tx_size = 0;
-  while (uv_tx_size < 19 && ((1 << r1tx::kTxWLog2[uv_tx_size]) != uw || (1 << r1tx::kTxHLog2[uv_tx_size]) != uh)) uv_tx_size++;
-  R1_REQUIRE(uv_tx_size < 19);
-  // the chroma grid, literally (encoder.rs:2327-2338; 2492-2505 has max_txsize_rect_lookup[bsize] in place of the block,
-  // the same dimensions up to 64x64)
-  int bw_uv = (bw >> 2) >> xdec, bh_uv = (bh >> 2) >> ydec;
-  if (bw_uv == 0 || bh_uv == 0) bw_uv = 1, bh_uv = 1;
-  bw_uv /= uw >> 2, bh_uv /= uh >> 2;
+  const R1BlockGeom b = r1_block_geom(bw, bh, xdec, ydec);
+  uv_tx_size = b.uv_tx_size;
 
   c.r[0].n_slots = n > 0 ? n : 0;
   c.r[1] = c.r[0];
@@ -181,18 +159,18 @@ static int block_args(r1_ctx *ctx, const void *qcoeffs_y, const uint16_t *eobs_y
   rate_shape(ctx, uv_tx_size, 1, is_inter, use_reduced_tx_set, c.r[1]);
   for (int t = 0; t < 16; t++) {
     c.r[0].type[t] = c.r[1].type[t] = (uint8_t)t;
-    c.r[0].tx_sym[t] = kTxInd[set][t];
+    c.r[0].tx_sym[t] = r1tx::kTxInd[set][t];
   }
-  c.mask[0] = kSetMask[set];
-  c.mask[1] = (uw == 32 || uh == 32) ? 0x0201u : 0xFFFFu;   // the scans av1_scan_orders holds for the size
+  c.mask[0] = r1tx::kTxUsed[set];
+  c.mask[1] = (b.uw == 32 || b.uh == 32) ? 0x0201u : 0xFFFFu;   // the scans av1_scan_orders holds for the size
   c.pl[0] = {qcoeffs_y, eobs_y, n_txb_y, step_y, g};
   c.pl[1] = {qcoeffs_u, eobs_u, n_txb_uv, step_uv,
-             {bw_uv * bh_uv, bw_uv > 0 ? bw_uv : 1, uw >> 2, uh >> 2, xdec, ydec, (bw == 4) * xdec, (bh == 4) * ydec}};
+             {b.bw_uv * b.bh_uv, b.bw_uv > 0 ? b.bw_uv : 1, b.uw >> 2, b.uh >> 2, xdec, ydec, b.adj_x, b.adj_y}};
   c.pl[2] = c.pl[1];
   c.pl[2].qc = qcoeffs_v, c.pl[2].eobs = eobs_v;
   c.trials = trials, c.blocks = blocks;
   c.n_blocks = n_blocks;
-  c.uv_skip_off = pw * ph > uw * uh ? 10 : 7;
+  c.uv_skip_off = b.uv_skip_off;
   return R1_OK;
 }
 
@@ -222,8 +200,7 @@ extern "C" int r1_coeff_rate_block_batch(r1_ctx *ctx, const void *qcoeffs_y, con
 static void cdf_map(int tx_size, int plane_type, int is_inter, int use_reduced_tx_set, CdfMap &m) {
   auto off = [](size_t bytes) { return (uint16_t)(bytes / 2); };
   const int wl = r1tx::kTxWLog2[tx_size], hl = r1tx::kTxHLog2[tx_size];
-  const int sqr = (wl < hl ? wl : hl) - 2, sqr_up = (wl > hl ? wl : hl) - 2;   // TX_4X4 = 0 .. TX_64X64 = 4
-  const int txs_ctx = (sqr + sqr_up + 1) >> 1;                                 // get_txsize_entropy_ctx
+  const int txs_ctx = r1_txs_ctx(tx_size);
   const int ems = wl + hl - 4 < 6 ? wl + hl - 4 : 6;                           // eob_multi_size; `_ =>`: eob_flag_cdf1024
   const int tp = txs_ctx * 2 + plane_type, br = (txs_ctx < 3 ? txs_ctx : 3) * 2 + plane_type;
   static const size_t kEobFlag[7] = {offsetof(R1CoeffCdfContext, eob_flag16),  offsetof(R1CoeffCdfContext, eob_flag32),
@@ -247,11 +224,9 @@ static void cdf_map(int tx_size, int plane_type, int is_inter, int use_reduced_t
   m.seg[6] = {off(offsetof(R1CoeffCdfContext, dc_sign) + plane_type * sizeof(uint16_t[R1_DC_SIGN_CONTEXTS][2])), 2,
               R1_DC_SIGN_CONTEXTS, 0, R1_DC_SIGN_CONTEXTS};
   // write_tx_type (transform_unit.rs:530-574): the table of get_tx_set_index at tx_size.sqr(); sets in TxSet order
-  const uint32_t allowed = r1_tx_type_mask(tx_size, is_inter, use_reduced_tx_set, 0);
-  int set = 0;
-  while (kSetMask[set] != allowed) set++;
-  if (plane_type == 0 && kNumTxSet[set] > 1) {
-    const uint16_t n = kNumTxSet[set];
+  const int set = r1_tx_set(tx_size, is_inter, use_reduced_tx_set);
+  if (plane_type == 0 && r1tx::kNumTxSet[set] > 1) {
+    const uint16_t n = r1tx::kNumTxSet[set];
     size_t at = 0;
     switch (set) {
       case 1: at = offsetof(R1CoeffCdfContext, inter_tx_3); break;   // TX_SET_INTER_3: index 3
@@ -261,7 +236,7 @@ static void cdf_map(int tx_size, int plane_type, int is_inter, int use_reduced_t
       default: at = offsetof(R1CoeffCdfContext, inter_tx_1); break;  // TX_SET_INTER_1: index 1
     }
     const uint16_t rows = is_inter ? 1 : R1_INTRA_MODES;             // row 0 for inter, row y_mode for intra
-    m.seg[7] = {(uint16_t)(off(at) + sqr * rows * n), n, rows, 0, rows};
+    m.seg[7] = {(uint16_t)(off(at) + r1_txsize_sqr_log2(tx_size) * rows * n), n, rows, 0, rows};
   }
 }
 

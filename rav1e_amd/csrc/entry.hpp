@@ -37,6 +37,12 @@ inline bool r1_offsets_fit_u32(const R1Plane &p) {
   return p.stride > 0 && p.stride < (1 << 24) && p.alloc_height > 0 && p.alloc_height < (1 << 24) &&
          (unsigned long long)p.stride * (unsigned long long)p.alloc_height * (unsigned long long)p.bytes_per_px < (1ull << 32);
 }
+inline bool r1_is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+inline int r1_ilog2(int v) {
+  int l = 0;
+  while ((1 << l) < v) l++;
+  return l;
+}
 
 // ---- the 19 transform sizes, written once: X(TxSize id, log2 width, log2 height) ----
 // The tables below and every tx_size -> instantiation switch (fwd_tx.hip, inv_tx.hip, mc.hip, rdo_cand_kernel.hpp)

@@ -592,6 +592,8 @@ extern "C" int r1_cfl_ac_batch(r1_ctx *ctx, const R1Plane *luma, int bw, int bh,
                                void *stream) {
   R1_REQUIRE(ctx && luma);
   R1_REQUIRE(r1_px_ok(*luma));
+  // bw x bh is the chroma block whose AC is taken, so this is not r1_block_size_ok (block_geom.hpp) and is wider on
+  // purpose: any two powers of two 4 .. 64, whatever their ratio.  The formats are r1_subsampling_ok's three.
   R1_REQUIRE(r1_is_pow2(bw) && r1_is_pow2(bh) && bw >= 4 && bh >= 4 && bw <= 64 && bh <= 64);
   R1_REQUIRE(r1_dec_ok(xdec, ydec) && (ydec == 0 || xdec == 1));
   if (n <= 0) return R1_OK;

@@ -6,6 +6,7 @@
 // r1_rd_commit_batch: the winner's eobs, coefficients, side bytes and reconstruction gathered to where the next step
 // reads them; the reconstruction goes into the plane, which is where the next block's edges come from.
 // Both enqueue on the caller's stream; nothing is read back.  Pinned by tests/golden/rd_pick_ref.npz.
+#include "block_geom.hpp"
 #include "common.hpp"
 
 #include <math.h>
@@ -259,8 +260,7 @@ extern "C" int r1_rd_commit_batch(r1_ctx *ctx, const R1RdPick *state, int n_stat
   if (side) R1_REQUIRE(side_bytes >= 1 && side_bytes <= 128);
   int bpp = 1;
   if (n_rec) {
-    R1_REQUIRE(r1_is_pow2(bw) && r1_is_pow2(bh) && bw >= 4 && bh >= 4 && bw <= 64 && bh <= 64);
-    R1_REQUIRE(bw <= 4 * bh && bh <= 4 * bw);            // a block size
+    R1_REQUIRE(r1_block_size_ok(bw, bh));
     R1_REQUIRE(r1_px_ok(*rec) && r1_depth_ok(rec->bit_depth) && r1_px_fits_depth(*rec));
     R1_REQUIRE(rec->data && rec->stride > 0 && rec->alloc_height > 0 && rec->xorigin >= 0 && rec->yorigin >= 0);
     // the store rectangle: the visible plane and its padding to the right and below, as far as the allocation goes

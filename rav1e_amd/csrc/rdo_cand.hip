@@ -2,6 +2,7 @@
 // fifteen (bit depth, slice) objects (twelve more for the intra prediction source) and the C entry points.  The
 // kernel itself is rdo_cand_kernel.hpp, compiled by rdo_cand_slice.hip; this unit sees only what it shares with
 // the slices (rdo_cand_args.hpp, and through it the plan of rdo_cand_plan.hpp).
+#include "block_geom.hpp"
 #include "itx_common.hpp"   // kInvShift
 #include "rdo_cand_args.hpp"
 
@@ -174,15 +175,7 @@ extern "C" int r1_rdo_pred_cand_batch(r1_ctx *ctx, const R1Plane *org, const voi
 // the types the loop of rdo_tx_type_decision (src/rdo.rs:1732-1736) does not skip.
 extern "C" uint32_t r1_tx_type_mask(int tx_size, int is_inter, int use_reduced_set, int rav1e_types_only) {
   if (!r1_tx_size_ok(tx_size)) return 0;
-  const int wl = r1tx::kTxWLog2[tx_size], hl = r1tx::kTxHLog2[tx_size];
-  const int up = wl > hl ? wl : hl, dn = wl < hl ? wl : hl;   // sqr_up / sqr as log2 of the side
-  // TxSet rows of av1_tx_used
-  constexpr uint32_t DCTONLY = 0x0001, INTER_3 = 0x0201, INTRA_2 = 0x020F, INTRA_1 = 0x0E0F, INTER_2 = 0x0FFF,
-                     INTER_1 = 0xFFFF;
-  uint32_t m;
-  if (up > 5) m = DCTONLY;
-  else if (is_inter) m = (use_reduced_set || up == 5) ? INTER_3 : (dn == 4 ? INTER_2 : INTER_1);
-  else m = up == 5 ? DCTONLY : ((use_reduced_set || dn == 4) ? INTRA_2 : INTRA_1);
+  const uint32_t m = r1tx::kTxUsed[r1_tx_set(tx_size, is_inter, use_reduced_set)];
   return rav1e_types_only ? (m & 0x0E0Fu) : m;
 }
 

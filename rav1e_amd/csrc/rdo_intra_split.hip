@@ -19,6 +19,7 @@
 // reconstruction is the one k_rdo_cand (rdo_cand_kernel.hpp) runs for a single transform block, phase by phase.
 #include <type_traits>
 
+#include "block_geom.hpp"
 #include "common.hpp"
 #include "dist_common.hpp"
 #include "intra_pred_common.hpp"
@@ -301,10 +302,10 @@ extern "C" int r1_rdo_intra_split_batch(r1_ctx *ctx, const R1Plane *org, const R
   // square transforms 4x4 .. 32x32 (TxSize 0 .. 3); the 2:1 sizes and 64x64 are not built
   R1_REQUIRE(tx_size >= 0 && tx_size <= 3);
   const int tl = r1tx::kTxWLog2[tx_size], tn = 1 << tl;
-  R1_REQUIRE(r1_is_pow2(bw) && r1_is_pow2(bh) && bw >= 4 && bh >= 4 && bw <= 64 && bh <= 64);
-  R1_REQUIRE(bw <= 4 * bh && bh <= 4 * bw);
-  R1_REQUIRE(bw % tn == 0 && bh % tn == 0);
-  const int ntx = (bw / tn) * (bh / tn);
+  R1_REQUIRE(r1_block_size_ok(bw, bh));
+  const R1LumaGrid lg = r1_luma_grid(bw, bh, tx_size);
+  R1_REQUIRE(lg.divides);
+  const int ntx = lg.ntx;
   R1_REQUIRE(ntx >= 2 && ntx <= 16);
   R1_REQUIRE(tile_x >= 0 && tile_y >= 0 && tile_w > 0 && tile_h > 0);
   R1_REQUIRE(tile_x + tile_w <= rec->width && tile_y + tile_h <= rec->height);

@@ -128,7 +128,8 @@ const char *r1_last_error(void);
  * r1_rd_commit_batch, R1RdPick), and the device-resident coefficient CDF context (r1_coeff_cdf_slice_batch,
  * r1_coeff_cdf_adapt_batch, R1CoeffCdfContext), and the device-resident coefficient neighbour contexts with the
  * winner's transform type (r1_coeff_nbr_gather_batch, r1_coeff_nbr_store_batch, r1_coeff_nbr_reset_left_batch,
- * r1_rd_winner_tx_type_batch, R1CoeffNbrContext, R1NbrBlock). */
+ * r1_rd_winner_tx_type_batch, R1CoeffNbrContext, R1NbrBlock), and the partition decision on the device
+ * (r1_rd_partition_pick_batch, r1_part_select_batch, r1_part_select_rect_batch, R1PartPick). */
 int r1_abi_version(void);
 
 /* ---- dist:: (reference: src/dist.rs get_sad 31, get_satd 156; dispatch
@@ -1576,6 +1577,98 @@ int r1_coeff_nbr_reset_left_batch(r1_ctx *ctx, R1CoeffNbrContext *contexts, int 
 int r1_rd_winner_tx_type_batch(r1_ctx *ctx, const R1RdPick *state, int n_states, int call_id, uint32_t tx_type_mask,
                                int is_inter, int uv_tx_size, const uint16_t *eob_win, int ntx, R1BlockRateTrial *trials,
                                void *stream);
+
+/* ---- the partition decision on the device (added under ABI 7): the RD comparison a node of the partition quad-tree
+ * makes between coding its block whole and coding it as two or four sub-blocks -- encode_partition_bottomup
+ * (src/encoder.rs:2683-2843) and rdo_partition_decision with rdo_partition_none / rdo_partition_simple
+ * (src/rdo.rs:1849-2024) -- behind the children's chains on the same stream, with no copy and no synchronisation.  A
+ * node's decision is an R1PartPick that is carried from call to call; the two selects then move the state the winning
+ * trial left to where the next node reads it.  The partition SYMBOL stays a head symbol: its rate (the tell_frac
+ * difference of write_partition) is the host's, handed in as part_rate exactly as rate_add is handed to the pick.
+ * All pointers are DEVICE pointers except srcs / src_planes / dst_plane, which are host arrays of device addresses.
+ * One call is ONE partition type tried at n nodes: the same node of n tiles, or any n nodes whose children are
+ * finished.  Node s reads
+ *   state[s]                       best_rd on entry is what the trial has to beat
+ *   part_rate[s]                   u32, 1/8 bit; cost = fma(lambda, part_rate / 8, 0.0), ONE rounding as compute_rd_cost
+ *                                  with a zero distortion.  part_rate == NULL is the reference's `0.0` arm (a block
+ *                                  below 8x8, or the whole-block trial of a non-square block)
+ *   child_idx[4 * s + k]           entry k of the node's children: an index into the array at `children` whose
+ *                                  elements lie child_stride bytes apart and BEGIN with a double, the child's best_rd
+ *                                  (R1RdPick and R1PartPick both do) -- or -1, or any value outside
+ *                                  0 .. n_children_states - 1, for "absent": such an index loads nothing.
+ *                                  PARTITION_NONE visits entry 0, HORZ and VERT entries 0 and 1, SPLIT all four
+ *                                  (get_sub_partitions, src/rdo.rs:1825-1846); the others are not read
+ *   must_split[s]                  optional (NULL = 0 everywhere)
+ *   parent[parent_idx[s]].best_rd  the node's ref_rd_cost; parent or parent_idx NULL, or an index outside
+ *                                  0 .. n_parent_states - 1, means f64::MAX
+ * Every addition is the reference's, in its order, in f64, each rounded on its own; none is fused with the multiply
+ * of the cost.
+ *   R1_PART_BOTTOMUP, partition NONE:  rd = child0 + cost, kept UNCONDITIONALLY (encoder.rs:2708-2711); an absent
+ *       child 0 keeps nothing.  early_exit = 0.
+ *   R1_PART_BOTTOMUP, otherwise:       rd = cost; for each visited child in order: absent or == f64::MAX: skipped;
+ *       else rd += child, and when !must_split && enable_early_exit && (rd >= best_rd || rd >= ref_rd_cost) the trial
+ *       ends early: nothing kept, early_exit = 1.  Behind the loop the trial is kept when rd < best_rd, strictly.
+ *   R1_PART_TOPDOWN, partition NONE:   rd = child0: no partition symbol (rdo_partition_none); kept when rd < best_rd.
+ *   R1_PART_TOPDOWN, otherwise:        sum = 0.0; for each visited child in order: absent: the trial is refused
+ *       (early_exit = 0); else sum += child, and when enable_early_exit && sum > best_rd (strictly; the cost is not in
+ *       it) the trial is refused with early_exit = 1.  rd = cost + sum, kept when rd < best_rd.  best_rd on entry is
+ *       what the caller put into the state: cached_block.rd_cost.
+ * The two rules add in different orders -- ((cost + c0) + c1) + ... against cost + (((0 + c0) + c1) + ...) -- and can
+ * differ in the last bit; each is kept.  A kept trial writes best_rd, best_partition = partition and best_call =
+ * call_id; every visited node has early_exit written; nothing else is written, the padding included.
+ * rdo_glue.partition_pick_bottomup / partition_pick_topdown are the statements.
+ * R1_EINVAL: a NULL ctx, state or child_idx; children NULL with n_children_states > 0; n < 0; partition outside
+ * NONE..SPLIT; rule outside 0..1; call_id outside 0..127; child_stride below 8 or no multiple of 8; a negative
+ * n_children_states or n_parent_states; state, children or parent not 8-byte aligned; a lambda that is negative,
+ * infinite or NaN.  n == 0 returns 0 and touches nothing.  Every loop is bounded by the arguments, never by data;
+ * no atomics, no spin-waits. */
+typedef struct R1PartPick {     /* 16 bytes; the decision state of one quad-tree node, carried from call to call */
+  double  best_rd;              /* f64::MAX (DBL_MAX) = nothing kept */
+  int8_t  best_partition;       /* R1_PARTITION_* of the kept trial, R1_PARTITION_INVALID = none */
+  int8_t  best_call;            /* call_id of the kept trial, -1 = none */
+  uint8_t early_exit;           /* whether the LAST trial visited ended early */
+  uint8_t reserved[5];          /* never read, never written */
+} R1PartPick;
+#define R1_PARTITION_NONE     0   /* PartitionType's discriminants, src/partition.rs:114-126 */
+#define R1_PARTITION_HORZ     1
+#define R1_PARTITION_VERT     2
+#define R1_PARTITION_SPLIT    3
+#define R1_PARTITION_INVALID (-1) /* the state's "nothing kept" (the reference's own discriminant, 10, indexes nothing) */
+#define R1_PART_BOTTOMUP 0      /* encode_partition_bottomup */
+#define R1_PART_TOPDOWN  1      /* rdo_partition_decision */
+int r1_rd_partition_pick_batch(r1_ctx *ctx, R1PartPick *state, int n, int partition, int call_id, int rule,
+                               double lambda, int enable_early_exit, const uint32_t *part_rate,
+                               const void *children, int child_stride, int n_children_states,
+                               const int32_t *child_idx, const uint8_t *must_split, const R1PartPick *parent,
+                               int n_parent_states, const int32_t *parent_idx, void *stream);
+/* The winner's state where the next node reads it; both calls are gated by the pick and both are byte movers.
+ * r1_part_select_batch: for node s < n with c = state[s].best_call in 0 .. n_src - 1 and srcs[c] non-NULL, `bytes`
+ * bytes go from srcs[c] + s * src_stride to dst + s * dst_stride; every other node has NOTHING written.  Meant for the
+ * snapshots of R1CoeffCdfContext and R1CoeffNbrContext the caller cloned behind each trial, and for the winner arrays
+ * of r1_rd_commit_batch.  srcs[c] == dst (with equal strides) is allowed -- the trial that ran last left the live
+ * state standing -- and copies nothing.  Apart from that case no source range may overlap a destination range.
+ * srcs is a HOST array of n_src device addresses.  Where bytes, both strides and every address are multiples of 16
+ * the copy runs in 16-byte pieces, otherwise in 4-byte pieces.
+ * R1_EINVAL: a NULL ctx, state, srcs or dst; n < 0; n_src outside 1..4; bytes negative or no multiple of 4; a stride
+ * that is negative or no multiple of 4; dst_stride below bytes; an address that is no multiple of 4; srcs[c] == dst
+ * with unequal strides.  n == 0 or bytes == 0 returns 0 and touches nothing. */
+int r1_part_select_batch(r1_ctx *ctx, const R1PartPick *state, int n, int n_src, const void *const *srcs,
+                         long long src_stride, void *dst, long long dst_stride, int bytes, void *stream);
+/* r1_part_select_rect_batch: the node's bw x bh rectangle at (pos_xy[2s], pos_xy[2s + 1]) goes from the winning
+ * trial's plane, src_planes[state[s].best_call], into dst_plane, clipped to [0, store_w) x [0, store_h) exactly as
+ * the `rec` part of r1_rd_commit_batch clips: nothing outside that rectangle and nothing outside the allocation is
+ * read or written.  src_planes is a HOST array of n_src R1Plane; one whose data is NULL is "no plane" (its nodes have
+ * nothing written), one whose data is dst_plane's copies nothing; every other must have the destination's geometry
+ * (stride, alloc_height, xorigin, yorigin, bytes_per_px, bit_depth).  Widths from 4 pixels (the 4:2:0 chroma block of
+ * an 8x8) to 64, pos_xy at multiples of 4 pixels where the widest stores are wanted; any position is correct.  The
+ * rectangles of one call MUST NOT overlap, and no source plane may share memory with the destination.
+ * R1_EINVAL: a NULL pointer; n < 0; n_src outside 1..4; bw / bh that are no block size up to 64x64; the plane checks
+ * of r1_rd_commit_batch (1 / 8 or 2 / 10, 12 bits; store_w above stride - xorigin or store_h above alloc_height -
+ * yorigin, or negative); a source plane of another geometry; a plane whose data is not aligned to its pixel.
+ * n == 0 returns 0. */
+int r1_part_select_rect_batch(r1_ctx *ctx, const R1PartPick *state, int n, int n_src, const R1Plane *src_planes,
+                              const R1Plane *dst_plane, const int16_t *pos_xy, int bw, int bh, int store_w, int store_h,
+                              void *stream);
 
 /* ---- multi-GPU: the tile-boundary exchange and the reference-frame all-gather (RCCL over
  * xGMI), SURVEY.md 8(e).  One process (or host thread) per GPU, tile r on rank r.  Rendezvous:

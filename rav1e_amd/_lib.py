@@ -184,6 +184,10 @@ SYMBOLS = {
     "r1_coeff_nbr_store_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp]),
     "r1_coeff_nbr_reset_left_batch": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp]),
     "r1_rd_winner_tx_type_batch": (_i, [_vp, _vp, _i, _i, C.c_uint32, _i, _i, _vp, _i, _vp, _vp]),
+    "r1_rd_partition_pick_batch": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_double, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp,
+                                        _vp]),
+    "r1_part_select_batch": (_i, [_vp, _vp, _i, _i, _vp, C.c_longlong, _vp, C.c_longlong, _i, _vp]),
+    "r1_part_select_rect_batch": (_i, [_vp, _vp, _i, _i, _PP, _PP, _vp, _i, _i, _i, _i, _vp]),
     "r1_lrf_sgrproj_plane": (_i, [_vp, _PP, _PP, _PP, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "r1_sgrproj_solve_batch": (_i, [_vp, _PP, _PP, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "r1_lrf_search_batch": (_i, [_vp, _PP, _PP, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, C.c_uint32, _vp, _vp, _vp, _vp]),

@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 from .types import (BLOCK_CHAIN_CTX, BLOCK_RATE_TRIAL, COEFF_CDF_CONTEXT, COEFF_CDFS, COEFF_RATE_INVALID, PICK_FIRST_MIN, PICK_TX_TYPE,  # noqa: F401
-                    COEFF_NBR_CONTEXT, NBR_BLOCK, RD_PICK, TX_DIMS, TXB_CHAIN_CTX, TXB_CTX, TxSize, valid_av1_transform)
+                    COEFF_NBR_CONTEXT, NBR_BLOCK, PART_BOTTOMUP, PART_PICK, PART_TOPDOWN, RD_PICK, TX_DIMS, TXB_CHAIN_CTX, TXB_CTX, TxSize, valid_av1_transform)
 
 DIST_CAND = np.dtype([("ox", "<i2"), ("oy", "<i2"), ("rx", "<i2"), ("ry", "<i2")])
 MC_CAND = np.dtype([("rx", "<i2"), ("ry", "<i2"), ("col_frac", "u1"), ("row_frac", "u1"),
@@ -1322,6 +1322,80 @@ class Context:
             o["qcoeffs_win"].data_ptr() if eobs is not None else None, int(stride),
             o["side_win"].data_ptr() if side is not None else None, _stream_ptr()), "r1_rd_commit_batch")
         return o
+
+    # ---- the partition decision on the device ----
+    @staticmethod
+    def part_pick_state(n, best_rd=None):
+        """n initial R1PartPick states -- (f64::MAX, PARTITION_INVALID, -1, 0): nothing kept -- as an (n, 16) uint8
+        device tensor (PART_PICK records; .cpu().numpy().view(PART_PICK) reads them).  best_rd: the costs a top-down
+        node starts from (cached_block.rd_cost), per node"""
+        import sys
+        st = np.zeros(n, PART_PICK)
+        st["best_rd"] = sys.float_info.max if best_rd is None else best_rd
+        st["best_partition"], st["best_call"] = -1, -1
+        return torch.from_numpy(st.view(np.uint8).reshape(n, PART_PICK.itemsize)).cuda()
+
+    def rd_partition_pick_batch(self, state, partition, call_id, rule, lam, children, child_idx, enable_early_exit=True,
+                                part_rate=None, must_split=None, parent=None, parent_idx=None):
+        """r1_rd_partition_pick_batch: one partition type tried at every node of `state` ((n, 16) uint8 device tensor,
+        part_pick_state; updated in place), on the current stream behind the children's chains, no copy.
+        children: a 2-D uint8 device tensor of R1RdPick or R1PartPick records, one per row (a row begins with the
+        child's best_rd; rows may be strided); child_idx: (n, 4) int32 device tensor of rows, -1 = absent.
+        part_rate: (n,) 4-byte device tensor (uint32 1/8 bits) or None (the reference's 0.0 arm); must_split: (n,)
+        uint8 or None; parent / parent_idx: the R1PartPick records whose best_rd is the nodes' ref_rd_cost and (n,)
+        int32 rows into them, or None (f64::MAX).  Nothing is allocated.  -> state"""
+        assert state.is_cuda and state.is_contiguous() and state.element_size() == 1 and state.numel() % PART_PICK.itemsize == 0
+        n = state.numel() // PART_PICK.itemsize
+        assert children.is_cuda and children.dim() == 2 and children.element_size() == 1 and children.stride(1) == 1
+        assert child_idx.is_cuda and child_idx.is_contiguous() and child_idx.dtype == torch.int32 and child_idx.numel() == 4 * n
+        for t, size in ((part_rate, 4), (must_split, 1), (parent_idx, 4)):
+            assert t is None or (t.is_cuda and t.is_contiguous() and t.element_size() == size and t.numel() == n), t
+        n_parent = 0
+        if parent is not None:
+            assert parent.is_cuda and parent.is_contiguous() and parent.element_size() == 1 and parent_idx is not None
+            n_parent = parent.numel() // PART_PICK.itemsize
+        self._check(self.lib.r1_rd_partition_pick_batch(
+            self.h, state.data_ptr(), n, int(partition), int(call_id), int(rule), float(lam), int(bool(enable_early_exit)),
+            part_rate.data_ptr() if part_rate is not None else None, children.data_ptr(), int(children.stride(0)),
+            int(children.shape[0]), child_idx.data_ptr(), must_split.data_ptr() if must_split is not None else None,
+            parent.data_ptr() if parent is not None else None, n_parent,
+            parent_idx.data_ptr() if parent_idx is not None else None, _stream_ptr()), "r1_rd_partition_pick_batch")
+        return state
+
+    def part_select_batch(self, state, srcs, dst):
+        """r1_part_select_batch: for every node whose best_call names one of `srcs` (a list of up to four 2-D device
+        tensors, one row per node, or None; entry c belongs to call_id c), that row goes to the node's row of `dst`;
+        every other row of dst stays.  A source that IS dst copies nothing.  Rows are multiples of 4 bytes.  -> dst"""
+        assert state.is_cuda and state.is_contiguous() and state.element_size() == 1
+        n = state.numel() // PART_PICK.itemsize
+        assert dst.is_cuda and dst.dim() == 2 and dst.shape[0] == n and dst.stride(1) == 1
+        row = dst.shape[1] * dst.element_size()
+        live = [t for t in srcs if t is not None]
+        for t in live:
+            assert t.is_cuda and t.dim() == 2 and t.shape == dst.shape and t.dtype == dst.dtype and t.stride(1) == 1 and \
+                t.stride(0) == live[0].stride(0), (t.shape, t.stride())
+        ptrs = (C.c_void_p * 4)(*[t.data_ptr() if t is not None else None for t in srcs])
+        src_stride = live[0].stride(0) * dst.element_size() if live else 0
+        self._check(self.lib.r1_part_select_batch(
+            self.h, state.data_ptr(), n, len(srcs), ptrs, src_stride, dst.data_ptr(), dst.stride(0) * dst.element_size(),
+            row, _stream_ptr()), "r1_part_select_batch")
+        return dst
+
+    def part_select_rect_batch(self, state, src_planes, dst_plane, pos_xy, bw, bh, store_w=None, store_h=None):
+        """r1_part_select_rect_batch: the node's bw x bh rectangle at pos_xy ((n, 2) int16 device tensor) from the plane
+        of the winning trial (src_planes: a list of up to four Planes of dst_plane's geometry, or None; entry c belongs
+        to call_id c) into dst_plane, clipped to store_w x store_h (the visible size by default).  Rectangles must not
+        overlap.  -> dst_plane"""
+        assert state.is_cuda and state.is_contiguous() and state.element_size() == 1
+        n = state.numel() // PART_PICK.itemsize
+        assert pos_xy.is_cuda and pos_xy.is_contiguous() and pos_xy.element_size() == 2 and pos_xy.numel() == 2 * n
+        planes = (_lib.R1Plane * 4)(*[p.cstruct() if p is not None else _lib.R1Plane() for p in src_planes])
+        pd = dst_plane.cstruct()
+        self._check(self.lib.r1_part_select_rect_batch(
+            self.h, state.data_ptr(), n, len(src_planes), planes, C.byref(pd), pos_xy.data_ptr(), int(bw), int(bh),
+            int(dst_plane.width if store_w is None else store_w), int(dst_plane.height if store_h is None else store_h),
+            _stream_ptr()), "r1_part_select_rect_batch")
+        return dst_plane
 
     # ---- the coefficient neighbour contexts carried on the device ----
     @staticmethod

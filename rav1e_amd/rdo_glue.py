@@ -699,3 +699,56 @@ def tx_size_type_decision(per_depth_rates, per_depth_dists, lam):
         if slot is not None and rd < best_rd:
             best_depth, best_slot, best_rd = depth, slot, rd
     return best_depth, best_slot, best_rd
+
+
+F64_MAX = 1.7976931348623157e308      # f64::MAX: "no cost" of the partition search
+
+
+def _partition_children(partition):
+    """how many entries of a node's four children a partition type visits (get_sub_partitions, src/rdo.rs:1825-1846)"""
+    return {0: 1, 1: 2, 2: 2, 3: 4}[int(partition)]
+
+
+def partition_pick_bottomup(best_rd, partition, lam, rate, children, must_split=False, ref_rd=F64_MAX,
+                            enable_early_exit=True):
+    """One trial of encode_partition_bottomup (src/encoder.rs:2683-2843) -- the statement r1_rd_partition_pick_batch is
+    held to under R1_PART_BOTTOMUP.  best_rd: what the node holds (f64::MAX: nothing); rate: the partition symbol's
+    tell_frac difference in 1/8 bit, None for the reference's 0.0 arm; children: up to four costs, None = absent.
+    Python floats add as the reference's f64: cost + c0, then + c1, ... each rounded on its own.
+    -> (kept, rd, early_exit): kept says whether best_rd becomes rd and best_partition the trial's."""
+    cost = 0.0 if rate is None else compute_rd_cost(lam, rate, 0)
+    kids = list(children)[:_partition_children(partition)]
+    if int(partition) == 0:
+        if not kids or kids[0] is None:
+            return False, 0.0, False
+        return True, kids[0] + cost, False                                 # 2708-2711: unconditionally
+    rd = cost
+    for c in kids:
+        if c is None or c == F64_MAX:                                      # 2802, 2820
+            continue
+        rd = rd + c
+        if not must_split and enable_early_exit and (rd >= best_rd or rd >= ref_rd):   # 2822-2828
+            return False, rd, True
+    return rd < best_rd, rd, False                                         # 2835
+
+
+def partition_pick_topdown(best_rd, partition, lam, rate, children, enable_early_exit=True):
+    """One trial of rdo_partition_decision (src/rdo.rs:1849-2024; rdo_partition_none / rdo_partition_simple) -- the
+    statement of R1_PART_TOPDOWN.  best_rd: cached_block.rd_cost or what an earlier trial left.  The children are summed
+    from 0.0 and the partition cost is added to the sum LAST; the early exit looks at the sum without the cost.
+    -> (kept, rd, early_exit); a refused trial (an absent child, or the early exit) keeps nothing."""
+    kids = list(children)[:_partition_children(partition)]
+    if int(partition) == 0:
+        if not kids or kids[0] is None:
+            return False, 0.0, False
+        return kids[0] < best_rd, kids[0], False                           # 1856-1861, 2006: no partition symbol
+    cost = 0.0 if rate is None else compute_rd_cost(lam, rate, 0)
+    total = 0.0
+    for c in kids + [None] * (_partition_children(partition) - len(kids)):
+        if c is None:                                                      # 1933-1936
+            return False, total, False
+        total = total + c
+        if enable_early_exit and total > best_rd:                          # 1912
+            return False, total, True
+    rd = cost + total                                                      # 1939
+    return rd < best_rd, rd, False

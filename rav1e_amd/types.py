@@ -8,6 +8,7 @@ dimensions are the reference's (src/context/transform_unit.rs:27, 200-219).  TXB
 (r1_coeff_rate_chain_batch).  BLOCK_CHAIN_CTX / BLOCK_RATE_TRIAL: R1BlockChainCtx / R1BlockRateTrial
 (r1_coeff_rate_block_batch).  COEFF_CDF_CONTEXT: R1CoeffCdfContext (r1_coeff_cdf_slice_batch, r1_coeff_cdf_adapt_batch).
 COEFF_NBR_CONTEXT / NBR_BLOCK: R1CoeffNbrContext / R1NbrBlock (r1_coeff_nbr_gather_batch, r1_coeff_nbr_store_batch).
+PartitionType  src/partition.rs:114-126; PART_PICK: R1PartPick (r1_rd_partition_pick_batch, r1_part_select_batch).
 """
 import enum
 
@@ -105,6 +106,16 @@ class FilterMode(enum.IntEnum):
     BILINEAR = 3
 
 
+class PartitionType(enum.IntEnum):
+    """the four the encoder tries (RAV1E_PARTITION_TYPES) with the reference's discriminants; PARTITION_INVALID is the
+    device state's "nothing kept", -1 (the reference's own discriminant, 10, indexes nothing)"""
+    PARTITION_NONE = 0
+    PARTITION_HORZ = 1
+    PARTITION_VERT = 2
+    PARTITION_SPLIT = 3
+    PARTITION_INVALID = -1
+
+
 class DistKind(enum.IntEnum):
     SAD = 0
     SATD = 1
@@ -173,3 +184,9 @@ NBR_BLOCK = np.dtype([("nbr", "<u4"), ("bo_x", "<u2"), ("bo_y", "<u2"), ("mi_wid
                       ("flags", "u1")])
 assert COEFF_NBR_CONTEXT.itemsize == 3120 and NBR_BLOCK.itemsize == 20
 NBR_DO_CHROMA, NBR_SKIP = 1, 2        # R1NbrBlock.flags
+# R1PartPick (r1_rd_partition_pick_batch / r1_part_select_batch / r1_part_select_rect_batch): the decision state of one
+# node of the partition quad-tree, carried from call to call; best_rd leads it as it leads RD_PICK
+PART_PICK = np.dtype([("best_rd", "<f8"), ("best_partition", "i1"), ("best_call", "i1"), ("early_exit", "u1"),
+                      ("reserved", "u1", (5,))])
+assert PART_PICK.itemsize == 16
+PART_BOTTOMUP, PART_TOPDOWN = 0, 1    # R1_PART_*

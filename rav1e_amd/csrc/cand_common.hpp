@@ -2,7 +2,7 @@
 // (me_blocks.hip), the put / prep of transform-sized blocks (mc.hip, k_mc_fast; mc_mfma.hip) and the compound
 // candidate (mc_compound.hip) share: the DPP Hadamard (SATD with lane = column) and its LDS-tile form for the fused
 // kernel, v_sad, the packed i16 helpers, and the put_8tap / prep_8tap column filters on v_dot4 / v_dot2 with their
-// packed tap tables and tap loads.
+// packed tap tables and tap loads -- and, for the fused kernel's 64x64 and 32x32, the horizontal taps on the matrix pipe.
 #pragma once
 #include <type_traits>
 
@@ -227,8 +227,22 @@ __device__ __forceinline__ bool taps_six(const Taps<2> &t) {
 // fraction bits of each half after the v_perm leaves 4 * mid there: two instructions per row pair instead of three.
 // The vertical sums are then exactly four times what they were, below 2^23 in magnitude, and >> 13 returns the bits
 // of >> 11.  Every other caller keeps PACK4 off and its code.
-template <int W, int H, int WS, bool PREP, bool PACK4 = false>
-__device__ __forceinline__ void mc8_column_t(const uint8_t *win, int c, const Taps<1> &tp, int32_t *pred, bool six) {
+// MXNC (the fused coefficient kernels at 64x64 and 32x32, rdo_mc_matrix of rdo_cand_plan.hpp; 0 = off, every other
+// caller, the code it had): the horizontal pass on the matrix pipe.  The wave holds MXNC = 1 or 2 windows, lane =
+// (candidate, column); `win` is then the FIRST window of the wave, `lane` the lane and `zero` (MXNC == 2) a run of
+// r1mc::mx_zero_bytes zeros.  hacc(r) becomes register r % 4 of quad r / 4: one 8-byte LDS read and one
+// v_mfma_i32_16x16x32_i8 per candidate of the wave, with the window bytes as A, the candidate's half-taps as a band in
+// B (r1mc::mx_band8, built once per wave) and the bias as C -- the layout, stated with its index algebra in
+// mc_window.hpp, hands every lane the four accumulators of its own column, so nothing is moved between lanes and the
+// pack, the rolling pairs and the vertical pass below are untouched.  With two candidates the second MFMA accumulates
+// into the first one's D, and the row groups of the other candidate read `zero` through the same offsets: no VALU
+// instruction per quad.  Bytes past a row's W + 7 meet zero band entries; the rows past H + 6 of the last quad are
+// computed and never consumed.  The MFMAs take operands from all 64 lanes: a branch around the call must be one that
+// every lane of the wave takes.
+typedef int v4i_t __attribute__((ext_vector_type(4)));
+template <int W, int H, int WS, bool PREP, bool PACK4 = false, int MXNC = 0>
+__device__ __forceinline__ void mc8_column_t(const uint8_t *win, int c, const Taps<1> &tp, int32_t *pred, bool six,
+                                             int lane = 0, const uint8_t *zero = nullptr) {
   const uint32_t fx0 = tp.fx0, fx1 = tp.fx1;
   uint32_t ty[4], tz[5];
 #pragma unroll
@@ -252,7 +266,34 @@ __device__ __forceinline__ void mc8_column_t(const uint8_t *win, int c, const Ta
   const uint32_t t0 = (uint32_t)t64, t1 = (uint32_t)(t64 >> 32);
   const uint32_t t2 = (uint32_t)(((uint64_t)fx1 << sh8) >> 32);
   // the window holds pixels already biased by -128 (staged with xor 0x80)
+  // MXNC: the A fragments' addresses (quad q: + 4 q WS), the band(s), the bias as C, and the quad in flight
+  static_assert(MXNC == 0 || ((MXNC == 1 || MXNC == 2) && W == 64 / MXNC && WS % 8 == 0), "matrix pass: 64x64, 32x32");
+  const uint8_t *ap0 = win, *ap1 = win;
+  long bb0 = 0, bb1 = 0;
+  if constexpr (MXNC != 0) {
+    const uint8_t *ad = win + r1mc::mx_a_offset(lane, MXNC, H, WS);
+    const bool second = MXNC == 2 && r1mc::mx_a_cand(lane, MXNC) == 1;
+    ap0 = second ? zero : ad;
+    ap1 = second ? ad : zero;
+    bb0 = (long)r1mc::mx_band8((uint32_t)__builtin_amdgcn_readlane((int)fx0, 0),
+                               (uint32_t)__builtin_amdgcn_readlane((int)fx1, 0), lane);
+    if constexpr (MXNC == 2)
+      bb1 = (long)r1mc::mx_band8((uint32_t)__builtin_amdgcn_readlane((int)fx0, 32),
+                                 (uint32_t)__builtin_amdgcn_readlane((int)fx1, 32), lane);
+  }
+  const v4i_t cbias = {bias, bias, bias, bias};
+  v4i_t quad = cbias;
+  int quad_at = -1;   // a constant once the calls below are unrolled
   auto hacc = [&](int r) -> int32_t {   // 4 * intermediate + rounding, before the >> 2
+    if constexpr (MXNC != 0) {
+      if ((r >> 2) != quad_at) {
+        quad_at = r >> 2;
+        quad = __builtin_amdgcn_mfma_i32_16x16x32_i8(*(const long *)(ap0 + quad_at * 4 * WS), bb0, cbias, 0, 0, 0);
+        if constexpr (MXNC == 2)
+          quad = __builtin_amdgcn_mfma_i32_16x16x32_i8(*(const long *)(ap1 + quad_at * 4 * WS), bb1, quad, 0, 0, 0);
+      }
+      return quad[r & 3];
+    }
     const uint32_t d0 = wrow[r * WSD], d1 = wrow[r * WSD + 1], d2 = wrow[r * WSD + 2];
     int32_t acc = dot4_seed(d0, t0, bias);
     acc = __builtin_amdgcn_sdot4((int)d1, (int)t1, acc, false);
@@ -418,11 +459,13 @@ __device__ __forceinline__ void mc16_column_t(const uint8_t *win, int c, const T
 
 // One column of put_8tap (PREP: prep_8tap) of a W x H block at either pixel width, from a window staged with row
 // stride WS (8-bit: pixels biased by -128); `six` is taps_six(tp), voted by every lane that makes the call.
-template <int BPP, int W, int H, int WS, bool PREP, bool PACK4 = false>
+// MXNC != 0 (8-bit only): the horizontal pass on the matrix pipe, see mc8_column_t for what win / lane / zero are then.
+template <int BPP, int W, int H, int WS, bool PREP, bool PACK4 = false, int MXNC = 0>
 __device__ __forceinline__ void mc_column_fast(const uint8_t *win, int c, const Taps<BPP> &tp, int bit_depth,
-                                               int32_t *pred, bool six) {
+                                               int32_t *pred, bool six, int lane = 0, const uint8_t *zero = nullptr) {
   static_assert(!PACK4 || BPP == 1, "8 * mid of 16-bit pixels does not fit i16");
-  if constexpr (BPP == 1) mc8_column_t<W, H, WS, PREP, PACK4>(win, c, tp, pred, six);
+  static_assert(MXNC == 0 || BPP == 1, "there is no i16 matrix type");
+  if constexpr (BPP == 1) mc8_column_t<W, H, WS, PREP, PACK4, MXNC>(win, c, tp, pred, six, lane, zero);
   else mc16_column_t<W, H, WS, PREP>(win, c, tp, bit_depth, pred, six);
 }
 

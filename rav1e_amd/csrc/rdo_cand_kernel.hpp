@@ -23,6 +23,10 @@
 //     All four (col_frac==0?, row_frac==0?) cases of mc.rs:264-352 go through
 //     this one code path: a 128-valued tap at phase 0 reproduces the copy and
 //     1-D paths bit for bit (see the derivation at mc8_column_t, cand_common.hpp).
+//     8-bit 64x64 and 32x32 coefficient kernels (MC_MATRIX, rdo_cand_plan.hpp): the
+//     horizontal taps are one v_mfma_i32_16x16x32_i8 per candidate and quad of
+//     window rows instead -- window bytes as A, the taps as a band in B, every
+//     lane receives the accumulators of its own column.
 //     The residual COLUMN stays in registers.  SAD is a lane sum.  SATD: the
 //     vertical Hadamard on 8 registers, the horizontal one across the 8
 //     neighbouring lanes with DPP (quad_perm / row_half_mirror) -- no LDS; blocks
@@ -122,6 +126,10 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
   constexpr int SH1C = COL_FOLD ? 0 : SH1;
   // HALVE2 / MC_PACK4 (rdo_cand_plan.hpp): the networks of m24h in both passes; the shift-free pack of the 8-bit filter
   constexpr bool HALVE2 = PL::HALVE2, MC_PACK4 = PL::MC_PACK4;
+  // MC_MATRIX (rdo_cand_plan.hpp): the 8-bit filter's horizontal pass on the matrix pipe, MX_NC candidates per wave
+  constexpr int MX_NC = PL::MX_NC;
+  static_assert(MX_NC == 0 || (BPP == 1 && QM == 0 && !INTRA && P == W && NC * W == 64),
+                "a coefficient kernel of 8-bit pixels, lane = (candidate, column) with no idle lane");
   __shared__ __attribute__((aligned(16))) uint8_t smem[LDS_BYTES];
   T *buf = (T *)smem;
   TB *tbuf = (TB *)smem;
@@ -218,6 +226,13 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
   if (from_ref) tp = r1cand::load_taps<BPP, W, H>(cd.col_frac, cd.row_frac, cd.mode_x, cd.mode_y);
   // every filter of the wave with zero outer taps (anything but SHARP): the short column filter
   const bool six = r1cand::taps_six(tp);
+  // MC_MATRIX, two candidates: the zeros that the other candidate's row groups supply (under the loads' round trip)
+  if constexpr (PL::MX_ZERO_BYTES != 0) {
+#pragma unroll
+    for (int k = 0; k < (PL::MX_ZERO_BYTES / 16 + 63) / 64; k++)
+      if (lane + 64 * k < PL::MX_ZERO_BYTES / 16)
+        *(uint4 *)(smem + PL::MX_ZERO_OFF + 16 * (lane + 64 * k)) = make_uint4(0u, 0u, 0u, 0u);
+  }
   // A.2: into LDS
   auto stage_source = [&]() {
     if (live) {
@@ -320,6 +335,13 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
 #pragma unroll
         for (int r = 0; r < H; r++) pred[r] = pi[(size_t)r * W];
       } else {
+        // MC_MATRIX: the MFMAs take their operands from every lane.  All 64 lanes are here then -- lane = (candidate,
+        // column) with no idle lane, a wave that runs has its first candidate, and the second slot of the last 32x32
+        // wave repeats the launch's last one (UNMASK) -- under the wave-uniform branch on the kernel argument above.
+        if constexpr (MX_NC != 0)
+          r1cand::mc_column_fast<BPP, W, H, WS, false, MC_PACK4, MX_NC>(smem, c, tp, BD, pred, six, lane,
+                                                                         smem + PL::MX_ZERO_OFF);
+        else
         r1cand::mc_column_fast<BPP, W, H, WS, false, MC_PACK4>(win, c, tp, BD, pred, six);
       }
       if (pred_out && live_st) {

@@ -132,6 +132,20 @@ constexpr bool rdo_halve2(int bd, int wl, int hl, int qm, bool mt, int ps) {
 constexpr bool rdo_mc_pack4(int bd, int wl, int hl, int qm, bool mt, int ps) {
   return bd == 8 && rdo_plain_square(wl, hl, qm, mt, ps) && wl <= 5;
 }
+// Whether an instantiation's 8-bit motion compensation runs its horizontal 8-tap pass on the matrix pipe
+// (mc8_column_t<.., MXNC>, cand_common.hpp; the fragment geometry is r1mc::mx_*, mc_window.hpp): a quad of window
+// rows is one 8-byte LDS read and one v_mfma_i32_16x16x32_i8 per candidate of the wave instead of twelve v_dot4 on
+// twelve LDS dwords, every lane receives the accumulators of its own column, and the pack and the vertical pass stay
+// as they are.  Candidates are the family of HALVE2 / MC_PACK4.  Built for 64x64 (one candidate per wave) and 32x32
+// (two: two chained MFMAs, the other candidate's row groups read a zeroed shadow behind the source block); 16x16 and
+// 8x8 (four and eight tap sets per wave) have no layout here and keep the v_dot4 pass, as does everything else.
+// Measured like COL_FOLD / HALVE2, the parent's library against this one on one box, three sessions of alternated passes
+// (profiles/r22_mc_matrix_notes.md): 64x64 launch -8.2 %, 32x32 -4.2 %, every pass below every parent pass;
+// SQ_INSTS_VALU per wave 4069 -> 3839 and 1772 -> 1706, a third of the LDS instructions gone; registers, LDS and waves
+// per SIMD as before (tools/kres.py).
+constexpr bool rdo_mc_matrix(int bd, int wl, int hl, int qm, bool mt, int ps) {
+  return bd == 8 && rdo_plain_square(wl, hl, qm, mt, ps) && wl >= 5;
+}
 
 // ---- one instantiation: geometry, choices, LDS layout ----
 // PS: where the prediction comes from -- 0 = put_8tap of the reference window (or the dense qa.pred_in buffer),
@@ -245,4 +259,17 @@ struct RdoCandPlan {
   static constexpr int LDS_CHAIN =
       COLSHARE ? TKEEP_OFF + H * LSTRIDE * (int)sizeof(TB) : LDS_WORK + (SRC_KEEP ? SRC_BYTES : 0);
   static constexpr int LDS_BYTES = LDS_CHAIN > EDGE_BYTES ? LDS_CHAIN : EDGE_BYTES;
+  // MC_MATRIX (rdo_mc_matrix): the horizontal pass on the matrix pipe.  MX_NC = candidates per wave there, 0 where it
+  // is off.  With two candidates the zeroed shadow (MX_ZERO_BYTES at MX_ZERO_OFF) lies behind the staged source block,
+  // inside what the transpose tile needs anyway; phase A clears it and nothing writes there until every lane has
+  // filtered its column.  No instantiation's LDS grows: what the fragments read lies inside LDS_BYTES.
+  static constexpr bool MC_MATRIX = rdo_mc_matrix(BD, WL, HL, QM, MT, PS);
+  static constexpr int MX_NC = MC_MATRIX ? NC : 0;
+  static constexpr int MX_ZERO_BYTES = MC_MATRIX && NC > 1 ? r1mc::mx_zero_bytes(H, WS) : 0;
+  static constexpr int MX_ZERO_OFF = (WIN_PAD + SRC_BYTES + 15) & ~15;
+  static_assert(!MC_MATRIX || (NC <= 2 && WS % 8 == 0 && !SRC_LATE && !SRC_KEEP && SRC_OFF == WIN_PAD),
+                "the matrix pass reads aligned 8-byte fragments of one or two windows; the shadow follows the source");
+  static_assert(!MC_MATRIX || r1mc::mx_a_end(NC > 2 ? 2 : NC, H, WS) <= LDS_BYTES,
+                "the furthest byte an A fragment reads lies inside the allocation");
+  static_assert(!MC_MATRIX || MX_ZERO_OFF + MX_ZERO_BYTES <= LDS_BYTES, "the zeroed shadow lies inside the allocation");
 };

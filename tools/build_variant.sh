@@ -12,7 +12,9 @@ mkdir -p ../../build
 HIPCC=/opt/rocm/bin/hipcc
 FLAGS=$(make -s flags)
 for b in 8 10; do
-  $HIPCC $FLAGS -DR1_RDO_TU_BD=$b -DR1_RDO_TU_QM=$QM "$@" -c rdo_cand_slice.hip -o ../../build/rdo_cand_b${b}_q${QM}_$NAME.o &
+  # the 8-bit coefficient slice is built with its MFMA results in VGPRs (MFMA_VGPR, csrc/Makefile)
+  MX=""; [ "$b$QM" = 80 ] && MX="-mllvm -amdgpu-mfma-vgpr-form"
+  $HIPCC $FLAGS $MX -DR1_RDO_TU_BD=$b -DR1_RDO_TU_QM=$QM "$@" -c rdo_cand_slice.hip -o ../../build/rdo_cand_b${b}_q${QM}_$NAME.o &
 done
 wait
 OBJS=$(ls *.o | grep -v "^rdo_cand_b8_q${QM}.o\|^rdo_cand_b10_q${QM}.o\|_prof.o$")

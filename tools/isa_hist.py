@@ -4,6 +4,7 @@
   python tools/isa_hist.py rav1e_amd/csrc/lrf_search.hip [kernel-name-substring ...]
   python tools/isa_hist.py --json OUT.json -DR1_RDO_TU_BD=8 -DR1_RDO_TU_QM=0 -DR1_HEADLINE_ONLY
       rav1e_amd/csrc/rdo_cand_slice.hip k_rdo_cand
+      (add -mllvm=-amdgpu-mfma-vgpr-form for the 8-bit slice 0, as csrc/Makefile builds it)
       (one slice of the fused kernel; the 8- and 10-bit slices 0 together are the per-kernel VALU mix of
       profiles/r03_isa_mix.json, which bench.py's `roofline` prices the VALU-issue roof with)
 
@@ -32,8 +33,13 @@ def main():
     jpath = None
     if argv and argv[0] == "--json":
         jpath, argv = argv[1], argv[2:]
-    defs = [a for a in argv if a.startswith("-D")]      # e.g. the slice of rdo_cand_slice.hip
-    argv = [a for a in argv if not a.startswith("-D")]
+    # -D...: e.g. the slice of rdo_cand_slice.hip; -mllvm=OPTION: a back-end option the Makefile gives that object
+    # (the 8-bit coefficient slice is built with -mllvm -amdgpu-mfma-vgpr-form)
+    defs = [a for a in argv if a.startswith("-D")]
+    for a in argv:
+        if a.startswith("-mllvm="):
+            defs += ["-mllvm", a[len("-mllvm="):]]
+    argv = [a for a in argv if not a.startswith(("-D", "-mllvm="))]
     src = argv[0]
     pats = argv[1:]
     jout = {"_model": {"fast_cycles": COST_FAST, "slow_cycles": COST_SLOW,

@@ -1316,7 +1316,8 @@ int r1_coeff_rate_chain_batch(r1_ctx *ctx, const void *qcoeffs, int coeff_bytes,
  * Every loop is bounded by ntx, the coded area, the four base-range rounds or the Golomb length; no spin-waits, no atomics.
  * The adapted CDFs are dropped here: r1_coeff_cdf_adapt_batch below replays the winner on a device-resident
  * R1CoeffCdfContext and leaves it adapted; r1_coeff_cdf_slice_batch cuts this call's `cdfs` out of one.
- * OUT OF SCOPE: the head symbols themselves (the host's dozen); skip = true (no coefficient
+ * OUT OF SCOPE: the head symbols themselves (the host's dozen, or for intra frames r1_intra_head_rate_batch below,
+ * which stores the rng this call starts from into `trials`); skip = true (no coefficient
  * is written); making the serial range-coder chain itself faster. */
 typedef struct R1BlockChainCtx {        /* 108 bytes */
   uint8_t ctx[3][2][16];  /* [plane][0: above, 1: left][16]: above_coeff_context[p][(tx_bo.x >> xdec) + c] and
@@ -1427,7 +1428,7 @@ int r1_rd_commit_batch(r1_ctx *ctx, const R1RdPick *state, int n_states, int cal
  * block's winner on it and leaves it adapted.  Per block, on one stream with nothing read back:
  *     slice -> rates (cdf_sel = the context's index) -> pick -> commit -> adapt (gated by the pick's state).
  * A rollback (rdo_partition_decision codes sub-block after sub-block and rolls everything back) is the caller's
- * device copy of the struct.  Head symbols use CDFs the coefficients never touch; they stay the host's.
+ * device copy of the struct.  Head symbols use CDFs the coefficients never touch: R1HeadCdfContext, further down.
  * R1CoeffCdfContext: every field write_coeffs_lv_map and write_tx_type can touch, in the reference's shapes
  * (src/context/cdf_context.rs:23-96; [TxSize::TX_SIZES = 5][PLANE_TYPES = 2], TX_SIZE_SQR_CONTEXTS = 4), so a host
  * fills it field by field.  The padding is never read and never written. */
@@ -1500,7 +1501,8 @@ int r1_coeff_cdf_adapt_batch(r1_ctx *ctx, const void *qcoeffs_y, const uint16_t 
  *     gather -> search -> slice -> rates -> pick -> commit -> winner tx type -> adapt -> store.
  * A fresh tile is the struct zeroed (BlockContext::new); a rollback (rdo_partition_decision) is the caller's device copy
  * of the struct, as for R1CoeffCdfContext -- the reference's 16-entry checkpoint window restores nothing a whole copy
- * would not.  Head symbols, the above_tx_context / partition contexts and the partition decision stay the host's. */
+ * would not.  The above_tx_context / partition contexts and the head symbols have a context pair of their own
+ * (R1HeadNbrContext / R1HeadCdfContext, further down); the partition decision is r1_rd_partition_pick_batch. */
 #define R1_COEFF_NBR_WIDTH 1024            /* COEFF_CONTEXT_MAX_WIDTH = MAX_TILE_WIDTH / MI_SIZE (block_unit.rs:36) */
 typedef struct R1CoeffNbrContext {         /* 3120 bytes: one per tile, or per speculative branch of one */
   uint8_t above[3][R1_COEFF_NBR_WIDTH];    /* above_coeff_context[p][x >> xdec_p] */
@@ -1583,8 +1585,9 @@ int r1_rd_winner_tx_type_batch(r1_ctx *ctx, const R1RdPick *state, int n_states,
  * (src/encoder.rs:2683-2843) and rdo_partition_decision with rdo_partition_none / rdo_partition_simple
  * (src/rdo.rs:1849-2024) -- behind the children's chains on the same stream, with no copy and no synchronisation.  A
  * node's decision is an R1PartPick that is carried from call to call; the two selects then move the state the winning
- * trial left to where the next node reads it.  The partition SYMBOL stays a head symbol: its rate (the tell_frac
- * difference of write_partition) is the host's, handed in as part_rate exactly as rate_add is handed to the pick.
+ * trial left to where the next node reads it.  The partition SYMBOL is a head symbol: its rate (the tell_frac
+ * difference of write_partition) is handed in as part_rate exactly as rate_add is handed to the pick -- the host's, or
+ * for intra frames r1_partition_rate_batch's (further down).
  * All pointers are DEVICE pointers except srcs / src_planes / dst_plane, which are host arrays of device addresses.
  * One call is ONE partition type tried at n nodes: the same node of n tiles, or any n nodes whose children are
  * finished.  Node s reads
@@ -1669,6 +1672,154 @@ int r1_part_select_batch(r1_ctx *ctx, const R1PartPick *state, int n, int n_src,
 int r1_part_select_rect_batch(r1_ctx *ctx, const R1PartPick *state, int n, int n_src, const R1Plane *src_planes,
                               const R1Plane *dst_plane, const int16_t *pos_xy, int bw, int bh, int store_w, int store_h,
                               void *stream);
+
+/* ---- the intra head symbols on the device (added under ABI 7): what a mode trial of luma_chroma_mode_rdo writes in
+ * front of its coefficients (src/rdo.rs:866-907) -- the partition symbol, skip, the luma mode and its angle delta, the
+ * chroma mode with its CFL alphas or angle delta, the transform size -- on a fresh WriterCounter, against head CDFs that
+ * adapt with every winner and neighbour contexts that hold every winner's mode and transform size.  Both are decided on
+ * the device, so these calls keep them there.  With the coefficient contexts above, a tile's intra blocks are enqueued in
+ * coding order on one stream with nothing read back:
+ *     gather -> search -> slice -> head rate -> rates -> pick -> commit -> winner tx type -> adapt -> store -> head commit.
+ * r1_intra_head_rate_batch writes rate_add, the head's tell_frac difference that r1_rd_pick_batch adds, and the writer's
+ * rng behind the head straight into R1BlockRateTrial.rng, where r1_coeff_rate_block_batch starts from.
+ * r1_partition_rate_batch writes the part_rate r1_rd_partition_pick_batch reads.  r1_intra_head_commit_batch replays
+ * the winner.  All pointers are DEVICE pointers except tx_sizes.  rdo_glue.head_symbols / partition_symbol /
+ * head_nbr_store / head_nbr_reset_left are the statements; tests/golden/head_ref.npz pins them to the reference.
+ * R1HeadCdfContext: the head fields of the reference's CDFContext in its own shapes (src/context/cdf_context.rs:42-92),
+ * so a host fills it field by field.  y_mode and partition_w128 are carried for the layout; nothing here reads them.
+ * OUT OF SCOPE: inter frames (write_is_inter, y_mode_cdf, reference frames, motion vectors and the is_inter arms of
+ * get_tx_size_context); write_segmentation; deblock deltas, palette and filter-intra symbols, which the reference never
+ * enables here; skip = true trials; 128x128 superblocks (a size with a 128-point side is refused); carrying the TILE
+ * writer's rng from partition symbol to partition symbol (r1_partition_rate_batch starts from the rng it is given). */
+#define R1_HEAD_NBR_WIDTH 1024             /* COEFF_CONTEXT_MAX_WIDTH; above_partition_context has half of it */
+typedef struct R1HeadCdfContext {          /* 2192 bytes */
+  uint16_t partition_w8[4][4];
+  uint16_t partition[12][10];
+  uint16_t partition_w128[4][8];
+  uint16_t skip[3][2];                     /* skip_cdfs */
+  uint16_t kf_y[5][5][R1_INTRA_MODES];
+  uint16_t y_mode[4][R1_INTRA_MODES];
+  uint16_t uv_mode[R1_INTRA_MODES][13];
+  uint16_t uv_mode_cfl[R1_INTRA_MODES][14];
+  uint16_t angle_delta[8][7];
+  uint16_t cfl_sign[8];
+  uint16_t cfl_alpha[6][16];
+  uint16_t tx_size_8x8[3][2];
+  uint16_t tx_size[3][3][3];
+  uint16_t pad[1];                         /* to a multiple of 16 bytes; never read, never written */
+} R1HeadCdfContext;
+/* One per tile, or per speculative branch of one, beside R1CoeffNbrContext: the arrays of BlockContext the head contexts
+ * read (src/context/block_unit.rs:233-236) and, as ROW BUFFERS, what they read through blocks.above_of / left_of:
+ * above_mode[x] / above_skip[x] belong to the block coded last over column x, left_mode[r] / left_skip[r] to the block
+ * coded last over the rows r mod 16 -- in coding order that is the cell above_of / left_of names.  A fresh tile is the
+ * struct zeroed (DC_PRED is 0); a rollback is the caller's device copy, as for the other two contexts. */
+typedef struct R1HeadNbrContext {          /* 3640 bytes */
+  uint8_t above_partition[R1_HEAD_NBR_WIDTH / 2], left_partition[8];
+  uint8_t above_tx[R1_HEAD_NBR_WIDTH], left_tx[16];
+  uint8_t above_mode[R1_HEAD_NBR_WIDTH], left_mode[16];
+  uint8_t above_skip[R1_HEAD_NBR_WIDTH], left_skip[16];
+} R1HeadNbrContext;
+typedef struct R1HeadBlock {               /* 20 bytes: a block's static geometry, which the host knows */
+  uint32_t nbr, cdf;                       /* which R1HeadNbrContext, which R1HeadCdfContext */
+  uint16_t bo_x, bo_y;                     /* tile block offset, 4x4 units */
+  uint16_t mi_cols, mi_rows;               /* the tile's blocks.cols() / rows() */
+  uint8_t bsize;                           /* BlockSize, the reference's discriminant (src/partition.rs:130-153) */
+  uint8_t has_chroma, tx_mode_select;      /* has_chroma(..) and not Cs400; fi.tx_mode_select */
+  uint8_t reserved;
+} R1HeadBlock;
+typedef struct R1HeadTrial {               /* 16 bytes: one mode trial of a block */
+  uint32_t block;                          /* index into blocks */
+  uint8_t y_mode, uv_mode;                 /* PredictionMode; uv_mode 13 = UV_CFL_PRED */
+  int8_t angle_y, angle_uv;                /* angle_delta.y / .uv, -3 .. 3 */
+  int16_t alpha_u, alpha_v;                /* CFLParams::from_alpha(u, v), -16 .. 16 */
+  uint8_t tx_size, reserved[3];            /* TxSize */
+} R1HeadTrial;
+/* rate_add_out[t] = tell_frac behind the head of trials[t] less tell_frac of the fresh counter, 1/8 bit; the writer's
+ * rng behind the head goes to (uint16_t *)((char *)rng_out + t * rng_stride) (rng_out optional) -- &trials24[0].rng with
+ * stride 24 lands it in an R1BlockRateTrial array.  In coding order: write_partition(PARTITION_NONE) for a square block
+ * of 8x8 and up; write_skip(false); write_intra_mode_kf; write_angle_delta for a directional luma mode at
+ * bsize >= BLOCK_8X8 IN THE ENUM'S ORDER (4x16 and 16x4 write one); with has_chroma write_intra_uv_mode (uv_mode_cfl_cdf
+ * where bsize.cfl_allowed(), bsize <= BLOCK_32X32 in the enum's order), write_cfl_alphas for UV_CFL_PRED, write_angle_delta
+ * for a directional chroma mode; with tx_mode_select and bsize > BLOCK_4X4 write_tx_size_intra.  Every symbol is written
+ * with its CDF update (symbol_with_update!), so a second symbol on the same row -- the chroma angle delta when the chroma
+ * mode equals the luma mode, the V alpha when both signs are equal -- reads what the first adapted.  has_above /
+ * has_left are bo_y > 0 / bo_x > 0; above_tx / left_tx are read raw.  Contexts are never written; many trials may share a
+ * block.
+ *   depth_state / tx_sizes (optional, both or none): one R1RdPick per trial; the trial's transform size is
+ *                tx_sizes[depth_state[t].best_call] (a HOST table of three TxSize), in place of the record's.
+ *   cfl_alpha (optional): int16 pairs, (u, v) of trial t at [2t], [2t + 1] -- r1_cfl_alpha_search_batch's alpha_out with
+ *                a trial's U and V candidates adjacent -- in place of the record's alphas.
+ * A trial the device must refuse gets rate 0xFFFFFFFF and nothing else of it is written: block >= n_blocks, nbr / cdf out
+ * of range, a bsize past the enum or with a 128-point side, mi_cols > 1024, a place outside the tile, y_mode >= 13, a
+ * neighbour mode >= 13 in the context, with has_chroma a uv_mode >= 14 (13 where cfl_allowed() is false), CFL with both
+ * alphas zero or one outside -16 .. 16, an angle delta that would be written outside -3 .. 3, a tx_size past the enum
+ * or, where it is written, no depth 0 .. 2 of the block, PARTITION_NONE where the tile's edge cuts the block (the
+ * reference asserts), best_call outside 0 .. 2 with depth_state given.
+ * R1_EINVAL: a NULL ctx, nbrs, cdfs, blocks, trials or rate_add_out; n < 0; n_nbrs, n_cdfs or n_blocks < 1; exactly one
+ * of depth_state / tx_sizes; a tx_sizes entry that is no TxSize; rng_out with a stride below 2 or odd, or not 2-byte
+ * aligned.  n == 0 returns 0.  One lane per trial; every loop is bounded by 4; no atomics, no spin-waits. */
+int r1_intra_head_rate_batch(r1_ctx *ctx, const R1HeadNbrContext *nbrs, int n_nbrs, const R1HeadCdfContext *cdfs,
+                             int n_cdfs, const R1HeadBlock *blocks, int n_blocks, const R1HeadTrial *trials, int n,
+                             const R1RdPick *depth_state, const uint8_t *tx_sizes, const int16_t *cfl_alpha,
+                             uint32_t *rate_add_out, void *rng_out, long long rng_stride, void *stream);
+/* write_partition (src/context/partition_unit.rs:267-357) alone: partitions[i] (R1_PARTITION_NONE .. SPLIT, uint8) at
+ * node nodes[i] -- an R1HeadBlock whose bsize is the node's; has_chroma and tx_mode_select are not read -- from
+ * rng_in[i] (NULL: 0x8000 everywhere).  part_rate_out[i] is the tell_frac difference, the array
+ * r1_rd_partition_pick_batch reads; rng_out (optional) the rng behind it.  With rows and columns (bo + half the block
+ * inside the tile) the symbol goes to partition_w8_cdf[ctx] for an 8x8 node, else partition_cdf[ctx - 4]; with only one
+ * of them to the two-entry CDF of partition_gather_vert_alike / _horz_alike, as SPLIT or not; with neither nothing is
+ * written: rate 0, rng unchanged.  Contexts are never written.
+ * Refused with rate 0xFFFFFFFF: what the reference asserts against (a node below 8x8 or not square, HORZ / VERT / NONE
+ * where the edge does not admit it, an 8x8 node at a one-sided edge), a type above SPLIT, an rng below 0x8000, and the
+ * place and index cases of r1_intra_head_rate_batch.
+ * R1_EINVAL: a NULL ctx, nbrs, cdfs, nodes, partitions or part_rate_out; n < 0; n_nbrs or n_cdfs < 1.  n == 0 returns 0. */
+int r1_partition_rate_batch(r1_ctx *ctx, const R1HeadNbrContext *nbrs, int n_nbrs, const R1HeadCdfContext *cdfs,
+                            int n_cdfs, const R1HeadBlock *nodes, const uint8_t *partitions, int n,
+                            const uint16_t *rng_in, uint32_t *part_rate_out, uint16_t *rng_out, void *stream);
+/* What the winner leaves.  State s acts when state[s].best_call == call_id, as in r1_rd_commit_batch; its trial is
+ * t = (s * group + best_row) * nt + best_slot of `trials`, its desc commits[s].  In this order:
+ *   the partition event (part_type >= 0): the walker's write_partition(part_type) at the node (node_x, node_y,
+ *       node_bsize) adapts the node's partition row -- nothing where an edge arm or the corner writes it.  SPLIT is allowed;
+ *   the winner's head symbols as the block is coded for real -- r1_intra_head_rate_batch's from write_skip on, with the
+ *       same depth_state / tx_sizes / cfl_alpha; the trial's own PARTITION_NONE is no part of them, the real partition
+ *       symbol being the walker's (src/encoder.rs:2688, 2781, 2862), the event above -- adapt cdfs[block.cdf] in place;
+ *   on nbrs[block.nbr]: y_mode and skip = 0 over above_mode / above_skip [bo_x ..] and left_mode / left_skip
+ *       [bo_y % 16 ..], the block's extent clipped to mi_cols / mi_rows as TileBlocksMut::for_each clips set_mode /
+ *       set_skip; with tx_mode_select the transform's width over above_tx[bo_x .. bo_x + bw / 4] and its height over
+ *       left_tx[bo_y % 16 ..] (update_tx_size_context, skip = false), clipped to the arrays;
+ *   update_partition_context (subsize != R1_HEAD_NO_SUBSIZE): partition_context_lookup[subsize] over the node's spans
+ *       above_partition[node_x / 2 ..] and left_partition[(node_y % 16) / 2 ..], clipped to the arrays.  The caller
+ *       names it where the reference calls it: bsize >= 8x8 && (bsize == 8x8 || partition != SPLIT), behind the node's
+ *       last block.
+ * flags bit 0 (R1_HEAD_EVENT_ONLY): the event alone -- a SPLIT above the node the block's own event names; no trial is
+ * read and a subsize is refused.
+ * Acting descs of one call MUST name distinct contexts (both kinds); the call does not detect it.  Every byte outside the
+ * spans and every CDF entry outside the rows touched stays bit-identical.  A desc with a device-resident fault writes
+ * NOTHING: the refusal cases of the rate call (less the edge case of its PARTITION_NONE), a best_row / best_slot outside group / nt, t >= n_trials, a trial of
+ * another block, a node that is not square, below 8x8 or outside the tile, a part_type the reference asserts against.
+ * R1_EINVAL: a NULL ctx, nbrs, cdfs, blocks, trials, commits or state; n_states < 0; n_nbrs, n_cdfs, n_blocks or n_trials
+ * < 1; call_id outside 0..127; group outside 1..4096; nt outside 1..16; depth_state / tx_sizes as above.
+ * One lane per state; every loop is bounded by 16; no atomics, no spin-waits. */
+#define R1_HEAD_NO_SUBSIZE 255
+#define R1_HEAD_EVENT_ONLY 1
+typedef struct R1HeadCommit {              /* 16 bytes */
+  uint32_t block;                          /* index into blocks */
+  uint16_t node_x, node_y;                 /* the walker's node: tile block offset */
+  uint8_t node_bsize;                      /* and its (square) BlockSize */
+  int8_t part_type;                        /* R1_PARTITION_* written in front of the block, -1 = none */
+  uint8_t subsize;                         /* update_partition_context's subsize, R1_HEAD_NO_SUBSIZE = none */
+  uint8_t flags, reserved[4];
+} R1HeadCommit;
+int r1_intra_head_commit_batch(r1_ctx *ctx, R1HeadNbrContext *nbrs, int n_nbrs, R1HeadCdfContext *cdfs, int n_cdfs,
+                               const R1HeadBlock *blocks, int n_blocks, const R1HeadTrial *trials, int n_trials,
+                               const R1HeadCommit *commits, const R1RdPick *state, int n_states, int call_id, int group,
+                               int nt, const R1RdPick *depth_state, const uint8_t *tx_sizes, const int16_t *cfl_alpha,
+                               void *stream);
+/* The head part of reset_left_contexts (src/context/block_unit.rs:394-401) at the start of a superblock row:
+ * left_partition and left_tx of nbrs[sel[i]] = 0, i < n; a sel[i] >= n_nbrs writes nothing.  left_mode / left_skip are
+ * NOT cleared: the reference's blocks array is not.  R1_EINVAL: a NULL pointer, n < 0, n_nbrs < 1.  n == 0 returns 0. */
+int r1_head_nbr_reset_left_batch(r1_ctx *ctx, R1HeadNbrContext *nbrs, int n_nbrs, const uint32_t *sel, int n,
+                                 void *stream);
 
 /* ---- multi-GPU: the tile-boundary exchange and the reference-frame all-gather (RCCL over
  * xGMI), SURVEY.md 8(e).  One process (or host thread) per GPU, tile r on rank r.  Rendezvous:

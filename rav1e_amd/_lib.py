@@ -188,6 +188,12 @@ SYMBOLS = {
                                         _vp]),
     "r1_part_select_batch": (_i, [_vp, _vp, _i, _i, _vp, C.c_longlong, _vp, C.c_longlong, _i, _vp]),
     "r1_part_select_rect_batch": (_i, [_vp, _vp, _i, _i, _PP, _PP, _vp, _i, _i, _i, _i, _vp]),
+    "r1_intra_head_rate_batch": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, C.c_longlong,
+                                      _vp]),
+    "r1_partition_rate_batch": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "r1_intra_head_commit_batch": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp,
+                                        _vp]),
+    "r1_head_nbr_reset_left_batch": (_i, [_vp, _vp, _i, _vp, _i, _vp]),
     "r1_lrf_sgrproj_plane": (_i, [_vp, _PP, _PP, _PP, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "r1_sgrproj_solve_batch": (_i, [_vp, _PP, _PP, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "r1_lrf_search_batch": (_i, [_vp, _PP, _PP, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, C.c_uint32, _vp, _vp, _vp, _vp]),

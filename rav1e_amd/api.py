@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 from .types import (BLOCK_CHAIN_CTX, BLOCK_RATE_TRIAL, COEFF_CDF_CONTEXT, COEFF_CDFS, COEFF_RATE_INVALID, PICK_FIRST_MIN, PICK_TX_TYPE,  # noqa: F401
-                    COEFF_NBR_CONTEXT, NBR_BLOCK, PART_BOTTOMUP, PART_PICK, PART_TOPDOWN, RD_PICK, TX_DIMS, TXB_CHAIN_CTX, TXB_CTX, TxSize, valid_av1_transform)
+                    COEFF_NBR_CONTEXT, HEAD_BLOCK, HEAD_CDF_CONTEXT, HEAD_COMMIT, HEAD_NBR_CONTEXT, HEAD_TRIAL, NBR_BLOCK, PART_BOTTOMUP, PART_PICK, PART_TOPDOWN, RD_PICK, TX_DIMS, TXB_CHAIN_CTX, TXB_CTX, TxSize, valid_av1_transform)
 
 DIST_CAND = np.dtype([("ox", "<i2"), ("oy", "<i2"), ("rx", "<i2"), ("ry", "<i2")])
 MC_CAND = np.dtype([("rx", "<i2"), ("ry", "<i2"), ("col_frac", "u1"), ("row_frac", "u1"),
@@ -1468,6 +1468,110 @@ class Context:
             eob_win.data_ptr() if eob_win is not None else None, int(ntx), trials.data_ptr(), _stream_ptr()),
             "r1_rd_winner_tx_type_batch")
         return trials
+
+    # ---- the intra head symbols on the device ----
+    @staticmethod
+    def head_nbr_contexts(n):
+        """n fresh R1HeadNbrContext (BlockContext::new and a blocks array of DC_PRED: all zero) as an (n, 3640) uint8
+        device tensor (HEAD_NBR_CONTEXT records; .cpu().numpy().view(HEAD_NBR_CONTEXT) reads them)"""
+        return torch.zeros((n, HEAD_NBR_CONTEXT.itemsize), dtype=torch.uint8, device="cuda")
+
+    @staticmethod
+    def _head_contexts(nbrs, cdfs):
+        for t, dt in ((nbrs, HEAD_NBR_CONTEXT), (cdfs, HEAD_CDF_CONTEXT)):
+            assert isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.element_size() == 1 and \
+                t.numel() % dt.itemsize == 0 and t.data_ptr() % 2 == 0, "(n, %d) uint8 on the device" % dt.itemsize
+        return nbrs.numel() // HEAD_NBR_CONTEXT.itemsize, cdfs.numel() // HEAD_CDF_CONTEXT.itemsize
+
+    @staticmethod
+    def _head_decided(n, depth_state, tx_sizes, cfl_alpha):
+        """the two optional inputs that carry what the device decided -> (depth_state pointer, host table, alpha pointer)"""
+        assert (depth_state is None) == (tx_sizes is None)
+        table = None
+        if depth_state is not None:
+            _rd_pick_states(depth_state, n)
+            table = (C.c_uint8 * 3)(*[int(t) for t in tx_sizes])
+        if cfl_alpha is not None:
+            assert cfl_alpha.is_cuda and cfl_alpha.is_contiguous() and cfl_alpha.element_size() == 2 and cfl_alpha.numel() == 2 * n
+        return (depth_state.data_ptr() if depth_state is not None else None, table,
+                cfl_alpha.data_ptr() if cfl_alpha is not None else None)
+
+    def intra_head_rate_batch(self, nbrs, cdfs, blocks, trials, depth_state=None, tx_sizes=None, cfl_alpha=None,
+                              rng_into=None, outs=None):
+        """r1_intra_head_rate_batch: what every intra mode trial writes in front of its coefficients, as rate_add of
+        rd_pick_batch, on the current stream -- rdo_glue.head_symbols on the device.  nbrs: (n_nbrs, 3640) uint8 device
+        tensor of HEAD_NBR_CONTEXT, cdfs: (n_cdfs, 2192) uint8 of HEAD_CDF_CONTEXT; blocks / trials: HEAD_BLOCK /
+        HEAD_TRIAL records, NumPy arrays or uint8 device tensors.  depth_state / tx_sizes: (n, 24) RD_PICK states and
+        the three TxSize of their call ids, in place of the trials' tx_size; cfl_alpha: (n, 2) int16 device tensor in
+        place of their alphas.  rng_into: an (n, 24) uint8 device tensor of BLOCK_RATE_TRIAL whose rng fields take the
+        writer's rng behind the head; otherwise the rng comes back as "rng" (n,) int16.
+        -> {"rate_add": (n,) int32 (uint32 1/8 bits, 0xFFFFFFFF = refused), "rng": ...}"""
+        n_nbrs, n_cdfs = self._head_contexts(nbrs, cdfs)
+        db, n_blocks = _dev_cands(blocks, HEAD_BLOCK)
+        dt, n = _dev_cands(trials, HEAD_TRIAL)
+        ds, table, da = self._head_decided(n, depth_state, tx_sizes, cfl_alpha)
+        o, ptr = _bind_wanted(outs, {"rate_add": (True, (n,), torch.int32), "rng": (rng_into is None, (n,), torch.int16)},
+                              nbrs.device)
+        rng_ptr, stride = ptr["rng"], 2
+        if rng_into is not None:
+            assert rng_into.is_cuda and rng_into.is_contiguous() and rng_into.element_size() == 1 and \
+                rng_into.numel() == n * BLOCK_RATE_TRIAL.itemsize
+            rng_ptr, stride = rng_into.data_ptr() + BLOCK_RATE_TRIAL.fields["rng"][1], BLOCK_RATE_TRIAL.itemsize
+        self._check(self.lib.r1_intra_head_rate_batch(
+            self.h, nbrs.data_ptr(), n_nbrs, cdfs.data_ptr(), n_cdfs, db.data_ptr(), n_blocks, dt.data_ptr(), n, ds, table,
+            da, ptr["rate_add"], rng_ptr, stride, _stream_ptr()), "r1_intra_head_rate_batch")
+        return o
+
+    def partition_rate_batch(self, nbrs, cdfs, nodes, partitions, rng_in=None, want_rng=False, outs=None):
+        """r1_partition_rate_batch: write_partition alone at every node (HEAD_BLOCK records whose bsize is the node's),
+        partitions: (n,) uint8 PartitionType, rng_in: (n,) 2-byte device tensor or None (0x8000) -- rdo_glue.
+        partition_symbol on the device.  -> {"part_rate": (n,) int32, what rd_partition_pick_batch takes as part_rate,
+        "rng": (n,) int16 when wanted}"""
+        n_nbrs, n_cdfs = self._head_contexts(nbrs, cdfs)
+        dn, n = _dev_cands(nodes, HEAD_BLOCK)
+        if not isinstance(partitions, torch.Tensor):
+            partitions = torch.from_numpy(np.ascontiguousarray(partitions, dtype=np.uint8)).to(nbrs.device)
+        assert partitions.is_cuda and partitions.is_contiguous() and partitions.element_size() == 1 and partitions.numel() == n
+        if rng_in is not None:
+            assert rng_in.is_cuda and rng_in.is_contiguous() and rng_in.element_size() == 2 and rng_in.numel() == n
+        o, ptr = _bind_wanted(outs, {"part_rate": (True, (n,), torch.int32), "rng": (want_rng, (n,), torch.int16)}, nbrs.device)
+        self._check(self.lib.r1_partition_rate_batch(
+            self.h, nbrs.data_ptr(), n_nbrs, cdfs.data_ptr(), n_cdfs, dn.data_ptr(), partitions.data_ptr(), n,
+            rng_in.data_ptr() if rng_in is not None else None, ptr["part_rate"], ptr["rng"], _stream_ptr()),
+            "r1_partition_rate_batch")
+        return o
+
+    def intra_head_commit_batch(self, nbrs, cdfs, blocks, trials, commits, state, call_id, group, nt, depth_state=None,
+                                tx_sizes=None, cfl_alpha=None):
+        """r1_intra_head_commit_batch: for every state the call `call_id` won, the winner's head symbols adapt its
+        HEAD_CDF_CONTEXT and its mode, skip, transform size and partition context go to its HEAD_NBR_CONTEXT, both in
+        place -- rdo_glue.head_symbols / head_nbr_store on the device.  commits: HEAD_COMMIT records, one per state;
+        trials: the array the rate call read (trial (s * group + best_row) * nt + best_slot is the winner); the
+        decided inputs as there.  Acting states must name distinct contexts.  -> (nbrs, cdfs)"""
+        n_nbrs, n_cdfs = self._head_contexts(nbrs, cdfs)
+        db, n_blocks = _dev_cands(blocks, HEAD_BLOCK)
+        dt, n_trials = _dev_cands(trials, HEAD_TRIAL)
+        dc, n = _dev_cands(commits, HEAD_COMMIT)
+        _rd_pick_states(state, n)
+        ds, table, da = self._head_decided(n_trials, depth_state, tx_sizes, cfl_alpha)
+        self._check(self.lib.r1_intra_head_commit_batch(
+            self.h, nbrs.data_ptr(), n_nbrs, cdfs.data_ptr(), n_cdfs, db.data_ptr(), n_blocks, dt.data_ptr(), n_trials,
+            dc.data_ptr(), state.data_ptr(), n, int(call_id), int(group), int(nt), ds, table, da, _stream_ptr()),
+            "r1_intra_head_commit_batch")
+        return nbrs, cdfs
+
+    def head_nbr_reset_left_batch(self, nbrs, sel):
+        """r1_head_nbr_reset_left_batch: left_partition and left_tx of nbrs[sel[i]] = 0 (the head part of
+        reset_left_contexts at the start of a superblock row; left_mode / left_skip stay).  sel: indices, a sequence or
+        an int32 device tensor."""
+        assert nbrs.is_cuda and nbrs.is_contiguous() and nbrs.element_size() == 1 and nbrs.numel() % HEAD_NBR_CONTEXT.itemsize == 0
+        if not isinstance(sel, torch.Tensor):
+            sel = torch.from_numpy(np.ascontiguousarray(sel, dtype=np.int32)).to(nbrs.device)
+        assert sel.is_cuda and sel.is_contiguous() and sel.element_size() == 4
+        self._check(self.lib.r1_head_nbr_reset_left_batch(
+            self.h, nbrs.data_ptr(), nbrs.numel() // HEAD_NBR_CONTEXT.itemsize, sel.data_ptr(), sel.numel(), _stream_ptr()),
+            "r1_head_nbr_reset_left_batch")
+        return nbrs
 
     # ---- lrf:: ----
     def lrf_sgrproj_plane(self, cdeffed, deblocked, out, ydec, crop_w, crop_h, frame_height, unit_size,

@@ -51,6 +51,16 @@ the kernels by executing the reference's own text (tests/golden/gen_rdo_glue_ref
                              the host statements of r1_coeff_nbr_store_batch, r1_coeff_nbr_reset_left_batch and
                              r1_rd_winner_tx_type_batch; pinned by tests/golden/coeff_nbr_ref.npz /
                              tests/test_coeff_nbr_ref.py
+  head_symbols               src/rdo.rs:870-877, src/encoder.rs:1913, 2086-2102, 2132-2136  (the head of an intra mode
+                                                       trial as a list of (CDF row, symbol))
+  partition_symbol / partition_context   src/context/partition_unit.rs:267-357, 416-429, 131-193
+  tx_size_symbol             src/context/transform_unit.rs:576-667
+  head_nbr_store             src/tiling/tile_blocks.rs:206-256, src/context/block_unit.rs:362-386,
+                             src/context/partition_unit.rs:480-503  (what the coded block leaves)
+  head_nbr_reset_left        src/context/block_unit.rs:356-360, 388-401
+                             the host statements of r1_intra_head_rate_batch, r1_partition_rate_batch,
+                             r1_intra_head_commit_batch and r1_head_nbr_reset_left_batch; pinned by
+                             tests/golden/head_ref.npz / tests/test_head_ref.py
 """
 from .types import BlockSize, TxSize
 
@@ -752,3 +762,187 @@ def partition_pick_topdown(best_rd, partition, lam, rate, children, enable_early
             return False, total, True
     rd = cost + total                                                      # 1939
     return rd < best_rd, rd, False
+
+
+# ---- the head symbols of an intra block of an intra frame (r1_intra_head_rate_batch, r1_partition_rate_batch,
+# r1_intra_head_commit_batch); pinned by tests/golden/head_ref.npz / tests/test_head_ref.py
+HEAD_REFUSED = "refused"    # what the device answers with rate 0xFFFFFFFF (the reference would assert! or index out of range)
+_INTRA_MODE_CONTEXT = (0, 1, 2, 3, 4, 4, 4, 4, 3, 0, 1, 2, 0)     # write_intra_mode_kf, src/context/block_unit.rs:703-704
+_PARTITION_GATHER = {2: (2, 3, 4, 6, 7, 9),      # partition_gather_vert_alike (partition_unit.rs:163-193): VERT, SPLIT,
+                     1: (1, 3, 4, 5, 6, 8)}      # HORZ_A, VERT_A, VERT_B, VERT_4; _horz_alike (131-161): HORZ, SPLIT, ..
+_BLOCK_8X8, _BLOCK_32X32 = 3, 9
+
+
+def _head_block_ok(bsize, bo_x, bo_y, mi_cols, mi_rows):
+    return (0 <= int(bsize) < 22 and max(BlockSize(bsize).dims) <= 64 and 0 <= bo_x < mi_cols <= 1024 and
+            0 <= bo_y < mi_rows)
+
+
+def partition_context(above_partition, left_partition, bo_x, bo_y, bsize):
+    """partition_plane_context (src/context/partition_unit.rs:416-429) of a square block of 8x8 and up"""
+    w, h = BlockSize(bsize).dims
+    assert w == h and w >= 8
+    bsl = w.bit_length() - 4
+    above = (int(above_partition[bo_x >> 1]) >> bsl) & 1
+    left = (int(left_partition[(bo_y % 16) >> 1]) >> bsl) & 1
+    return left * 2 + above + bsl * 4
+
+
+def partition_symbol(nbr, bsize, bo_x, bo_y, mi_cols, mi_rows, partition):
+    """write_partition (src/context/partition_unit.rs:267-357) as one symbol: None where it writes nothing (neither rows
+    nor columns), HEAD_REFUSED where it asserts (a block below 8x8 or not square, a type the edge does not admit, an 8x8
+    at an edge) or where the device refuses (a 128-point size, a place outside the tile), else
+    (field, row, n, symbol, gather): field / row name the CDF row -- `partition_w8` for ctx < 4, else `partition`[ctx - 4];
+    n its symbol count; gather 0 for a symbol written with its update, 2 / 1 for the two-entry CDF of
+    partition_gather_vert_alike / _horz_alike written with w.symbol alone: nothing adapts."""
+    if not _head_block_ok(bsize, bo_x, bo_y, mi_cols, mi_rows) or not 0 <= int(partition) <= 3:
+        return HEAD_REFUSED
+    w, h = BlockSize(bsize).dims
+    if w != h or w < 8:
+        return HEAD_REFUSED
+    hbs = (w >> MI_SIZE_LOG2) // 2
+    has_cols, has_rows = bo_x + hbs < mi_cols, bo_y + hbs < mi_rows
+    ctx = partition_context(nbr["above_partition"], nbr["left_partition"], bo_x, bo_y, bsize)
+    if not has_rows and not has_cols:
+        return None
+    field, row, n = ("partition_w8", ctx, 4) if ctx < 4 else ("partition", ctx - 4, 10)
+    if has_rows and has_cols:
+        return field, row, n, int(partition), 0
+    if int(partition) not in ((3, 1) if has_cols else (3, 2)) or int(bsize) <= _BLOCK_8X8:
+        return HEAD_REFUSED
+    return field, row, n, int(int(partition) == 3), 2 if has_cols else 1
+
+
+def tx_size_symbol(nbr, bsize, bo_x, bo_y, tx_size):
+    """write_tx_size_intra (src/context/transform_unit.rs:576-667) for an intra frame: -> (field, row, n, depth) or
+    HEAD_REFUSED where tx_size is no depth 0..2 of the block.  above_tx_context / left_tx_context are read raw; has_above
+    / has_left are the tile's."""
+    mw, mh = BlockSize(bsize).dims                       # max_txsize_rect_lookup: the block itself up to 64x64
+    t = TxSize.by_dims(mw, mh)
+    depth = 0
+    while int(t) != int(tx_size):
+        if depth == 2 or sub_tx_size(t) == t:
+            return HEAD_REFUSED
+        t, depth = sub_tx_size(t), depth + 1
+    t, steps = TxSize.by_dims(mw, mh), 0
+    while int(t) != 0:
+        t, steps = sub_tx_size(t), steps + 1
+    above = int(int(nbr["above_tx"][bo_x]) >= mw)
+    left = int(int(nbr["left_tx"][bo_y % 16]) >= mh)
+    ctx = (above if bo_y > 0 else 0) + (left if bo_x > 0 else 0)
+    if steps - 1 > 0:
+        return ("tx_size", (steps - 2, ctx), 3, depth)
+    return ("tx_size_8x8", ctx, 2, depth)
+
+
+def head_symbols(nbr, bsize, bo_x, bo_y, mi_cols, mi_rows, has_chroma_, tx_mode_select, y_mode, uv_mode, angle_y,
+                 angle_uv, alpha_u, alpha_v, tx_size, coded=False):
+    """What one intra mode trial of an intra frame writes in front of its coefficients (src/rdo.rs:870-877 and
+    encode_block_pre_cdef / encode_block_post_cdef, src/encoder.rs:1913, 2086-2102, 2132-2136), skip = false: the
+    statement of r1_intra_head_rate_batch.  nbr: the arrays of a types.HEAD_NBR_CONTEXT record (never written).
+    -> HEAD_REFUSED, or the list of (field, row, n, symbol, gather) in coding order, as partition_symbol returns them:
+    partition (PARTITION_NONE, for a square block of 8x8 and up), skip, kf_y, angle_delta (directional, bsize >= BLOCK_8X8
+    IN THE ENUM'S ORDER: 4x16 and 16x4 write one), uv_mode_cfl / uv_mode, cfl_sign and cfl_alpha, angle_delta again,
+    tx_size_8x8 / tx_size.  Two symbols may name one row (equal directional modes; equal CFL signs): the second is
+    written on what the first adapted.
+    coded=True: the block as it is coded for real (encode_block_pre_cdef / encode_block_post_cdef alone), the symbols
+    r1_intra_head_commit_batch replays: without the trial's PARTITION_NONE -- the real partition symbol is the walker's
+    (src/encoder.rs:2688, 2781, 2862), the commit's partition event."""
+    if not _head_block_ok(bsize, bo_x, bo_y, mi_cols, mi_rows):
+        return HEAD_REFUSED
+    bsize, y_mode, uv_mode = int(bsize), int(y_mode), int(uv_mode)
+    if not 0 <= y_mode < 13:
+        return HEAD_REFUSED
+    w, h = BlockSize(bsize).dims
+    syms = []
+    if not coded and bsize >= _BLOCK_8X8 and w == h:
+        p = partition_symbol(nbr, bsize, bo_x, bo_y, mi_cols, mi_rows, 0)
+        if p == HEAD_REFUSED:
+            return HEAD_REFUSED
+        if p is not None:
+            syms.append(p)
+    above_skip = bo_y > 0 and bool(nbr["above_skip"][bo_x])
+    left_skip = bo_x > 0 and bool(nbr["left_skip"][bo_y % 16])
+    syms.append(("skip", int(above_skip) + int(left_skip), 2, 0, 0))
+    above_mode = int(nbr["above_mode"][bo_x]) if bo_y > 0 else 0
+    left_mode = int(nbr["left_mode"][bo_y % 16]) if bo_x > 0 else 0
+    if above_mode >= 13 or left_mode >= 13:
+        return HEAD_REFUSED
+    syms.append(("kf_y", (_INTRA_MODE_CONTEXT[above_mode], _INTRA_MODE_CONTEXT[left_mode]), 13, y_mode, 0))
+    directional = lambda m: 1 <= m <= 8                  # V_PRED ..= D67_PRED (src/predict.rs:262-264)
+    if directional(y_mode) and bsize >= _BLOCK_8X8:
+        if not -3 <= int(angle_y) <= 3:
+            return HEAD_REFUSED
+        syms.append(("angle_delta", y_mode - 1, 7, int(angle_y) + 3, 0))
+    if has_chroma_:
+        cfl_allowed = bsize <= _BLOCK_32X32              # BlockSize::cfl_allowed (src/partition.rs:228-231), enum order
+        if not 0 <= uv_mode < (14 if cfl_allowed else 13):
+            return HEAD_REFUSED
+        syms.append(("uv_mode_cfl" if cfl_allowed else "uv_mode", y_mode, 14 if cfl_allowed else 13, uv_mode, 0))
+        if uv_mode == 13:
+            au, av = int(alpha_u), int(alpha_v)
+            if (au == 0 and av == 0) or not (-16 <= au <= 16 and -16 <= av <= 16):
+                return HEAD_REFUSED
+            sign = [1 if a < 0 else (2 if a > 0 else 0) for a in (au, av)]      # CFLSign::from_alpha
+            syms.append(("cfl_sign", (), 8, sign[0] * 3 + sign[1] - 1, 0))
+            for uv, a in enumerate((au, av)):
+                if sign[uv]:
+                    syms.append(("cfl_alpha", (sign[uv] - 1) * 3 + sign[1 - uv], 16, abs(a) - 1, 0))
+        if directional(uv_mode) and bsize >= _BLOCK_8X8:
+            if not -3 <= int(angle_uv) <= 3:
+                return HEAD_REFUSED
+            syms.append(("angle_delta", uv_mode - 1, 7, int(angle_uv) + 3, 0))
+    if tx_mode_select and bsize > 0:
+        t = tx_size_symbol(nbr, bsize, bo_x, bo_y, tx_size)
+        if t == HEAD_REFUSED:
+            return HEAD_REFUSED
+        syms.append(t + (0,))
+    elif not 0 <= int(tx_size) < 19:
+        return HEAD_REFUSED
+    return syms
+
+
+def head_nbr_store(nbr, bsize, bo_x, bo_y, mi_cols, mi_rows, y_mode, tx_size, tx_mode_select, node=None):
+    """What a coded intra block (skip = false) leaves in the arrays of a types.HEAD_NBR_CONTEXT record, IN PLACE -- the
+    stores of r1_intra_head_commit_batch: set_skip / set_mode over the block's extent clipped to the tile as
+    TileBlocksMut::for_each clips (src/tiling/tile_blocks.rs:206-224), as row buffers: above_mode / above_skip [bo_x ..],
+    left_mode / left_skip [bo_y % 16 ..]; with tx_mode_select update_tx_size_context (src/context/block_unit.rs:362-386):
+    the transform's width over above_tx[bo_x .. bo_x + bw / 4], its height over left_tx[bo_y % 16 ..], clipped to the
+    arrays; node = (node_x, node_y, node_bsize, subsize): update_partition_context (partition_unit.rs:480-503) of the
+    walker's node."""
+    w, h = BlockSize(bsize).dims
+    bw4, bh4 = w >> MI_SIZE_LOG2, h >> MI_SIZE_LOG2
+    cw = mi_cols - bo_x if bo_x + bw4 >= mi_cols else bw4
+    for k in range(cw):
+        nbr["above_mode"][bo_x + k], nbr["above_skip"][bo_x + k] = int(y_mode), 0
+    for k in range(bh4):
+        if bo_y + k < mi_rows:
+            nbr["left_mode"][(bo_y + k) % 16], nbr["left_skip"][(bo_y + k) % 16] = int(y_mode), 0
+    if tx_mode_select:
+        tw, th = TxSize(tx_size).dims
+        for k in range(bw4):
+            if bo_x + k < len(nbr["above_tx"]):
+                nbr["above_tx"][bo_x + k] = tw
+        for k in range(bh4):
+            if bo_y % 16 + k < 16:
+                nbr["left_tx"][bo_y % 16 + k] = th
+    if node is not None:
+        node_x, node_y, node_bsize, subsize = node
+        nw, nh = BlockSize(node_bsize).dims
+        sw, sh = BlockSize(subsize).dims
+        # partition_context_lookup[subsize]: the bits of the sizes the sub-block is smaller than (partition_unit.rs:15-38)
+        above, left = 31 & ~((sw >> 2) - 1), 31 & ~((sh >> 2) - 1)
+        for k in range((nw >> 2) >> 1):
+            if (node_x >> 1) + k < len(nbr["above_partition"]):
+                nbr["above_partition"][(node_x >> 1) + k] = above
+        for k in range((nh >> 2) >> 1):
+            if ((node_y % 16) >> 1) + k < 8:
+                nbr["left_partition"][((node_y % 16) >> 1) + k] = left
+
+
+def head_nbr_reset_left(nbr):
+    """The head part of reset_left_contexts (src/context/block_unit.rs:356-360, 388-401), IN PLACE: the statement of
+    r1_head_nbr_reset_left_batch.  left_mode / left_skip stay: the reference's blocks array is not reset."""
+    for name in ("left_partition", "left_tx"):
+        for k in range(len(nbr[name])):
+            nbr[name][k] = 0

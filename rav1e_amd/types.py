@@ -9,6 +9,8 @@ dimensions are the reference's (src/context/transform_unit.rs:27, 200-219).  TXB
 (r1_coeff_rate_block_batch).  COEFF_CDF_CONTEXT: R1CoeffCdfContext (r1_coeff_cdf_slice_batch, r1_coeff_cdf_adapt_batch).
 COEFF_NBR_CONTEXT / NBR_BLOCK: R1CoeffNbrContext / R1NbrBlock (r1_coeff_nbr_gather_batch, r1_coeff_nbr_store_batch).
 PartitionType  src/partition.rs:114-126; PART_PICK: R1PartPick (r1_rd_partition_pick_batch, r1_part_select_batch).
+HEAD_CDF_CONTEXT / HEAD_NBR_CONTEXT / HEAD_BLOCK / HEAD_TRIAL / HEAD_COMMIT: R1HeadCdfContext / R1HeadNbrContext /
+R1HeadBlock / R1HeadTrial / R1HeadCommit (r1_intra_head_rate_batch, r1_partition_rate_batch, r1_intra_head_commit_batch).
 """
 import enum
 
@@ -190,3 +192,31 @@ PART_PICK = np.dtype([("best_rd", "<f8"), ("best_partition", "i1"), ("best_call"
                       ("reserved", "u1", (5,))])
 assert PART_PICK.itemsize == 16
 PART_BOTTOMUP, PART_TOPDOWN = 0, 1    # R1_PART_*
+# R1HeadCdfContext (r1_intra_head_rate_batch / r1_partition_rate_batch / r1_intra_head_commit_batch): the head fields of
+# the reference's CDFContext in its own shapes (src/context/cdf_context.rs:42-92), padded to a multiple of 16 bytes
+HEAD_CDF_CONTEXT = np.dtype(
+    [("partition_w8", "<u2", (4, 4)), ("partition", "<u2", (12, 10)), ("partition_w128", "<u2", (4, 8)),
+     ("skip", "<u2", (3, 2)), ("kf_y", "<u2", (5, 5, INTRA_MODES)), ("y_mode", "<u2", (4, INTRA_MODES)),
+     ("uv_mode", "<u2", (INTRA_MODES, INTRA_MODES)), ("uv_mode_cfl", "<u2", (INTRA_MODES, 14)),
+     ("angle_delta", "<u2", (8, 7)), ("cfl_sign", "<u2", (8,)), ("cfl_alpha", "<u2", (6, 16)),
+     ("tx_size_8x8", "<u2", (3, 2)), ("tx_size", "<u2", (3, 3, 3)), ("pad", "<u2", (1,))])
+# R1HeadNbrContext: what the head contexts read of BlockContext (src/context/block_unit.rs:233-236) and, as row buffers,
+# of blocks.above_of / left_of -- one per tile or speculative branch, beside COEFF_NBR_CONTEXT; a fresh tile is zeros
+HEAD_NBR_CONTEXT = np.dtype(
+    [("above_partition", "u1", (COEFF_NBR_WIDTH // 2,)), ("left_partition", "u1", (8,)),
+     ("above_tx", "u1", (COEFF_NBR_WIDTH,)), ("left_tx", "u1", (16,)), ("above_mode", "u1", (COEFF_NBR_WIDTH,)),
+     ("left_mode", "u1", (16,)), ("above_skip", "u1", (COEFF_NBR_WIDTH,)), ("left_skip", "u1", (16,))])
+assert HEAD_CDF_CONTEXT.itemsize == 2192 and HEAD_CDF_CONTEXT.itemsize % 16 == 0 and HEAD_NBR_CONTEXT.itemsize == 3640
+# R1HeadBlock / R1HeadTrial / R1HeadCommit: a block's static geometry, one mode trial of it, and what the winner's commit
+# is told of the partition walker
+HEAD_BLOCK = np.dtype([("nbr", "<u4"), ("cdf", "<u4"), ("bo_x", "<u2"), ("bo_y", "<u2"), ("mi_cols", "<u2"),
+                       ("mi_rows", "<u2"), ("bsize", "u1"), ("has_chroma", "u1"), ("tx_mode_select", "u1"),
+                       ("reserved", "u1")])
+HEAD_TRIAL = np.dtype([("block", "<u4"), ("y_mode", "u1"), ("uv_mode", "u1"), ("angle_y", "i1"), ("angle_uv", "i1"),
+                       ("alpha_u", "<i2"), ("alpha_v", "<i2"), ("tx_size", "u1"), ("reserved", "u1", (3,))])
+HEAD_COMMIT = np.dtype([("block", "<u4"), ("node_x", "<u2"), ("node_y", "<u2"), ("node_bsize", "u1"),
+                        ("part_type", "i1"), ("subsize", "u1"), ("flags", "u1"), ("reserved", "u1", (4,))])
+assert HEAD_BLOCK.itemsize == 20 and HEAD_TRIAL.itemsize == 16 and HEAD_COMMIT.itemsize == 16
+HEAD_NO_SUBSIZE = 255                 # R1HeadCommit.subsize: no update_partition_context
+HEAD_EVENT_ONLY = 1                   # R1HeadCommit.flags bit 0: the partition event alone, no block
+UV_CFL_PRED = 13                      # PredictionMode::UV_CFL_PRED (src/predict.rs)

@@ -1821,6 +1821,122 @@ int r1_intra_head_commit_batch(r1_ctx *ctx, R1HeadNbrContext *nbrs, int n_nbrs, 
 int r1_head_nbr_reset_left_batch(r1_ctx *ctx, R1HeadNbrContext *nbrs, int n_nbrs, const uint32_t *sel, int n,
                                  void *stream);
 
+/* ---- the MV reference stack of an inter block on the device (mvref.hip; added under ABI 7): the tile's blocks array
+ * and find_mvrefs / setup_mvref_list (src/context/block_unit.rs:795-1442, has_tr of src/partition.rs:900-955) over it.
+ * The stack is built from the winning mode, references and vectors of the blocks above and left -- what the device
+ * decides and the host no longer sees -- so the array lives on the device, one cell per 4x4 unit, written by
+ * r1_tile_blocks_store_batch behind every coded block and read by r1_mvref_stack_batch in front of the next.
+ * rdo_glue.find_mvrefs / has_tr / tile_blocks_store / tile_blocks_default / mvref_pmv are the statements;
+ * tests/golden/mvref_ref.npz executes the reference.  Vectors are (row, col) in 1/8 pel, as MotionVector.
+ * NOT here (the host's still): the inter head symbols and their CDFs (write_is_inter, references, write_inter_mode,
+ * write_drl_mode, write_mv); fill_neighbours_ref_counts and the reference contexts; building inter_mode_set / mvs_set
+ * and the R1RdoCand descriptors from the stack; intrabc, temporal and global-motion candidates (the reference has
+ * none: block_unit.rs:1423-1442 are TODOs); 128x128 superblocks (has_tr assumes 64x64); a select call for the blocks
+ * array across partition branches -- a speculative branch is the caller's device copy of the array, as for the
+ * other three carried contexts. */
+#define R1_INTRA_FRAME 0          /* RefType discriminants (src/partition.rs) */
+#define R1_NONE_FRAME 8
+#define R1_NEARESTMV 14           /* Block::is_inter: mode >= NEARESTMV */
+#define R1_MVREF_MAX_TILES 64     /* R1TileBlocks descriptors per call (they travel in the launch's arguments) */
+#define R1_MVREF_MAX_QUERIES 64   /* queries per block: one lane each */
+#define R1_MVREF_REFUSED 0xFF     /* R1MvStack.count of a query the device refuses */
+typedef struct R1TileBlock {      /* 16 bytes: Block (src/context/block_unit.rs:159-183) as far as the stack and the
+                                   * inter head contexts read it */
+  int16_t mv[2][2];               /* [list][row, col] */
+  uint8_t ref_frames[2];          /* RefType discriminants */
+  uint8_t mode;                   /* PredictionMode discriminant */
+  uint8_t n4_w, n4_h;             /* the coded block's sides in 4x4 units: the scans step by them */
+  uint8_t bsize;                  /* carried for intra_inter_context and the reference-count contexts: only stored */
+  uint8_t skip;                   /* likewise */
+  uint8_t reserved;
+} R1TileBlock;
+typedef struct R1TileBlocks {     /* HOST descriptor of one tile's (or branch's) array */
+  R1TileBlock *cells;             /* DEVICE, 16-byte aligned: cell (x, y) at cells[y * stride + x] */
+  int32_t stride;                 /* cells per row, >= cols */
+  int32_t cols, rows;             /* the tile's blocks.cols() / rows() */
+  int32_t tile_x, tile_y;         /* the tile's origin in the frame, 4x4 units: blocks.x() / y() */
+  int32_t frame_cols, frame_rows; /* blocks.frame_cols() / frame_rows(): the final clamp reads the last four */
+  int32_t reserved;
+} R1TileBlocks;
+typedef struct R1MvBlock {        /* 16 bytes: one block and where its queries lie */
+  uint32_t tile;                  /* index into the descriptors */
+  uint16_t bo_x, bo_y;            /* tile-relative, 4x4 units */
+  uint8_t bsize;                  /* BlockSize, sides up to 64 */
+  uint8_t n_queries;              /* queries[query_off .. query_off + n_queries) are this block's; 0 is allowed */
+  uint16_t reserved;
+  uint32_t query_off;
+} R1MvBlock;
+typedef struct R1MvQuery {
+  uint32_t block;                 /* the R1MvBlock that lists it */
+  uint8_t ref_frames[2];
+  uint8_t is_compound;
+  uint8_t reserved;
+} R1MvQuery;
+typedef struct R1CandidateMv {    /* CandidateMV, 12 bytes */
+  int16_t this_mv[2], comp_mv[2];
+  uint32_t weight;
+} R1CandidateMv;
+typedef struct R1MvStack {        /* 112 bytes */
+  uint8_t count;                  /* 0 .. 9 entries, sorted by descending weight, ties in insertion order */
+  uint8_t reserved;
+  uint16_t mode_context;
+  R1CandidateMv cand[9];          /* entries at and past count are written as zero */
+} R1MvStack;
+typedef struct R1MvTrial {        /* 16 bytes: what one trial would leave in the array were it the winner */
+  uint32_t block;                 /* index into the R1MvBlock array */
+  uint8_t mode, ref_frames[2], skip;
+  int16_t mv[2][2];
+} R1MvTrial;
+/* Block::default() (block_unit.rs:194-211) over the whole of arrays tiles[sel[i]], i < n (rows x stride cells each, the
+ * row padding included): DC_PRED, both references INTRA_FRAME, zero vectors, n4_w = n4_h = 16, BLOCK_64X64, skip 0.
+ * A zeroed array is NOT a fresh tile: the scans step by a cell's n4_w / n4_h.  sel: HOST indices, or NULL for every
+ * descriptor (then n == n_tiles).
+ * R1_EINVAL: a NULL ctx or tiles; n_tiles outside 1..R1_MVREF_MAX_TILES; a descriptor with NULL or unaligned cells,
+ * cols or rows < 1, stride < cols, cols or stride > 1024, rows > 65535, negative tile_x / tile_y, frame_cols <
+ * tile_x + cols or frame_rows < tile_y + rows, frame_cols or frame_rows above 2^20; n < 0; a sel[i] outside the descriptors.  n == 0 returns 0. */
+int r1_tile_blocks_reset_batch(r1_ctx *ctx, const R1TileBlocks *tiles, int n_tiles, const int32_t *sel, int n, void *stream);
+/* What a coded block leaves in its tile's array: set_skip (src/encoder.rs:1900), set_block_size, set_mode,
+ * set_ref_frames, set_motion_vectors (1968-1972) over the block's extent clipped as TileBlocksMut::for_each clips
+ * (src/tiling/tile_blocks.rs:206-224): the width is cut to the tile where bo_x + bw >= cols, rows past the tile are
+ * left out.  Every cell outside the extent stays bit-identical.
+ * Gating as r1_intra_head_commit_batch: state s of n acts when state[s].best_call == call_id, on trial
+ * t = (s * group + best_row) * nt + best_slot; with state == NULL every s acts on trial s (n <= n_trials).  The trial
+ * names its block.  An intra winner (mode < NEARESTMV) stores its mode, {INTRA_FRAME, NONE_FRAME} and zero vectors
+ * whatever the trial holds.  Acting states must name disjoint extents.  tiles: HOST; blocks, trials, state: DEVICE.
+ * Nothing is written for a state whose trial or block index is out of range, whose best_row / best_slot lie outside
+ * group / nt, whose block has a bsize past the enum or with a 128-point side, names no descriptor or lies outside its
+ * tile, or whose mode is past NEW_NEWMV (33).
+ * R1_EINVAL: the descriptor cases above; a NULL blocks or trials; n < 0, n_blocks < 1, n_trials < 1; call_id outside
+ * 0..127; group outside 1..4096; nt outside 1..16; state == NULL with n > n_trials.  n == 0 returns 0. */
+int r1_tile_blocks_store_batch(r1_ctx *ctx, const R1TileBlocks *tiles, int n_tiles, const R1MvBlock *blocks, int n_blocks,
+                               const R1MvTrial *trials, int n_trials, const R1RdPick *state, int n, int call_id,
+                               int group, int nt, void *stream);
+/* find_mvrefs for every query of n_blocks blocks: stacks_out[query_off + q] for q < n_queries of each block, whole
+ * structs.  sign_bias: HOST, 8 bytes: fi.ref_frame_sign_bias, entry r - 1 for reference r (RefType::to_index); entry 7
+ * is not read.  A query with ref_frames[0] == INTRA_FRAME returns count 0 and context 0, as the reference.
+ * One wave per block: the wave stages the block's neighbourhood (rows -1 .. -5 over its columns and one to the right,
+ * columns -1 .. -5 over its rows and one below, the top-left cell; at most 171 cells) in LDS, one 16-byte cell per lane
+ * and load, and lane q walks query q from there.
+ * The device refuses a query -- count = R1_MVREF_REFUSED and nothing else of the struct written -- where: the block
+ * names no descriptor; its bsize is past the enum or has a 128-point side; it lies outside its tile; it has more than
+ * max_queries queries; the query's `block` is not the block that lists it; ref_frames[0] == NONE_FRAME; a reference
+ * above NONE_FRAME; a compound query whose second reference is INTRA_FRAME or NONE_FRAME; the walk reads a cell whose
+ * n4_w or n4_h is 0, not a power of two or above 16, or -- in the extra search -- one with a reference above NONE_FRAME;
+ * or where the reference would panic on such a state (a scan that indexes past cols or rows, assert!(inc >= 0)).  The
+ * device reads nothing outside the arrays; a query index at or past n_queries is not written at all.
+ * R1_EINVAL: the descriptor cases above; a NULL blocks, queries, sign_bias or stacks_out; a stacks_out that is not
+ * 4-byte aligned; n_blocks < 0; n_queries < 1;
+ * max_queries outside 1..R1_MVREF_MAX_QUERIES.  n_blocks == 0 returns 0. */
+int r1_mvref_stack_batch(r1_ctx *ctx, const R1TileBlocks *tiles, int n_tiles, const R1MvBlock *blocks, int n_blocks,
+                         const R1MvQuery *queries, int n_queries, int max_queries, const uint8_t *sign_bias,
+                         R1MvStack *stacks_out, void *stream);
+/* The stack's hand-over to the block motion search (src/rdo.rs:1175-1181): for q < n, at
+ * (int16_t *)((char *)pmv_out + q * stride): pmv[0] = cand[0].this_mv if count > 0 else zero, pmv[1] = cand[1].this_mv if
+ * count > 1 else zero -- four int16.  With pmv_out = &cands[0].pmv and stride = sizeof(R1MeBlockCand) it fills the
+ * array r1_estimate_motion_batch then runs on.  A refused stack writes nothing.
+ * R1_EINVAL: a NULL ctx, stacks or pmv_out; n < 0; a pmv_out or stride that is odd; stride < 8.  n == 0 returns 0. */
+int r1_mvref_pmv_batch(r1_ctx *ctx, const R1MvStack *stacks, int n, void *pmv_out, long long stride, void *stream);
+
 /* ---- multi-GPU: the tile-boundary exchange and the reference-frame all-gather (RCCL over
  * xGMI), SURVEY.md 8(e).  One process (or host thread) per GPU, tile r on rank r.  Rendezvous:
  * rank 0 calls r1_comm_unique_id and hands the 128 bytes to the other ranks by any channel the

@@ -194,6 +194,10 @@ SYMBOLS = {
     "r1_intra_head_commit_batch": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp,
                                         _vp]),
     "r1_head_nbr_reset_left_batch": (_i, [_vp, _vp, _i, _vp, _i, _vp]),
+    "r1_tile_blocks_reset_batch": (_i, [_vp, _vp, _i, _vp, _i, _vp]),
+    "r1_tile_blocks_store_batch": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
+    "r1_mvref_stack_batch": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    "r1_mvref_pmv_batch": (_i, [_vp, _vp, _i, _vp, C.c_longlong, _vp]),
     "r1_lrf_sgrproj_plane": (_i, [_vp, _PP, _PP, _PP, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "r1_sgrproj_solve_batch": (_i, [_vp, _PP, _PP, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "r1_lrf_search_batch": (_i, [_vp, _PP, _PP, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, C.c_uint32, _vp, _vp, _vp, _vp]),

@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 from .types import (BLOCK_CHAIN_CTX, BLOCK_RATE_TRIAL, COEFF_CDF_CONTEXT, COEFF_CDFS, COEFF_RATE_INVALID, PICK_FIRST_MIN, PICK_TX_TYPE,  # noqa: F401
-                    COEFF_NBR_CONTEXT, HEAD_BLOCK, HEAD_CDF_CONTEXT, HEAD_COMMIT, HEAD_NBR_CONTEXT, HEAD_TRIAL, NBR_BLOCK, PART_BOTTOMUP, PART_PICK, PART_TOPDOWN, RD_PICK, TX_DIMS, TXB_CHAIN_CTX, TXB_CTX, TxSize, valid_av1_transform)
+                    COEFF_NBR_CONTEXT, HEAD_BLOCK, HEAD_CDF_CONTEXT, HEAD_COMMIT, HEAD_NBR_CONTEXT, HEAD_TRIAL, MV_BLOCK, MV_QUERY, MV_STACK, MV_TRIAL, MVREF_MAX_QUERIES, MVREF_MAX_TILES, NBR_BLOCK, PART_BOTTOMUP, PART_PICK, PART_TOPDOWN, RD_PICK, TILE_BLOCK, TILE_BLOCKS, TX_DIMS, TXB_CHAIN_CTX, TXB_CTX, TxSize, valid_av1_transform)
 
 DIST_CAND = np.dtype([("ox", "<i2"), ("oy", "<i2"), ("rx", "<i2"), ("ry", "<i2")])
 MC_CAND = np.dtype([("rx", "<i2"), ("ry", "<i2"), ("col_frac", "u1"), ("row_frac", "u1"),
@@ -1572,6 +1572,101 @@ class Context:
             self.h, nbrs.data_ptr(), nbrs.numel() // HEAD_NBR_CONTEXT.itemsize, sel.data_ptr(), sel.numel(), _stream_ptr()),
             "r1_head_nbr_reset_left_batch")
         return nbrs
+
+    # ---- the MV reference stack and the tile's blocks array ----
+    @staticmethod
+    def tile_blocks(cols, rows, tile_x=0, tile_y=0, frame_cols=None, frame_rows=None, stride=None, cells=None):
+        """One tile's (or branch's) blocks array: a dict with `cells`, a uint8 device tensor of rows * stride TILE_BLOCK
+        records -- NOT initialised (tile_blocks_reset_batch) unless handed in -- and the fields of R1TileBlocks."""
+        stride = cols if stride is None else int(stride)
+        if cells is None:
+            cells = torch.empty(rows * stride * TILE_BLOCK.itemsize, dtype=torch.uint8, device="cuda")
+        return {"cells": cells, "stride": stride, "cols": int(cols), "rows": int(rows), "tile_x": int(tile_x),
+                "tile_y": int(tile_y), "frame_cols": int(tile_x + cols if frame_cols is None else frame_cols),
+                "frame_rows": int(tile_y + rows if frame_rows is None else frame_rows)}
+
+    @staticmethod
+    def _tile_descs(tiles):
+        """tile_blocks dicts -> the HOST R1TileBlocks array of the C calls"""
+        if len(tiles) > MVREF_MAX_TILES:
+            raise ValueError("at most %d blocks arrays per call" % MVREF_MAX_TILES)
+        d = np.zeros(len(tiles), TILE_BLOCKS)
+        for k, t in enumerate(tiles):
+            c = t["cells"]
+            assert c.is_cuda and c.is_contiguous() and c.element_size() == 1
+            assert c.numel() >= t["rows"] * t["stride"] * TILE_BLOCK.itemsize
+            d[k] = (c.data_ptr(), t["stride"], t["cols"], t["rows"], t["tile_x"], t["tile_y"], t["frame_cols"],
+                    t["frame_rows"], 0)
+        return d
+
+    def tile_blocks_reset_batch(self, tiles, sel=None):
+        """r1_tile_blocks_reset_batch: Block::default() over the whole arrays tiles[sel[i]] (every one without sel) --
+        rdo_glue.tile_blocks_default on the device"""
+        d = self._tile_descs(tiles)
+        s = None if sel is None else np.ascontiguousarray(sel, dtype=np.int32)
+        self._check(self.lib.r1_tile_blocks_reset_batch(
+            self.h, d.ctypes.data, len(d), None if s is None else s.ctypes.data, len(d) if s is None else s.size,
+            _stream_ptr()), "r1_tile_blocks_reset_batch")
+        return tiles
+
+    def tile_blocks_store_batch(self, tiles, blocks, trials, state=None, call_id=0, group=1, nt=1, n=None):
+        """r1_tile_blocks_store_batch: what the winners leave in their arrays -- rdo_glue.tile_blocks_store on the device.
+        blocks: MV_BLOCK records; trials: MV_TRIAL records; state: RD_PICK records (state s acts when its best_call ==
+        call_id, on trial (s * group + best_row) * nt + best_slot), or None: desc s acts on trial s."""
+        d = self._tile_descs(tiles)
+        db, n_blocks = _dev_cands(blocks, MV_BLOCK)
+        dt, n_trials = _dev_cands(trials, MV_TRIAL)
+        if state is not None:
+            n = _rd_pick_states(state, n)
+        elif n is None:
+            n = n_trials
+        self._check(self.lib.r1_tile_blocks_store_batch(
+            self.h, d.ctypes.data, len(d), db.data_ptr(), n_blocks, dt.data_ptr(), n_trials,
+            None if state is None else state.data_ptr(), n, int(call_id), int(group), int(nt), _stream_ptr()),
+            "r1_tile_blocks_store_batch")
+        return tiles
+
+    def mvref_stack_batch(self, tiles, blocks, queries, sign_bias, out=None, max_queries=None):
+        """r1_mvref_stack_batch: find_mvrefs for every query of every block -- rdo_glue.find_mvrefs on the device, one
+        wave per block.  blocks: MV_BLOCK records (query_off / n_queries name each block's run of `queries`, MV_QUERY
+        records); sign_bias: fi.ref_frame_sign_bias, entry r - 1 for reference r.  Host arrays are checked here: a block
+        with more than 64 queries is refused (ValueError); device arrays need max_queries.
+        -> a uint8 device tensor of MV_STACK records, one per query (count 0xFF: the device refused the query)"""
+        d = self._tile_descs(tiles)
+        if not isinstance(blocks, torch.Tensor):
+            blocks = np.ascontiguousarray(blocks, dtype=MV_BLOCK)
+            most = int(blocks["n_queries"].max()) if blocks.size else 1
+            if most > MVREF_MAX_QUERIES:
+                raise ValueError("a block has %d queries: at most %d (one lane each)" % (most, MVREF_MAX_QUERIES))
+            if max_queries is None:
+                max_queries = max(most, 1)
+        if max_queries is None:
+            max_queries = MVREF_MAX_QUERIES
+        db, n_blocks = _dev_cands(blocks, MV_BLOCK)
+        dq, n_queries = _dev_cands(queries, MV_QUERY)
+        if out is None:
+            out = torch.empty(n_queries * MV_STACK.itemsize, dtype=torch.uint8, device="cuda")
+        assert out.is_cuda and out.is_contiguous() and out.numel() >= n_queries * MV_STACK.itemsize
+        bias = np.zeros(8, np.uint8)
+        sb = np.asarray(sign_bias).astype(np.uint8).reshape(-1)
+        bias[:min(sb.size, 8)] = sb[:8]
+        self._check(self.lib.r1_mvref_stack_batch(
+            self.h, d.ctypes.data, len(d), db.data_ptr(), n_blocks, dq.data_ptr(), n_queries, int(max_queries),
+            bias.ctypes.data, out.data_ptr(), _stream_ptr()), "r1_mvref_stack_batch")
+        return out
+
+    def mvref_pmv_batch(self, stacks, pmv_out, stride, offset=0, n=None):
+        """r1_mvref_pmv_batch: pmv[0], pmv[1] of stack q (rdo_glue.mvref_pmv) at byte offset + q * stride of the uint8
+        device tensor pmv_out -- offset 8 and stride 16 fill the pmv of an ME_BLOCK_CAND array.  A refused stack writes
+        nothing."""
+        assert stacks.is_cuda and stacks.is_contiguous() and stacks.element_size() == 1
+        assert pmv_out.is_cuda and pmv_out.is_contiguous() and pmv_out.element_size() == 1
+        if n is None:
+            n = stacks.numel() // MV_STACK.itemsize
+        assert n == 0 or (offset >= 0 and offset + (n - 1) * stride + 8 <= pmv_out.numel())
+        self._check(self.lib.r1_mvref_pmv_batch(self.h, stacks.data_ptr(), n, pmv_out.data_ptr() + int(offset), int(stride),
+                                                _stream_ptr()), "r1_mvref_pmv_batch")
+        return pmv_out
 
     # ---- lrf:: ----
     def lrf_sgrproj_plane(self, cdeffed, deblocked, out, ydec, crop_w, crop_h, frame_height, unit_size,

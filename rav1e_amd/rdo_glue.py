@@ -61,8 +61,17 @@ the kernels by executing the reference's own text (tests/golden/gen_rdo_glue_ref
                              the host statements of r1_intra_head_rate_batch, r1_partition_rate_batch,
                              r1_intra_head_commit_batch and r1_head_nbr_reset_left_batch; pinned by
                              tests/golden/head_ref.npz / tests/test_head_ref.py
+  find_mvrefs                src/context/block_unit.rs:795-1442 (setup_mvref_list and everything it calls)
+  has_tr                     src/partition.rs:900-955 (has_top_right above is the intra edge rule: another rule)
+  tile_blocks_store / tile_blocks_default   src/tiling/tile_blocks.rs:206-277, src/context/block_unit.rs:194-211
+  mvref_pmv                  src/rdo.rs:1175-1181
+                             the host statements of r1_mvref_stack_batch, r1_tile_blocks_store_batch,
+                             r1_tile_blocks_reset_batch and r1_mvref_pmv_batch; pinned by
+                             tests/golden/mvref_ref.npz / tests/test_mvref_ref.py
 """
-from .types import BlockSize, TxSize
+import numpy as np
+
+from .types import TILE_BLOCK, BlockSize, TxSize
 
 MI_SIZE_LOG2 = 2
 DIST_SCALE_SHIFT = 14
@@ -946,3 +955,262 @@ def head_nbr_reset_left(nbr):
     for name in ("left_partition", "left_tx"):
         for k in range(len(nbr[name])):
             nbr[name][k] = 0
+
+
+# ---- the MV reference stack of an inter block (r1_mvref_stack_batch, r1_mvref_pmv_batch) and the tile's blocks array it
+# is built from (r1_tile_blocks_reset_batch, r1_tile_blocks_store_batch); pinned by tests/golden/mvref_ref.npz /
+# tests/test_mvref_ref.py.  A tile is a dict: `cells`, a (rows, cols) array of types.TILE_BLOCK, and tile_x, tile_y,
+# frame_cols, frame_rows in 4x4 units.
+MV_REFUSED = "refused"      # what the device answers with count 0xFF (the reference would panic, or the ABI is left)
+INTRA_FRAME, NONE_FRAME = 0, 8
+NEARESTMV = 14              # Block::is_inter: mode >= NEARESTMV (src/context/block_unit.rs:186-188)
+REF_CAT_LEVEL = 640
+MAX_REF_MV_STACK_SIZE = 8
+_NEWMV_MODES = frozenset((19, 24, 25, 26, 27, 28, 29, 30, 31, 33))      # PredictionMode::has_newmv (src/predict.rs:173-184)
+_BLOCK_64X64 = 12
+
+
+def tile_blocks_default(rows, cols):
+    """Block::default() (src/context/block_unit.rs:194-211) over a fresh array: the statement of
+    r1_tile_blocks_reset_batch"""
+    cells = np.zeros((rows, cols), TILE_BLOCK)
+    cells["n4_w"], cells["n4_h"], cells["bsize"] = 16, 16, _BLOCK_64X64
+    return cells
+
+
+def tile_blocks_store(tile, bo_x, bo_y, bsize, mode, ref_frames, mvs, skip):
+    """What a coded block leaves in the tile's blocks array, IN PLACE: set_skip, set_block_size, set_mode, set_ref_frames
+    and set_motion_vectors (src/encoder.rs:1900, 1968-1972) over the block's extent clipped as TileBlocksMut::for_each
+    clips it (src/tiling/tile_blocks.rs:206-224): the width is cut to the tile where bo_x + bw >= cols, rows past the tile
+    are left out.  An intra winner (mode < NEARESTMV) stores {INTRA_FRAME, NONE_FRAME} and zero vectors.  The statement
+    of r1_tile_blocks_store_batch."""
+    cells = tile["cells"]
+    rows, cols = cells.shape
+    w, h = BlockSize(bsize).dims
+    bw, bh = w >> MI_SIZE_LOG2, h >> MI_SIZE_LOG2
+    if int(mode) < NEARESTMV:
+        ref_frames, mvs = (INTRA_FRAME, NONE_FRAME), ((0, 0), (0, 0))
+    cw = cols - bo_x if bo_x + bw >= cols else bw
+    for y in range(bo_y, bo_y + bh):
+        if y >= rows:
+            continue
+        for x in range(bo_x, bo_x + cw):
+            c = cells[y, x]
+            c["mv"], c["ref_frames"], c["mode"] = mvs, ref_frames, int(mode)
+            c["n4_w"], c["n4_h"], c["bsize"], c["skip"] = bw, bh, int(bsize), int(bool(skip))
+
+
+def has_tr(bo_x, bo_y, bsize):
+    """has_tr (src/partition.rs:900-955): whether the block's top-right neighbour is coded before it, by its place in a
+    64x64 superblock.  (has_top_right above is the intra edge rule: another rule.)"""
+    w, h = BlockSize(bsize).dims
+    n4_w, n4_h = w >> MI_SIZE_LOG2, h >> MI_SIZE_LOG2
+    mask_row, mask_col = bo_y & (SB_MI - 1), bo_x & (SB_MI - 1)
+    bs = max(n4_w, n4_h)
+    if bs > SB_MI:
+        return False
+    tr = not ((mask_row & bs) != 0 and (mask_col & bs) != 0)
+    while bs < SB_MI:
+        if (mask_col & bs) == 0:
+            break
+        if (mask_col & (2 * bs)) != 0 and (mask_row & (2 * bs)) != 0:
+            tr = False
+            break
+        bs <<= 1
+    if n4_w < n4_h and (bo_x & n4_w) == 0:      # the left of two vertical rectangles
+        tr = True
+    if n4_w > n4_h and (bo_y & n4_h) != 0:      # the bottom of two horizontal rectangles
+        tr = False
+    return tr
+
+
+class _MvRefused(Exception):
+    pass
+
+
+def find_mvrefs(tile, bo_x, bo_y, bsize, ref_frames, is_compound, sign_bias):
+    """find_mvrefs / setup_mvref_list (src/context/block_unit.rs:795-1442): the statement of r1_mvref_stack_batch.
+    sign_bias: fi.ref_frame_sign_bias, entry r - 1 for reference r (RefType::to_index).
+    -> MV_REFUSED, or (mode_context, [(this_row, this_col, comp_row, comp_col, weight), ..]) sorted by descending weight,
+    ties in insertion order, at most 9 entries, the vectors clamped around the block's place IN THE FRAME."""
+    cells = tile["cells"]
+    rows, cols = cells.shape
+    r0, r1 = int(ref_frames[0]), int(ref_frames[1])
+    is_compound = bool(is_compound)
+    if not 0 <= int(bsize) < 22 or max(BlockSize(bsize).dims) > 64 or not (0 <= bo_x < cols <= 1024 and 0 <= bo_y < rows):
+        return MV_REFUSED
+    if r0 == NONE_FRAME or r0 > NONE_FRAME or r1 > NONE_FRAME or (is_compound and r1 in (INTRA_FRAME, NONE_FRAME)):
+        return MV_REFUSED
+    if r0 == INTRA_FRAME:
+        return 0, []
+    w, h = BlockSize(bsize).dims
+    n4_w, n4_h = w >> MI_SIZE_LOG2, h >> MI_SIZE_LOG2
+    stack = []                                   # [this_row, this_col, comp_row, comp_col, weight]
+    st = {"rows": 0, "cols": 0, "newmv": 0}
+    wrap = lambda v: ((v + 0x8000) & 0xFFFF) - 0x8000                           # i16, as the device negates
+    neg = lambda mv: (wrap(-mv[0]), wrap(-mv[1]))
+
+    def cell(x, y):
+        if not (0 <= x < cols and 0 <= y < rows):
+            raise _MvRefused                     # the reference indexes past the row (it panics)
+        c = cells[y, x]
+        if int(c["n4_w"]) not in (1, 2, 4, 8, 16) or int(c["n4_h"]) not in (1, 2, 4, 8, 16):
+            raise _MvRefused
+        return c
+
+    def add_ref_mv_candidate(c, weight, count_key):
+        if int(c["mode"]) < NEARESTMV:
+            return False
+        refs = (int(c["ref_frames"][0]), int(c["ref_frames"][1]))
+        mvs = [(int(c["mv"][i][0]), int(c["mv"][i][1])) for i in range(2)]
+        newmv = int(c["mode"]) in _NEWMV_MODES
+        if is_compound:
+            if refs != (r0, r1):
+                return False
+            keys = [mvs[0] + mvs[1]]
+        else:
+            keys = [mvs[i] + (0, 0) for i in range(2) if refs[i] == r0]
+        for key in keys:
+            n = 4 if is_compound else 2          # a single search compares this_mv alone
+            for e in stack:
+                if tuple(e[:n]) == key[:n]:
+                    e[4] += weight
+                    break
+            else:
+                if len(stack) < MAX_REF_MV_STACK_SIZE:
+                    stack.append(list(key) + [weight])
+            if newmv and count_key:
+                st[count_key] += 1
+        return bool(keys)
+
+    def scan(horizontal, offset, max_offs, count_key):
+        """scan_row_mbmi (horizontal) / scan_col_mbmi: 967-1097"""
+        target, other_n4 = (n4_w, "n4_h") if horizontal else (n4_h, "n4_w")
+        along_n4 = "n4_w" if horizontal else "n4_h"
+        pos, room = (bo_x, cols - bo_x) if horizontal else (bo_y, rows - bo_y)
+        end_mi = min(target, room, 16)
+        shift = 0
+        if abs(offset) > 1:
+            shift = 1
+            if (pos & 1) and target < 2:
+                shift -= 1
+        found = False
+        i = 0
+        while i < end_mi:
+            c = cell(bo_x + shift + i, bo_y + offset) if horizontal else cell(bo_x + offset, bo_y + shift + i)
+            n4 = int(c[along_n4])
+            length = min(target, n4)
+            if target >= 16:
+                length = max(4, length)
+            elif abs(offset) > 1:
+                length = max(length, 2)
+            weight = 2
+            if 2 <= target <= n4:
+                inc = min(-max_offs + offset + 1, int(c[other_n4]))
+                if inc < 0:
+                    raise _MvRefused             # assert!(inc >= 0)
+                weight = max(weight, inc)
+                st["rows" if horizontal else "cols"] = inc - offset - 1
+            if add_ref_mv_candidate(c, length * weight, count_key):
+                found = True
+            i += length
+        return found
+
+    def scan_blk(x, y, count_key):
+        if x >= cols or y >= rows:
+            return False
+        return add_ref_mv_candidate(cell(x, y), 4, count_key)
+
+    try:
+        row_adj, col_adj = int(n4_h < 2 and (bo_y & 1)), int(n4_w < 2 and (bo_x & 1))
+        up_avail, left_avail = bo_y > 0, bo_x > 0
+        max_row_offs = max_col_offs = 0
+        if up_avail:
+            max_row_offs = (-4 if n4_h < 2 else -6) + row_adj
+            max_row_offs = min(max(max_row_offs, -bo_y), rows - bo_y - 1)       # find_valid_row_offs
+        if left_avail:
+            max_col_offs = (-4 if n4_w < 2 else -6) + col_adj
+            max_col_offs = min(max(max_col_offs, -bo_x), cols - bo_x - 1)
+        row_match = col_match = False
+        if abs(max_row_offs) >= 1:
+            row_match |= scan(True, -1, max_row_offs, "newmv")
+        if abs(max_col_offs) >= 1:
+            col_match |= scan(False, -1, max_col_offs, "newmv")
+        if has_tr(bo_x, bo_y, bsize) and bo_y > 0:
+            row_match |= scan_blk(bo_x + n4_w, bo_y - 1, "newmv")
+        nearest_match = int(row_match) + int(col_match)
+        for e in stack:                                                        # add_offset
+            e[4] += REF_CAT_LEVEL
+        if bo_x > 0 and bo_y > 0:
+            row_match |= scan_blk(bo_x - 1, bo_y - 1, None)
+        for idx in (2, 3):
+            row_offset, col_offset = -2 * idx + 1 + row_adj, -2 * idx + 1 + col_adj
+            if abs(row_offset) <= abs(max_row_offs) and abs(row_offset) > st["rows"]:
+                row_match |= scan(True, row_offset, max_row_offs, None)
+            if abs(col_offset) <= abs(max_col_offs) and abs(col_offset) > st["cols"]:
+                col_match |= scan(False, col_offset, max_col_offs, None)
+        total_match = int(row_match) + int(col_match)
+        newmv = min(st["newmv"], 1)
+        if nearest_match == 0:
+            mode_context = min(total_match, 1) + (total_match << 4)
+        elif nearest_match == 1:
+            mode_context = 3 - newmv + ((2 + total_match) << 4)
+        else:
+            mode_context = 5 - newmv + (5 << 4)
+        stack.sort(key=lambda e: -e[4])                                        # sort_by: stable, descending weight
+        if len(stack) < 2:                                                     # 7.10.2.12, the extra search
+            num4x4 = min(n4_w, 16, cols - bo_x, n4_h, rows - bo_y)
+            id_mvs, diff_mvs = ([], []), ([], [])
+            for pas in range(int(not up_avail), int(left_avail) + 1):
+                idx = 0
+                while idx < num4x4 and len(stack) < 2:
+                    c = cell(bo_x + idx, bo_y - 1) if pas == 0 else cell(bo_x - 1, bo_y + idx)
+                    for k in range(2):
+                        cand_ref = int(c["ref_frames"][k])
+                        if cand_ref in (INTRA_FRAME, NONE_FRAME):
+                            continue
+                        if cand_ref > NONE_FRAME:
+                            raise _MvRefused                                   # to_index past ref_frame_sign_bias
+                        mv = (int(c["mv"][k][0]), int(c["mv"][k][1]))
+                        if is_compound:
+                            for lst, want in enumerate((r0, r1)):
+                                if cand_ref == want and len(id_mvs[lst]) < 2:
+                                    id_mvs[lst].append(mv)
+                                elif len(diff_mvs[lst]) < 2:
+                                    flip = bool(sign_bias[cand_ref - 1]) != bool(sign_bias[want - 1])
+                                    diff_mvs[lst].append(neg(mv) if flip else mv)
+                        else:
+                            if bool(sign_bias[cand_ref - 1]) != bool(sign_bias[r0 - 1]):
+                                mv = neg(mv)
+                            if all((e[0], e[1]) != mv for e in stack):
+                                stack.append([mv[0], mv[1], 0, 0, 2])
+                    idx += int(c["n4_w"]) if pas == 0 else int(c["n4_h"])
+            if is_compound:
+                combined = [[(0, 0), (0, 0)], [(0, 0), (0, 0)]]
+                for lst in range(2):
+                    both = (id_mvs[lst] + diff_mvs[lst])[:2]
+                    for k, mv in enumerate(both):
+                        combined[k][lst] = mv
+                if len(stack) == 1:
+                    first = combined[0][0] + combined[0][1]
+                    pick = combined[1] if tuple(stack[0][:4]) == first else combined[0]
+                    stack.append(list(pick[0] + pick[1]) + [2])
+                else:
+                    for k in range(2):
+                        stack.append(list(combined[k][0] + combined[k][1]) + [2])
+    except _MvRefused:
+        return MV_REFUSED
+    fx, fy = int(tile["tile_x"]) + bo_x, int(tile["tile_y"]) + bo_y            # the clamp is on the frame's coordinates
+    border_w, border_h = 128 + w * 8, 128 + h * 8
+    x_min, x_max = -fx * 32 - border_w, (int(tile["frame_cols"]) - fx - n4_w) * 32 + border_w
+    y_min, y_max = -fy * 32 - border_h, (int(tile["frame_rows"]) - fy - n4_h) * 32 + border_h
+    out = []
+    for e in stack:
+        out.append((min(max(e[0], y_min), y_max), min(max(e[1], x_min), x_max),
+                    min(max(e[2], y_min), y_max), min(max(e[3], x_min), x_max), e[4]))
+    return mode_context, out
+
+
+def mvref_pmv(stack):
+    """pmv of estimate_motion from a stack (src/rdo.rs:1175-1181): the statement of r1_mvref_pmv_batch"""
+    return tuple((stack[k][0], stack[k][1]) if len(stack) > k else (0, 0) for k in range(2))

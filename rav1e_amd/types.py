@@ -11,6 +11,8 @@ COEFF_NBR_CONTEXT / NBR_BLOCK: R1CoeffNbrContext / R1NbrBlock (r1_coeff_nbr_gath
 PartitionType  src/partition.rs:114-126; PART_PICK: R1PartPick (r1_rd_partition_pick_batch, r1_part_select_batch).
 HEAD_CDF_CONTEXT / HEAD_NBR_CONTEXT / HEAD_BLOCK / HEAD_TRIAL / HEAD_COMMIT: R1HeadCdfContext / R1HeadNbrContext /
 R1HeadBlock / R1HeadTrial / R1HeadCommit (r1_intra_head_rate_batch, r1_partition_rate_batch, r1_intra_head_commit_batch).
+TILE_BLOCK / TILE_BLOCKS / MV_BLOCK / MV_QUERY / CANDIDATE_MV / MV_STACK / MV_TRIAL: R1TileBlock / R1TileBlocks / R1MvBlock /
+R1MvQuery / R1CandidateMv / R1MvStack / R1MvTrial (r1_tile_blocks_*_batch, r1_mvref_stack_batch, r1_mvref_pmv_batch).
 """
 import enum
 
@@ -220,3 +222,21 @@ assert HEAD_BLOCK.itemsize == 20 and HEAD_TRIAL.itemsize == 16 and HEAD_COMMIT.i
 HEAD_NO_SUBSIZE = 255                 # R1HeadCommit.subsize: no update_partition_context
 HEAD_EVENT_ONLY = 1                   # R1HeadCommit.flags bit 0: the partition event alone, no block
 UV_CFL_PRED = 13                      # PredictionMode::UV_CFL_PRED (src/predict.rs)
+
+# R1TileBlock: one 4x4 unit of a tile's blocks array (Block, src/context/block_unit.rs:159-183, as far as find_mvrefs and
+# the inter head contexts read it); R1TileBlocks: the host descriptor of one array; the records of r1_mvref_stack_batch
+TILE_BLOCK = np.dtype([("mv", "<i2", (2, 2)), ("ref_frames", "u1", (2,)), ("mode", "u1"), ("n4_w", "u1"), ("n4_h", "u1"),
+                       ("bsize", "u1"), ("skip", "u1"), ("reserved", "u1")])
+TILE_BLOCKS = np.dtype([("cells", "<u8"), ("stride", "<i4"), ("cols", "<i4"), ("rows", "<i4"), ("tile_x", "<i4"),
+                        ("tile_y", "<i4"), ("frame_cols", "<i4"), ("frame_rows", "<i4"), ("reserved", "<i4")])
+MV_BLOCK = np.dtype([("tile", "<u4"), ("bo_x", "<u2"), ("bo_y", "<u2"), ("bsize", "u1"), ("n_queries", "u1"),
+                     ("reserved", "<u2"), ("query_off", "<u4")])
+MV_QUERY = np.dtype([("block", "<u4"), ("ref_frames", "u1", (2,)), ("is_compound", "u1"), ("reserved", "u1")])
+CANDIDATE_MV = np.dtype([("this_mv", "<i2", (2,)), ("comp_mv", "<i2", (2,)), ("weight", "<u4")])
+MV_STACK = np.dtype([("count", "u1"), ("reserved", "u1"), ("mode_context", "<u2"), ("cand", CANDIDATE_MV, (9,))])
+MV_TRIAL = np.dtype([("block", "<u4"), ("mode", "u1"), ("ref_frames", "u1", (2,)), ("skip", "u1"), ("mv", "<i2", (2, 2))])
+assert TILE_BLOCK.itemsize == 16 and TILE_BLOCKS.itemsize == 40 and MV_BLOCK.itemsize == 16 and MV_QUERY.itemsize == 8
+assert CANDIDATE_MV.itemsize == 12 and MV_STACK.itemsize == 112 and MV_TRIAL.itemsize == 16
+MVREF_MAX_TILES = 64                  # R1_MVREF_MAX_TILES: descriptors per call
+MVREF_MAX_QUERIES = 64                # R1_MVREF_MAX_QUERIES: queries per block
+MVREF_REFUSED = 0xFF                  # R1MvStack.count of a refused query

@@ -453,6 +453,11 @@ class RSlice:
 
     sort_unstable_by_key = sort_by_key
 
+    def sort_by(self, f):  # the comparator closure returns an Ordering; stable, like Rust's merge sort
+        import functools
+        self.b[self.o:self.o + self.n] = sorted(self.b[self.o:self.o + self.n],
+                                                key=functools.cmp_to_key(lambda a, b: int(f(a, b).disc)))
+
     def binary_search(self, x):
         x = deref(x)
         lo, hi = 0, self.n

@@ -239,8 +239,18 @@ __device__ __forceinline__ bool taps_six(const Taps<2> &t) {
 // instruction per quad.  Bytes past a row's W + 7 meet zero band entries; the rows past H + 6 of the last quad are
 // computed and never consumed.  The MFMAs take operands from all 64 lanes: a branch around the call must be one that
 // every lane of the wave takes.
+// MX4 (the fused coefficient kernels at 16x16 and 8x8 where rdo_mc_matrix4 of rdo_cand_plan.hpp ships them; off = every
+// other caller, the code it had): the same pass for waves of four or eight candidates with taps of their own, on
+// v_mfma_i32_4x4x4_16b_i8 -- sixteen independent 4x4x4 blocks, a block = four adjacent columns of one candidate (W is a
+// multiple of 4), each with its own A and B (r1mc::mx4_*, mc_window.hpp, states the index algebra).  `win` stays the
+// lane's OWN window and `c` its column, as on the v_dot4 path.  A quad of window rows is three chained MFMAs on three
+// LDS dwords: A_s = the aligned dword s of row 4 q + (c & 3) at the lane's column group, B_s = t0 / t1 / t2 below (the
+// half-taps shifted up by c & 3 bytes: what the v_dot4 pass multiplies by), C = the bias.  Register i of D is
+// hacc(4 q + i) of the lane's own column: no band builder, no shadow, no v_readlane, nothing moves between lanes.  The
+// row past H + 6 of the last quad is read (inside the allocation: r1mc::mx4_a_end) and never consumed.  As with MXNC
+// the call must sit under branches the whole wave takes.
 typedef int v4i_t __attribute__((ext_vector_type(4)));
-template <int W, int H, int WS, bool PREP, bool PACK4 = false, int MXNC = 0>
+template <int W, int H, int WS, bool PREP, bool PACK4 = false, int MXNC = 0, bool MX4 = false>
 __device__ __forceinline__ void mc8_column_t(const uint8_t *win, int c, const Taps<1> &tp, int32_t *pred, bool six,
                                              int lane = 0, const uint8_t *zero = nullptr) {
   const uint32_t fx0 = tp.fx0, fx1 = tp.fx1;
@@ -281,6 +291,9 @@ __device__ __forceinline__ void mc8_column_t(const uint8_t *win, int c, const Ta
       bb1 = (long)r1mc::mx_band8((uint32_t)__builtin_amdgcn_readlane((int)fx0, 32),
                                  (uint32_t)__builtin_amdgcn_readlane((int)fx1, 32), lane);
   }
+  // MX4: the row of a quad whose dwords this lane supplies as A (quad q: + 4 q WSD dwords)
+  static_assert(!MX4 || (MXNC == 0 && W % 4 == 0 && W <= 16 && 64 % W == 0), "4x4x4 blocks: 16x16, 8x8");
+  const uint32_t *arow = wrow + (c & 3) * WSD;
   const v4i_t cbias = {bias, bias, bias, bias};
   v4i_t quad = cbias;
   int quad_at = -1;   // a constant once the calls below are unrolled
@@ -291,6 +304,16 @@ __device__ __forceinline__ void mc8_column_t(const uint8_t *win, int c, const Ta
         quad = __builtin_amdgcn_mfma_i32_16x16x32_i8(*(const long *)(ap0 + quad_at * 4 * WS), bb0, cbias, 0, 0, 0);
         if constexpr (MXNC == 2)
           quad = __builtin_amdgcn_mfma_i32_16x16x32_i8(*(const long *)(ap1 + quad_at * 4 * WS), bb1, quad, 0, 0, 0);
+      }
+      return quad[r & 3];
+    }
+    if constexpr (MX4) {
+      if ((r >> 2) != quad_at) {
+        quad_at = r >> 2;
+        const uint32_t *ar = arow + quad_at * 4 * WSD;
+        quad = __builtin_amdgcn_mfma_i32_4x4x4i8((int)ar[0], (int)t0, cbias, 0, 0, 0);
+        quad = __builtin_amdgcn_mfma_i32_4x4x4i8((int)ar[1], (int)t1, quad, 0, 0, 0);
+        quad = __builtin_amdgcn_mfma_i32_4x4x4i8((int)ar[2], (int)t2, quad, 0, 0, 0);
       }
       return quad[r & 3];
     }
@@ -460,12 +483,13 @@ __device__ __forceinline__ void mc16_column_t(const uint8_t *win, int c, const T
 // One column of put_8tap (PREP: prep_8tap) of a W x H block at either pixel width, from a window staged with row
 // stride WS (8-bit: pixels biased by -128); `six` is taps_six(tp), voted by every lane that makes the call.
 // MXNC != 0 (8-bit only): the horizontal pass on the matrix pipe, see mc8_column_t for what win / lane / zero are then.
-template <int BPP, int W, int H, int WS, bool PREP, bool PACK4 = false, int MXNC = 0>
+// MX4 (8-bit only): the same on sixteen 4x4x4 blocks; win and c are the lane's own, as without it.
+template <int BPP, int W, int H, int WS, bool PREP, bool PACK4 = false, int MXNC = 0, bool MX4 = false>
 __device__ __forceinline__ void mc_column_fast(const uint8_t *win, int c, const Taps<BPP> &tp, int bit_depth,
                                                int32_t *pred, bool six, int lane = 0, const uint8_t *zero = nullptr) {
   static_assert(!PACK4 || BPP == 1, "8 * mid of 16-bit pixels does not fit i16");
-  static_assert(MXNC == 0 || BPP == 1, "there is no i16 matrix type");
-  if constexpr (BPP == 1) mc8_column_t<W, H, WS, PREP, PACK4, MXNC>(win, c, tp, pred, six, lane, zero);
+  static_assert((MXNC == 0 && !MX4) || BPP == 1, "there is no i16 matrix type");
+  if constexpr (BPP == 1) mc8_column_t<W, H, WS, PREP, PACK4, MXNC, MX4>(win, c, tp, pred, six, lane, zero);
   else mc16_column_t<W, H, WS, PREP>(win, c, tp, bit_depth, pred, six);
 }
 

@@ -43,4 +43,31 @@ constexpr unsigned long long mx_band8(unsigned fx0, unsigned fx1, int l) {
   return d >= 8 || d <= -8 ? 0ull : (d >= 0 ? t << (8 * d) : t >> (8 * -d));
 }
 
+// ---- the same pass as sixteen small products (mc8_column_t<.., MX4>): windows narrower than 32 ----
+// v_mfma_i32_4x4x4_16b_i8, D = A B + C, is sixteen independent 4x4x4 blocks; block b is lanes 4 b .. 4 b + 3.  Lane
+// 4 b + i supplies A[i][K = 0 .. 3] as the four bytes of a dword, lane 4 b + j supplies B[K = 0 .. 3][j] and receives
+// D[i = 0 .. 3][j] in registers 0 .. 3.  Every block has an A and a B of its own, so the candidates of a wave need not
+// share their taps.  Lane = (candidate, column c) and w a multiple of 4: a block is four adjacent columns cb = c & ~3
+// .. cb + 3 of ONE candidate, i = j = c & 3.  A quad q of window rows is three chained products, s = 0, 1, 2:
+//   A_s[i][K] = byte cb + 4 s + K of row 4 q + i of the lane's OWN window: one aligned dword of row 4 q + (c & 3)
+//   B_s[K][j] = h[4 s + K - j]: dword s of the eight half-taps shifted up by c & 3 bytes into twelve (zero elsewhere)
+//   D[i][j]   = C + sum_s sum_K A_s[i][K] B_s[K][j] = C + sum_t h[t] win[4 q + i][cb + j + t]
+// so the lane receives the accumulators of its own column for rows 4 q .. 4 q + 3 and nothing moves between lanes.
+// the window row whose dwords the lane of column c supplies as A for quad q
+constexpr int mx4_a_row(int c, int q) { return 4 * q + (c & 3); }
+// byte offset, from the lane's own window, of the dword it supplies as A_s for quad q
+constexpr int mx4_a_offset(int c, int q, int s, int ws) { return mx4_a_row(c, q) * ws + (c & ~3) + 4 * s; }
+// one past the furthest byte any A fragment of a wave of nc windows reads, from the first window: the last lane's last
+// dword of the last quad (whose rows past h + 6 are read and never consumed)
+constexpr int mx4_a_end(int nc, int w, int h, int ws) {
+  return (nc - 1) * (h + 7) * ws + mx4_a_offset(w - 1, mx_quads(h) - 1, 2, ws) + 4;
+}
+// The dword the lane of column c supplies as B_s, from the candidate's half-taps as two little-endian dwords (kTapI8):
+// byte K is h[4 s + K - (c & 3)].
+constexpr unsigned mx4_band(unsigned fx0, unsigned fx1, int c, int s) {
+  const int sh8 = 8 * (c & 3);
+  const unsigned long long t64 = (((unsigned long long)fx1 << 32) | fx0) << sh8;
+  return s == 0 ? (unsigned)t64 : (s == 1 ? (unsigned)(t64 >> 32) : (unsigned)(((unsigned long long)fx1 << sh8) >> 32));
+}
+
 }  // namespace r1mc

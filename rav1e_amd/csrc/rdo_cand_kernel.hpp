@@ -26,7 +26,11 @@
 //     8-bit 64x64 and 32x32 coefficient kernels (MC_MATRIX, rdo_cand_plan.hpp): the
 //     horizontal taps are one v_mfma_i32_16x16x32_i8 per candidate and quad of
 //     window rows instead -- window bytes as A, the taps as a band in B, every
-//     lane receives the accumulators of its own column.
+//     lane receives the accumulators of its own column.  8-bit 16x16 and 8x8
+//     coefficient kernels (MC_MATRIX4), four and eight candidates per wave: three
+//     chained v_mfma_i32_4x4x4_16b_i8 per quad -- sixteen independent blocks of four
+//     adjacent columns of one candidate, three dwords of the lane's own window as A,
+//     its candidate's shifted taps as B, the same accumulators out.
 //     The residual COLUMN stays in registers.  SAD is a lane sum.  SATD: the
 //     vertical Hadamard on 8 registers, the horizontal one across the 8
 //     neighbouring lanes with DPP (quad_perm / row_half_mirror) -- no LDS; blocks
@@ -130,6 +134,10 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
   constexpr int MX_NC = PL::MX_NC;
   static_assert(MX_NC == 0 || (BPP == 1 && QM == 0 && !INTRA && P == W && NC * W == 64),
                 "a coefficient kernel of 8-bit pixels, lane = (candidate, column) with no idle lane");
+  // MC_MATRIX4 (rdo_cand_plan.hpp): the same pass on sixteen 4x4x4 blocks, four or eight candidates per wave
+  constexpr bool MC_MATRIX4 = PL::MC_MATRIX4;
+  static_assert(!MC_MATRIX4 || (BPP == 1 && QM == 0 && !INTRA && P == W && NC * W == 64),
+                "a coefficient kernel of 8-bit pixels, lane = (candidate, column) with no idle lane");
   __shared__ __attribute__((aligned(16))) uint8_t smem[LDS_BYTES];
   T *buf = (T *)smem;
   TB *tbuf = (TB *)smem;
@@ -154,6 +162,7 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
   // keeps its masked regions.
   constexpr bool UNMASK = !(BD == 8 && WL == 6 && HL == 6);
   const bool live_st = cand_i < n;
+  static_assert(!MC_MATRIX4 || UNMASK, "the 4x4x4 MFMAs take operands from all 64 lanes: dead slots repeat a candidate");
   const bool live = UNMASK || live_st;
   const int cl_ld = live_st ? cl : n - 1 - (int)wg * NC;     // >= 0: the wave's first candidate exists
   const long long cand_ld = live_st ? cand : (long long)n - 1;
@@ -341,6 +350,10 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
         if constexpr (MX_NC != 0)
           r1cand::mc_column_fast<BPP, W, H, WS, false, MC_PACK4, MX_NC>(smem, c, tp, BD, pred, six, lane,
                                                                          smem + PL::MX_ZERO_OFF);
+        // MC_MATRIX4: likewise all 64 lanes (UNMASK: the dead slots of the last wave repeat the launch's last
+        // candidate); every lane on its own window and column, with its own candidate's taps
+        else if constexpr (MC_MATRIX4)
+          r1cand::mc_column_fast<BPP, W, H, WS, false, MC_PACK4, 0, true>(win, c, tp, BD, pred, six);
         else
         r1cand::mc_column_fast<BPP, W, H, WS, false, MC_PACK4>(win, c, tp, BD, pred, six);
       }

@@ -138,13 +138,30 @@ constexpr bool rdo_mc_pack4(int bd, int wl, int hl, int qm, bool mt, int ps) {
 // twelve LDS dwords, every lane receives the accumulators of its own column, and the pack and the vertical pass stay
 // as they are.  Candidates are the family of HALVE2 / MC_PACK4.  Built for 64x64 (one candidate per wave) and 32x32
 // (two: two chained MFMAs, the other candidate's row groups read a zeroed shadow behind the source block); 16x16 and
-// 8x8 (four and eight tap sets per wave) have no layout here and keep the v_dot4 pass, as does everything else.
+// 8x8 (four and eight tap sets per wave) have no layout in this form -- theirs is rdo_mc_matrix4, below -- and everything
+// else keeps the v_dot4 pass.
 // Measured like COL_FOLD / HALVE2, the parent's library against this one on one box, three sessions of alternated passes
 // (profiles/r22_mc_matrix_notes.md): 64x64 launch -8.2 %, 32x32 -4.2 %, every pass below every parent pass;
 // SQ_INSTS_VALU per wave 4069 -> 3839 and 1772 -> 1706, a third of the LDS instructions gone; registers, LDS and waves
 // per SIMD as before (tools/kres.py).
 constexpr bool rdo_mc_matrix(int bd, int wl, int hl, int qm, bool mt, int ps) {
   return bd == 8 && rdo_plain_square(wl, hl, qm, mt, ps) && wl >= 5;
+}
+// The same pass for the waves of four and eight candidates, on v_mfma_i32_4x4x4_16b_i8 (mc8_column_t<.., MX4>,
+// cand_common.hpp; geometry r1mc::mx4_*, mc_window.hpp): sixteen independent 4x4x4 blocks, each four adjacent columns of
+// one candidate with that candidate's taps, so a quad of window rows is three chained MFMAs on three LDS dwords of the
+// lane's own window instead of twelve v_dot4 on twelve, with no shadow and no band builder.  rdo_mc_matrix4_layout: the
+// sizes the layout is stated and checked for (the 8-bit QM 0 plain squares 16x16 and 8x8); rdo_mc_matrix4: those of them
+// that ship, each only where its launch was measured faster than the parent's.  Both are on.  Measured like MC_MATRIX,
+// the parent's library against this one on one box per session, three sessions of four to five alternated passes
+// (profiles/r23_mc_matrix4_notes.md): 16x16 launch -6.7 / -6.1 / -6.5 %, 8x8 -4.4 / -3.8 / -3.8 %, every pass below every
+// parent pass; SQ_INSTS_VALU per wave (MFMAs included) 810 -> 769 and 468 -> 445, 18 / 12 MFMAs per wave, SQ_INSTS_LDS
+// -25 / -29 %; 50 -> 53 and 40 -> 42 VGPRs, LDS as before, no scratch, 8 waves per SIMD as before (tools/kres.py).
+constexpr bool rdo_mc_matrix4_layout(int bd, int wl, int hl, int qm, bool mt, int ps) {
+  return bd == 8 && rdo_plain_square(wl, hl, qm, mt, ps) && (wl == 4 || wl == 3);
+}
+constexpr bool rdo_mc_matrix4(int bd, int wl, int hl, int qm, bool mt, int ps) {
+  return rdo_mc_matrix4_layout(bd, wl, hl, qm, mt, ps) && (wl == 4 || wl == 3);
 }
 
 // ---- one instantiation: geometry, choices, LDS layout ----
@@ -272,4 +289,14 @@ struct RdoCandPlan {
   static_assert(!MC_MATRIX || r1mc::mx_a_end(NC > 2 ? 2 : NC, H, WS) <= LDS_BYTES,
                 "the furthest byte an A fragment reads lies inside the allocation");
   static_assert(!MC_MATRIX || MX_ZERO_OFF + MX_ZERO_BYTES <= LDS_BYTES, "the zeroed shadow lies inside the allocation");
+  // MC_MATRIX4 (rdo_mc_matrix4): the pass on sixteen 4x4x4 blocks, every lane on its own window.  MX4_A_END = one past
+  // the furthest byte a fragment reads (the row past H + 6 of the last candidate's last quad: in the staged source
+  // block), stated for every size the layout covers whether it ships or not.  Nothing is added to any allocation.
+  static constexpr bool MC_MATRIX4 = rdo_mc_matrix4(BD, WL, HL, QM, MT, PS);
+  static constexpr int MX4_A_END = rdo_mc_matrix4_layout(BD, WL, HL, QM, MT, PS) ? r1mc::mx4_a_end(NC, W, H, WS) : 0;
+  static_assert(!MC_MATRIX4 || !MC_MATRIX, "one matrix form per instantiation");
+  static_assert(MX4_A_END == 0 || (NC * W == 64 && W % 4 == 0 && WS % 4 == 0 && WS >= W + 8 && !SRC_LATE),
+                "lane = (candidate, column) with no idle lane; a block is four columns of one candidate; its three "
+                "dwords stay inside the row");
+  static_assert(MX4_A_END <= LDS_BYTES, "the furthest byte an A fragment reads lies inside the allocation");
 };

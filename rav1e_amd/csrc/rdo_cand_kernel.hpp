@@ -130,6 +130,10 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
   constexpr int SH1C = COL_FOLD ? 0 : SH1;
   // HALVE2 / MC_PACK4 (rdo_cand_plan.hpp): the networks of m24h in both passes; the shift-free pack of the 8-bit filter
   constexpr bool HALVE2 = PL::HALVE2, MC_PACK4 = PL::MC_PACK4;
+  // MUL_HW (rdo_mul_hiword, rdo_cand_plan.hpp): the networks of m24w in both passes, products at scale 2^16 where the
+  // pass's input bound allows (CB: columns, RB: rows)
+  constexpr bool MUL_HW = PL::MUL_HW;
+  constexpr int CB = rdo_mul_col_bound(BD, SH0, COL_FOLD), RB = rdo_mul_row_bound(BD, WL, HL);
   // MC_MATRIX (rdo_cand_plan.hpp): the 8-bit filter's horizontal pass on the matrix pipe, MX_NC candidates per wave
   constexpr int MX_NC = PL::MX_NC;
   static_assert(MX_NC == 0 || (BPP == 1 && QM == 0 && !INTRA && P == W && NC * W == 64),
@@ -541,13 +545,23 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
       }
     }
     if constexpr (COL_FOLD) {   // shift[0], the network and shift[1] as one: the column family on the unshifted residuals
-      if (TX_VOTE && col_uni) r1tx::fwd_col_m24_kernel<H, SH0, SH1, HALVE2>(v, r1tx::vtx_1d(tx_s));
-      else r1tx::fwd_col_m24<H, SH0, SH1, HALVE2>(v, r1tx::vtx_1d(tx_col));
+      if constexpr (MUL_HW) {
+        if (TX_VOTE && col_uni) r1tx::fwd_col_m24w_kernel<H, SH0, SH1, CB>(v, r1tx::vtx_1d(tx_s));
+        else r1tx::fwd_col_m24w<H, SH0, SH1, CB>(v, r1tx::vtx_1d(tx_col));
+      } else {
+        if (TX_VOTE && col_uni) r1tx::fwd_col_m24_kernel<H, SH0, SH1, HALVE2>(v, r1tx::vtx_1d(tx_s));
+        else r1tx::fwd_col_m24<H, SH0, SH1, HALVE2>(v, r1tx::vtx_1d(tx_col));
+      }
     } else {
 #pragma unroll
       for (int r = 0; r < H; r++) v[r] = r1tx::shift_fwd_ct<SH0>(v[r]);
-      if (TX_VOTE && col_uni) r1tx::fwd_1d_m24_kernel<H, HALVE2>(v, r1tx::vtx_1d(tx_s));
-      else r1tx::fwd_1d_m24<H, HALVE2>(v, r1tx::vtx_1d(tx_col));
+      if constexpr (MUL_HW) {
+        if (TX_VOTE && col_uni) r1tx::fwd_1d_m24w_kernel<H, CB>(v, r1tx::vtx_1d(tx_s));
+        else r1tx::fwd_1d_m24w<H, CB>(v, r1tx::vtx_1d(tx_col));
+      } else {
+        if (TX_VOTE && col_uni) r1tx::fwd_1d_m24_kernel<H, HALVE2>(v, r1tx::vtx_1d(tx_s));
+        else r1tx::fwd_1d_m24<H, HALVE2>(v, r1tx::vtx_1d(tx_col));
+      }
     }
     if constexpr (!SPLIT_T) {
       const int cc = cl * W + (r1tx::lr_flip(tx_col) ? W - 1 - c : c);
@@ -598,8 +612,13 @@ __global__ __launch_bounds__(64, rdo_waves_hint(BD, WL, HL, QM, MT)) void k_rdo_
       for (int k = 0; k < W; k++) u[k] = tkeep[r * LSTRIDE + cl2 * W + k];
     }
     // the switch on the scalar or per lane, as in phase C (the left-right flip is the tile store's column)
-    if (TX_VOTE && row_uni) r1tx::fwd_1d_m24_kernel<W, HALVE2>(u, r1tx::htx_1d(tx_s));
-    else r1tx::fwd_1d_m24<W, HALVE2>(u, r1tx::htx_1d(tt));
+    if constexpr (MUL_HW) {
+      if (TX_VOTE && row_uni) r1tx::fwd_1d_m24w_kernel<W, RB>(u, r1tx::htx_1d(tx_s));
+      else r1tx::fwd_1d_m24w<W, RB>(u, r1tx::htx_1d(tt));
+    } else {
+      if (TX_VOTE && row_uni) r1tx::fwd_1d_m24_kernel<W, HALVE2>(u, r1tx::htx_1d(tx_s));
+      else r1tx::fwd_1d_m24<W, HALVE2>(u, r1tx::htx_1d(tt));
+    }
 #pragma unroll
     for (int k = 0; k < W; k++) {
       u[k] = r1tx::shift_fwd_ct<SH2>(u[k]);

@@ -132,6 +132,32 @@ constexpr bool rdo_halve2(int bd, int wl, int hl, int qm, bool mt, int ps) {
 constexpr bool rdo_mc_pack4(int bd, int wl, int hl, int qm, bool mt, int ps) {
   return bd == 8 && rdo_plain_square(wl, hl, qm, mt, ps) && wl <= 5;
 }
+// Whether an instantiation's forward networks, both passes, keep their multiplies' products at scale 2^16 where the
+// factor's bound allows (m24w, tx_common.hpp: exact while |a| (M << (16 - s)) + 2^15 < 2^31), so that an add or a
+// subtract reads the product's high word and the rounding shift is not executed.  rdo_mul_hiword_built: the
+// instantiations the form is stated, bounded and tested for -- the 8-bit coefficient kernels of the square sizes, the
+// family of HALVE2, whose halving the form keeps.  rdo_mul_hiword: those of them that ship.
+// rdo_mul_col_bound / rdo_mul_row_bound: the bound B of the inputs' magnitude each pass hands to the networks --
+// columns: the unshifted residual where the column family runs (COL_FOLD), residual << shift[0] elsewhere; rows: the
+// column outputs after shift[1], the largest over the transform types the size admits (tools/tx_range.py
+// chain_input_bounds(): 8x8 5774, 16x16 8164, 32x32 5776, 64x64 16334; tests/test_tx_mul_hiword.py holds the header
+// to them).  At those bounds every multiply of the column networks takes the form but 24 of fdct64's 191; of the
+// row networks' all of fdct8 / fdst8, 27 of 31 (fdct16), 42 of 48 (fdst16), 70 of 81 (fdct32), 87 of 191 (fdct64).
+// Measured like HALVE2 / MC_MATRIX, the parent's library against this one on one box per session, three sessions of four
+// to five alternated passes (profiles/r24_mul_hiword_notes.md): 64x64 launch -4.9 / -4.5 / -4.7 %, 32x32 -6.7 / -6.4 /
+// -6.6 %, 16x16 -5.5 / -5.3 / -5.4 %, 8x8 -1.6 / -1.2 / -1.4 %, every pass below every parent pass: all four ship.
+// SQ_INSTS_VALU per wave 3839 -> 3614, 1706 -> 1560, 769 -> 713, 445 -> 418; registers 118 -> 115 at 64x64 and as before
+// elsewhere, LDS and waves per SIMD as before, no scratch (tools/kres.py).
+constexpr bool rdo_mul_hiword_built(int bd, int wl, int hl, int qm, bool mt, int ps) {
+  return bd == 8 && rdo_plain_square(wl, hl, qm, mt, ps);
+}
+constexpr bool rdo_mul_hiword(int bd, int wl, int hl, int qm, bool mt, int ps) {
+  return rdo_mul_hiword_built(bd, wl, hl, qm, mt, ps);
+}
+constexpr int rdo_mul_col_bound(int bd, int sh0, bool col_fold) { return ((1 << bd) - 1) << (col_fold ? 0 : sh0); }
+constexpr int rdo_mul_row_bound(int bd, int wl, int hl) {
+  return bd == 8 && wl == hl ? (wl == 3 ? 5774 : wl == 4 ? 8164 : wl == 5 ? 5776 : wl == 6 ? 16334 : 0) : 0;
+}
 // Whether an instantiation's 8-bit motion compensation runs its horizontal 8-tap pass on the matrix pipe
 // (mc8_column_t<.., MXNC>, cand_common.hpp; the fragment geometry is r1mc::mx_*, mc_window.hpp): a quad of window
 // rows is one 8-byte LDS read and one v_mfma_i32_16x16x32_i8 per candidate of the wave instead of twelve v_dot4 on
@@ -177,6 +203,8 @@ struct RdoCandPlan {
   static constexpr bool COL_FOLD = rdo_col_fold(BD, WL, HL, QM, MT, PS);
   static constexpr bool HALVE2 = rdo_halve2(BD, WL, HL, QM, MT, PS);
   static constexpr bool MC_PACK4 = rdo_mc_pack4(BD, WL, HL, QM, MT, PS);
+  static constexpr bool MUL_HW = rdo_mul_hiword(BD, WL, HL, QM, MT, PS);
+  static_assert(!MUL_HW || (HALVE2 && rdo_mul_row_bound(BD, WL, HL) > 0), "m24w keeps m24h's halving; a stated row bound");
   static constexpr int WS = r1mc::window_stride(W, BPP);
   // INTRA: no reference window.  The candidate's edge arrays (raw edge + the four filter / upsample arrays, FL
   // entries each) take its place and may lie over the WHOLE allocation: the source block waits in registers until

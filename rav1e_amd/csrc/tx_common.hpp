@@ -100,6 +100,67 @@ using m24::shl_subr;
 #undef TX_RSHIFT1
 #define TX_RSHIFT1(a) (TX_ADD((a), (T)((a) < 0)) >> 1)
 }  // namespace m24h
+// Fourth instantiation, both families of the networks of 8 points and more (fwd_tx_1d_hw.inc, tools/gen_tx1d.py
+// hiword_family()), on m24h's halving: a multiply's product stays at scale 2^16,
+//   (a M + 2^(s-1)) >> s  ==  (a (M << (16 - s)) + 2^15) >> 16,     s <= 16 the shift the multiply executes,
+// exact while |a| (M << (16 - s)) + 2^15 < 2^31 and M << (16 - s) < 2^23 (still a 24-bit operand of the mad).  The value
+// is stated as P >> 16: a consumer that adds or subtracts it reads the product's high word (v_add_u32_sdwa /
+// v_sub_u32_sdwa, src_sel:WORD_1 sign-extended, as m24h's halving reads BYTE_3), and the shift is executed only where
+// the value feeds something else.  Every function takes B, a bound of its inputs' magnitude (column family: of the
+// unshifted residual), and every multiply carries QB, the largest B at which it qualifies (the generator's, from the
+// node's L1 gain; tools/tx_range.py mul_bounds()): B <= QB takes the form, anything else is mul_rs / mul_rk as in m24h.
+// The bounds the fused kernels pass are rdo_mul_col_bound / rdo_mul_row_bound (rdo_cand_plan.hpp), checked against
+// tx_range.py and run on the host by tests/test_tx_mul_hiword.py.
+namespace m24w {
+using m24::mul_rk;
+using m24::mul_rs;
+using m24::shl_subr;
+template <int M, int S, bool HW>
+__device__ __forceinline__ T mul_rsw(T a) {
+  if constexpr (HW) {
+    static_assert(S >= 1 && S <= 16 && M > 0 && (long long)M * (1 << (16 - S)) < (1 << 23), "a 24-bit multiplier");
+    T r;
+    asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(M * (1 << (16 - S))), "v"(1 << 15));
+    return r >> 16;
+  } else {
+    return mul_rs<M, S>(a);
+  }
+}
+template <int M, int S, int K, bool HW>
+__device__ __forceinline__ T mul_rkw(T a) {
+  static_assert(K >= 1 && K <= S - 1, "the rounding term stays an integer");
+  if constexpr (HW) return mul_rsw<M, S - K, true>(a);
+  else return mul_rk<M, S, K>(a);
+}
+// The halving of a product: its operand is hidden from the compiler's range analysis, which otherwise knows a value of
+// 16 bits and narrows the halving to four 16-bit instructions (v_lshrrev 31, v_and_sdwa, v_ashrrev_i16_sdwa,
+// v_add_u16) where the shift by 16, m24h's v_sub_u32_sdwa and the shift by 1 are three.
+__device__ __forceinline__ T halve_prod(T a) {
+  asm("" : "+v"(a));
+  return TX_SUB(a, a >> 24) >> 1;
+}
+#define TX_RSHIFT1W(a) (halve_prod(a))
+// ... and the column family's output (x +- y + 1) >> 1 of two products, which it otherwise narrows to v_or_b32_sdwa,
+// v_xor_b32_sdwa, v_ashrrev_i16 and v_sub_u16 where the add or subtract of two high words, the add of 1 and the shift
+// are three
+template <int S>
+__device__ __forceinline__ T rnd_sum(T a) {
+  asm("" : "+v"(a));
+  return (a + (1 << (S - 1))) >> S;
+}
+#define TX_RNDW(a, s) (rnd_sum<(s)>(a))
+#define TX_MULW(a, m, s, qb) (mul_rsw<(m), (s), (B <= (qb))>(a))
+#define TX_MULKW(a, m, s, k, qb) (mul_rkw<(m), (s), (k), (B <= (qb))>(a))
+#undef TX_RSHIFT1
+#define TX_RSHIFT1(a) (TX_SUB((a), (a) >> 24) >> 1)
+#include "fwd_tx_1d_hw.inc"
+#undef TX_RSHIFT1
+#define TX_RSHIFT1(a) (TX_ADD((a), (T)((a) < 0)) >> 1)
+#undef TX_MULW
+#undef TX_MULKW
+#undef TX_RSHIFT1W
+#undef TX_RNDW
+}  // namespace m24w
 #undef TX_MULK
 #undef TX_SHL
 #undef TX_SHL_ADD
@@ -290,6 +351,49 @@ template <int N, int SH0, int SH1, bool H2 = false>
 __device__ __forceinline__ void fwd_col_m24(T *c, int k) { fwd_col_m24_sw<N, SH0, SH1, true, H2>(c, k); }
 template <int N, int SH0, int SH1, bool H2 = false>
 __device__ __forceinline__ void fwd_col_m24_kernel(T *c, int k) { fwd_col_m24_sw<N, SH0, SH1, false, H2>(c, k); }
+
+// The same switches on m24w (products at scale 2^16 where the bound B of the call's inputs allows; N >= 8): the
+// siblings of fwd_1d_m24<N, true>, fwd_1d_m24_kernel<N, true>, fwd_col_m24<.., true> and fwd_col_m24_kernel<.., true>.
+// B: |c[i]| <= B on entry -- for the column family the unshifted residual.
+#define R1_M24W_SWITCH(N, SUF, ...)                                                            \
+  do {                                                                                         \
+    static_assert(N >= 8, "the 4-point networks have no member in m24w");                      \
+    if constexpr (N == 8) {                                                                    \
+      if (k == 0) m24w::r1_fdct8##SUF<__VA_ARGS__>(c); else m24w::r1_fdst8##SUF<__VA_ARGS__>(c);   \
+    } else if constexpr (N == 16) {                                                            \
+      if (k == 0) m24w::r1_fdct16##SUF<__VA_ARGS__>(c); else m24w::r1_fdst16##SUF<__VA_ARGS__>(c); \
+    } else if constexpr (N == 32) {                                                            \
+      m24w::r1_fdct32##SUF<__VA_ARGS__>(c);                                                    \
+    } else {                                                                                   \
+      m24w::r1_fdct64##SUF<__VA_ARGS__>(c);                                                    \
+    }                                                                                          \
+  } while (0)
+template <int N, int B>
+__device__ __forceinline__ void fwd_1d_m24w(T *c, int k) {
+  if (k == 3) return;
+  R1_M24W_SWITCH(N, , B);
+}
+template <int N, int B>
+__device__ __forceinline__ void fwd_1d_m24w_kernel(T *c, int k) {
+  R1_M24W_SWITCH(N, , B);
+}
+template <int N, int SH0, int SH1, bool IDENT, int B>
+__device__ __forceinline__ void fwd_col_m24w_sw(T *c, int k) {
+  static_assert(SH0 > 0 && SH1 <= 0, "shift[0] = 0 and a left shift[1] have no member in the column family");
+  if constexpr (IDENT) {
+    if (k == 3) {
+#pragma unroll
+      for (int r = 0; r < N; r++) c[r] = shift_col_ident<SH0, SH1>(c[r]);
+      return;
+    }
+  }
+  R1_M24W_SWITCH(N, _col, SH0, -SH1, B);
+}
+template <int N, int SH0, int SH1, int B>
+__device__ __forceinline__ void fwd_col_m24w(T *c, int k) { fwd_col_m24w_sw<N, SH0, SH1, true, B>(c, k); }
+template <int N, int SH0, int SH1, int B>
+__device__ __forceinline__ void fwd_col_m24w_kernel(T *c, int k) { fwd_col_m24w_sw<N, SH0, SH1, false, B>(c, k); }
+#undef R1_M24W_SWITCH
 
 // One 1-D forward transform of length N on a register array, class `k`
 // (0 DCT, 1/2 ADST (flip handled by the caller), 3 identity, 4 WHT).

@@ -92,9 +92,9 @@ def _parse(expr):
     return m.group(1), [a.strip() for a in m.group(2).split(",")]
 
 
-def value_bounds(n, ops, inmax):
-    """|value| bound of every SSA name of the PLAIN network fed with |input| <= inmax: inmax * L1 norm of the value's
-    response to the inputs (the networks are linear up to rounding) + the accumulated rounding error."""
+def value_gains(n, ops):
+    """{SSA name of the PLAIN network: (L1 norm of the value's response to the inputs, accumulated rounding error)}:
+    the networks are linear up to rounding, so |value| <= |input| bound * L1 + error"""
     vec = {"c%d" % i: [float(j == i) for j in range(n)] for i in range(n)}
     err = {"c%d" % i: 0.0 for i in range(n)}
     for name, expr in ops:
@@ -113,7 +113,13 @@ def value_bounds(n, ops, inmax):
             err[name] = err[a[0]] * abs(g) + 0.5
         else:
             raise ValueError(expr)
-    return {k: int(math.ceil(inmax * sum(abs(x) for x in v) + err[k])) for k, v in vec.items()}
+    return {k: (sum(abs(x) for x in v), err[k]) for k, v in vec.items()}
+
+
+def value_bounds(n, ops, inmax):
+    """|value| bound of every SSA name of the PLAIN network fed with |input| <= inmax: inmax * L1 norm of the value's
+    response to the inputs (the networks are linear up to rounding) + the accumulated rounding error."""
+    return {k: int(math.ceil(inmax * l1 + e)) for k, (l1, e) in value_gains(n, ops).items()}
 
 
 def halving_bound(n, ops, outs, inmax):
@@ -146,12 +152,9 @@ def plain_counts(n, ops, k0, s):
     return fast, slow
 
 
-def fold(n, ops, outs, k0, s, inmax):
-    """-> (body lines, (fast, slow), mad-input bound folded, mad-input bound plain)"""
-    vb = value_bounds(n, ops, inmax << k0)
-    parsed = [(name,) + tuple(_parse(expr)) for name, expr in ops]
-    plain_mad = max(vb[a[0]] for _, op, a in parsed if op == "MUL")
-    # pass 1: the pending scale of every value (independent of how operands get aligned)
+def pending_scales(n, parsed, k0):
+    """pass 1 of fold(): the pending scale k of every value, value = reg * 2^k (independent of how operands get
+    aligned)"""
     k = {"c%d" % i: k0 for i in range(n)}
     for name, op, a in parsed:
         if op in ("ADD", "SUB"):
@@ -163,6 +166,15 @@ def fold(n, ops, outs, k0, s, inmax):
         else:
             assert k[a[0]] <= int(a[2]) - 1, (name, a)
             k[name] = 0
+    return k
+
+
+def fold(n, ops, outs, k0, s, inmax):
+    """-> (body lines, (fast, slow), mad-input bound folded, mad-input bound plain)"""
+    vb = value_bounds(n, ops, inmax << k0)
+    parsed = [(name,) + tuple(_parse(expr)) for name, expr in ops]
+    plain_mad = max(vb[a[0]] for _, op, a in parsed if op == "MUL")
+    k = pending_scales(n, parsed, k0)
 
     def mad_ok(b):   # may `b` be the 24-bit factor of a v_mad_i32_i24?
         return (vb[b] >> k[b]) <= plain_mad
@@ -319,6 +331,149 @@ def col_family():
     return hdr + "\n\n".join(body) + "\n", table
 
 
+# ---- the high-word family: products kept at scale 2^16 ----
+#   (a M + 2^(s-1)) >> s  ==  (a (M << (16 - s)) + 2^15) >> 16        s <= 16
+# exact while the scaled product plus 2^15 fits an i32 and M << (16 - s) stays a 24-bit operand; s is the shift the
+# multiply EXECUTES (S of the plain family, S - k of the column family).  With the value stated as P >> 16 a consumer
+# `x +- (P >> 16)` is one add / sub that reads the product's high word (src_sel:WORD_1, sign-extended): the shift of a
+# product that only feeds adds and subs is never executed.  fwd_tx_1d_hw.inc states every multiply of the networks of
+# 8 points and more, both families, as TX_MULW(a, M, S, QB) / TX_MULKW(a, M, S, k, QB): QB is the largest bound of the
+# network's INPUTS (the unshifted residual for the column family) at which the node still qualifies, and the
+# functions take the bound of the call, B, as a template parameter -- a node is scaled where B <= QB and is the
+# plain family's mul_rs / mul_rk otherwise (csrc/tx_common.hpp, m24w).
+HIWORD = 16
+HW_NAMES = ("fdct8", "fdct16", "fdct32", "fdct64", "fdst8", "fdst16")
+_GAINS = {}
+
+
+def net(t):
+    """(n, ops, outs, gains) of network t, traced once"""
+    if t not in _GAINS:
+        n, ops, outs = trace_ops(t)
+        _GAINS[t] = (n, ops, outs, value_gains(n, ops))
+    return _GAINS[t]
+
+
+def hiword_ok(bound, m, s):
+    """may a multiply by m, rounding shift s, whose factor is bounded by `bound`, keep its product at scale 2^16?"""
+    if s < 1 or s > HIWORD:
+        return False
+    ms = abs(m) << (HIWORD - s)
+    return ms < (1 << 23) and bound * ms + (1 << 15) < (1 << 31)
+
+
+def mul_nodes(t, inmax, k0=None):
+    """[(name, |factor| bound, M, shift executed, L1 gain, rounding error, k)] for every live multiply of network t in
+    trace order, inputs bounded by inmax.  k0 None: the plain family.  Otherwise the column family on unshifted
+    inputs at pending scale k0: the factor is the register, plain value >> k, and the shift executed is S - k."""
+    n, ops, _outs, gains = net(t)
+    parsed = [(name,) + tuple(_parse(expr)) for name, expr in ops]
+    k = pending_scales(n, parsed, k0) if k0 is not None else None
+    res = []
+    for name, op, a in parsed:
+        if op != "MUL":
+            continue
+        l1, e = gains[a[0]]
+        ka = k[a[0]] if k is not None else 0
+        b = int(math.ceil((inmax << (k0 or 0)) * l1 + e)) >> ka
+        res.append((name, b, int(a[1]), int(a[2]) - ka, l1, e, ka))
+    return res
+
+
+def hiword_qb(l1, e, m, s, k0, ka):
+    """the largest input bound at which the node qualifies (0: never)"""
+    def ok(b):
+        return hiword_ok(int(math.ceil((b << k0) * l1 + e)) >> ka, m, s)
+    lo, hi = 0, 1 << 24          # ok(lo) or lo == 0; not ok(hi) unless capped
+    if ok(hi):
+        return hi
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if ok(mid):
+            lo = mid
+        else:
+            hi = mid
+    return lo
+
+
+def _halve_w(text, prods):
+    """a halving whose operand is a product is stated as TX_RSHIFT1W: its operand is materialised (see m24w)"""
+    m = re.search(r"TX_RSHIFT1\((\w+)\)", text)
+    return text.replace("TX_RSHIFT1(", "TX_RSHIFT1W(") if m and m.group(1) in prods else text
+
+
+def _rnd_w(text, prods, defs):
+    """an output (x +- y + 1) >> 1 of two products is stated as TX_RNDW: its operand is materialised (see m24w)"""
+    m = re.match(r"  c\[\d+\] = TX_RND\((\w+), 1\);$", text)
+    if m:
+        d = re.match(r"  const T \w+ = TX_(ADD|SUB)\((\w+), (\w+)\);$", defs.get(m.group(1), ""))
+        if d and d.group(2) in prods and d.group(3) in prods:
+            return text.replace("TX_RND(", "TX_RNDW(")
+    return text
+
+
+def hiword_family():
+    """-> (text of fwd_tx_1d_hw.inc, {(name, k0, s): [QB per multiply in trace order]}); k0 = s = None: plain"""
+    pairs = col_pairs()
+    body, marks = [], {}
+    for t, nm in enumerate(NAMES):
+        if nm not in HW_NAMES:
+            continue
+        n, ops, outs, _g = net(t)
+        ins = "  const T " + ", ".join("c%d = c[%d]" % (i, i) for i in range(n)) + ";"
+        qbs = [hiword_qb(l1, e, m, s, 0, 0) for _nm, _b, m, s, l1, e, _k in mul_nodes(t, 0)]
+        marks[nm, None, None] = qbs
+        it = iter(qbs)
+        lines = ["template <int B> TX1D_FN void r1_%s(T *c) {" % nm, ins]
+        prods = set(name for name, expr in ops if expr.startswith("TX_MUL("))
+        for name, expr in ops:
+            if expr.startswith("TX_MUL("):
+                qb = next(it)
+                assert hiword_ok(0, *[int(v) for v in _parse(expr)[1][1:]]) or qb == 0
+                expr = "TX_MULW(%s, %d)" % (expr[len("TX_MUL("):-1], qb)
+            lines.append("  const T %s = %s;" % (name, _halve_w(expr, prods)))
+        lines += ["  c[%d] = %s;" % (i, o) for i, o in enumerate(outs)]
+        lines.append("}")
+        body.append("\n".join(lines))
+        # the column family: fold()'s text, its multiplies marked
+        lines = ["template <int K0, int S, int B> TX1D_FN void r1_%s_col(T *c) {" % nm,
+                 "  static_assert(%s, \"a (shift[0], -shift[1]) pair the column pass meets\");" %
+                 " || ".join("(K0 == %d && S == %d)" % (k0, s) for k0, s, _m in pairs[n]), ins]
+        for k0, s, inmax in pairs[n]:
+            flines, _cnt, _fm, _pm = fold(n, ops, outs, k0, s, inmax)
+            nodes = mul_nodes(t, inmax, k0)
+            qbs = [hiword_qb(l1, e, m, se, k0, ka) for _nm, _b, m, se, l1, e, ka in nodes]
+            marks[nm, k0, s] = qbs
+            it = iter(zip(nodes, qbs))
+            lines.append("  if constexpr (K0 == %d && S == %d) {" % (k0, s))
+            defs = {}
+            for ln in flines:
+                mm = re.match(r"  const T (\w+) = TX_MUL(K?)\((.*)\);$", ln)
+                if mm:
+                    nd, qb = next(it)
+                    a = [v.strip() for v in mm.group(3).split(",")]
+                    ka = int(a[3]) if mm.group(2) else 0
+                    assert nd[0] == mm.group(1) and nd[2] == int(a[1]) and nd[3] == int(a[2]) - ka and nd[6] == ka
+                    # what the generator asserts for every node it emits in the new form: at its QB the node qualifies,
+                    # one past it no longer does
+                    assert qb == 0 or hiword_ok(int(math.ceil((qb << k0) * nd[4] + nd[5])) >> ka, nd[2], nd[3])
+                    ln = "  const T %s = TX_MUL%sW(%s, %d);" % (mm.group(1), mm.group(2), mm.group(3), qb)
+                defs[mm.group(1) if mm else ln.split(" = ")[0].split()[-1]] = ln
+                lines.append("  " + _rnd_w(_halve_w(ln, prods), prods, defs))
+            assert next(it, None) is None
+            lines.append("  }")
+        lines.append("}")
+        body.append("\n".join(lines))
+    hdr = ("/* GENERATED by tools/gen_tx1d.py from oracle/fwd_tx_np.py -- do not edit.\n"
+           " * High-word family of the forward 1-D networks of 8 points and more, plain and column form: the text of\n"
+           " * fwd_tx_1d.inc / fwd_tx_1d_col.inc with every multiply stated as TX_MULW(a, M, S, QB) /\n"
+           " * TX_MULKW(a, M, S, k, QB).  QB = the largest bound of the network's inputs (column form: of the unshifted\n"
+           " * residual) at which |a| * (M << (16 - s)) + 2^15 < 2^31 and M << (16 - s) < 2^23, s the shift the multiply\n"
+           " * executes; B = the bound of the call.  Where B <= QB the product stays at scale 2^16 and the value is\n"
+           " * P >> 16 (tools/gen_tx1d.py, hiword_family()). */\n")
+    return hdr + "\n\n".join(body) + "\n", marks
+
+
 def main():
     body = []
     stats = []
@@ -344,6 +499,11 @@ def main():
         f.write(text)
     print("wrote", rel, len(text), "bytes")
     print("\n".join(table))
+    text, _marks = hiword_family()
+    rel = "rav1e_amd/csrc/fwd_tx_1d_hw.inc"
+    with open(os.path.join(ROOT, rel), "w") as f:
+        f.write(text)
+    print("wrote", rel, len(text), "bytes")
 
 
 if __name__ == "__main__":

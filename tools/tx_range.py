@@ -117,6 +117,54 @@ def halving_bounds():
     return res
 
 
+def chain_input_bounds(bd, ts, tt):
+    """(|input| bound of the column network = pixel range << shift[0], |input| bound of the row network = the column
+    outputs after shift[1]) of a fused kernel's chain, residuals from pixels; the composition is halving_bounds()'s"""
+    import math
+    import gen_tx1d as G
+    w, h = F.TX_DIMS[ts]
+    sh = F.FWD_SHIFT[ts][(bd - 8) // 2]
+    tcol = F.TXFM_TYPE_LS[h.bit_length() - 3][F.VTX_TAB[tt]]
+    b0 = ((1 << bd) - 1) << sh[0]
+    if G.NAMES[tcol] is None:            # the identity
+        ocol = b0
+    else:
+        n, ops, outs, gains = G.net(tcol)
+        ocol = max(int(math.ceil(b0 * gains[o][0] + gains[o][1])) for o in outs)
+    return b0, int(math.ceil(ocol * 2.0 ** sh[1])) + 1
+
+
+def mul_bounds():
+    """{(bit depth, tx_size, tx_type, pass): [(worst-case |a|, M, shift executed)] for every multiply of the pass's
+    network in trace order}, residuals from pixels.  pass: "col" = the plain network fed with residual << shift[0];
+    "colk" = the column family on the unshifted residual (tools/gen_tx1d.py fold(): the factor is the register,
+    the plain value >> k, and the multiply shifts by S - k), where shift[0] > 0; "row" = the plain network fed with the
+    column outputs after shift[1].  |a| = the input bound times the node's L1 gain plus the accumulated rounding, as
+    for the 24-bit mads and the halvings.  A product may stay at scale 2^16 (m24w, csrc/tx_common.hpp) where
+    gen_tx1d.hiword_ok(|a|, M, shift) holds."""
+    import gen_tx1d as G
+    res = {}
+    for bd in (8, 10, 12):
+        for ts, (w, h) in enumerate(F.TX_DIMS):
+            for tt in range(16):
+                if not F.valid_av1_transform(ts, tt):
+                    continue
+                sh = F.FWD_SHIFT[ts][(bd - 8) // 2]
+                tcol = F.TXFM_TYPE_LS[h.bit_length() - 3][F.VTX_TAB[tt]]
+                trow = F.TXFM_TYPE_LS[w.bit_length() - 3][F.HTX_TAB[tt]]
+                b0, b1 = chain_input_bounds(bd, ts, tt)
+
+                def nodes(t, inmax, k0=None):
+                    if G.NAMES[t] is None:
+                        return []
+                    return [(b, m, s) for _n, b, m, s, _l, _e, _k in G.mul_nodes(t, inmax, k0)]
+                res[bd, ts, tt, "col"] = nodes(tcol, b0)
+                if sh[0] > 0:
+                    res[bd, ts, tt, "colk"] = nodes(tcol, (1 << bd) - 1, int(sh[0]))
+                res[bd, ts, tt, "row"] = nodes(trow, b1)
+    return res
+
+
 if __name__ == "__main__":
     hb = halving_bounds()
     for bd in (8, 10, 12):
